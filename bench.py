@@ -1,6 +1,12 @@
 """bench.py — headline benchmark of the Zonos hot path on MI355X (contract: task brief ④).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step` = wall milliseconds of
+one timed step).  `--full` adds the measurements that take runs of their own: the AR-only time of one generate() call, the
+roofline of the dominant kernel and of the decode step, the other kernels of the launches path and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step returned (codes, and the waveform when the DAC decode is timed) as
+float32 `DIR/<name>.npy`; the inputs are seeded, so two builds can be compared output for output.
 
 N > 1 without a launcher environment: this process spawns the N ranks itself (`python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`) BEFORE anything touches the GPU, relays rank 0's JSON line
@@ -33,6 +39,7 @@ HBM_PEAK = 8.0e12                 # B/s, MI355X spec (MI355X_MICROARCH.md)
 PMC_FILES = {5: os.path.join(ROOT, "profiles", "pmc_chain.json"), 6: os.path.join(ROOT, "profiles", "pmc_step_kernel.json")}
 KERNEL_SOURCES = ("zonos_amd/csrc/zn_step_kernel.h", "zonos_amd/csrc/zn_step_sched.h", "zonos_amd/csrc/zn_chain_kernel.h", "zonos_amd/csrc/zn_decode_kernels.h", "zonos_amd/csrc/zn_common.h")
 STEP_KERNEL_CTX = 450             # keys in the cache for the whole-step kernel's roofline launches: the mean context of a 10 s utterance
+DUMP_BYTES = (64 << 20) - (1 << 16)   # --dump-outputs: values in all (a seeded sample of a larger output), headers kept within 64 MB
 
 
 def algorithmic_bytes_per_step(cfg, B, L):
@@ -54,11 +61,20 @@ def parse_args(argv=None):
     ap.add_argument("--batch-per-gpu", type=int, default=1,
                     help="utterances per GPU (default 1 = BASELINE config 2).  BASELINE config 3 (64 utterances over 8 GPUs) is "
                          "`--gpus 8 --batch-per-gpu 8`; its one-GPU share is `--batch-per-gpu 8`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-dac", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the AR-only time, the kernel and step rooflines, the launches-path kernels and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as float32 DIR/<name>.npy (rank 0)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher/sharding rehearsal on CPU over gloo with a stand-in generate(); the line carries dry_run=true and no measurement")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def log(msg):
@@ -196,9 +212,10 @@ def run_rank(args) -> int:
     def one_step():
         mine = parallel.generate_sharded(gen, conds, gather=False, batch_size=B)      # this rank's utterances (i mod world == rank)
         wav = dac.decode(torch.stack(mine)) if use_dac else None
+        codes = mine
         if dist is not None:
-            parallel.gather_codes(mine, n_utt)                   # C1: optional gather of the output codes (all_gather)
-        return mine, wav
+            codes = parallel.gather_codes(mine, n_utt)           # C1: optional gather of the output codes (all_gather)
+        return mine, wav, codes
 
     for i in range(args.warmup):
         one_step()
@@ -219,7 +236,7 @@ def run_rank(args) -> int:
     t0 = time.perf_counter()
     frames = 0
     for _ in range(args.steps):
-        mine, wav = one_step()
+        mine, wav, codes = one_step()
         frames += sum(int(c.shape[-1]) for c in mine)
     fence()
     elapsed = time.perf_counter() - t0
@@ -237,6 +254,13 @@ def run_rank(args) -> int:
         dist.all_reduce(ev, op=dist.ReduceOp.SUM)
         timed_events, h1 = [int(v) for v in ev[:3].tolist()], tuple(int(v) for v in ev[3:].tolist())
     assert all(c.shape[-1] == max_new for c in mine), [c.shape for c in mine]
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the codes of every utterance (gathered when N > 1) and, when
+        # the DAC decode is timed, the waveforms of this rank's utterances
+        outs = {"codes": torch.stack(codes)}
+        if wav is not None:
+            outs["wav"] = wav
+        dump_outputs(args.dump_outputs, outs)
 
     audio_s = frames / FRAME_RATE
     value = audio_s / elapsed
@@ -261,19 +285,20 @@ def run_rank(args) -> int:
         result["dry_run"] = True
         result["value"] = None
     else:
-        # AR-only time of one generate() call (reported beside the whole-job value)
-        cond = torch.cat([c[0:1] for c in conds[rank::world]] + [c[1:2] for c in conds[rank::world]], 0)
-        torch.cuda.synchronize()
-        ta = time.perf_counter()
-        gen(cond, B)
-        torch.cuda.synchronize()
-        t_ar = time.perf_counter() - ta
-        result["ar_only"] = {"s_per_utterance": round(t_ar, 4), "ms_per_decode_step": round(1e3 * t_ar / (steps_per_utt + 1), 4),
-                             "audio_sec_per_sec": round(B * max_new / FRAME_RATE / t_ar, 3)}
+        if args.full:
+            # AR-only time of one generate() call (reported beside the whole-job value)
+            cond = torch.cat([c[0:1] for c in conds[rank::world]] + [c[1:2] for c in conds[rank::world]], 0)
+            torch.cuda.synchronize()
+            ta = time.perf_counter()
+            gen(cond, B)
+            torch.cuda.synchronize()
+            t_ar = time.perf_counter() - ta
+            result["ar_only"] = {"s_per_utterance": round(t_ar, 4), "ms_per_decode_step": round(1e3 * t_ar / (steps_per_utt + 1), 4),
+                                 "audio_sec_per_sec": round(B * max_new / FRAME_RATE / t_ar, 3)}
         result["hipgraph_step"] = bool(eng.lib.zn_graph_active(eng.h))
         result["chain_kernel_path"] = bool(eng.lib.zn_decode_path(eng.h))     # the generation just run: persistent kernels or launches
         result["decode_path"] = int(eng.lib.zn_decode_path_detail(eng.h))      # 0 launches, 1 chain launch per block, 2 whole-step kernel
-    if rank == 0 and not dry:
+    if rank == 0 and not dry and args.full:
         from zonos_amd import _lib
         # ---- roofline of the dominant kernel, HIP events on the launch stream; the launches cycle over the 26 layers' weights so
         # that each streams from HBM.  Batch 1: the persistent chain launch (out_proj x2, LayerNorm+fc1+SiLU, fc2, next in_proj:
@@ -361,6 +386,23 @@ def cpu_baseline(w_cpu, cfg, seed, l_c, max_new, ar_steps: int = 128, budget_s: 
                       f"{s_per_step * 1e3:.1f} ms (torch CPU bf16, {cores} threads, wall budget {budget_s:g} s), extrapolated to {max_new + 7} steps; {dac_note}",
             "s_per_decode_step": round(s_per_step, 5), "dac_decode_s": None if dac_s is None else round(dac_s, 3),
             "ar_only_audio_sec_per_sec": round(1.0 / s_per_step / FRAME_RATE, 4)}
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """Writes each tensor as float32 `dirname/<name>.npy` (codes are integers below 2**24: exact).  Past DUMP_BYTES in all, each
+    array keeps its share of the budget as a fixed sample: the values at the sorted flat indices of a draw seeded with 0, which
+    depends on nothing but the array's size."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    for name, a in arrs.items():
+        if total > DUMP_BYTES and a.size > 1:
+            keep = max(1, DUMP_BYTES * a.size // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed step written to {dirname}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in arrs.items()))
 
 
 def kernel_source_hash() -> str:
