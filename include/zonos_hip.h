@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define ZN_ABI_VERSION 5
+#define ZN_ABI_VERSION 6
 
 enum zn_status {
   ZN_OK = 0,
@@ -109,7 +109,8 @@ typedef struct zn_sampling {
 /* ---------------------------------------------------------------- lifecycle */
 int zn_abi_version(void);
 /* Replaces Zonos.__init__/from_local weight binding (zonos/model.py:68-86,128-176).  Weights stay owned by the
- * caller and must outlive the handle.  max_rows = 2 * max batch (CFG doubles rows, generation_utils.py:192). */
+ * caller and must outlive the handle.  max_rows = rows of the largest generation, even: R = 2 B with guidance (CFG doubles rows,
+ * generation_utils.py:192), R = B when cfg_scale == 1. */
 int zn_create(const zn_config* cfg, const zn_weights* w, int32_t max_rows, zn_handle* out);
 int zn_destroy(zn_handle h);
 const char* zn_last_error(zn_handle h); /* h may be NULL: last creation error */
@@ -123,17 +124,19 @@ size_t zn_mamba_state_bytes_per_layer(const zn_config* cfg, int32_t rows, size_t
 
 /* ---------------------------------------------------------------- generation (Zonos.generate, model.py:354-548) */
 /* Binds the per-call state that zonos/model.py:410-463 builds: KV caches (one device pointer per layer, layout
- * [2B, max_len, 2, Hkv, hd] bf16 = TorchZonosBackbone.allocate_inference_cache), lengths_per_sample int32[2B]
+ * [R, max_len, 2, Hkv, hd] bf16 = TorchZonosBackbone.allocate_inference_cache), lengths_per_sample int32[R]
  * (device, zeroed by the caller), the delay-patterned code buffer int32 [B, n_codebooks, t_total] with -1 for
- * unknown (model.py:414-420), the first column to write `offset0` = prefix_len + 1, cfg_scale and sampling. */
+ * unknown (model.py:414-420), the first column to write `offset0` = prefix_len + 1, cfg_scale and sampling.
+ * R = 2B rows [cond ‖ uncond] with guidance; cfg_scale == 1: R = B conditional rows and no CFG mix (model.py:230).
+ * R <= max_rows. */
 /* (zn_gen_begin discards the hipGraphs captured for the previous generation: call it only when that generation's steps have drained from
  * their stream - `Zonos.generate` synchronises before it returns.) */
 int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_layers_dev, int32_t max_len,
                  int32_t* lengths_dev, int32_t* delayed_codes_dev, int32_t t_total, int32_t offset0,
                  int32_t max_new_tokens, float cfg_scale, const zn_sampling* sp, zn_stream stream);
-/* prefill_static (generation_utils.py:206-244) + _compute_logits: hidden bf16 [2B, S, d] = [cond ‖ uncond]
- * conditioning concatenated with embed(delayed[..., :prefix+1]); fills KV positions [0,S), lengths += S and
- * leaves the CFG-mixed fp32 logits [B, n_codebooks, vocab_head] in the handle. */
+/* prefill_static (generation_utils.py:206-244) + _compute_logits: hidden bf16 [R, S, d] = [cond ‖ uncond] (R = 2B), or the
+ * B conditional rows when cfg_scale == 1, conditioning concatenated with embed(delayed[..., :prefix+1]); fills KV positions
+ * [0,S), lengths += S and leaves the fp32 logits [B, n_codebooks, vocab_head] (CFG-mixed with guidance) in the handle. */
 int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_stream stream);
 /* model.py:423-431: sample the first frame from the prefill logits (no repetition penalty, no logit bias) and
  * write it into column offset0 where that column is -1. */
@@ -144,14 +147,15 @@ int zn_sample_first(zn_handle h, zn_stream stream);
 int zn_decode_steps(zn_handle h, int32_t n, zn_stream stream);
 /* 1 if the decode step is currently replayed as an instantiated hipGraph, 0 if launched kernel by kernel. */
 int zn_graph_active(zn_handle h);
-/* 1 if the decode steps of the generation begun by zn_gen_begin run the persistent kernels (batch 1 on a model whose shapes they
- * serve), 0 if every op is a launch of its own.  Both paths give bit-identical results at the Zonos-v0.1 shapes (same tiles, same
+/* 1 if the decode steps of the generation begun by zn_gen_begin run the persistent kernels (one or two rows - batch 1 with guidance,
+ * batch 1 or 2 without - on a model whose shapes they serve), 0 if every op is a launch of its own.  Both paths give bit-identical results at the Zonos-v0.1 shapes (same tiles, same
  * summation order in every GEMV; ONE arithmetic for the decode attention on every path: scores on the matrix cores, contexts of one
  * 512-key block accumulated in place, longer ones block by block with the partials combined in block order). */
 int zn_decode_path(zn_handle h);
 /* Which kernels served the decode step enqueued last: 0 = one launch per op, 1 = one attention launch (two beyond 512 keys) + one
- * persistent chain launch per block, 2 = the whole-step persistent kernel (every block of the step in one launch; contexts up to
- * 6144 keys: one attention workgroup per (row, kv head, 512-key block)).  All give bit-identical results. */
+ * persistent chain launch per block (two rows only), 2 = the whole-step persistent kernel (every block of the step in one launch;
+ * contexts up to 6144 keys: one attention workgroup per (row, kv head, 512-key block); two rows or, without guidance, one row - a
+ * one-row step beyond 6144 keys runs the launches path).  All give bit-identical results. */
 int zn_decode_path_detail(zn_handle h);
 /* Hand-off timeouts are never silent: out[0] = bounded in-kernel hand-off waits that gave up and were reported on this handle (each voids
  * its generation; zn_all_stopped* returns the error), [1] generations begun, [2] batch-1 generations that ran the launches path because
@@ -236,7 +240,7 @@ int zn_op_backbone_forward(zn_handle h, const void* hidden_dev, void* out_dev, c
  * 4 = LayerNorm+in_proj+RoPE+KV-append (into a scratch cache), 5 = the persistent post-attention chain of one block
  * (out_proj twice, LayerNorm+fc1+SiLU-gate, fc2, next block's LayerNorm+in_proj+RoPE+KV-append in ONE launch: batch 1 only;
  * bytes = those four weight matrices, out_proj counted once), 6 = the whole-step kernel (every block of a decode step and the heads in
- * ONE launch, batch 1 only) on scratch KV caches of its own holding `ctx` keys per row; bytes = every weight the step reads once
+ * ONE launch, one or two rows) on scratch KV caches of its own holding `ctx` keys per row; bytes = every weight the step reads once
  * (in_proj of block 0 included: the launch's pre-block; excluded under zn_debug_tune(18, 2), where it is a launch of its own) + K/V of
  * ctx keys read and one row written per layer.
  * rows: bits 0-7 = activation rows; bit 8 = keep streaming layer 0's weights (cache-hot variant); bits 16-30 = ctx for which == 6

@@ -12,7 +12,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZONOS_HIP_LIB") or os.path.join(_HERE, "libzonos_hip.so")   # the override selects an experimental build (A/B runs)
 
-ZN_ABI_VERSION = 5
+ZN_ABI_VERSION = 6
 
 
 class ZonosHipError(RuntimeError):

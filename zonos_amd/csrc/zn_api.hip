@@ -44,6 +44,8 @@ struct zn_handle_s {
   unsigned long long *ch_gbmax = nullptr, *ch_gpart = nullptr;   // key-block attention role: per-block score maxima and P.V partials (zn_step_kernel.h)
   int stack_nbk = 1;                         // key blocks (8 attention workgroups each) of the whole-step launches being enqueued
   bool stackv_ok[4] = {};                    // whole-step kernel instantiations 1 .. 3 that fit this model and device (stack_variant_ok)
+  bool stackv1_ok[4] = {};                   // the same for the one-row kernel (step_r1_kernel: generations without guidance)
+  bool stack1_ok = false;
   StackLayer* stack_layers = nullptr;        // device table [n_layer], rebuilt by zn_gen_begin (it holds the KV cache pointers)
   bool use_stack = false, stack_ok = false, stack_checked = false;   // use_stack: the steps being enqueued run the whole-step kernel
   unsigned* ch_epoch = nullptr;
@@ -267,13 +269,14 @@ extern "C" int zn_create(const zn_config* cfg, const zn_weights* w, int32_t max_
   ZC(hipMalloc(&h->mbuf, R * c.d_ff * 2));
   ZC(hipMalloc(&h->nbuf, R * c.d_model * 2));
   ZC(hipMalloc(&h->logits_raw, R * c.n_codebooks * c.vocab_head * sizeof(float)));
-  ZC(hipMalloc(&h->last_logits, (R / 2) * c.n_codebooks * c.vocab_head * sizeof(float)));
-  ZC(hipMalloc(&h->tok_raw, (R / 2) * c.n_codebooks * sizeof(int)));
+  // per-utterance buffers: up to R utterances (one row each) when generating without guidance, R / 2 with it
+  ZC(hipMalloc(&h->last_logits, R * c.n_codebooks * c.vocab_head * sizeof(float)));
+  ZC(hipMalloc(&h->tok_raw, R * c.n_codebooks * sizeof(int)));
   ZC(hipMalloc(&h->fw_lengths, R * sizeof(int)));
   ZC(hipMalloc(&h->st, sizeof(GenState)));
   ZC(hipMemset(h->st, 0, sizeof(GenState)));
-  ZC(hipMalloc(&h->remaining, (R / 2) * sizeof(int)));
-  ZC(hipMalloc(&h->stopping, (R / 2) * sizeof(int)));
+  ZC(hipMalloc(&h->remaining, R * sizeof(int)));
+  ZC(hipMalloc(&h->stopping, R * sizeof(int)));
   ZC(hipHostMalloc(&h->done_host, sizeof(int) * 8));
   ZC(hipEventCreateWithFlags(&h->stop_event, hipEventDisableTiming));
   for (unsigned long long** g : {&h->ch_gy1, &h->ch_gx1, &h->ch_gx2}) {
@@ -651,6 +654,10 @@ static int layer_decode(zn_handle h, int li, bf16_t* x, bf16_t* kv, int max_len,
 // The persistent chain serves the step when the model fits an instantiation, at batch 1 (two rows), unless switched off
 // (zn_debug_tune(8, 2), or ZN_CHAIN=0 in the environment at zn_create): 1.07 vs 1.16 ms per decode step at the Zonos-v0.1 dimensions.
 static bool chain_active(zn_handle h, int rows) { return h->ch_variant != 0 && rows == 2 && h->tune[8] != 2 && !h->demoted && h->persist_ok; }
+// Row counts a persistent kernel can serve on this model: two (the per-block chain and step_kernel) or one (step_r1_kernel, the whole-step
+// kernel only: one row beyond its 6144-key bound, or with it switched off, runs the launches path).
+static bool persist_shape(zn_handle h, int rows) { return h->ch_variant != 0 && (rows == 2 || (rows == 1 && h->ch_variant == 1)); }
+static bool persist_active(zn_handle h, int rows) { return persist_shape(h, rows) && h->tune[8] != 2 && !h->demoted && h->persist_ok; }
 
 // The chain never updates the residual stream in place (zn_chain_kernel.h): block li reads it from one buffer and leaves it
 // in the other.
@@ -709,11 +716,13 @@ static int launch_chain(zn_handle h, int li, const std::vector<const void*>& kv_
 //   variant 1  <4, 2, 10, 5, 6, 6>   1 .. 6 key blocks  (8 .. 48 attention workgroups: contexts up to 3072 keys)
 //   variant 2  <4, 2, 11, 6, 7, 8>   7 .. 8 blocks   (up to 4096 keys)
 //   variant 3  <4, 2, 13, 7, 8, 12>  9 .. 12 blocks  (up to 6144 keys); longer contexts take the per-block path
+// One row (step_r1_kernel, cfg_scale == 1) uses the same three instantiations with Hkv * NBK attention workgroups: the streaming workgroups
+// grow from 256 - 8 NBK to 256 - 4 NBK, and their fullest share of every matrix never exceeds the two-row launch's.
 #define ZN_SK_T1 4, 2, 10, 5, 6, 6
 #define ZN_SK_T2 4, 2, 11, 6, 7, 8
 #define ZN_SK_T3 4, 2, 13, 7, 8, 12
 static int stack_variant_of(int mode) { return mode <= 6 ? 1 : mode <= 8 ? 2 : 3; }
-template <int NCH, int T_OUT, int T_FC1, int T_FC2, int T_IN, int NBV>
+template <int R, int NCH, int T_OUT, int T_FC1, int T_FC2, int T_IN, int NBV>
 static bool stack_variant_ok(zn_handle h, int natt) {
   const zn_config& c = h->cfg;
   const int nsw = ZN_CH_GRID - natt;
@@ -725,11 +734,11 @@ static bool stack_variant_ok(zn_handle h, int natt) {
   if (p_qkv > 10) return false;                                                                                                   // the pre-block: five row pairs per helper wave
   if (p_out * 2 > 64 || p_out * 4 > 64 || p_fc1 > 64 || p_qkv * 2 > 64 || p_hd * 2 > 64 || nqkv % 2) return false;              // one epilogue lane per (unit, row); s_res slots
   // every workgroup of the grid must be resident at once (the hand-offs wait on all of them): one per CU by its LDS, no scratch
-  const void* fn = (const void*)step_kernel<NCH, T_OUT, T_FC1, T_FC2, T_IN, NBV>;
+  const void* fn = R == 1 ? (const void*)step_r1_kernel<NCH, T_OUT, T_FC1, T_FC2, T_IN, NBV> : (const void*)step_kernel<NCH, T_OUT, T_FC1, T_FC2, T_IN, NBV>;
   int dev = 0, n_cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return false; }
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ZN_SK_DYN_LDS) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel<NCH, T_OUT, T_FC1, T_FC2, T_IN, NBV>, ZN_SK_THREADS, ZN_SK_DYN_LDS) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, ZN_SK_THREADS, ZN_SK_DYN_LDS) != hipSuccess) { (void)hipGetLastError(); return false; }
   hipFuncAttributes fa{};
   if (hipFuncGetAttributes(&fa, fn) != hipSuccess) { (void)hipGetLastError(); return false; }
   return per_cu >= 1 && n_cus >= ZN_CH_GRID && fa.localSizeBytes == 0;
@@ -737,23 +746,28 @@ static bool stack_variant_ok(zn_handle h, int natt) {
 static bool stack_shapes_ok(zn_handle h) {
   const zn_config& c = h->cfg;
   if (h->ch_variant != 1 || h->hd != 128 || c.n_heads_kv < 1 || c.n_heads != 4 * c.n_heads_kv) return false;
-  const int npairs = 2 * c.n_heads_kv;
+  const int npairs = 2 * c.n_heads_kv, nkvh = c.n_heads_kv;
   h->stackv_ok[0] = false;
-  h->stackv_ok[1] = stack_variant_ok<ZN_SK_T1>(h, npairs * 6);
-  h->stackv_ok[2] = stack_variant_ok<ZN_SK_T2>(h, npairs * 8);
-  h->stackv_ok[3] = stack_variant_ok<ZN_SK_T3>(h, npairs * ZN_SK_KB_MAXNB);
+  h->stackv_ok[1] = stack_variant_ok<2, ZN_SK_T1>(h, npairs * 6);
+  h->stackv_ok[2] = stack_variant_ok<2, ZN_SK_T2>(h, npairs * 8);
+  h->stackv_ok[3] = stack_variant_ok<2, ZN_SK_T3>(h, npairs * ZN_SK_KB_MAXNB);
+  h->stackv1_ok[0] = false;
+  h->stackv1_ok[1] = stack_variant_ok<1, ZN_SK_T1>(h, nkvh * 6);
+  h->stackv1_ok[2] = stack_variant_ok<1, ZN_SK_T2>(h, nkvh * 8);
+  h->stackv1_ok[3] = stack_variant_ok<1, ZN_SK_T3>(h, nkvh * ZN_SK_KB_MAXNB);
+  h->stack1_ok = h->stackv1_ok[1];
   return h->stackv_ok[1];
 }
 // The key blocks a whole-step launch covering `keys_upper_bound` keys needs: -1 = the whole-step kernel does not serve the step (the
-// per-block path does), n >= 1 = 8 n attention workgroups.
+// per-block path does at two rows, the launches path at one), n >= 1 = rows * Hkv * n attention workgroups.
 static int stack_mode_for(zn_handle h, int rows, int keys_upper_bound) {
-  if (!chain_active(h, rows) || h->tune[15] == 2 || !h->stack_ok) return -1;
+  if (!persist_active(h, rows) || h->tune[15] == 2 || !(rows == 1 ? h->stack1_ok : h->stack_ok)) return -1;
   const int nb = keys_upper_bound <= 512 ? 1 : (keys_upper_bound + 511) / 512;
   if (nb > ZN_SK_KB_MAXNB) return -1;
-  return h->stackv_ok[stack_variant_of(nb)] ? nb : -1;
+  return (rows == 1 ? h->stackv1_ok : h->stackv_ok)[stack_variant_of(nb)] ? nb : -1;
 }
 static bool stack_pre(zn_handle h) { return h->tune[18] != 2; }
-static int launch_stack(zn_handle h, hipStream_t s) {
+static int launch_stack(zn_handle h, hipStream_t s, int rows) {
   const zn_config& c = h->cfg;
   ChainArgs a{};
   a.eps = c.norm_eps; a.F = c.d_ff; a.nqkv = (c.n_heads + 2 * c.n_heads_kv) * h->hd;
@@ -767,13 +781,22 @@ static int launch_stack(zn_handle h, hipStream_t s) {
   a.rope_positions = c.rope_positions;
   a.layers = h->stack_layers; a.n_layer = c.n_layer; a.q0 = h->q; a.scale = (float)(1.0 / std::sqrt((double)h->hd));
   a.heads_rows = c.n_codebooks * c.vocab_head; a.heads_out = h->logits_raw; a.trace = h->dbg_trace;
-  const int mode = h->stack_nbk, npairs = 2 * c.n_heads_kv;
+  const int mode = h->stack_nbk, npairs = rows * c.n_heads_kv;
   a.natt = npairs * (mode < 1 ? 1 : mode);
   if (stack_pre(h)) {       // block 0's LayerNorm + in_proj + RoPE + KV append inside the launch (zn_debug_tune(18, 2): as a launch before it)
     a.pre_W = (const bf16_t*)h->layers[0].in_proj; a.pre_ln_w = (const bf16_t*)h->layers[0].norm_w; a.pre_ln_b = (const bf16_t*)h->layers[0].norm_b;
     a.pre_kv = (bf16_t*)h->kv_layers[0];
   }
   const dim3 grid(ZN_CH_GRID), block(ZN_SK_THREADS);
+  if (rows == 1) {
+    switch (stack_variant_of(mode)) {
+      case 1: hipLaunchKernelGGL((step_r1_kernel<ZN_SK_T1>), grid, block, ZN_SK_DYN_LDS, s, a); break;
+      case 2: hipLaunchKernelGGL((step_r1_kernel<ZN_SK_T2>), grid, block, ZN_SK_DYN_LDS, s, a); break;
+      default: hipLaunchKernelGGL((step_r1_kernel<ZN_SK_T3>), grid, block, ZN_SK_DYN_LDS, s, a); break;
+    }
+    return ZN_OK;
+  }
+  if (rows != 2) ZN_FAIL(h, ZN_ERR_STATE, "launch_stack: %d rows (the whole-step kernel serves one or two)", rows);
   switch (stack_variant_of(mode)) {
     case 1: hipLaunchKernelGGL((step_kernel<ZN_SK_T1>), grid, block, ZN_SK_DYN_LDS, s, a); break;
     case 2: hipLaunchKernelGGL((step_kernel<ZN_SK_T2>), grid, block, ZN_SK_DYN_LDS, s, a); break;
@@ -982,18 +1005,22 @@ static SampleArgs make_sample_args(zn_handle h, const zn_sampling& sp) {
   return a;
 }
 
+// With guidance every utterance has a conditional and an unconditional row (rows = 2 batch); cfg_scale == 1: one row per utterance.
+static bool guided(zn_handle h) { return h->rows == 2 * h->batch; }
+
 static EmbedArgs make_embed_args(zn_handle h) {
   const zn_config& c = h->cfg;
   EmbedArgs e{};
   e.tables = h->emb_tables_dev; e.codes = h->codes; e.col_dev = &h->st->offset; e.sb = c.n_codebooks * h->t_total; e.si = h->t_total;
-  e.col = 0; e.n_q = c.n_codebooks; e.d = c.d_model; e.batch = h->batch; e.vocab_embed = c.vocab_embed; e.out = h->x_emb; e.dup = 1;
+  e.col = 0; e.n_q = c.n_codebooks; e.d = c.d_model; e.batch = h->batch; e.vocab_embed = c.vocab_embed; e.out = h->x_emb; e.dup = guided(h) ? 1 : 0;
   return e;
 }
 
 // Batch 1 on the chain path: the step's tail (bookkeeping + next step's embedding) runs in the sampler launch's last workgroup.
 // Larger batches keep three launches (embed_kernel spreads the utterances over workgroups; one workgroup embedding 8 utterances
-// in turn cost 31 us per step at batch 8), and so does everything off the chain path (its first op reads h->x).
-static bool tail_fused(zn_handle h) { return h->cfg.arch == 0 && chain_active(h, h->rows) && h->batch <= 2; }
+// in turn cost 31 us per step at batch 8), and so does everything off the chain path (its first op reads h->x).  One row: only the
+// steps the whole-step kernel serves read the fused tail's embedding (enqueue_step, zn_decode_steps).
+static bool tail_fused(zn_handle h) { return h->cfg.arch == 0 && persist_active(h, h->rows) && h->batch <= 2; }
 
 // One iteration of model.py:467-502: embed -> 26 blocks -> heads -> CFG/bias/penalty/sample -> bookkeeping.  With the fused tail the
 // embedding of the current column is already in h->x_emb when the step starts (zn_decode_steps launches embed_kernel before the
@@ -1001,7 +1028,7 @@ static bool tail_fused(zn_handle h) { return h->cfg.arch == 0 && chain_active(h,
 static int enqueue_step(zn_handle h, hipStream_t s) {
   const zn_config& c = h->cfg;
   int rc;
-  const bool fused = tail_fused(h);
+  const bool fused = tail_fused(h) && (h->use_stack || chain_active(h, h->rows));
   if (!fused) {
     EmbedArgs e = make_embed_args(h);
     e.out = h->x;
@@ -1013,13 +1040,13 @@ static int enqueue_step(zn_handle h, hipStream_t s) {
     bool heads_done = false;
     if (h->use_stack) {                                    // every block + the heads in one launch (in_proj of block 0 inside it, or as a launch before it)
       if (!stack_pre(h) && (rc = layer_in_proj(h, 0, h->x_emb, (bf16_t*)h->kv_layers[0], h->max_len, h->lengths, h->rows, s))) return rc;
-      if ((rc = launch_stack(h, s))) return rc;
+      if ((rc = launch_stack(h, s, h->rows))) return rc;
       heads_done = true;
     } else if ((rc = decode_blocks(h, nullptr, 0, s, fused ? h->x_emb : nullptr, &heads_done))) return rc;
     if (!heads_done && (rc = heads_logits(h, h->x, h->rows, s))) return rc;
   }
   SampleArgs a = make_sample_args(h, h->sp);
-  a.raw = h->logits_raw; a.mix = 1; a.cfg_scale = h->cfg_scale; a.apply_bias = 1; a.batch = h->batch;
+  a.raw = h->logits_raw; a.mix = guided(h) ? 1 : 0; a.cfg_scale = h->cfg_scale; a.apply_bias = 1; a.batch = h->batch;
   a.codes = h->codes; a.t_total = h->t_total; a.ctx = h->max_new < 100 ? h->max_new : 100;
   a.use_penalty = (h->sp.repetition_penalty != 1.0f); a.st = h->st; a.logits_out = h->last_logits; a.tokens = h->tok_raw;
   a.draw = 1;
@@ -1047,9 +1074,10 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   if (!h) return ZN_ERR_ARG;
   if (!kv_layers_dev || !lengths_dev || !delayed_codes_dev || !sp) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_begin: null argument");
   if (!h->has_io) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_begin: handle was created without embeddings/heads");
-  if (batch < 1 || 2 * batch > h->max_rows) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_begin: batch %d exceeds max_rows %d / 2", batch, h->max_rows);
+  // cfg_scale == 1: no guidance, one row per utterance (the reference's _compute_logits skips the mix, model.py:230); else [cond ‖ uncond]
+  const int rows = cfg_scale == 1.0f ? batch : 2 * batch;
+  if (batch < 1 || rows > h->max_rows) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_begin: batch %d needs %d rows, max_rows is %d", batch, rows, h->max_rows);
   if (max_len < 1 || t_total < 1 || offset0 < 1 || offset0 >= t_total) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_begin: bad lengths");
-  if (cfg_scale == 1.0f) ZN_FAIL(h, ZN_ERR_ARG, "cfg_scale == 1 is not supported (zonos/model.py:399)");
   if (max_len > h->cfg.rope_positions)
     ZN_FAIL(h, ZN_ERR_ARG, "sequence length %d exceeds the %d-position RoPE table (zonos/backbone/_torch.py:206)", max_len, h->cfg.rope_positions);
   if (sp->repetition_penalty_window < 0 || sp->repetition_penalty_window > 64) ZN_FAIL(h, ZN_ERR_ARG, "repetition_penalty_window out of range");
@@ -1057,7 +1085,7 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   int rc = ensure_attn_ws(h, max_len);
   if (rc) return rc;
   free_graph(h);
-  h->batch = batch; h->rows = 2 * batch; h->max_len = max_len; h->t_total = t_total; h->offset0 = offset0; h->max_new = max_new_tokens;
+  h->batch = batch; h->rows = rows; h->max_len = max_len; h->t_total = t_total; h->offset0 = offset0; h->max_new = max_new_tokens;
   h->cfg_scale = cfg_scale; h->sp = *sp;
   h->kv_layers.assign(kv_layers_dev, kv_layers_dev + h->cfg.n_layer);
   h->lengths = lengths_dev; h->codes = delayed_codes_dev;
@@ -1081,9 +1109,10 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   // every later utterance on a say-so of one event).
   h->n_generations++;
   if (h->demoted && h->clean_since_demotion >= ZN_REARM_AFTER) { h->demoted = false; h->clean_since_demotion = 0; h->n_rearms++; }
-  if (h->demoted && h->cfg.arch == 0 && h->ch_variant != 0 && batch == 1 && h->tune[8] != 2) h->n_fallback_generations++;
-  // batch 1 on a model the persistent kernels serve: claim the device for them, or run this generation on the launches path
-  h->persist_ok = !(h->cfg.arch == 0 && h->ch_variant != 0 && batch == 1) || zn_tenant_try_claim(h->device, h) != 0;
+  const bool persist_rows = h->cfg.arch == 0 && persist_shape(h, rows);
+  if (h->demoted && persist_rows && h->tune[8] != 2) h->n_fallback_generations++;
+  // one or two rows on a model the persistent kernels serve: claim the device for them, or run this generation on the launches path
+  h->persist_ok = !persist_rows || zn_tenant_try_claim(h->device, h) != 0;
   if (h->cfg.arch == 0 && h->ch_variant == 1) {
     if (!h->stack_checked) { h->stack_ok = stack_shapes_ok(h); h->stack_checked = true; }
     if (h->stack_ok) { int rc = build_stack_table(h); if (rc) return rc; }
@@ -1097,8 +1126,8 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   std::vector<int> rem(batch, t_total - offset0), stop(batch, 0);   // model.py:439-441
   HIPCHK(h, hipMemcpyAsync(h->remaining, rem.data(), batch * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemcpyAsync(h->stopping, stop.data(), batch * sizeof(int), hipMemcpyHostToDevice, s));
-  std::vector<int> len0(2 * batch, 0);
-  HIPCHK(h, hipMemcpyAsync(len0.data(), lengths_dev, 2 * batch * sizeof(int), hipMemcpyDeviceToHost, s));
+  std::vector<int> len0(rows, 0);
+  HIPCHK(h, hipMemcpyAsync(len0.data(), lengths_dev, rows * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));  // host vectors go out of scope
   h->len_hi = 0;
   for (int v : len0) if (v > h->len_hi) h->len_hi = v;
@@ -1395,7 +1424,7 @@ extern "C" int zn_sample_first(zn_handle h, zn_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   const zn_config& c = h->cfg;
   SampleArgs a = make_sample_args(h, h->sp);
-  a.raw = h->logits_raw; a.mix = 1; a.cfg_scale = h->cfg_scale; a.apply_bias = 0; a.batch = h->batch;
+  a.raw = h->logits_raw; a.mix = guided(h) ? 1 : 0; a.cfg_scale = h->cfg_scale; a.apply_bias = 0; a.batch = h->batch;
   a.use_penalty = 0; a.st = h->st; a.logits_out = h->last_logits; a.tokens = h->tok_raw; a.draw = 0;
   hipLaunchKernelGGL(sample_kernel, dim3(c.n_codebooks, h->batch), dim3(256), 0, s, a);
   FrameArgs f{};
@@ -1414,10 +1443,6 @@ extern "C" int zn_decode_steps(zn_handle h, int32_t n, zn_stream stream) {
   if (n < 0) ZN_FAIL(h, ZN_ERR_ARG, "n < 0");
   hipStream_t s = (hipStream_t)stream;
   h->gen_stream = s;
-  if (n > 0 && tail_fused(h) && !h->emb_valid) {   // first step of the generation: later ones find the embedding their predecessor's tail left
-    hipLaunchKernelGGL(embed_kernel, dim3(h->batch), dim3(256), 0, s, make_embed_args(h));
-    h->emb_valid = true;
-  }
   for (int i = 0; i < n;) {
     // this step appends one key per row; a run of ZN_GRAPH_STEPS steps with one launch shape replays the long graph
     const int fused = attn_fused_for(h, h->len_hi + 1, h->rows);
@@ -1433,6 +1458,14 @@ extern "C" int zn_decode_steps(zn_handle h, int32_t n, zn_stream stream) {
     const int k = stack ? (8 + (run > 1 ? ZN_SK_KB_MAXNB + 1 : 0) + mode) : (fused + (run > 1 ? 4 : 0));      // launches path: slots 0..2 and 4..6
     h->attn_fused = fused; h->use_stack = stack;
     if (stack) h->stack_nbk = mode;
+    // steps with the fused tail read the embedding their predecessor's tail left: the first of them gets it from embed_kernel; steps
+    // without it (one row off the whole-step kernel) embed into h->x themselves and leave x_emb stale
+    const bool tail = st_ok && (stack || chain_active(h, h->rows));
+    if (tail && !h->emb_valid) {
+      hipLaunchKernelGGL(embed_kernel, dim3(h->batch), dim3(256), 0, s, make_embed_args(h));
+      h->emb_valid = true;
+    }
+    if (!tail) h->emb_valid = false;
     if (!h->graph_exec[k] && !h->graph_tried[k] && n > 1) {
       // capture; every step-varying quantity (column, positions) is read from device memory
       h->graph_tried[k] = true;
@@ -1477,11 +1510,11 @@ extern "C" int zn_get_counters(zn_handle h, int64_t* out, int32_t n) {
   return ZN_OK;
 }
 
-extern "C" int zn_decode_path(zn_handle h) { return (h && h->gen_active && h->cfg.arch == 0 && chain_active(h, h->rows)) ? 1 : 0; }
 extern "C" int zn_decode_path_detail(zn_handle h) {
-  if (!h || !h->gen_active || h->cfg.arch != 0 || !chain_active(h, h->rows)) return 0;
-  return h->use_stack ? 2 : 1;
+  if (!h || !h->gen_active || h->cfg.arch != 0 || !persist_active(h, h->rows)) return 0;
+  return h->use_stack ? 2 : chain_active(h, h->rows) ? 1 : 0;   // (one row: the whole-step kernel or the launches path)
 }
+extern "C" int zn_decode_path(zn_handle h) { return zn_decode_path_detail(h) != 0 ? 1 : 0; }
 extern "C" int zn_graph_active(zn_handle h) {
   if (!h) return 0;
   for (int k = 0; k < ZN_NGRAPHS; ++k) if (h->graph_exec[k]) return 1;
@@ -1612,7 +1645,7 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   const int saved_max_len = h->max_len; int* const saved_lengths = h->lengths;
   const int ctx = ctx_arg > 0 ? ctx_arg : 450;
   if (which == 6) {
-    if (!chain_active(h, rows)) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the whole-step kernel serves batch 1 (2 rows) of the transformer only");
+    if (!persist_active(h, rows)) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the whole-step kernel serves one or two rows of the transformer only");
     if (!h->stack_checked) { h->stack_ok = stack_shapes_ok(h); h->stack_checked = true; }
     h->stack_nbk = stack_mode_for(h, rows, ctx + 1);
     if (h->stack_nbk < 0) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the whole-step kernel does not serve this model / context");
@@ -1663,7 +1696,7 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
         a.W = (const bf16_t*)lw.out_proj; a.N = d; a.K = c.n_heads * h->hd; a.x = h->o1; a.resid = h->x; a.out = h->x;
         rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[1], s);
       } else if (which == 6) {
-        rc = launch_stack(h, s);
+        rc = launch_stack(h, s, rows);
       } else if (which == 5) {
         if (i % c.n_layer == c.n_layer - 1) continue;       // the last block's launch has no in_proj: not the launch being priced
         rc = launch_chain(h, i % c.n_layer, std::vector<const void*>(c.n_layer, tkv), 8, tlen, s);

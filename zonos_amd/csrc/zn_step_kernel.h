@@ -24,6 +24,9 @@
 // compare for equality.  Every wait is bounded and describes itself when it gives up (sweep_granules, SpinBound, SweepWho).
 //
 // Results (codes, logits) are bit-identical to the per-block path and to the launches path at every context length.
+//
+// One row (generation without guidance, cfg_scale == 1): step_r1_kernel runs the same body at R = 1 - Hkv * NBK attention workgroups
+// (4 NBK with Zonos-v0.1's 4 kv heads), one communication wave; contexts up to 6144 keys as well (step_body, at the end of this file).
 #pragma once
 #include "zn_chain_kernel.h"
 #include "zn_step_sched.h"
@@ -204,10 +207,11 @@ ZN_DEVINL void kb_combine_chunk(__amdgpu_buffer_rsrc_t rs_part, int voff, int lo
   });
 }
 
-template <int NBV>          // blocks this instantiation's launches can be asked to cover (<= ZN_SK_KB_MAXNB): the unroll bound of the combine
+// NBV: blocks this instantiation's launches can be asked to cover (<= ZN_SK_KB_MAXNB): the unroll bound of the combine.  R: activation rows.
+template <int NBV, int R>
 ZN_DEVINL void step_attention_kb_role(const ChainArgs& a, StepKbLds& S, const unsigned tag0, const int c, const int wave, const int lane_in) {
   static_assert(NBV >= 1 && NBV <= ZN_SK_KB_MAXNB, "blocks covered");
-  constexpr int HD = 128, G = 4, NW = 8, KST = HD / 32, TPW = 4, R = 2, MAXNB = ZN_SK_KB_MAXNB, PSZ = ZN_SK_KB_PSZ;
+  constexpr int HD = 128, G = 4, NW = 8, KST = HD / 32, TPW = 4, MAXNB = ZN_SK_KB_MAXNB, PSZ = ZN_SK_KB_PSZ;
   typedef __attribute__((ext_vector_type(4))) float f32x4_t;
   const int npairs = a.n_heads_kv * R;
   const int pair = c % npairs, jb = c / npairs, kvh = pair % a.n_heads_kv, ar = pair / a.n_heads_kv;
@@ -442,16 +446,16 @@ ZN_DEVINL void step_attention_kb_role(const ChainArgs& a, StepKbLds& S, const un
 // ------------------------------------------------------------------------------------------------ the launch
 // T_* = tiles per compute wave per op (upper bounds: the matrices do not divide evenly over 224 workgroups; a wave skips the tiles
 // its workgroup does not have).  d_model = 512 * NCH, d_ff = 4 * d_model (host-checked, as are the bounds).
-// NBV: key blocks a launch of this instantiation may be asked to cover (a.natt = 8 * blocks of the launch's context bound <= 8 * NBV).
-template <int NCH, int T_OUT, int T_FC1, int T_FC2, int T_IN, int NBV>
-__global__ __launch_bounds__(ZN_SK_THREADS) void step_kernel(ChainArgs a_in) {
-  // Integer arguments that the whole kernel keeps using are detached from the kernarg segment's wide scalar loads: read as parts of an
-  // s_load_dwordx8 they made the register allocator spill the 256-bit tuple, rematerialise it instead, and leave its 32-byte stack slot
-  // behind - a private segment without a single scratch instruction, which a persistent kernel must not have (tests/test_abi.py).
-  // (Pointers are left alone: an asm operand has no address space, and accesses through a laundered pointer become flat_ instructions.)
-  ChainArgs a = a_in;
-  asm volatile("" : "+s"(a.max_len), "+s"(a.hd), "+s"(a.n_heads), "+s"(a.n_heads_kv), "+s"(a.rope_positions), "+s"(a.F), "+s"(a.nqkv), "+s"(a.natt), "+s"(a.dbg_pause));
-  constexpr int R = 2, D = NCH * 512, CW = ZN_SK_CW;
+// NBV: key blocks a launch of this instantiation may be asked to cover (a.natt = R * Hkv * blocks of the launch's context bound <= R * Hkv * NBV).
+// R: activation rows - 2 (batch 1 with guidance: step_kernel) or 1 (one utterance without guidance: step_r1_kernel).  A row's arithmetic
+// does not depend on R: every dot8 chain, wave_sum and epilogue of row r is the same instruction sequence on the same operands; at R = 1
+// the attention role has Hkv * NBK workgroups instead of 2 Hkv * NBK (more CUs stream), communication wave CW + 1 only runs the barriers,
+// and the epilogue lanes of row 1 stay idle.
+// `a` is the launch's copy of its arguments, detached in the kernel itself (ZN_SK_DETACH_ARGS).
+template <int R, int NCH, int T_OUT, int T_FC1, int T_FC2, int T_IN, int NBV>
+ZN_DEVINL void step_body(const ChainArgs& a) {
+  static_assert(R == 1 || R == 2, "one or two activation rows");
+  constexpr int D = NCH * 512, CW = ZN_SK_CW;
   constexpr int NS = 2 * T_OUT + T_FC1 + T_FC2 + T_IN;         // slots of a block (StepSched)
   constexpr int NOPS = 5;
   constexpr int MASK = ZN_CH_DEFER_MASK;
@@ -466,7 +470,7 @@ __global__ __launch_bounds__(ZN_SK_THREADS) void step_kernel(ChainArgs a_in) {
   extern __shared__ __attribute__((aligned(16))) unsigned char zn_dyn_lds[];
   const int natt = a.natt;
   if (c < natt) {
-    step_attention_kb_role<NBV>(a, *reinterpret_cast<StepKbLds*>(zn_dyn_lds), tag0, c, wave, lane);
+    step_attention_kb_role<NBV, R>(a, *reinterpret_cast<StepKbLds*>(zn_dyn_lds), tag0, c, wave, lane);
     return;
   }
   // ------------------------------------------------------------------------------------------------ streaming role
@@ -488,7 +492,7 @@ __global__ __launch_bounds__(ZN_SK_THREADS) void step_kernel(ChainArgs a_in) {
   // row pairs (requested at kernel entry) and contract them, communication wave 0 runs the epilogue and publishes q | k | v under tag0 - while
   // the compute waves park block 0's tiles as in every block.  The four waves meet through two counters in LDS, not through workgroup
   // barriers (the compute waves would have to join those).  Same arithmetic as gemv_kernel<PRO_LN, EPI_ROPE_KV> / the op-4 path of a block.
-  __shared__ int s_pf[2];                                                   // [0] rows normalised (2), [1] helper waves done (2)
+  __shared__ int s_pf[2];                                                   // [0] rows normalised (R), [1] helper waves done (2)
   constexpr int NPT = 5;                                                    // pre-block row pairs per helper wave (host-checked: <= 10 per workgroup)
   const bool pre = a.pre_W != nullptr;
   if (tid < 2) s_pf[tid] = 0;
@@ -560,7 +564,7 @@ __global__ __launch_bounds__(ZN_SK_THREADS) void step_kernel(ChainArgs a_in) {
       for (int t = 0; t < NPT; ++t) {
         const int j = hw + 2 * t;
         if (j < n_qkv) {
-          float accA[R] = {0.f, 0.f}, accB[R] = {0.f, 0.f};
+          float accA[R] = {}, accB[R] = {};
 #pragma unroll
           for (int c2 = 0; c2 < NCH; ++c2) {
 #pragma unroll
@@ -672,7 +676,7 @@ __global__ __launch_bounds__(ZN_SK_THREADS) void step_kernel(ChainArgs a_in) {
         bool ok; const bf16_t *pa, *pb; int ridx;
         tile(s, ok, pa, pb, ridx);
         if (!ok) return;
-        float accA[R] = {0.f, 0.f}, accB[R] = {0.f, 0.f};
+        float accA[R] = {}, accB[R] = {};
 #pragma unroll
         for (int c2 = 0; c2 < NCH; ++c2) {
 #pragma unroll
@@ -766,15 +770,24 @@ __global__ __launch_bounds__(ZN_SK_THREADS) void step_kernel(ChainArgs a_in) {
   // -------------------------------------------------------------------------------------- communication waves
   // Wave CW + r gathers (sweeps), normalises and stages row r of every hand-off; wave CW also runs the row-pair epilogues.
   const int myr = wave - CW;
+  if constexpr (R == 1) {
+    if (myr >= R) {                                          // one row: wave CW + 1 has no row and only keeps the workgroup's barrier count
+#pragma unroll 1
+      for (int li = 0; li < a.n_layer; ++li)
+#pragma unroll
+        for (int b = 0; b < NBAR; ++b) __syncthreads();
+      return;
+    }
+  }
   const bool epi = myr == 0;
   u32x4 g[NCH];
-  const int ij = lane >> 1, ir = lane & 1;
-  const bool it_out = epi && ij < n_out;
+  const int ij = lane >> 1, ir = lane & 1;                   // epilogue lane = (unit, row); at R = 1 the odd lanes idle
+  const bool it_out = epi && ij < n_out && ir < R;
   const int u_out = s_out + (it_out ? ij : 0);
   unsigned resid = 0;
   if (it_out) resid = *(const unsigned*)(a.xin + (size_t)ir * D + 2 * u_out);
   const int nq = a.n_heads * a.hd, nk = a.n_heads_kv * a.hd;
-  const bool it_qkv = epi && ij < n_qkv;
+  const bool it_qkv = epi && ij < n_qkv && ir < R;
   const int u_qkv = s_qkv + (it_qkv ? ij : 0);
   int pos = 0; float cs = 1.f, sn = 0.f;
   if (it_qkv) {
@@ -878,7 +891,7 @@ __global__ __launch_bounds__(ZN_SK_THREADS) void step_kernel(ChainArgs a_in) {
         }
       } else {
         if (last) {                                        // EPI_F32 (gemv_epilogue): bf16-valued fp32 logits
-          if (epi && ij < n_hd) {
+          if (epi && ij < n_hd && ir < R) {
             const int u = s_hd + ij;
             a.heads_out[(size_t)irq * a.heads_rows + 2 * u] = bfround(s_res[par][ij][0][ir]);
             if (2 * u + 1 < a.heads_rows) a.heads_out[(size_t)irq * a.heads_rows + 2 * u + 1] = bfround(s_res[par][ij][1][ir]);
@@ -928,4 +941,26 @@ __global__ __launch_bounds__(ZN_SK_THREADS) void step_kernel(ChainArgs a_in) {
   }
   pace.report(a.diag, lane);
   if (epi && sc == 0 && lane == 0) st_sc1_u32(a.epoch, tag0 + 1u + (unsigned)a.n_layer);   // every workgroup read the epoch before its first publish, which this one has seen
+}
+
+// Integer arguments that the whole kernel keeps using are detached from the kernarg segment's wide scalar loads: read as parts of an
+// s_load_dwordx8 they made the register allocator spill the 256-bit tuple, rematerialise it instead, and leave its 32-byte stack slot
+// behind - a private segment without a single scratch instruction, which a persistent kernel must not have (tests/test_abi.py).
+// (Pointers are left alone: an asm operand has no address space, and accesses through a laundered pointer become flat_ instructions.)
+// Done in the kernel, not in step_body: through a reference the kernarg loads are scheduled differently.
+#define ZN_SK_DETACH_ARGS(a, a_in) \
+  ChainArgs a = a_in;                \
+  asm volatile("" : "+s"(a.max_len), "+s"(a.hd), "+s"(a.n_heads), "+s"(a.n_heads_kv), "+s"(a.rope_positions), "+s"(a.F), "+s"(a.nqkv), "+s"(a.natt), "+s"(a.dbg_pause))
+
+template <int NCH, int T_OUT, int T_FC1, int T_FC2, int T_IN, int NBV>
+__global__ __launch_bounds__(ZN_SK_THREADS) void step_kernel(ChainArgs a_in) {
+  ZN_SK_DETACH_ARGS(a, a_in);
+  step_body<2, NCH, T_OUT, T_FC1, T_FC2, T_IN, NBV>(a);
+}
+
+// One row (an utterance generated without guidance, cfg_scale == 1): the same body, instantiated at R = 1 (zn_api.hip launch_stack).
+template <int NCH, int T_OUT, int T_FC1, int T_FC2, int T_IN, int NBV>
+__global__ __launch_bounds__(ZN_SK_THREADS) void step_r1_kernel(ChainArgs a_in) {
+  ZN_SK_DETACH_ARGS(a, a_in);
+  step_body<1, NCH, T_OUT, T_FC1, T_FC2, T_IN, NBV>(a);
 }

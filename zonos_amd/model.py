@@ -198,7 +198,8 @@ class Zonos(nn.Module):
 
     @torch.inference_mode()
     def prepare_conditioning(self, cond_dict: dict, uncond_dict: dict | None = None, use_cache: bool = False, cfg_scale: float = 1.0) -> torch.Tensor:
-        """model.py:237-265 -> conditioning_cache.py:139-193: [2B or B, L_c, d] bf16 ([cond ‖ uncond] when cfg_scale != 1)."""
+        """model.py:237-265 -> conditioning_cache.py:139-193: [2B or B, L_c, d] bf16 ([cond ‖ uncond] when cfg_scale != 1; the B
+        conditional rows at the default cfg_scale=1.0, which generate(cfg_scale=1.0) takes)."""
         return prepare_conditioning_with_cache(self.prefix_conditioner, cond_dict=cond_dict, uncond_dict=uncond_dict, use_cache=use_cache,
                                                cfg_scale=cfg_scale, cache=self._conditioning_cache if use_cache else None)
 
@@ -218,19 +219,29 @@ class Zonos(nn.Module):
                  cfg_scale: float = 2.0, batch_size: int = 1, sampling_params: dict = dict(min_p=0.1),
                  disable_torch_compile: bool = False, callback: Callable[[torch.Tensor, int, int], bool] | None = None,
                  seed: int | None = None, _trace: dict | None = None):
-        """zonos/model.py:354-548.  prefix_conditioning bf16 [2B, L_c, d] = [cond ‖ uncond]; returns int64
-        [B, 9, T_out] with values in [0, 1023].  Batch semantics for B > 1 (the reference crashes there,
-        SURVEY.md §0.6): B independent utterances, rows [cond_0..cond_{B-1}, uncond_0..uncond_{B-1}].
-        `seed` seeds the device Gumbel-max stream (default: drawn from torch's generator)."""
-        assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
+        """zonos/model.py:354-548.  prefix_conditioning bf16 [2B, L_c, d] = [cond ‖ uncond] with guidance, or the B conditional
+        rows [B, L_c, d] when cfg_scale == 1 (what `prepare_conditioning` returns at its default cfg_scale=1.0: no unconditional
+        half, no CFG mix, half the rows per utterance); returns int64 [B, 9, T_out] with values in [0, 1023].  Batch semantics
+        for B > 1 (the reference crashes there): B independent utterances, rows [cond_0..cond_{B-1},
+        uncond_0..uncond_{B-1}] (or [cond_0..cond_{B-1}] without guidance).  `seed` seeds the device Gumbel-max stream (default:
+        drawn from torch's generator)."""
+        B = batch_size
+        n = prefix_conditioning.shape[0]
+        if cfg_scale == 1:
+            # [cond ‖ uncond] rows without guidance: the reference's prepare_conditioning would have returned B rows (conditioning_cache.py:172)
+            assert n != 2 * B, f"cfg_scale=1 takes the batch_size={B} conditional rows only, got {n} rows ([cond ‖ uncond] is for cfg_scale != 1)"
+            if n != B:
+                raise ValueError(f"prefix_conditioning must have batch_size={B} rows when cfg_scale == 1, got {n}")
+        elif n != 2 * B:
+            raise ValueError(f"prefix_conditioning must have 2*batch_size={2 * B} rows, got {n}")
         dev = self.device
         if dev.type != "cuda":
             raise _lib.ZonosHipError("zonos_amd runs on MI355X only: move the model to a cuda device (no CPU fallback)")
-        B = batch_size
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        # an engine's handle holds this generation's state: a third concurrent generate() call on one model queues here
-        eng = self._acquire_engine(B)
+        # an engine's handle holds this generation's state: a third concurrent generate() call on one model queues here.  Engines are
+        # sized by rows (engine(b) holds 2 b): one unguided utterance runs on engine(1), like a guided one
+        eng = self._acquire_engine((n + 1) // 2)
         try:
             return self._generate_on(eng, dev, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, B, sampling_params, callback, seed, _trace)
         finally:
@@ -262,13 +273,12 @@ class Zonos(nn.Module):
                          _trace):
         dev = self.device
         B, nq = batch_size, self.config.codebook_dimension
-        if prefix_conditioning.shape[0] != 2 * B:
-            raise ValueError(f"prefix_conditioning must have 2*batch_size={2 * B} rows, got {prefix_conditioning.shape[0]}")
+        R = prefix_conditioning.shape[0]                          # 2B with guidance, B when cfg_scale == 1 (checked by generate)
         P = 0 if audio_prefix_codes is None else audio_prefix_codes.shape[2]
         L_c = prefix_conditioning.shape[1]
         audio_len = P + max_new_tokens
         seq_len = L_c + audio_len + nq
-        ip = self.setup_cache(batch_size=2 * B, max_seqlen=seq_len)
+        ip = self.setup_cache(batch_size=R, max_seqlen=seq_len)
         codes = torch.full((B, nq, audio_len), -1, dtype=torch.int32, device=dev)
         if audio_prefix_codes is not None:
             codes[..., :P] = audio_prefix_codes.to(device=dev, dtype=torch.int32)
@@ -300,9 +310,11 @@ class Zonos(nn.Module):
     def _decode_loop(self, eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st) -> int:
         """Prefill, first frame and the hot loop (model.py:421-509); returns the final column offset."""
         dev = self.device
-        # prefill (generation_utils.py:236-244): [cond ‖ uncond] conditioning + embed(delayed[..., :P+1]) for both halves
+        # prefill (generation_utils.py:236-244): [cond ‖ uncond] conditioning + embed(delayed[..., :P+1]) for both halves; without
+        # guidance the B conditional rows and the embedding once (generation_utils.py:237)
         emb = self.embed_codes(delayed[..., :offset], _eng=eng)
-        hidden = torch.cat([prefix_conditioning.to(device=dev, dtype=torch.bfloat16), emb.repeat(2, 1, 1)], dim=1).contiguous()
+        reps = prefix_conditioning.shape[0] // B
+        hidden = torch.cat([prefix_conditioning.to(device=dev, dtype=torch.bfloat16), emb.repeat(reps, 1, 1)], dim=1).contiguous()
         S = hidden.shape[1]
         eng.call("zn_prefill", hidden.data_ptr(), S, st)
         eng.call("zn_sample_first", st)
