@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define ZN_ABI_VERSION 6
+#define ZN_ABI_VERSION 7
 
 enum zn_status {
   ZN_OK = 0,
@@ -310,6 +310,17 @@ int zn_dac_destroy(zn_dac d);
 const char* zn_dac_last_error(zn_dac d);
 /* DACAutoencoder.decode: codes int32 [B, n_codebooks, T] -> wav fp32 [B, 1, hop*T]. */
 int zn_dac_decode(zn_dac d, const int32_t* codes_dev, int32_t batch, int32_t T, float* wav_dev, zn_stream stream);
+/* ABI 7 - span decode (streaming).  A window of code frames [c0, c0 + n) of a longer sequence; at_end != 0 says that c0 + n is the
+ * sequence's true end.  zn_dac_span (host only, no handle, no device) gives the largest sample range [s0, s1) whose receptive field
+ * lies inside the window: frame 0 is a true left edge (the decoder's zero padding applies there), c0 + n a right edge only when
+ * at_end.  s0 == s1 when the window holds no complete sample.  The receptive field follows from cfg->ratios (7-tap residual convs with
+ * dilations 1/3/9, ConvTranspose1d k = 2s pad ceil(s/2), the 7-tap convs at both ends). */
+int zn_dac_span(const zn_dac_config* cfg, int32_t c0, int32_t n, int32_t at_end, int64_t* s0, int64_t* s1);
+/* codes int32 [B, n_codebooks, n] = frames [c0, c0 + n) -> wav fp32 [B, s1 - s0]: samples [s0, s1) of zn_dac_span, bit-identical to the
+ * same samples of a whole-sequence zn_dac_decode on the three-term path.  No state is kept between calls.  ZN_ERR_UNSUPPORTED on a
+ * handle built with ZONOS_DAC_CONV=fp32; ZN_ERR_ARG when the range is empty. */
+int zn_dac_decode_span(zn_dac d, const int32_t* codes_dev, int32_t batch, int32_t c0, int32_t n, int32_t at_end, float* wav_dev,
+                       zn_stream stream);
 /* DACAutoencoder.encode (zonos/autoencoder.py:103-117 -> DacModel.encode): wav fp32 [B, T] at the codec rate, T a
  * positive multiple of the hop (preprocess pads) -> codes int32 [B, n_codebooks, T / hop].  Needs the encoder.* and
  * quantizer.quantizers.{i}.in_proj tensors at zn_dac_create. */

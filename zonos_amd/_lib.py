@@ -12,7 +12,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZONOS_HIP_LIB") or os.path.join(_HERE, "libzonos_hip.so")   # the override selects an experimental build (A/B runs)
 
-ZN_ABI_VERSION = 6
+ZN_ABI_VERSION = 7
 
 
 class ZonosHipError(RuntimeError):
@@ -103,6 +103,8 @@ SIGNATURES = {
     "zn_dac_last_error": (C.c_char_p, [C.c_void_p]),
     "zn_dac_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "zn_dac_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "zn_dac_span": (C.c_int, [C.POINTER(zn_dac_config), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "zn_dac_decode_span": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "zn_spk_create": (C.c_int, [C.POINTER(zn_dac_tensor), C.c_int32, C.POINTER(C.c_void_p)]),
     "zn_spk_destroy": (C.c_int, [C.c_void_p]),
     "zn_spk_last_error": (C.c_char_p, [C.c_void_p]),

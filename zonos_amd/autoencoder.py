@@ -105,12 +105,7 @@ class DACAutoencoder:
         if self.device.type != "cuda":
             raise _lib.ZonosHipError("zonos_amd runs on MI355X only (no CPU fallback)")
         lib = _lib.load()
-        c = self.cfg
-        zc = _lib.zn_dac_config(n_codebooks=c["n_codebooks"], codebook_size=c["codebook_size"], codebook_dim=c["codebook_dim"],
-                                hidden_size=c["hidden_size"], decoder_hidden_size=c["decoder_hidden_size"], n_ratios=len(c["upsampling_ratios"]),
-                                encoder_hidden_size=c["encoder_hidden_size"] if "encoder.conv1.weight" in self._weights else 0)
-        for i, r in enumerate(c["upsampling_ratios"]):
-            zc.ratios[i] = r
+        zc = self._config(encoder="encoder.conv1.weight" in self._weights)
         names = sorted(self._weights)
         arr = (_lib.zn_dac_tensor * len(names))()
         for i, k in enumerate(names):
@@ -120,6 +115,29 @@ class DACAutoencoder:
             _lib.check_dac(lib.zn_dac_create(C.byref(zc), arr, len(names), C.byref(h)), None, "zn_dac_create")
         self._h = h
         return h
+
+    def _config(self, encoder: bool = False) -> _lib.zn_dac_config:
+        c = self.cfg
+        zc = _lib.zn_dac_config(n_codebooks=c["n_codebooks"], codebook_size=c["codebook_size"], codebook_dim=c["codebook_dim"],
+                                hidden_size=c["hidden_size"], decoder_hidden_size=c["decoder_hidden_size"], n_ratios=len(c["upsampling_ratios"]),
+                                encoder_hidden_size=c["encoder_hidden_size"] if encoder else 0)
+        for i, r in enumerate(c["upsampling_ratios"]):
+            zc.ratios[i] = r
+        return zc
+
+    def span(self, c0: int, n: int, at_end: bool) -> tuple[int, int]:
+        """zn_dac_span: the samples [s0, s1) that code frames [c0, c0 + n) of a longer sequence determine (`at_end`: c0 + n ends it).
+        Host arithmetic only."""
+        s0, s1 = C.c_int64(), C.c_int64()
+        zc = self._config()
+        _lib.check_dac(_lib.load().zn_dac_span(C.byref(zc), int(c0), int(n), int(bool(at_end)), C.byref(s0), C.byref(s1)), None, "zn_dac_span")
+        return s0.value, s1.value
+
+    def stream(self, stream: "torch.cuda.Stream | None" = None) -> "DACStream":
+        """Incremental decode: `push(codes [B, 9, k]) -> wav [B, 1, m]` returns the samples the frames pushed so far determine, `flush()`
+        the rest.  The concatenated outputs equal `decode(all codes)` bit for bit (below ~126 s, where decode() runs the three-term
+        kernels).  `stream`: the torch stream every launch goes to (default: the current stream of each call)."""
+        return DACStream(self, stream)
 
     def preprocess(self, wav: torch.Tensor, sr: int) -> torch.Tensor:
         """autoencoder.py:80-101: resample to 44.1 kHz, zero-pad on the LEFT to a multiple of 512 samples."""
@@ -164,6 +182,76 @@ class DACAutoencoder:
         """autoencoder.py:142-170: clamp(wav * 32767, +-32767) -> int16 [512*T, 1] (batch 1)."""
         wav = self.decode(codes).squeeze(1)
         return torch.clamp(wav * 32767.0, -32767.0, 32767.0).to(torch.int16).squeeze(0).unsqueeze(1)
+
+
+class DACStream:
+    """Rolling decode over `zn_dac_decode_span`: keeps on the device only the code frames that samples not yet returned still read
+    (the decoder's receptive field, ~10 frames on each side at the 44.1 kHz ratios), and no activations: every call decodes its window
+    from the codes, so an abandoned stream holds nothing but that window."""
+
+    def __init__(self, ae: DACAutoencoder, stream=None):
+        self.ae, self._stream = ae, stream
+        self._win: torch.Tensor | None = None     # int32 [B, 9, n]: frames [c0, c0 + n)
+        self._c0 = 0
+        self._emitted = 0                         # samples returned so far
+        self._closed = False
+        # frames [c, ...) determine the samples from c * hop + lead on (c >= 1; the receptive field is shift-invariant by one hop per frame)
+        self._lead = ae.span(1, 1 << 12, True)[0] - ae.hop
+
+    def _torch_stream(self):
+        return self._stream if self._stream is not None else torch.cuda.current_stream(self.ae.device)
+
+    @torch.inference_mode()
+    def push(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes [B, 9, k] (the next k frames) -> float32 [B, 1, m]: the samples that became final (m may be 0)."""
+        if self._closed:
+            raise RuntimeError("DACStream.push() after flush()")
+        B, nq, k = codes.shape
+        if nq != self.ae.num_codebooks:
+            raise ValueError(f"expected {self.ae.num_codebooks} codebooks, got {nq}")
+        if self._win is not None and B != self._win.shape[0]:
+            raise ValueError(f"batch size changed from {self._win.shape[0]} to {B}")
+        with torch.cuda.device(self.ae.device), torch.cuda.stream(self._torch_stream()):
+            c32 = codes.to(device=self.ae.device, dtype=torch.int32)
+            self._win = c32.contiguous() if self._win is None else torch.cat([self._win, c32], dim=2)
+            return self._emit(False)
+
+    @torch.inference_mode()
+    def flush(self) -> torch.Tensor:
+        """The samples that the end of the sequence completes: float32 [B, 1, m']."""
+        if self._closed:
+            raise RuntimeError("DACStream.flush() called twice")
+        self._closed = True
+        if self._win is None:
+            return torch.empty(0, 1, 0, dtype=torch.float32, device=self.ae.device)
+        with torch.cuda.device(self.ae.device), torch.cuda.stream(self._torch_stream()):
+            out = self._emit(True)
+        self._win = None
+        return out
+
+    def _emit(self, at_end: bool) -> torch.Tensor:
+        ae, win = self.ae, self._win
+        B, n = win.shape[0], win.shape[2]
+        if n == 0:
+            return torch.empty(B, 1, 0, dtype=torch.float32, device=ae.device)
+        s0, s1 = ae.span(self._c0, n, at_end)
+        if s1 <= self._emitted:
+            return torch.empty(B, 1, 0, dtype=torch.float32, device=ae.device)
+        if s0 > self._emitted:
+            raise RuntimeError(f"DACStream: window from frame {self._c0} starts at sample {s0}, past {self._emitted}")
+        h = ae._handle()
+        wav = torch.empty(B, 1, s1 - s0, dtype=torch.float32, device=ae.device)
+        with ae._lock:
+            _lib.check_dac(_lib.load().zn_dac_decode_span(h, win.data_ptr(), B, self._c0, n, int(at_end), wav.data_ptr(),
+                                                          torch.cuda.current_stream(ae.device).cuda_stream), h, "zn_dac_decode_span")
+        out = wav[..., self._emitted - s0:]
+        self._emitted = s1
+        # drop the frames that no sample from s1 on reads
+        c = (s1 - self._lead) // ae.hop if s1 >= ae.hop + self._lead else 0
+        if c > self._c0:
+            self._win = win[..., c - self._c0:].contiguous()
+            self._c0 = c
+        return out
 
 
 _GLOBAL_DAC_AUTOENCODER = None

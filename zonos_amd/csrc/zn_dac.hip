@@ -75,19 +75,21 @@ __global__ void dac_wconvt_kernel(const float* w, float* o, int Cin, int Cout, i
 #define DAC_FIN_T 128
 #define DAC_FIN_MAXP 16
 __global__ __launch_bounds__(256) void dac_final_kernel(const float* in, const float* alpha, const float* w /*[1][C][7]*/, const float* bias,
-                                                        float* out, int T, int C) {
+                                                        float* out, int T, int C, int Tin, int ioff) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* s_x = smem;                         // [DAC_FIN_T + 6][C + 1]
   float* s_w = smem + (DAC_FIN_T + 6) * (C + 1);   // [7][C]
+  // output time t reads input rows t + ioff - 3 .. t + ioff + 3 of the [Tin]-row input; rows outside [0, Tin) are the zero padding (a whole
+  // clip: Tin = T, ioff = 0; a span: the window's buffer, which reaches past its ends only where the sequence ends)
   const int t0 = blockIdx.x * DAC_FIN_T, b = blockIdx.y, tid = threadIdx.x;
-  const float* inb = in + (size_t)b * T * C;
+  const float* inb = in + (size_t)b * Tin * C;
   const int c4n = C / 4, npiece = (DAC_FIN_T + 6) * c4n;
   f32x4 r[DAC_FIN_MAXP];
 #pragma unroll
   for (int j = 0; j < DAC_FIN_MAXP; ++j) {
     const int i = tid + j * 256, row = i / c4n, c4 = i - row * c4n;
-    int t = t0 - 3 + row;
-    t = t < 0 ? 0 : (t >= T ? T - 1 : t);
+    int t = t0 + ioff - 3 + row;
+    t = t < 0 ? 0 : (t >= Tin ? Tin - 1 : t);
     if (i < npiece) r[j] = *(const f32x4*)(inb + (size_t)t * C + c4 * 4);
   }
   for (int i = tid; i < 7 * C; i += 256) { const int k = i / C, c = i - k * C; s_w[i] = w[(size_t)c * 7 + k]; }
@@ -98,13 +100,13 @@ __global__ __launch_bounds__(256) void dac_final_kernel(const float* in, const f
   for (int j = 0; j < DAC_FIN_MAXP; ++j) {
     const int i = tid + j * 256, row = i / c4n, c4 = i - row * c4n;
     if (i < npiece) {
-      const int t = t0 - 3 + row;
+      const int t = t0 + ioff - 3 + row;
       const float* al = s_al + c4 * 4;       // (the LDS offsets of s_w / s_al are not 16-byte aligned: scalar reads)
       const float x[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
       float* d = s_x + row * (C + 1) + c4 * 4;
 #pragma unroll
-      for (int e = 0; e < 4; ++e)            // Snake (modeling_dac.py:98) with the decoder kernels' sin^2 (zn_conv3_kernels.h); zero padding outside [0, T)
-        d[e] = (t >= 0 && t < T) ? x[e] + al[C + e] * c3_sin2(al[e] * x[e]) : 0.f;
+      for (int e = 0; e < 4; ++e)            // Snake (modeling_dac.py:98) with the decoder kernels' sin^2 (zn_conv3_kernels.h); zero padding outside [0, Tin)
+        d[e] = (t >= 0 && t < Tin) ? x[e] + al[C + e] * c3_sin2(al[e] * x[e]) : 0.f;
     }
   }
   __syncthreads();
@@ -504,7 +506,7 @@ extern "C" int zn_dac_decode(zn_dac d, const int32_t* codes, int32_t B, int32_t 
       }
     }
     const size_t lds = (size_t)((DAC_FIN_T + 6) * (d->fin_C + 1) + 9 * d->fin_C) * sizeof(float);
-    hipLaunchKernelGGL(dac_final_kernel, dim3((t + DAC_FIN_T - 1) / DAC_FIN_T, B), dim3(256), lds, s, x, d->fin_alpha, d->fin_w, d->fin_b, wav, t, d->fin_C);
+    hipLaunchKernelGGL(dac_final_kernel, dim3((t + DAC_FIN_T - 1) / DAC_FIN_T, B), dim3(256), lds, s, x, d->fin_alpha, d->fin_w, d->fin_b, wav, t, d->fin_C, t, 0);
     DHIP(d, hipGetLastError());
     return ZN_OK;
   }
@@ -524,7 +526,142 @@ extern "C" int zn_dac_decode(zn_dac d, const int32_t* codes, int32_t B, int32_t 
     }
   }
   const size_t lds = (size_t)((DAC_FIN_T + 6) * (d->fin_C + 1) + 9 * d->fin_C) * sizeof(float);
-  hipLaunchKernelGGL(dac_final_kernel, dim3((t + DAC_FIN_T - 1) / DAC_FIN_T, B), dim3(256), lds, s, x, d->fin_alpha, d->fin_w, d->fin_b, wav, t, d->fin_C);
+  hipLaunchKernelGGL(dac_final_kernel, dim3((t + DAC_FIN_T - 1) / DAC_FIN_T, B), dim3(256), lds, s, x, d->fin_alpha, d->fin_w, d->fin_b, wav, t, d->fin_C, t, 0);
+  DHIP(d, hipGetLastError());
+  return ZN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ span decode (streaming)
+// Rows each layer of a span needs, found backwards from the output samples [a, b).  A residual unit's 7-tap conv (dilation d) widens a range by
+// 3 d on each side (its 1-tap conv2 and the skip do not); a conv_t1 output row t reads input rows m - 1 and m, m = floor((t + pad) / s)
+// (zn_conv3_kernels.h's phase split, pad = ceil(s / 2)); the 7-tap convs at both ends widen by 3.  Every range is clipped to [0, rows of the
+// layer): outside it the decoder's zero padding applies.  `frames` < 0: no right edge (the window does not end the sequence).
+struct DacSpan {
+  int64_t lat[2];            // latent frames read by decoder.conv1
+  int64_t c1[2];             // decoder.conv1 output rows
+  int64_t xt[8][2];          // block bi: conv_t1 output rows (the block's window: its residual stream and activations live there)
+  int64_t un[8][3][2];       // block bi, residual unit u: output rows
+};
+static int64_t floordiv(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+static void dac_span_back(const zn_dac_config& c, int64_t a, int64_t b, int64_t frames, DacSpan& P) {
+  int64_t rate = 1;
+  for (int i = 0; i < c.n_ratios; ++i) rate *= c.ratios[i];
+  auto clip = [&](int64_t r) { a = std::max<int64_t>(a, 0); if (frames >= 0) b = std::min<int64_t>(b, frames * r); };
+  const int dils[3] = {1, 3, 9};
+  a -= 3; b += 3; clip(rate);                                           // decoder.conv2 (k = 7) reads the last unit's output
+  for (int bi = c.n_ratios - 1; bi >= 0; --bi) {
+    for (int u = 2; u >= 0; --u) {
+      P.un[bi][u][0] = a; P.un[bi][u][1] = b;
+      a -= 3 * dils[u]; b += 3 * dils[u]; clip(rate);                   // res_unit conv1 (k = 7, dilation d)
+    }
+    P.xt[bi][0] = a; P.xt[bi][1] = b;
+    const int64_t s = c.ratios[bi], pad = (s + 1) / 2;
+    rate /= s;
+    a = floordiv(a + pad, s) - 1; b = floordiv(b - 1 + pad, s) + 1; clip(rate);
+  }
+  P.c1[0] = a; P.c1[1] = b;
+  a -= 3; b += 3; clip(1);                                              // decoder.conv1 (k = 7)
+  P.lat[0] = a; P.lat[1] = b;
+}
+
+extern "C" int zn_dac_span(const zn_dac_config* cfg, int32_t c0, int32_t n, int32_t at_end, int64_t* s0, int64_t* s1) {
+  if (!cfg || !s0 || !s1 || c0 < 0 || n < 1 || cfg->n_ratios < 1 || cfg->n_ratios > 8) DFAIL((zn_dac) nullptr, ZN_ERR_ARG, "zn_dac_span: bad argument");
+  int64_t hop = 1;
+  for (int i = 0; i < cfg->n_ratios; ++i) {
+    if (cfg->ratios[i] < 2 || cfg->ratios[i] % 2) DFAIL((zn_dac) nullptr, ZN_ERR_ARG, "zn_dac_span: ratio %d is not an even stride", cfg->ratios[i]);
+    hop *= cfg->ratios[i];
+  }
+  const int64_t end = (int64_t)c0 + n, total = end * hop;
+  DacSpan P;
+  // the first latent frame / one past the last that sample s reads, without a right edge: both non-decreasing in s
+  auto first = [&](int64_t s) { dac_span_back(*cfg, s, s + 1, -1, P); return P.lat[0]; };
+  auto last = [&](int64_t s) { dac_span_back(*cfg, s, s + 1, -1, P); return P.lat[1]; };
+  int64_t lo = 0, hi = total;
+  if (c0 > 0) {                                                         // smallest s that reads no frame before c0 (total if none)
+    while (lo < hi) { const int64_t m = lo + (hi - lo) / 2; if (first(m) >= c0) hi = m; else lo = m + 1; }
+  }
+  const int64_t a = lo;
+  int64_t b = total;
+  if (!at_end) {                                                        // one past the largest s that reads no frame at or past c0 + n
+    lo = 0; hi = total;
+    while (lo < hi) { const int64_t m = lo + (hi - lo + 1) / 2; if (last(m - 1) <= end) lo = m; else hi = m - 1; }
+    b = lo;
+  }
+  *s0 = std::min(a, b); *s1 = b;
+  return ZN_OK;
+}
+
+// Three-term layer over output rows [u0, u1) between windowed buffers: the input buffer's row j holds the layer input's row I0 + j (LI rows
+// per batch element), the output buffer's row j holds output row O0 + j (LO rows).  Buffer rows outside [0, LI) read as zeros (the kernel's
+// buffer-resource range check), which the span plan only lets happen where the sequence really ends.
+static void launch_conv3_win(const ConvLayer& L, const float* in, int64_t I0, int LI, const float* skip, float* out32, float* out_act,
+                             const float* alpha_next, int64_t O0, int LO, int64_t u0, int64_t u1, int B, bool transpose, hipStream_t s) {
+  Conv3Args a{};
+  a.in = in; a.Tin = LI; a.Cin = L.Cin; a.w = L.w3; a.bias = L.bias; a.alpha = alpha_next; a.skip = skip; a.out32 = out32; a.out_act = out_act;
+  a.Tout = LO; a.Cout = L.Cout; a.CoutPad = zn_conv3_pad(L.Cout);
+  if (!transpose) {                                   // GEMM row m: output row u0 + m
+    a.M = (int)(u1 - u0); a.taps = L.K; a.off0 = -((L.K - 1) * L.dil) / 2 + (int)(u0 - I0); a.offstep = L.dil; a.ostride = 1; a.ooff = (int)(u0 - O0);
+    a.phases = 1;
+  } else {                                            // GEMM row m: input row g0 + m, output rows (g0 + m) s - pad + p
+    const int64_t st = L.stride, padT = (st + 1) / 2, g0 = floordiv(u0 + padT, st), g1 = floordiv(u1 - 1 + padT, st);
+    a.M = (int)(g1 - g0 + 1); a.taps = 2; a.off0 = (int)(g0 - I0); a.offstep = -1; a.ostride = (int)st; a.ooff = (int)(g0 * st - padT - O0);
+    a.phases = (int)st;
+  }
+  zn_conv3_launch(a, B, s);
+}
+
+extern "C" int zn_dac_decode_span(zn_dac d, const int32_t* codes, int32_t B, int32_t c0, int32_t n, int32_t at_end, float* wav, zn_stream stream) {
+  if (!d) return ZN_ERR_ARG;
+  if (!d->split3)
+    DFAIL(d, ZN_ERR_UNSUPPORTED, "zn_dac_decode_span: the handle was created with ZONOS_DAC_CONV=fp32; span decode runs on the three-term kernels only");
+  if (!codes || !wav || B < 1 || c0 < 0 || n < 1) DFAIL(d, ZN_ERR_ARG, "zn_dac_decode_span: bad argument");
+  const zn_dac_config& c = d->cfg;
+  int64_t s0 = 0, s1 = 0;
+  if (zn_dac_span(&c, c0, n, at_end, &s0, &s1) != ZN_OK) DFAIL(d, ZN_ERR_ARG, "%s", g_dac_err.c_str());
+  if (s1 <= s0) DFAIL(d, ZN_ERR_ARG, "zn_dac_decode_span: frames [%d, %d) complete no sample (zn_dac_span)", c0, c0 + n);
+  DacSpan P;
+  dac_span_back(c, s0, s1, (int64_t)c0 + n, P);       // (with at_end == 0 the plan never reaches the window's end: clipping there is moot)
+  if (P.lat[0] < c0 || P.lat[1] > (int64_t)c0 + n) DFAIL(d, ZN_ERR_ARG, "zn_dac_decode_span: inconsistent plan");
+  hipStream_t s = (hipStream_t)stream;
+  auto len = [](const int64_t* r) { return r[1] - r[0]; };
+  size_t need = (size_t)n * c.hidden_size;
+  need = std::max(need, (size_t)len(P.c1) * c.decoder_hidden_size);
+  { int ch = c.decoder_hidden_size;
+    for (int i = 0; i < c.n_ratios; ++i) { ch /= 2; need = std::max(need, (size_t)len(P.xt[i]) * ch); } }
+  if (need * 4 >= 0x7fffffffull)                      // 32-bit buffer offsets of the three-term kernels (zn_dac_decode's limit)
+    DFAIL(d, ZN_ERR_UNSUPPORTED, "zn_dac_decode_span: a window of %d frames is too long for the three-term kernels", n);
+  need *= B;
+  if (need > d->buf_elems) {
+    DHIP(d, hipStreamSynchronize(s));
+    for (auto& p : d->buf) { if (p) (void)hipFree(p); p = nullptr; }
+    for (auto& p : d->buf) DHIP(d, hipMalloc(&p, need * sizeof(float)));
+    d->buf_elems = need;
+  }
+  float *x = d->buf[0], *p = d->buf[1], *q = d->buf[2];
+  hipLaunchKernelGGL(dac_codes_kernel, dim3(n, B), dim3(256), 0, s, codes, d->table, x, c.n_codebooks, n, c.hidden_size, c.codebook_size);
+  // as zn_dac_decode's three-term path, each layer over its rows of the plan.  x: the residual stream; p / q: activated inputs
+  int64_t I0 = c0; int LI = n;
+  launch_conv3_win(d->conv1, x, I0, LI, nullptr, nullptr, q, d->blocks[0].convt.alpha, P.c1[0], (int)len(P.c1), P.c1[0], P.c1[1], B, false, s);
+  std::swap(p, q);
+  I0 = P.c1[0]; LI = (int)len(P.c1);
+  for (int bi = 0; bi < c.n_ratios; ++bi) {
+    auto& Bk = d->blocks[bi];
+    const int64_t X0 = P.xt[bi][0]; const int Lx = (int)len(P.xt[bi]);
+    launch_conv3_win(Bk.convt, p, I0, LI, nullptr, x, q, Bk.c1[0].alpha, X0, Lx, P.xt[bi][0], P.xt[bi][1], B, true, s);
+    std::swap(p, q);
+    for (int u = 0; u < 3; ++u) {
+      const bool last_unit = u == 2, last_block = bi + 1 == c.n_ratios;
+      const float* an = !last_unit ? Bk.c1[u + 1].alpha : (!last_block ? d->blocks[bi + 1].convt.alpha : nullptr);
+      const int64_t* U = P.un[bi][u];
+      launch_conv3_win(Bk.c1[u], p, X0, Lx, nullptr, nullptr, q, Bk.c2[u].alpha, X0, Lx, U[0], U[1], B, false, s);
+      launch_conv3_win(Bk.c2[u], q, X0, Lx, x, x, (last_unit && last_block) ? nullptr : p, an, X0, Lx, U[0], U[1], B, false, s);
+    }
+    I0 = X0; LI = Lx;
+  }
+  const size_t lds = (size_t)((DAC_FIN_T + 6) * (d->fin_C + 1) + 9 * d->fin_C) * sizeof(float);
+  const int T = (int)(s1 - s0);
+  hipLaunchKernelGGL(dac_final_kernel, dim3((T + DAC_FIN_T - 1) / DAC_FIN_T, B), dim3(256), lds, s, x, d->fin_alpha, d->fin_w, d->fin_b, wav, T, d->fin_C,
+                     LI, (int)(s0 - I0));
   DHIP(d, hipGetLastError());
   return ZN_OK;
 }

@@ -12,7 +12,7 @@ import os
 import sys
 import threading
 import json
-from typing import Callable
+from typing import Callable, Iterator, NamedTuple
 
 import torch
 import torch.nn as nn
@@ -39,6 +39,50 @@ def _sampling_struct(params: dict, seed: int) -> _lib.zn_sampling:
     return _lib.zn_sampling(temperature=p["temperature"], top_p=p["top_p"], top_k=int(p["top_k"]), min_p=p["min_p"],
                             linear=p["linear"], conf=p["conf"], quad=p["quad"], repetition_penalty=p["repetition_penalty"],
                             repetition_penalty_window=int(p["repetition_penalty_window"]), seed=seed & (2 ** 64 - 1))
+
+
+class StreamChunk(NamedTuple):
+    """One step of `Zonos.stream`: the frames that became final (int64 [1, 9, k], as `generate()` returns them) and the samples they
+    completed (float32 [1, 1, m] on the model's device).  k or m may be 0, never both."""
+    codes: torch.Tensor
+    wav: torch.Tensor
+
+
+def map_codes(out: torch.Tensor) -> torch.Tensor:
+    """model.py:530-539: EOS / mask tokens to codes, clamped to the codebook."""
+    out = torch.where(out > 1024, 512, out)
+    out = torch.where(out == 1024, 0, out)
+    return torch.clamp(out, 0, 1023)
+
+
+def finalise_codes(out: torch.Tensor, offset: int, nq: int, eos_id: int) -> torch.Tensor:
+    """model.py:511-539 on the reverted codes [B, nq, audio_len] of a generation whose loop ended at column `offset`: the EOS boundary
+    search over the last min(50, valid_length // 4) frames, then the code mapping.  `generate()` and `stream()` both end here."""
+    valid_length = offset - nq
+    window = min(50, valid_length // 4)
+    for pos in range(max(0, valid_length - window), valid_length):   # model.py:516-528
+        if int((out[:, :, pos] == eos_id).sum()) >= nq // 2:
+            valid_length = pos
+            break
+    return map_codes(out[..., :valid_length])
+
+
+def release_limit(offset: int, nq: int, eos_frame: int | None) -> int:
+    """Frames [0, limit) that are final while the generation runs, once the steps up to column `offset` have run: a frame is complete
+    when its codebook nq-1 (column f + nq) is written, and every frame before the first one whose codebook 0 is EOS (`eos_frame`, None
+    while there is none) survives `finalise_codes` (codebooks 1.. cannot sample EOS before the stop; the EOS diagonal after it lands on
+    the stop frame itself).  What the end keeps beyond that, `finalise_codes` decides."""
+    limit = max(0, offset - nq + 1)
+    return limit if eos_frame is None else min(limit, eos_frame)
+
+
+def _drain(gen):
+    """Run a generation generator to its end and return its value."""
+    try:
+        while True:
+            next(gen)
+    except StopIteration as e:
+        return e.value
 
 
 class Zonos(nn.Module):
@@ -226,17 +270,8 @@ class Zonos(nn.Module):
         uncond_0..uncond_{B-1}] (or [cond_0..cond_{B-1}] without guidance).  `seed` seeds the device Gumbel-max stream (default:
         drawn from torch's generator)."""
         B = batch_size
-        n = prefix_conditioning.shape[0]
-        if cfg_scale == 1:
-            # [cond ‖ uncond] rows without guidance: the reference's prepare_conditioning would have returned B rows (conditioning_cache.py:172)
-            assert n != 2 * B, f"cfg_scale=1 takes the batch_size={B} conditional rows only, got {n} rows ([cond ‖ uncond] is for cfg_scale != 1)"
-            if n != B:
-                raise ValueError(f"prefix_conditioning must have batch_size={B} rows when cfg_scale == 1, got {n}")
-        elif n != 2 * B:
-            raise ValueError(f"prefix_conditioning must have 2*batch_size={2 * B} rows, got {n}")
+        n = self._check_rows(prefix_conditioning, cfg_scale, B)
         dev = self.device
-        if dev.type != "cuda":
-            raise _lib.ZonosHipError("zonos_amd runs on MI355X only: move the model to a cuda device (no CPU fallback)")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         # an engine's handle holds this generation's state: a third concurrent generate() call on one model queues here.  Engines are
@@ -247,6 +282,96 @@ class Zonos(nn.Module):
         finally:
             eng.generating = False
             eng.lock.release()
+
+    def _check_rows(self, prefix_conditioning, cfg_scale, B) -> int:
+        n = prefix_conditioning.shape[0]
+        if cfg_scale == 1:
+            # [cond ‖ uncond] rows without guidance: the reference's prepare_conditioning would have returned B rows (conditioning_cache.py:172)
+            assert n != 2 * B, f"cfg_scale=1 takes the batch_size={B} conditional rows only, got {n} rows ([cond ‖ uncond] is for cfg_scale != 1)"
+            if n != B:
+                raise ValueError(f"prefix_conditioning must have batch_size={B} rows when cfg_scale == 1, got {n}")
+        elif n != 2 * B:
+            raise ValueError(f"prefix_conditioning must have 2*batch_size={2 * B} rows, got {n}")
+        if self.device.type != "cuda":
+            raise _lib.ZonosHipError("zonos_amd runs on MI355X only: move the model to a cuda device (no CPU fallback)")
+        return n
+
+    def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor = None, max_new_tokens: int = 86 * 30,
+               cfg_scale: float = 2.0, sampling_params: dict = dict(min_p=0.1), seed: int | None = None, chunk_frames: int = 16,
+               batch_size: int = 1) -> Iterator[StreamChunk]:
+        """`generate()` + `autoencoder.decode()` as they happen: a generator of `StreamChunk(codes, wav)`.  Every `chunk_frames` decode steps
+        it yields the frames that have become final (`release_limit`) and the samples the DAC can decode from them (`DACAutoencoder.stream`);
+        the rest comes when the generation ends.  With the same arguments and seed, the concatenated codes equal `generate(...)` and the
+        concatenated wav `autoencoder.decode(generate(...))`, bit for bit.  Batch size 1 (guided, or cfg_scale=1).
+
+        The generation's engine and the device's persistent-kernel tenancy are held while the generator is alive; `close()`, leaving a for
+        loop early or garbage collection releases them.  Every launch (decode steps and DAC) goes to the stream current when stream() is
+        called.  A hand-off timeout raises: it is not repeated on the launches path, as the caller may already hold audio."""
+        if batch_size != 1:
+            raise ValueError(f"stream() generates one utterance at a time, got batch_size={batch_size}")
+        if int(chunk_frames) < 1:
+            raise ValueError(f"chunk_frames must be >= 1, got {chunk_frames}")
+        n = self._check_rows(prefix_conditioning, cfg_scale, 1)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        dev = self.device
+        return self._stream_gen(dev, torch.cuda.current_stream(dev), (n + 1) // 2, prefix_conditioning, audio_prefix_codes, max_new_tokens,
+                                cfg_scale, sampling_params, seed, int(chunk_frames))
+
+    def _stream_gen(self, dev, ts, rows, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, sampling_params, seed, chunk):
+        nq, eos = self.config.codebook_dimension, self.eos_token_id
+        eng = self._acquire_engine(rows)
+        gen, held = None, [True]
+
+        def release():
+            if not held[0]:
+                return
+            held[0] = False
+            try:
+                if gen is not None:
+                    with torch.cuda.device(dev), torch.cuda.stream(ts):
+                        gen.close()                        # a stream left early: its steps drain, zn_gen_end
+            finally:
+                eng.generating = False
+                eng.lock.release()
+        try:
+            # (each stretch between two yields runs with the generation's device and stream current, and leaves the caller's as it found them)
+            with torch.inference_mode(), torch.cuda.device(dev), torch.cuda.stream(ts):
+                dac = self.autoencoder.stream(ts)
+                gen = self._generation(eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, 1, sampling_params, None, seed,
+                                       None, ts, chunk)
+            released, scanned, eos_frame = 0, 0, None      # frames handed out; delayed columns of codebook 0 read; first EOS frame
+            while True:
+                with torch.inference_mode(), torch.cuda.device(dev), torch.cuda.stream(ts):
+                    try:
+                        delayed, offset = next(gen)
+                    except StopIteration as e:
+                        final = e.value                    # finalise_codes of the whole generation
+                        if final.shape[2] < released:
+                            raise _lib.ZonosHipError(f"stream(): {released} frames released, the generation kept {final.shape[2]}")
+                        codes = final[..., released:].to(dev)
+                        wav = torch.cat([dac.push(codes), dac.flush()], dim=2)
+                        chunk_out = StreamChunk(codes, wav) if codes.shape[2] or wav.shape[2] else None
+                        break
+                    if eos_frame is None and offset > scanned:
+                        col = delayed[0, 0, scanned + 1:offset + 1].cpu()       # codebook 0 of frames scanned .. offset - 1
+                        hit = (col == eos).nonzero()
+                        if len(hit):
+                            eos_frame = scanned + int(hit[0, 0])
+                        scanned = offset
+                    limit = release_limit(offset, nq, eos_frame)
+                    chunk_out = None
+                    if limit > released:
+                        codes = map_codes(revert_delay_pattern(delayed[..., released:limit + nq].cpu().to(torch.int64))).to(dev)
+                        released = limit
+                        chunk_out = StreamChunk(codes, dac.push(codes))
+                if chunk_out is not None:
+                    yield chunk_out
+            release()                                      # the generation has ended: the engine is free before the last chunk goes out
+            if chunk_out is not None:
+                yield chunk_out
+        finally:
+            release()
 
     def _generate_on(self, eng, dev, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, B, sampling_params, callback, seed, _trace):
         with torch.cuda.device(dev):
@@ -271,6 +396,13 @@ class Zonos(nn.Module):
 
     def _generate_locked(self, eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params, callback, seed,
                          _trace):
+        return _drain(self._generation(eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params, callback,
+                                       seed, _trace, torch.cuda.current_stream(self.device), None)).to(self.device)
+
+    def _generation(self, eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params, callback, seed,
+                    _trace, ts, chunk):
+        """One generation on `eng` (its lock held by the caller), with every launch on torch stream `ts`.  A generator: with `chunk` it yields
+        (delayed codes, last column written) every `chunk` decode steps (Zonos.stream), and it returns the final codes on the host."""
         dev = self.device
         B, nq = batch_size, self.config.codebook_dimension
         R = prefix_conditioning.shape[0]                          # 2B with guidance, B when cfg_scale == 1 (checked by generate)
@@ -285,30 +417,23 @@ class Zonos(nn.Module):
         delayed = apply_delay_pattern(codes, self.masked_token_id).contiguous()       # [B, nq, audio_len + nq]
         t_total = delayed.shape[2]
         offset = P + 1
-        st = eng.stream()
+        st = ts.cuda_stream
         sp = _sampling_struct(sampling_params, seed)
         kv_ptrs = (C.c_void_p * self.config.backbone.n_layer)(*[ip.key_value_memory_dict[i][0].data_ptr() for i in range(self.config.backbone.n_layer)])
         eng.call("zn_gen_begin", B, kv_ptrs, ip.max_seqlen, ip.lengths_per_sample.data_ptr(), delayed.data_ptr(), t_total, offset,
                  max_new_tokens, float(cfg_scale), C.byref(sp), st)
         try:
-            offset = self._decode_loop(eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st)
+            offset = yield from self._decode_loop(eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk)
         finally:
             # the device's persistent-kernel tenancy goes back once this generation's kernels have drained (include/zonos_hip.h)
-            torch.cuda.current_stream(dev).synchronize()
+            ts.synchronize()
             eng.call("zn_gen_end")
         out = revert_delay_pattern(delayed.to(torch.int64)).cpu()     # one device->host copy (model.py:511)
-        valid_length = offset - nq
-        window = min(50, valid_length // 4)
-        for pos in range(max(0, valid_length - window), valid_length):   # model.py:516-528
-            if int((out[:, :, pos] == self.eos_token_id).sum()) >= nq // 2:
-                valid_length = pos
-                break
-        out = torch.where(out > 1024, 512, out)
-        out = torch.where(out == 1024, 0, out)
-        return torch.clamp(out[..., :valid_length], 0, 1023).to(dev)
+        return finalise_codes(out, offset, nq, self.eos_token_id)
 
-    def _decode_loop(self, eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st) -> int:
-        """Prefill, first frame and the hot loop (model.py:421-509); returns the final column offset."""
+    def _decode_loop(self, eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk=None):
+        """Prefill, first frame and the hot loop (model.py:421-509); a generator that returns the final column offset.  With `chunk`, the
+        steps are enqueued at least every `chunk` steps and it yields (delayed, column offset written last) there."""
         dev = self.device
         # prefill (generation_utils.py:236-244): [cond ‖ uncond] conditioning + embed(delayed[..., :P+1]) for both halves; without
         # guidance the B conditional rows and the embedding once (generation_utils.py:237)
@@ -341,7 +466,8 @@ class Zonos(nn.Module):
             pending += 1
             ip.seqlen_offset += 1
             check = (step_idx % 16 == 15) or (step_idx % 8 == 7 and max(0, B * 10 - cpu_step_counter) < 5)
-            if check or callback is not None or _trace is not None:
+            hook = chunk is not None and step_idx % chunk == chunk - 1
+            if check or hook or callback is not None or _trace is not None:
                 eng.call("zn_decode_steps", pending, st)
                 pending = 0
                 if _trace is not None:
@@ -364,6 +490,8 @@ class Zonos(nn.Module):
                     break
             if callback is not None and not callback(frame, step_idx + 1, max_steps):
                 break
+            if hook:
+                yield delayed, offset
         if pending:
             eng.call("zn_decode_steps", pending, st)
         if begun_at is not None:
