@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define ZN_ABI_VERSION 7
+#define ZN_ABI_VERSION 8
 
 enum zn_status {
   ZN_OK = 0,
@@ -138,6 +138,17 @@ int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_layers_dev, i
  * B conditional rows when cfg_scale == 1, conditioning concatenated with embed(delayed[..., :prefix+1]); fills KV positions
  * [0,S), lengths += S and leaves the fp32 logits [B, n_codebooks, vocab_head] (CFG-mixed with guidance) in the handle. */
 int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_stream stream);
+/* ABI 8 - zn_prefill for utterances of different prompt lengths.  hidden bf16 [R, S, d] is RIGHT-padded: row r holds row_len[r] valid
+ * positions (its conditioning followed by the embedded audio prefix), then S - row_len[r] positions of padding whose contents are never
+ * visible to a result: no valid query attends a pad key, no pad position reaches a logit, a Mamba2 state or a KV entry that is read
+ * later (pad positions do write the cache slots [row_len[r], S) of their row; the row's own decode steps overwrite each of them before
+ * the attention extent reaches it).  row_len is a HOST array of R lengths in 1..S, at least one equal to S; the library copies it to a
+ * device array of its own.  Afterwards lengths[r] = row_len[r]; row r's first-frame logits come from position row_len[r] - 1, and its
+ * prefill attention uses the query split and key extents of a sequence of row_len[r] positions - the result a batch of utterances of that
+ * length gets.  zn_prefill(h, hidden, S, st) is this call with every length S (the same launches, the same bits).
+ * ZN_ERR_ARG: a length out of range, no length equal to S, or a guided pair with row_len[b] != row_len[B + b].  ZN_ERR_UNSUPPORTED: unequal
+ * lengths on the position-by-position prefill (zn_debug_prefill_mode(h, 0), and models whose dimensions fall back to it). */
+int zn_prefill_rows(zn_handle h, const void* hidden_dev, int32_t S, const int32_t* row_len, zn_stream stream);
 /* model.py:423-431: sample the first frame from the prefill logits (no repetition penalty, no logit bias) and
  * write it into column offset0 where that column is -1. */
 int zn_sample_first(zn_handle h, zn_stream stream);
@@ -155,7 +166,8 @@ int zn_decode_path(zn_handle h);
 /* Which kernels served the decode step enqueued last: 0 = one launch per op, 1 = one attention launch (two beyond 512 keys) + one
  * persistent chain launch per block (two rows only), 2 = the whole-step persistent kernel (every block of the step in one launch;
  * contexts up to 6144 keys: one attention workgroup per (row, kv head, 512-key block); two rows or, without guidance, one row - a
- * one-row step beyond 6144 keys runs the launches path).  All give bit-identical results. */
+ * one-row step beyond 6144 keys runs the launches path).  All give bit-identical results.  Two unguided utterances whose rows have
+ * different lengths (zn_prefill_rows) always report 0: the two-row persistent kernels are kept for rows that advance in lockstep. */
 int zn_decode_path_detail(zn_handle h);
 /* Hand-off timeouts are never silent: out[0] = bounded in-kernel hand-off waits that gave up and were reported on this handle (each voids
  * its generation; zn_all_stopped* returns the error), [1] generations begun, [2] batch-1 generations that ran the launches path because

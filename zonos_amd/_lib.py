@@ -12,7 +12,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZONOS_HIP_LIB") or os.path.join(_HERE, "libzonos_hip.so")   # the override selects an experimental build (A/B runs)
 
-ZN_ABI_VERSION = 7
+ZN_ABI_VERSION = 8
 
 
 class ZonosHipError(RuntimeError):
@@ -61,6 +61,7 @@ SIGNATURES = {
     "zn_gen_begin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                C.c_int32, C.c_float, C.POINTER(zn_sampling), C.c_void_p]),
     "zn_prefill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "zn_prefill_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
     "zn_sample_first": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zn_decode_steps": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "zn_graph_active": (C.c_int, [C.c_void_p]),

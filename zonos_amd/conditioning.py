@@ -303,3 +303,25 @@ def prepare_conditioning_with_cache(prefix_conditioner, cond_dict: dict, uncond_
     if key is not None:
         cache.put(key, out)
     return out
+
+
+def pad_conditionings(conds: list[torch.Tensor], cfg_scale: float = 2.0) -> tuple[torch.Tensor, list[int]]:
+    """Batch utterances whose conditionings differ in length for one `Zonos.generate(..., conditioning_lengths=lengths)` call.
+    `conds[i]` is utterance i's conditioning as `prepare_conditioning` returns it: [2, L_i, d] = [cond ‖ uncond] with guidance,
+    [1, L_i, d] when cfg_scale == 1.  Returns (tensor [R, L_max, d], lengths [L_0 .. L_{B-1}]) with rows in generate()'s batch layout
+    [cond_0..cond_{B-1}, uncond_0..uncond_{B-1}] (the B conditional rows without guidance), each RIGHT-padded with zeros: the padding
+    is never read (generate() places the audio prefix directly behind the L_i valid positions)."""
+    if not conds:
+        raise ValueError("pad_conditionings: no conditionings")
+    halves = 1 if cfg_scale == 1 else 2
+    d = conds[0].shape[-1]
+    for i, c in enumerate(conds):
+        if c.dim() != 3 or c.shape[0] != halves or c.shape[1] < 1 or c.shape[2] != d:
+            raise ValueError(f"pad_conditionings: conditioning {i} has shape {tuple(c.shape)}, expected [{halves}, L >= 1, {d}] "
+                             f"({'cfg_scale == 1: the conditional row only' if halves == 1 else '[cond ‖ uncond]'})")
+    B, lengths = len(conds), [int(c.shape[1]) for c in conds]
+    out = torch.zeros(halves * B, max(lengths), d, dtype=conds[0].dtype, device=conds[0].device)
+    for i, c in enumerate(conds):
+        for half in range(halves):
+            out[half * B + i, :lengths[i]] = c[half]
+    return out, lengths

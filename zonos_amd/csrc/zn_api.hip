@@ -83,6 +83,9 @@ struct zn_handle_s {
   bf16_t *pf_res = nullptr, *pf_zx = nullptr, *pf_xbc = nullptr, *pf_y = nullptr, *pf_g = nullptr;
   size_t pf_rows = 0;
   int* fw_lengths = nullptr;   // [max_rows] positions of zn_op_backbone_forward's rows
+  int* row_len = nullptr;      // [max_rows] valid positions per row of a right-padded prefill (zn_prefill_rows)
+  std::vector<int> row_len_host;   // source of the copy into row_len (kept until the next zn_gen_begin has drained the stream)
+  bool rows_unequal2 = false;  // this generation's two unguided rows have different lengths: its steps run the launches path (persist_active)
   bf16_t* qkv_tmp = nullptr;   // [rows][(H + 2 Hkv) hd]: in_proj output of an attention layer whose RoPE / bias form the fused epilogue does not cover
   int prefill_mode = 1;     // 1 = batched (MFMA GEMMs + tiled attention), 0 = position by position through the decode kernels
   int lcap = 0;
@@ -184,7 +187,7 @@ extern "C" int zn_destroy(zn_handle h) {
   if (!h) return ZN_OK;
   (void)zn_tenant_release(h->device, h);
   free_graph(h);
-  void* ptrs[] = {h->emb_tables_dev, h->x, h->q, h->o1, h->mbuf, h->nbuf, h->logits_raw, h->last_logits, h->tok_raw, h->scores, h->cmax, h->pv_part, h->pv_tickets, h->pf_x, h->pf_n, h->pf_qkv, h->pf_a, h->pf_u, h->pf_m, h->pf_res, h->pf_zx, h->pf_xbc, h->pf_y, h->pf_g, h->qkv_tmp, h->fw_lengths, h->st, h->remaining, h->stopping, h->res, h->hn, h->m_zx, h->m_xbc, h->m_y, h->m_g, h->m_vg, h->g16_part, h->g16_tickets, h->ln_part, h->ch_gy1, h->ch_gx1, h->ch_gx2, h->ch_gm, h->ch_epoch, h->ch_x2, h->x_emb, h->tail_ticket, h->ch_gqkv, h->ch_ga, h->ch_gbmax, h->ch_gpart, h->stack_layers, h->ch_diag};
+  void* ptrs[] = {h->emb_tables_dev, h->x, h->q, h->o1, h->mbuf, h->nbuf, h->logits_raw, h->last_logits, h->tok_raw, h->scores, h->cmax, h->pv_part, h->pv_tickets, h->pf_x, h->pf_n, h->pf_qkv, h->pf_a, h->pf_u, h->pf_m, h->pf_res, h->pf_zx, h->pf_xbc, h->pf_y, h->pf_g, h->qkv_tmp, h->fw_lengths, h->row_len, h->st, h->remaining, h->stopping, h->res, h->hn, h->m_zx, h->m_xbc, h->m_y, h->m_g, h->m_vg, h->g16_part, h->g16_tickets, h->ln_part, h->ch_gy1, h->ch_gx1, h->ch_gx2, h->ch_gm, h->ch_epoch, h->ch_x2, h->x_emb, h->tail_ticket, h->ch_gqkv, h->ch_ga, h->ch_gbmax, h->ch_gpart, h->stack_layers, h->ch_diag};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->done_host) (void)hipHostFree(h->done_host);
   if (h->stop_event) (void)hipEventDestroy(h->stop_event);
@@ -273,6 +276,7 @@ extern "C" int zn_create(const zn_config* cfg, const zn_weights* w, int32_t max_
   ZC(hipMalloc(&h->last_logits, R * c.n_codebooks * c.vocab_head * sizeof(float)));
   ZC(hipMalloc(&h->tok_raw, R * c.n_codebooks * sizeof(int)));
   ZC(hipMalloc(&h->fw_lengths, R * sizeof(int)));
+  ZC(hipMalloc(&h->row_len, R * sizeof(int)));
   ZC(hipMalloc(&h->st, sizeof(GenState)));
   ZC(hipMemset(h->st, 0, sizeof(GenState)));
   ZC(hipMalloc(&h->remaining, R * sizeof(int)));
@@ -653,11 +657,15 @@ static int layer_decode(zn_handle h, int li, bf16_t* x, bf16_t* kv, int max_len,
 
 // The persistent chain serves the step when the model fits an instantiation, at batch 1 (two rows), unless switched off
 // (zn_debug_tune(8, 2), or ZN_CHAIN=0 in the environment at zn_create): 1.07 vs 1.16 ms per decode step at the Zonos-v0.1 dimensions.
-static bool chain_active(zn_handle h, int rows) { return h->ch_variant != 0 && rows == 2 && h->tune[8] != 2 && !h->demoted && h->persist_ok; }
+// Two unguided rows of different lengths (zn_prefill_rows) stay off the persistent kernels: see persist_active.
+static bool chain_active(zn_handle h, int rows) { return h->ch_variant != 0 && rows == 2 && h->tune[8] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2; }
 // Row counts a persistent kernel can serve on this model: two (the per-block chain and step_kernel) or one (step_r1_kernel, the whole-step
 // kernel only: one row beyond its 6144-key bound, or with it switched off, runs the launches path).
 static bool persist_shape(zn_handle h, int rows) { return h->ch_variant != 0 && (rows == 2 || (rows == 1 && h->ch_variant == 1)); }
-static bool persist_active(zn_handle h, int rows) { return persist_shape(h, rows) && h->tune[8] != 2 && !h->demoted && h->persist_ok; }
+// rows_unequal2: the two-row persistent kernels read lengths[r] per row, but their hand-off schedules, key-block counts and graph slots were
+// built and measured for the guided pair, whose rows advance in lockstep; two unguided utterances of different lengths run the launches
+// path, which is bit-identical by construction.
+static bool persist_active(zn_handle h, int rows) { return persist_shape(h, rows) && h->tune[8] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2; }
 
 // The chain never updates the residual stream in place (zn_chain_kernel.h): block li reads it from one buffer and leaves it
 // in the other.
@@ -1132,6 +1140,7 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   h->len_hi = 0;
   for (int v : len0) if (v > h->len_hi) h->len_hi = v;
   h->gen_active = true;
+  h->rows_unequal2 = false;
   h->gen_ended = false;
   h->gen_timed_out = false;
   h->gen_stream = s;
@@ -1203,13 +1212,15 @@ static int qsplit(int S) { return S >= 768 ? 256 : S >= 192 ? 64 : 32; }   // qu
 
 // All S positions at once: row-wise kernels over M = R*S rows, MFMA GEMMs, tiled exact causal attention.
 // causal attention of S prefill positions over the keys already written for them (SDPA is_causal=True, _torch.py:415)
+// row_len (device, [R]): right-padded rows, row r holds row_len[r] <= S positions; each row then takes the query split and key extents of its own length
 static int prefill_attention(zn_handle h, const bf16_t* q, int ldq, const bf16_t* kv, int max_len, bf16_t* out, int ldo, int S, int R,
-                             hipStream_t s, int base = 0) {
+                             hipStream_t s, int base = 0, const int* row_len = nullptr) {
   const zn_config& c = h->cfg;
   const int hd = h->hd;
   PrefillAttnArgs pa{};
   pa.q = q; pa.ldq = ldq; pa.kv = kv; pa.out = out; pa.ldo = ldo; pa.S = S; pa.base = base; pa.max_len = max_len;
   pa.n_heads = c.n_heads; pa.n_heads_kv = c.n_heads_kv; pa.qsplit = qsplit(S); pa.scale = (float)(1.0 / std::sqrt((double)hd));
+  pa.row_len = row_len;
   const bool mfma = h->tune[10] != 2;   // tune[10] = 2: the VALU kernel at every head size
   int r2 = hd == 128 ? launch_prefill_attn<128>(pa, h->G, R, mfma, s) : hd == 64 ? launch_prefill_attn<64>(pa, h->G, R, mfma, s) : launch_prefill_attn<32>(pa, h->G, R, mfma, s);
   if (r2) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "prefill attention: unsupported group %d", h->G);
@@ -1253,8 +1264,12 @@ static bool run_gemm16k_rows(zn_handle h, const bf16_t* x, const void* ln_w, con
 }
 
 // Transformer blocks over all S positions of R rows (hidden [R][S][d]) with `base` keys already cached per row: the
-// residual stream of every position ends in h->pf_x.
-static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, int R, const void* const* kv_layers, int max_len, int base, hipStream_t s) {
+// residual stream of every position ends in h->pf_x.  row_len (device, [R]; base 0 only): right-padded rows.  The row-wise kernels and the
+// projections run over all R * S positions (pad rows are computed and dropped: no op mixes positions except the attention, which bounds
+// every row by row_len[r]); RoPE and the KV append run over the pad positions too - cache slots at or past row_len[r], which the row's own
+// decode steps overwrite, one per step, before the attention's extent reaches them.
+static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, int R, const void* const* kv_layers, int max_len, int base, hipStream_t s,
+                                    const int* row_len = nullptr) {
   const zn_config& c = h->cfg;
   const int M = R * S, d = c.d_model, hd = h->hd, nq = c.n_heads * hd, nkv = c.n_heads_kv * hd, nqkv = nq + 2 * nkv, F = c.d_ff;
   int rc = ensure_prefill_ws(h, (size_t)M);
@@ -1281,7 +1296,7 @@ static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, in
         launch_gemm(h->pf_n, d, (const bf16_t*)lw.in_proj, h->pf_qkv, nqkv, nullptr, M, nqkv, d, s);
       hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(S, R), dim3(256), 0, s, h->pf_qkv, kv, h->rope, S, base, max_len, c.n_heads, c.n_heads_kv, hd, c.rope_positions);
     }
-    rc = prefill_attention(h, h->pf_qkv, ldq, kv, max_len, h->pf_a, nq, S, R, s, base);
+    rc = prefill_attention(h, h->pf_qkv, ldq, kv, max_len, h->pf_a, nq, S, R, s, base, row_len);
     if (rc) return rc;
     if (c.double_out_proj) {
       if (!run_gemm16k_rows<PRO_NONE, EPI_STORE>(h, h->pf_a, nullptr, nullptr, lw.out_proj, d, nq, h->pf_n, nullptr, M, s) &&
@@ -1304,13 +1319,13 @@ static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, in
   return ZN_OK;
 }
 
-static int prefill_batched(zn_handle h, const bf16_t* hidden, int S, hipStream_t s) {
+static int prefill_batched(zn_handle h, const bf16_t* hidden, int S, hipStream_t s, const int* row_len) {
   const zn_config& c = h->cfg;
   const int R = h->rows, d = c.d_model;
-  int rc = transformer_prefill_core(h, hidden, S, R, h->kv_layers.data(), h->max_len, 0, s);
+  int rc = transformer_prefill_core(h, hidden, S, R, h->kv_layers.data(), h->max_len, 0, s, row_len);
   if (rc) return rc;
-  hipLaunchKernelGGL(gather_last_kernel, dim3(R), dim3(256), 0, s, h->pf_x, h->x, S, d);
-  hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > R ? 64 : R), 0, s, h->lengths, R, S);
+  hipLaunchKernelGGL(gather_last_kernel, dim3(R), dim3(256), 0, s, h->pf_x, h->x, S, d, row_len);
+  hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > R ? 64 : R), 0, s, h->lengths, R, S, row_len);
   return ZN_OK;
 }
 
@@ -1334,8 +1349,9 @@ static int proj_rows(zn_handle h, const bf16_t* A, int lda, const void* W, const
 // Hybrid blocks over all S positions of R rows (mamba_ssm Block semantics): Mamba2 layers run the sequence conv and the
 // selective scan (zn_mamba_kernels.h), attention layers the batched projections + tiled causal attention.  The mixer
 // output of every position ends in h->pf_x, the residual stream in h->pf_res; caches advance by S positions.
+// row_len (device, [R]; base 0 only): right-padded rows - the sequence conv and the scan stop at row_len[r], the attention bounds row r by it.
 static int hybrid_prefill_core(zn_handle h, const bf16_t* hidden, int S, int R, const void* const* caches, int max_len, int base, bool exact,
-                               hipStream_t s) {
+                               hipStream_t s, const int* row_len = nullptr) {
   const zn_config& c = h->cfg;
   const int M = R * S, d = c.d_model, hd = h->hd, nq = c.n_heads * hd, nkv = c.n_heads_kv * hd, nqkv = nq + 2 * nkv, F = c.d_ff;
   int rc = ensure_prefill_ws(h, (size_t)M);
@@ -1355,9 +1371,9 @@ static int hybrid_prefill_core(zn_handle h, const bf16_t* hidden, int S, int R, 
       m.norm_w = (const bf16_t*)lw.m_norm_w; m.xbc = h->pf_xbc; m.y = h->pf_y; m.g = h->pf_g; m.vg = nullptr;
       m.d_inner = c.m_d_inner; m.conv_dim = h->m_conv_dim; m.nheads = h->m_nheads; m.d_state = c.m_d_state; m.ngroups = c.m_ngroups;
       m.d_in_proj = h->m_d_in_proj; m.eps = c.norm_eps; m.rows = R;
-      hipLaunchKernelGGL(mamba_conv_seq_kernel, dim3((h->m_conv_dim + 255) / 256, R), dim3(256), 0, s, m, S);
-      if (c.m_d_state == 128) hipLaunchKernelGGL((mamba_scan_kernel<128>), dim3(h->m_nheads, R), dim3(256), 0, s, m, S);
-      else hipLaunchKernelGGL((mamba_scan_kernel<64>), dim3(h->m_nheads, R), dim3(256), 0, s, m, S);
+      hipLaunchKernelGGL(mamba_conv_seq_kernel, dim3((h->m_conv_dim + 255) / 256, R), dim3(256), 0, s, m, S, row_len);
+      if (c.m_d_state == 128) hipLaunchKernelGGL((mamba_scan_kernel<128>), dim3(h->m_nheads, R), dim3(256), 0, s, m, S, row_len);
+      else hipLaunchKernelGGL((mamba_scan_kernel<64>), dim3(h->m_nheads, R), dim3(256), 0, s, m, S, row_len);
       m.rows = M;
       hipLaunchKernelGGL(mamba_gated_norm_kernel, dim3(c.m_ngroups, M), dim3(256), 0, s, m);
       if ((rc = proj_rows(h, h->pf_g, c.m_d_inner, lw.m_out_proj, nullptr, h->pf_x, d, M, d, c.m_d_inner, exact, s))) return rc;
@@ -1367,7 +1383,7 @@ static int hybrid_prefill_core(zn_handle h, const bf16_t* hidden, int S, int R, 
     if ((rc = proj_rows(h, h->pf_n, d, lw.in_proj, lw.in_proj_bias, h->pf_qkv, nqkv, M, nqkv, d, exact, s))) return rc;
     hipLaunchKernelGGL(rope_kv_any_kernel, dim3(S, R), dim3(256), 0, s, h->pf_qkv, h->pf_qkv, nqkv, kv, h->rope, S, base, (const int*)nullptr, max_len,
                        c.n_heads, c.n_heads_kv, hd, c.rope_positions, c.rope_mode);
-    if ((rc = prefill_attention(h, h->pf_qkv, nqkv, kv, max_len, h->pf_a, nq, S, R, s, base))) return rc;
+    if ((rc = prefill_attention(h, h->pf_qkv, nqkv, kv, max_len, h->pf_a, nq, S, R, s, base, row_len))) return rc;
     if ((rc = proj_rows(h, h->pf_a, nq, lw.out_proj, lw.out_proj_bias, h->pf_x, d, M, d, nq, exact, s))) return rc;
     launch_add_ln(h, h->pf_x, h->pf_res, 1, 1, lw.norm2_w, lw.norm2_b, h->pf_n, M, s);
     if ((rc = proj_rows(h, h->pf_n, d, lw.fc1, nullptr, h->pf_u, 2 * F, M, 2 * F, d, exact, s))) return rc;
@@ -1379,23 +1395,28 @@ static int hybrid_prefill_core(zn_handle h, const bf16_t* hidden, int S, int R, 
 
 extern "C" int zn_debug_prefill_mode(zn_handle h, int32_t mode) { if (!h) return ZN_ERR_ARG; h->prefill_mode = mode; return ZN_OK; }
 
-extern "C" int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_stream stream) {
-  if (!h) return ZN_ERR_ARG;
-  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill before zn_gen_begin");
-  if (!hidden_dev || S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill: bad S=%d (max_len %d)", S, h->max_len);
-  hipStream_t s = (hipStream_t)stream;
+// All S positions at once (true), or position by position through the decode kernels (prefill_mode 0, S = 1, dimensions the batched kernels do not tile)?
+static bool prefill_all_at_once(zn_handle h, int S) {
+  const zn_config& c = h->cfg;
+  if (S <= 1 || c.d_model % 32 || c.d_ff % 32) return false;
+  return c.arch == 1 ? (h->prefill_mode >= 1 && c.m_d_inner % 32 == 0) : h->prefill_mode == 1;
+}
+
+// The prefill of S positions per row; row_len (device, [rows]) != nullptr: right-padded rows of row_len[r] <= S valid positions (batched prefill only).
+static int prefill_impl(zn_handle h, const void* hidden_dev, int32_t S, const int* row_len, hipStream_t s) {
   const zn_config& c = h->cfg;
   int rc;
-  if (c.arch == 1 && h->prefill_mode >= 1 && S > 1 && c.d_model % 32 == 0 && c.d_ff % 32 == 0 && c.m_d_inner % 32 == 0) {
+  const bool at_once = prefill_all_at_once(h, S);
+  if (c.arch == 1 && at_once) {
     // all positions at once (mode 2: projections row by row through the step's GEMV: bit-comparable with single steps)
-    if ((rc = hybrid_prefill_core(h, (const bf16_t*)hidden_dev, S, h->rows, h->kv_layers.data(), h->max_len, 0, h->prefill_mode == 2, s))) return rc;
-    hipLaunchKernelGGL(gather_last_kernel, dim3(h->rows), dim3(256), 0, s, h->pf_x, h->x, S, c.d_model);
-    hipLaunchKernelGGL(gather_last_bytes_kernel, dim3(h->rows), dim3(256), 0, s, (const void*)h->pf_res, (void*)h->res, S, c.d_model * (c.residual_in_fp32 ? 4 : 2));
-    hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > h->rows ? 64 : h->rows), 0, s, h->lengths, h->rows, S);
+    if ((rc = hybrid_prefill_core(h, (const bf16_t*)hidden_dev, S, h->rows, h->kv_layers.data(), h->max_len, 0, h->prefill_mode == 2, s, row_len))) return rc;
+    hipLaunchKernelGGL(gather_last_kernel, dim3(h->rows), dim3(256), 0, s, h->pf_x, h->x, S, c.d_model, row_len);
+    hipLaunchKernelGGL(gather_last_bytes_kernel, dim3(h->rows), dim3(256), 0, s, (const void*)h->pf_res, (void*)h->res, S, c.d_model * (c.residual_in_fp32 ? 4 : 2), row_len);
+    hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > h->rows ? 64 : h->rows), 0, s, h->lengths, h->rows, S, row_len);
     h->len_hi += S;
     if ((rc = hybrid_heads(h, s))) return rc;
-  } else if (c.arch == 0 && h->prefill_mode == 1 && S > 1 && c.d_model % 32 == 0 && c.d_ff % 32 == 0) {
-    if ((rc = prefill_batched(h, (const bf16_t*)hidden_dev, S, s))) return rc;
+  } else if (c.arch == 0 && at_once) {
+    if ((rc = prefill_batched(h, (const bf16_t*)hidden_dev, S, s, row_len))) return rc;
     h->len_hi += S;
   } else {
     // Position by position through the decode kernels.  Row-wise ops are independent of S; attention reproduces the
@@ -1416,6 +1437,41 @@ extern "C" int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_str
   if (c.arch == 0 && (rc = heads_logits(h, h->x, h->rows, s))) return rc;
   HIPCHK(h, hipGetLastError());
   return ZN_OK;
+}
+
+extern "C" int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill before zn_gen_begin");
+  if (!hidden_dev || S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill: bad S=%d (max_len %d)", S, h->max_len);
+  return prefill_impl(h, hidden_dev, S, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int zn_prefill_rows(zn_handle h, const void* hidden_dev, int32_t S, const int32_t* row_len, zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill_rows before zn_gen_begin");
+  if (!hidden_dev || !row_len || S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: null argument or bad S=%d (max_len %d)", S, h->max_len);
+  const int R = h->rows, B = h->batch;
+  int hi = 0;
+  bool uniform = true;
+  for (int r = 0; r < R; ++r) {
+    if (row_len[r] < 1 || row_len[r] > S) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: row %d holds %d positions, not in 1..%d", r, row_len[r], S);
+    if (row_len[r] > hi) hi = row_len[r];
+    uniform = uniform && row_len[r] == S;
+  }
+  if (hi != S) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: the longest row holds %d positions, S is %d (no row may be all padding at its end)", hi, S);
+  if (R == 2 * B)
+    for (int b = 0; b < B; ++b)
+      if (row_len[b] != row_len[B + b])
+        ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: utterance %d has %d conditional and %d unconditional positions (a guided pair advances in lockstep)", b, row_len[b], row_len[B + b]);
+  hipStream_t s = (hipStream_t)stream;
+  if (uniform) return prefill_impl(h, hidden_dev, S, nullptr, s);          // zn_prefill: the same launches, the same bits
+  if (!prefill_all_at_once(h, S))
+    ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_prefill_rows: rows of different lengths need the batched prefill; this handle prefills position by position "
+            "(zn_debug_prefill_mode 0, S = 1, or dimensions that are not multiples of 32)");
+  h->row_len_host.assign(row_len, row_len + R);
+  HIPCHK(h, hipMemcpyAsync(h->row_len, h->row_len_host.data(), R * sizeof(int), hipMemcpyHostToDevice, s));
+  h->rows_unequal2 = R == 2 && B == 2 && row_len[0] != row_len[1];
+  return prefill_impl(h, hidden_dev, S, h->row_len, s);                     // len_hi += S: the bound of the longest row
 }
 
 extern "C" int zn_sample_first(zn_handle h, zn_stream stream) {

@@ -1538,8 +1538,9 @@ __global__ __launch_bounds__(64) void layernorm_kernel(const bf16_t* x, const bf
     }
   }
 }
-__global__ void add_lengths_kernel(int* lengths, int rows, int n) {
-  if (threadIdx.x < rows) lengths[threadIdx.x] += n;
+// lengths[r] += row_len ? row_len[r] : n  (row_len: the rows' own position counts of a right-padded prefill)
+__global__ void add_lengths_kernel(int* lengths, int rows, int n, const int* row_len = nullptr) {
+  if (threadIdx.x < rows) lengths[threadIdx.x] += row_len ? row_len[threadIdx.x] : n;
 }
 
 // ------------------------------------------------------------------------------------------------ sampler

@@ -265,17 +265,22 @@ __global__ __launch_bounds__(256) void mamba_gated_norm_kernel(MambaArgs a) {
 // row, index r * S + s.  The conv kernel repeats the single-step arithmetic statement for statement (window and outputs bit-identical
 // to S single steps); the scan keeps its state in fp32 across the positions, as the reference's prefill does (below).
 
+// Right-padded rows (row_len != nullptr): row r holds row_len[r] <= S_ld valid positions, S_ld stays the row stride.  Both kernels stop
+// after position row_len[r] - 1: the conv window and the SSM state they store are those of the row's last valid position, and the pad
+// positions of xbc / y are not written (their rows of the later projections are computed from whatever the workspace holds and dropped).
+
 // causal conv + SiLU along the sequence: one thread per (row, channel) walks the S positions with the window in registers
-__global__ __launch_bounds__(256) void mamba_conv_seq_kernel(MambaArgs a, int S) {
+__global__ __launch_bounds__(256) void mamba_conv_seq_kernel(MambaArgs a, int S_ld, const int* row_len = nullptr) {
   const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
   if (c >= a.conv_dim) return;
+  const int S = row_len ? row_len[r] : S_ld;
   typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
   bf16_t* sp = a.conv_state + ((size_t)r * a.conv_dim + c) * 4;
   u32x2_t st = *(const u32x2_t*)sp;
   const u32x2_t wv = *(const u32x2_t*)(a.conv_w + (size_t)c * 4);
   const float bias = bf2f(a.conv_b[c]);
-  const bf16_t* xp = a.zx + (size_t)r * S * a.d_in_proj + a.d_inner + c;
-  bf16_t* op = a.xbc + (size_t)r * S * a.conv_dim + c;
+  const bf16_t* xp = a.zx + (size_t)r * S_ld * a.d_in_proj + a.d_inner + c;
+  bf16_t* op = a.xbc + (size_t)r * S_ld * a.conv_dim + c;
   constexpr int AH = 8;                                   // positions requested ahead
   bf16_t xq[AH];
 #pragma unroll
@@ -312,9 +317,10 @@ __global__ __launch_bounds__(256) void mamba_conv_seq_kernel(MambaArgs a, int S)
 // therefore NOT bit-identical to stepping the same tokens one by one (it is more accurate); position s's output uses the
 // unrounded state either way.  The next position's B, C, x, dt are requested while the current one is computed.
 template <int N>
-__global__ __launch_bounds__(256) void mamba_scan_kernel(MambaArgs a, int S) {
+__global__ __launch_bounds__(256) void mamba_scan_kernel(MambaArgs a, int S_ld, const int* row_len = nullptr) {
   constexpr int P = 64, NT = N / 4, NV = NT / 8;
   const int h = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
+  const int S = row_len ? row_len[r] : S_ld;
   const int p = tid >> 2, q = tid & 3;
   const int grp = h / (a.nheads / a.ngroups);
   bf16_t* sp = a.ssm_state + (((size_t)r * a.nheads + h) * P + p) * N + q * NT;
@@ -331,7 +337,7 @@ __global__ __launch_bounds__(256) void mamba_scan_kernel(MambaArgs a, int S) {
   u32x4 bn[NV], cn[NV];
   bf16_t xn, dn;
   auto request = [&](int s) {
-    const size_t rs = (size_t)r * S + min(s, S - 1);
+    const size_t rs = (size_t)r * S_ld + min(s, S - 1);
     const bf16_t* xb = a.xbc + rs * a.conv_dim;
     const bf16_t* Bp = xb + a.d_inner + grp * N + q * NT;
     const bf16_t* Cp = Bp + a.ngroups * N;
@@ -366,7 +372,7 @@ __global__ __launch_bounds__(256) void mamba_scan_kernel(MambaArgs a, int S) {
     }
     y += dpp_mov<ZN_DPP_XOR1>(y);
     y += dpp_mov<ZN_DPP_XOR2>(y);
-    if (q == 0) a.y[((size_t)r * S + s) * a.d_inner + h * P + p] = f2bf(__fadd_rn(y, __fmul_rn(x, Dh)));
+    if (q == 0) a.y[((size_t)r * S_ld + s) * a.d_inner + h * P + p] = f2bf(__fadd_rn(y, __fmul_rn(x, Dh)));
   }
 #pragma unroll
   for (int i = 0; i < NV; ++i)

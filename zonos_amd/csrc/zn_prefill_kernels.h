@@ -391,17 +391,20 @@ __global__ __launch_bounds__(256) void silu_mul_rows_kernel(const bf16_t* u, bf1
     *(unsigned*)(m + row * F + i) = pack2(lo_f(y) * s0, hi_f(y) * s1);
   }
 }
-// row r of dst <- the last of the S positions of row r of src (rows of row_bytes bytes, a multiple of 16)
-__global__ void gather_last_bytes_kernel(const void* src, void* dst, int S, int row_bytes) {
+// row r of dst <- the last of the S positions of row r of src (rows of row_bytes bytes, a multiple of 16); row_len: the last VALID
+// position row_len[r] - 1 of a right-padded row
+__global__ void gather_last_bytes_kernel(const void* src, void* dst, int S, int row_bytes, const int* row_len = nullptr) {
   const int r = blockIdx.x;
-  const u32x4* sp = (const u32x4*)((const char*)src + ((size_t)r * S + (S - 1)) * row_bytes);
+  const int last = (row_len ? row_len[r] : S) - 1;
+  const u32x4* sp = (const u32x4*)((const char*)src + ((size_t)r * S + last) * row_bytes);
   u32x4* dp = (u32x4*)((char*)dst + (size_t)r * row_bytes);
   for (int i = threadIdx.x; i < row_bytes / 16; i += blockDim.x) dp[i] = sp[i];
 }
 __global__ void fill_int_kernel(int* p, int n, int v) { if ((int)threadIdx.x < n) p[threadIdx.x] = v; }
-__global__ void gather_last_kernel(const bf16_t* xP, bf16_t* x, int S, int d) {
+__global__ void gather_last_kernel(const bf16_t* xP, bf16_t* x, int S, int d, const int* row_len = nullptr) {
   const int r = blockIdx.x;
-  for (int k = threadIdx.x * 8; k < d; k += blockDim.x * 8) *(u32x4*)(x + (size_t)r * d + k) = *(const u32x4*)(xP + ((size_t)r * S + S - 1) * d + k);
+  const int last = (row_len ? row_len[r] : S) - 1;
+  for (int k = threadIdx.x * 8; k < d; k += blockDim.x * 8) *(u32x4*)(x + (size_t)r * d + k) = *(const u32x4*)(xP + ((size_t)r * S + last) * d + k);
 }
 
 // ------------------------------------------------------------------------------------------------ causal attention
@@ -415,7 +418,14 @@ struct PrefillAttnArgs {
   bf16_t* out; int ldo;
   int S, base, max_len, n_heads, n_heads_kv, qsplit;
   float scale;
+  // Right-padded rows: row r holds row_len[r] <= S valid positions (S stays the row stride of q and out).  Its queries see the keys, the
+  // query split and the key extents of a sequence of row_len[r] positions; positions at or past row_len[r] are neither read as keys nor
+  // written as outputs.  nullptr: every row holds S positions.  One row per workgroup (blockIdx.z), so the row's length and split are
+  // wave-uniform: scalar loads, SGPRs.
+  const int* row_len;
 };
+// query split of the reference's CPU flash kernel for a sequence of S positions (the host's qsplit())
+ZN_DEVINL int prefill_qsplit(int S) { return S >= 768 ? 256 : S >= 192 ? 64 : 32; }
 template <int HD, int G>
 __global__ __launch_bounds__(256) void attn_prefill_kernel(PrefillAttnArgs a) {
   constexpr int TQ = 64 / G;              // positions per workgroup
@@ -428,14 +438,17 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(PrefillAttnArgs a) {
   const int rw = lane & 15, kq = lane >> 4;
   const int row = wave * 16 + rw;                     // 0..63
   const int s = s0 + row / G, g = row % G;
-  const bool row_ok = s < a.S;
+  const int Sv = a.row_len ? a.row_len[r] : a.S;      // valid positions of this sequence row (workgroup-uniform)
+  const int qs = a.row_len ? prefill_qsplit(Sv) : a.qsplit;
+  if (s0 >= Sv) return;                               // a tile of padding only (before any barrier: the whole workgroup leaves)
+  const bool row_ok = s < Sv;
   const int L_row = row_ok ? a.base + s + 1 : 0;      // keys this row may see
-  const int Lmax = a.base + min(s0 + TQ, a.S);
+  const int Lmax = a.base + min(s0 + TQ, Sv);
   const int sq = row_ok ? s : s0;
-  const int E = a.base + min((sq / a.qsplit) * a.qsplit + a.qsplit, a.S);   // keys spanned by this row's query block in the reference
+  const int E = a.base + min((sq / qs) * qs + qs, Sv);   // keys spanned by this row's query block in the reference
   u32x4 qv[NQ];
   {
-    const bf16_t* qp = a.q + ((size_t)r * a.S + (row_ok ? s : a.S - 1)) * a.ldq + (size_t)(kvh * G + g) * HD;
+    const bf16_t* qp = a.q + ((size_t)r * a.S + (row_ok ? s : Sv - 1)) * a.ldq + (size_t)(kvh * G + g) * HD;
 #pragma unroll
     for (int i = 0; i < NQ; ++i) qv[i] = ld16(qp + 8 * i);
   }
@@ -557,10 +570,13 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(PrefillAttnArgs 
   const int s0 = ((int)gridDim.x - 1 - (int)blockIdx.x) * TQ, kvh = blockIdx.y, r = blockIdx.z;     // longest rows first
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fn = lane & 15, fg = lane >> 4;
+  const int Sv = a.row_len ? a.row_len[r] : a.S;        // valid positions of this sequence row (workgroup-uniform)
+  const int qs = a.row_len ? prefill_qsplit(Sv) : a.qsplit;
+  if (s0 >= Sv) return;                                 // a tile of padding only (before any barrier: the whole workgroup leaves)
   u32x4 qa[4];                                          // A operand: row = fn, k = 32*st + 8*fg + j
   {
     const int arow = wave * 16 + fn;
-    const int as = min(s0 + arow / G, a.S - 1), ag = arow % G;
+    const int as = min(s0 + arow / G, Sv - 1), ag = arow % G;
     const bf16_t* qp = a.q + ((size_t)r * a.S + as) * a.ldq + (size_t)(kvh * G + ag) * HD + 8 * fg;
 #pragma unroll
     for (int st = 0; st < 4; ++st) qa[st] = ld16(qp + 32 * st);
@@ -569,12 +585,12 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(PrefillAttnArgs 
 #pragma unroll
   for (int reg = 0; reg < 4; ++reg) {
     const int row = wave * 16 + 4 * fg + reg, s = s0 + row / G;
-    const bool ok = s < a.S;
+    const bool ok = s < Sv;
     Lrow[reg] = ok ? a.base + s + 1 : 0;
     const int sq = ok ? s : s0;
-    Erow[reg] = a.base + min((sq / a.qsplit) * a.qsplit + a.qsplit, a.S);
+    Erow[reg] = a.base + min((sq / qs) * qs + qs, Sv);
   }
-  const int Lmax = a.base + min(s0 + TQ, a.S);
+  const int Lmax = a.base + min(s0 + TQ, Sv);
   f32x4 acc[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -707,7 +723,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(PrefillAttnArgs 
 #pragma unroll
   for (int j = 0; j < 4; ++j) {                          // 16 rows x 16 pieces of 8 dims per wave
     const int i = lane + 64 * j, row = i >> 4, pc = i & 15, grow = wave * 16 + row, s = s0 + grow / G, g = grow % G;
-    if (s >= a.S) continue;
+    if (s >= Sv) continue;
     const float* o = s_o + grow * OP + 8 * pc;
     u32x4 ov;
     ov.x = pack2(o[0], o[1]); ov.y = pack2(o[2], o[3]); ov.z = pack2(o[4], o[5]); ov.w = pack2(o[6], o[7]);

@@ -12,7 +12,7 @@ import os
 import sys
 import threading
 import json
-from typing import Callable, Iterator, NamedTuple
+from typing import Callable, Iterator, NamedTuple, Sequence
 
 import torch
 import torch.nn as nn
@@ -262,15 +262,20 @@ class Zonos(nn.Module):
     def generate(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor = None, max_new_tokens: int = 86 * 30,
                  cfg_scale: float = 2.0, batch_size: int = 1, sampling_params: dict = dict(min_p=0.1),
                  disable_torch_compile: bool = False, callback: Callable[[torch.Tensor, int, int], bool] | None = None,
-                 seed: int | None = None, _trace: dict | None = None):
+                 seed: int | None = None, _trace: dict | None = None, conditioning_lengths: Sequence[int] | None = None):
         """zonos/model.py:354-548.  prefix_conditioning bf16 [2B, L_c, d] = [cond ‖ uncond] with guidance, or the B conditional
         rows [B, L_c, d] when cfg_scale == 1 (what `prepare_conditioning` returns at its default cfg_scale=1.0: no unconditional
         half, no CFG mix, half the rows per utterance); returns int64 [B, 9, T_out] with values in [0, 1023].  Batch semantics
         for B > 1 (the reference crashes there): B independent utterances, rows [cond_0..cond_{B-1},
         uncond_0..uncond_{B-1}] (or [cond_0..cond_{B-1}] without guidance).  `seed` seeds the device Gumbel-max stream (default:
-        drawn from torch's generator)."""
+        drawn from torch's generator).
+
+        `conditioning_lengths` batches utterances of different prompt lengths: B valid lengths L_b in 1..L_c of a RIGHT-padded
+        `prefix_conditioning` (`conditioning.pad_conditionings` builds both).  Utterance b's audio prefix follows its L_b valid positions
+        directly and the padding is never read: every utterance gets the codes it would get in a batch of utterances of its own length
+        (DESIGN.md 4.1b).  The audio prefix length and max_new_tokens stay shared by the batch.  None: every row holds L_c positions."""
         B = batch_size
-        n = self._check_rows(prefix_conditioning, cfg_scale, B)
+        n = self._check_rows(prefix_conditioning, cfg_scale, B, conditioning_lengths)
         dev = self.device
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -278,12 +283,13 @@ class Zonos(nn.Module):
         # sized by rows (engine(b) holds 2 b): one unguided utterance runs on engine(1), like a guided one
         eng = self._acquire_engine((n + 1) // 2)
         try:
-            return self._generate_on(eng, dev, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, B, sampling_params, callback, seed, _trace)
+            return self._generate_on(eng, dev, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, B, sampling_params, callback, seed, _trace,
+                                     None if conditioning_lengths is None else [int(v) for v in conditioning_lengths])
         finally:
             eng.generating = False
             eng.lock.release()
 
-    def _check_rows(self, prefix_conditioning, cfg_scale, B) -> int:
+    def _check_rows(self, prefix_conditioning, cfg_scale, B, conditioning_lengths=None) -> int:
         n = prefix_conditioning.shape[0]
         if cfg_scale == 1:
             # [cond ‖ uncond] rows without guidance: the reference's prepare_conditioning would have returned B rows (conditioning_cache.py:172)
@@ -292,6 +298,13 @@ class Zonos(nn.Module):
                 raise ValueError(f"prefix_conditioning must have batch_size={B} rows when cfg_scale == 1, got {n}")
         elif n != 2 * B:
             raise ValueError(f"prefix_conditioning must have 2*batch_size={2 * B} rows, got {n}")
+        if conditioning_lengths is not None:
+            lens, L_c = list(conditioning_lengths), prefix_conditioning.shape[1]
+            if len(lens) != B:
+                raise ValueError(f"conditioning_lengths must hold batch_size={B} lengths, got {len(lens)}")
+            bad = [v for v in lens if int(v) != v or not 1 <= int(v) <= L_c]
+            if bad:
+                raise ValueError(f"conditioning_lengths must lie in 1..{L_c} (the padded prefix_conditioning's length), got {bad}")
         if self.device.type != "cuda":
             raise _lib.ZonosHipError("zonos_amd runs on MI355X only: move the model to a cuda device (no CPU fallback)")
         return n
@@ -373,10 +386,11 @@ class Zonos(nn.Module):
         finally:
             release()
 
-    def _generate_on(self, eng, dev, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, B, sampling_params, callback, seed, _trace):
+    def _generate_on(self, eng, dev, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, B, sampling_params, callback, seed, _trace,
+                     cond_lengths=None):
         with torch.cuda.device(dev):
             run = lambda: self._generate_locked(eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, B, sampling_params, callback,
-                                                seed, _trace)
+                                                seed, _trace, cond_lengths)
             return self._with_timeout_policy(run, caller_saw_frames=callback is not None or _trace is not None)
 
     def _with_timeout_policy(self, run, caller_saw_frames: bool):
@@ -395,19 +409,19 @@ class Zonos(nn.Module):
             return run()
 
     def _generate_locked(self, eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params, callback, seed,
-                         _trace):
+                         _trace, cond_lengths=None):
         return _drain(self._generation(eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params, callback,
-                                       seed, _trace, torch.cuda.current_stream(self.device), None)).to(self.device)
+                                       seed, _trace, torch.cuda.current_stream(self.device), None, cond_lengths)).to(self.device)
 
     def _generation(self, eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params, callback, seed,
-                    _trace, ts, chunk):
+                    _trace, ts, chunk, cond_lengths=None):
         """One generation on `eng` (its lock held by the caller), with every launch on torch stream `ts`.  A generator: with `chunk` it yields
         (delayed codes, last column written) every `chunk` decode steps (Zonos.stream), and it returns the final codes on the host."""
         dev = self.device
         B, nq = batch_size, self.config.codebook_dimension
         R = prefix_conditioning.shape[0]                          # 2B with guidance, B when cfg_scale == 1 (checked by generate)
         P = 0 if audio_prefix_codes is None else audio_prefix_codes.shape[2]
-        L_c = prefix_conditioning.shape[1]
+        L_c = prefix_conditioning.shape[1] if cond_lengths is None else max(cond_lengths)      # the KV capacity follows the longest VALID row
         audio_len = P + max_new_tokens
         seq_len = L_c + audio_len + nq
         ip = self.setup_cache(batch_size=R, max_seqlen=seq_len)
@@ -423,7 +437,7 @@ class Zonos(nn.Module):
         eng.call("zn_gen_begin", B, kv_ptrs, ip.max_seqlen, ip.lengths_per_sample.data_ptr(), delayed.data_ptr(), t_total, offset,
                  max_new_tokens, float(cfg_scale), C.byref(sp), st)
         try:
-            offset = yield from self._decode_loop(eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk)
+            offset = yield from self._decode_loop(eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk, cond_lengths)
         finally:
             # the device's persistent-kernel tenancy goes back once this generation's kernels have drained (include/zonos_hip.h)
             ts.synchronize()
@@ -431,7 +445,7 @@ class Zonos(nn.Module):
         out = revert_delay_pattern(delayed.to(torch.int64)).cpu()     # one device->host copy (model.py:511)
         return finalise_codes(out, offset, nq, self.eos_token_id)
 
-    def _decode_loop(self, eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk=None):
+    def _decode_loop(self, eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk=None, cond_lengths=None):
         """Prefill, first frame and the hot loop (model.py:421-509); a generator that returns the final column offset.  With `chunk`, the
         steps are enqueued at least every `chunk` steps and it yields (delayed, column offset written last) there."""
         dev = self.device
@@ -441,7 +455,22 @@ class Zonos(nn.Module):
         reps = prefix_conditioning.shape[0] // B
         hidden = torch.cat([prefix_conditioning.to(device=dev, dtype=torch.bfloat16), emb.repeat(reps, 1, 1)], dim=1).contiguous()
         S = hidden.shape[1]
-        eng.call("zn_prefill", hidden.data_ptr(), S, st)
+        if cond_lengths is None:
+            eng.call("zn_prefill", hidden.data_ptr(), S, st)
+        else:
+            # right-padded rows: row r = [cond_r[:L_r] ‖ emb_r ‖ padding] (the padding keeps whatever the caller's tensor holds there: it is never read)
+            L_c, E, L_max = prefix_conditioning.shape[1], emb.shape[1], max(cond_lengths)
+            embr = emb.repeat(reps, 1, 1)
+            for r in range(hidden.shape[0]):
+                L = cond_lengths[r % B]
+                if L < L_c:
+                    tail = hidden[r, L:L_c].clone()
+                    hidden[r, L:L + E] = embr[r]
+                    hidden[r, L + E:] = tail
+            S = L_max + E
+            hidden = hidden[:, :S].contiguous()
+            row_len = (C.c_int32 * hidden.shape[0])(*[cond_lengths[r % B] + E for r in range(hidden.shape[0])])
+            eng.call("zn_prefill_rows", hidden.data_ptr(), S, row_len, st)
         eng.call("zn_sample_first", st)
         ip.seqlen_offset += S
         if _trace is not None:

@@ -48,7 +48,9 @@ def generate_sharded(generate_fn, conditionings: list[torch.Tensor], gather: boo
     """Run `generate_fn` on this rank's share of `conditionings` (each [2, L_c, d] = [cond ‖ uncond] of one utterance);
     optionally gather.  batch_size == 1: `generate_fn(cond) -> int64 [1, n_q, T]` per utterance.  batch_size > 1: the
     share runs in groups of up to `batch_size` utterances, `generate_fn(cond [2b, L_c, d], b) -> int64 [b, n_q, T]`
-    with rows [cond_0..cond_{b-1}, uncond_0..uncond_{b-1}] (Zonos.generate's batch layout)."""
+    with rows [cond_0..cond_{b-1}, uncond_0..uncond_{b-1}] (Zonos.generate's batch layout).  A group whose conditionings differ in
+    length is right-padded (conditioning.pad_conditionings) and goes out as `generate_fn(cond [2b, L_max, d], b, lengths)`, lengths =
+    the b valid lengths (Zonos.generate's `conditioning_lengths`); groups of one length keep the two-argument call."""
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0
     share = shard_indices(len(conditionings), rank, world)
@@ -58,7 +60,12 @@ def generate_sharded(generate_fn, conditionings: list[torch.Tensor], gather: boo
         mine = []
         for j in range(0, len(share), batch_size):
             grp = [conditionings[i] for i in share[j:j + batch_size]]
-            cond = torch.cat([c[0:1] for c in grp] + [c[1:2] for c in grp], dim=0)
-            codes = generate_fn(cond, len(grp))
+            if len({c.shape[1] for c in grp}) > 1:
+                from .conditioning import pad_conditionings
+                cond, lengths = pad_conditionings(grp, cfg_scale=2.0)
+                codes = generate_fn(cond, len(grp), lengths)
+            else:
+                cond = torch.cat([c[0:1] for c in grp] + [c[1:2] for c in grp], dim=0)
+                codes = generate_fn(cond, len(grp))
             mine.extend(codes[b] for b in range(len(grp)))
     return gather_codes(mine, len(conditionings), group=group) if gather else mine
