@@ -172,7 +172,7 @@ int zn_decode_path_detail(zn_handle h);
 /* Hand-off timeouts are never silent: out[0] = bounded in-kernel hand-off waits that gave up and were reported on this handle (each voids
  * its generation; zn_all_stopped* returns the error), [1] generations begun, [2] batch-1 generations that ran the launches path because
  * an earlier timeout had demoted the handle, [3] 1 while the handle is demoted, [4] times it was re-armed (automatically after 4 clean
- * generations on the launches path, or by zn_debug_tune(8, 1)), [5] clean generations since the demotion, [6] the longest in-kernel hand-off
+ * generations on the launches path, or by zn_debug_tune(ZN_TUNE_PERSISTENT, 1)), [5] clean generations since the demotion, [6] the longest in-kernel hand-off
  * wait any whole-step launch of this handle measured, in microseconds (0: none beyond 0.1 ms; a pause of the device shows up here with its
  * length), [7] waits beyond 0.2 ms.  n <= 8 values are written; asking for [6], [7] synchronises with the device. */
 int zn_get_counters(zn_handle h, int64_t* out, int32_t n);
@@ -209,18 +209,41 @@ int zn_debug_token_override(zn_handle h, const int32_t* tokens_dev, int32_t call
 /* Test hook: 1 = batched prefill (default: MFMA GEMMs + tiled causal attention over all positions), 0 = position by
  * position through the decode kernels (both reproduce the reference's rounding points). */
 int zn_debug_prefill_mode(zn_handle h, int32_t mode);
-/* Tuning hook: target workgroup count of a GEMV class (0 in_proj, 1 out_proj, 2 fc1, 3 fc2, 4 heads); 5: longest context of the
- * fused attention launch (at most 512 keys, one block: beyond, every path walks the blocks with the split pass); 6: 1 = single-step
- * graphs only; 8: 2 = per-op launches instead of the persistent kernels (also ZN_CHAIN=0 at zn_create), 1 = back to the default and
- * re-arm a handle demoted by a hand-off timeout; 15: 2 = one chain launch per block instead of the whole-step kernel at batch 1; 18: 2 = block 0's in_proj as a launch before the
- * whole-step kernel instead of inside it; 16: 2 = the ticketed sampler launch instead of the one-workgroup step tail at batch 1 (the default for greedy decoding), 3 = the one-workgroup tail also with a temperature.  Every path gives bit-identical
- * results.  14: one-shot test hooks for the next generation (7: hand-off tags about to wrap; 9: the timeout word found set; 11: every
- * whole-step launch stops all its waves for 30 ms in block 2, as a paused device would; 13: forget the wait statistics of zn_get_counters
- * [6], [7] now).  Batches of 3 .. 8 utterances (5 .. 16 rows): 9: 2 = fc1's LayerNorm as a launch of its own (default: fc1 normalises its
- * activation chunks from statistics the preceding out_proj's epilogue left per 16-column tile - the same nn.LayerNorm with its sums taken
- * tile-wise, a bf16 ulp apart in about one value of a hundred); 19: value-column parts of the decode attention launches: 1 = never split,
- * 2 = always, other = the default (5 rows and more: 4 workgroups per (row, kv head) in the one-launch shape, 2 per (row, kv head, block)
- * beyond 512 keys; bit-identical either way).  Keys 0 .. 19. */
+/* Keys of zn_debug_tune.  Every setting gives bit-identical results unless its comment says otherwise; 1 restores a switch's default. */
+enum zn_tune_key {
+  ZN_TUNE_WG_IN_PROJ = 0,           /* target workgroups of the in_proj GEMV (up to 4 rows); default 256 */
+  ZN_TUNE_WG_OUT_PROJ = 1,          /* ... of out_proj; default 512 */
+  ZN_TUNE_WG_FC1 = 2,               /* ... of fc1; default 512 */
+  ZN_TUNE_WG_FC2 = 3,               /* ... of fc2 (and the Mamba2 out_proj); default 1024 */
+  ZN_TUNE_WG_HEADS = 4,             /* ... of the heads; default 512 */
+  ZN_TUNE_ATTN_FUSED_MAX_KEYS = 5,  /* longest context of the one-launch decode attention; values above 512 (one block) act as 512; default 512 */
+  ZN_TUNE_GRAPH_RUNS = 6,           /* 1 = single-step graphs only; default 2: graphs of 8 consecutive steps */
+  ZN_TUNE_SMALL_M_LDS = 7,          /* 1 = none of the small-M projection kernels of 5..64 rows (gemm16s, gemm16k, gemm64s); default 2 */
+  ZN_TUNE_PERSISTENT = 8,           /* 2 = per-op launches instead of the persistent kernels (also ZN_CHAIN=0 at zn_create); 1 = the default,
+                                       and re-arms a handle demoted by a hand-off timeout */
+  ZN_TUNE_FC1_LN_LAUNCH = 9,        /* 5..16 rows: 2 = fc1's LayerNorm as a launch of its own; default: fc1 normalises from statistics the preceding
+                                       out_proj's epilogue left per 16-column tile (sums taken tile-wise: a bf16 ulp apart in about one value of a hundred) */
+  ZN_TUNE_PREFILL_ATTN_VALU = 10,   /* 2 = the VALU prefill attention at every head size; default: matrix cores at head size 128 */
+  ZN_TUNE_NO_SPLIT_SMALL_M = 11,    /* 2 = no in-workgroup-split small-M kernel (gemm16k_kernel) anywhere */
+  ZN_TUNE_NO_PREFILL_GEMM16K = 12,  /* 2 = short-prompt prefill projections never take gemm16k_kernel */
+  ZN_TUNE_GEMM16K_MAX_TILES = 13,   /* 16-row weight tiles from which the 64-row workgroups take over from gemm16k_kernel; default (unset) 1024 */
+  ZN_TUNE_HOOK = 14,                /* not a setting: value = a one-shot test hook (enum zn_tune_hook) */
+  ZN_TUNE_WHOLE_STEP = 15,          /* 2 = one chain launch per block instead of the whole-step kernel (also ZN_STACK=0 at zn_create) */
+  ZN_TUNE_SAMPLER = 16,             /* batch 1: 2 = always the ticketed sampler launch, 3 = the one-workgroup step tail also with a temperature;
+                                       default: the one-workgroup tail for greedy decoding */
+  ZN_TUNE_RESERVED_17 = 17,         /* reserved, unused */
+  ZN_TUNE_STACK_PRE = 18,           /* 2 = block 0's in_proj as a launch before the whole-step kernel; default: inside it */
+  ZN_TUNE_ATTN_SPLIT_COLS = 19,     /* value-column parts of the decode attention: 1 = never split, 2 = always; default: from 5 rows on */
+  ZN_TUNE_NKEYS = 20
+};
+/* Values of ZN_TUNE_HOOK.  The first three arm the next zn_gen_begin, which consumes them. */
+enum zn_tune_hook {
+  ZN_HOOK_TAG_WRAP = 7,             /* the generation behaves as if the hand-off tags were about to wrap */
+  ZN_HOOK_TIMEOUT_WORD = 9,         /* the generation's hand-off waits find the timeout word set */
+  ZN_HOOK_PAUSE = 11,               /* every whole-step launch of the generation stops all its waves for 30 ms in block 2, as a paused device would */
+  ZN_HOOK_RESET_WAIT_STATS = 13     /* at once: forget the wait statistics of zn_get_counters [6], [7] */
+};
+/* Tuning and test hook: key in 0 .. ZN_TUNE_NKEYS - 1, value >= 1.  Drops the captured graphs. */
 int zn_debug_tune(zn_handle h, int32_t key, int32_t value);
 /* Diagnostic: workgroup 0 of every persistent chain launch records s_memrealtime (100 MHz) stamps of its phases into
  * stamps_dev [2 * n_layer][32] (NULL = off); rows n_layer.. hold the fused attention launch's (start, length known, scores
@@ -248,12 +271,12 @@ int zn_op_backbone_forward(zn_handle h, const void* hidden_dev, void* out_dev, c
 /* Average duration (HIP events on `stream`) of one of the decode step's weight-streaming kernels over `iters`
  * launches that cycle through the layers' weights, and its algorithmic bytes per launch (the weight matrix).
  * which: 0 = LayerNorm+fc1+SiLU-gate (5..16 rows: the one launch a decode step makes there, fc1 normalising from the statistics its
- * producer left - that producer runs once outside the timed loop; zn_debug_tune(9, 2): the LayerNorm launch + fc1), 1 = fc2+residual, 2 = out_proj+residual, 3 = LayerNorm+heads,
+ * producer left - that producer runs once outside the timed loop; zn_debug_tune(ZN_TUNE_FC1_LN_LAUNCH, 2): the LayerNorm launch + fc1), 1 = fc2+residual, 2 = out_proj+residual, 3 = LayerNorm+heads,
  * 4 = LayerNorm+in_proj+RoPE+KV-append (into a scratch cache), 5 = the persistent post-attention chain of one block
  * (out_proj twice, LayerNorm+fc1+SiLU-gate, fc2, next block's LayerNorm+in_proj+RoPE+KV-append in ONE launch: batch 1 only;
  * bytes = those four weight matrices, out_proj counted once), 6 = the whole-step kernel (every block of a decode step and the heads in
  * ONE launch, one or two rows) on scratch KV caches of its own holding `ctx` keys per row; bytes = every weight the step reads once
- * (in_proj of block 0 included: the launch's pre-block; excluded under zn_debug_tune(18, 2), where it is a launch of its own) + K/V of
+ * (in_proj of block 0 included: the launch's pre-block; excluded under zn_debug_tune(ZN_TUNE_STACK_PRE, 2), where it is a launch of its own) + K/V of
  * ctx keys read and one row written per layer.
  * rows: bits 0-7 = activation rows; bit 8 = keep streaming layer 0's weights (cache-hot variant); bits 16-30 = ctx for which == 6
  * (0 = 450, the mean context of a 10 s utterance). */

@@ -17,6 +17,32 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(zn_[a-z0-9_]+)\s*\(", src)))
 
 
+def declared_enumerators():
+    """name -> value of every enumerator of zn_tune_key and zn_tune_hook in the header."""
+    src = open(os.path.join(ROOT, "include", "zonos_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    out = {}
+    for enum in ("zn_tune_key", "zn_tune_hook"):
+        body = re.search(r"\benum\s+%s\s*\{(.*?)\}" % enum, src, flags=re.S).group(1)
+        for item in filter(None, (i.strip() for i in body.split(","))):
+            name, value = re.fullmatch(r"(ZN_[A-Z0-9_]+)\s*=\s*(\d+)", item).groups()      # every enumerator carries its number
+            assert name not in out
+            out[name] = int(value)
+    return out
+
+
+def test_tune_keys_agree_between_header_and_binding():
+    """zn_debug_tune's keys and hook values have one name and one number on both sides of the C ABI."""
+    header = declared_enumerators()
+    binding = {k: v for k, v in vars(_lib).items() if k.startswith(("ZN_TUNE_", "ZN_HOOK_"))}
+    assert binding == header
+    keys = {k: v for k, v in header.items() if k.startswith("ZN_TUNE_") and k != "ZN_TUNE_NKEYS"}
+    assert sorted(keys.values()) == list(range(header["ZN_TUNE_NKEYS"])), "one enumerator per key, no gaps, no aliases"
+    assert {k: v for k, v in header.items() if k.startswith("ZN_HOOK_")} == {
+        "ZN_HOOK_TAG_WRAP": 7, "ZN_HOOK_TIMEOUT_WORD": 9, "ZN_HOOK_PAUSE": 11, "ZN_HOOK_RESET_WAIT_STATS": 13}
+    assert (header["ZN_TUNE_PERSISTENT"], header["ZN_TUNE_HOOK"], header["ZN_TUNE_WHOLE_STEP"]) == (8, 14, 15)   # the numbers callers have always used
+
+
 @pytest.fixture(scope="module")
 def lib():
     from zonos_amd import build

@@ -90,7 +90,7 @@ def _traced(model, cond, pre, new, cfg_scale, B=1):
 def test_full_dims_one_row_kernel_is_bit_identical(full, prefix, new):
     """One unguided utterance at the Zonos-v0.1 dimensions runs the one-row whole-step kernel (zn_decode_path_detail == 2) up to 6144
     keys and the launches path beyond.  Codes and every traced step's logits are bit-identical to (i) the launches path at one row
-    (zn_debug_tune(8, 2)) and (ii) the guided run on [c ‖ c] at cfg_scale=2 (the two-row kernel); contexts from 26 keys, across
+    (zn_debug_tune(ZN_TUNE_PERSISTENT, 2)) and (ii) the guided run on [c ‖ c] at cfg_scale=2 (the two-row kernel); contexts from 26 keys, across
     512 keys, the 3072- and 4096-key changes of instantiation and 6144 keys; 8-step graphs; no hand-off timeout; a second run equal."""
     model, _ = full
     eng = model.engine(1)
@@ -104,10 +104,10 @@ def test_full_dims_one_row_kernel_is_bit_identical(full, prefix, new):
         assert eng.lib.zn_decode_path_detail(eng.h) == (2 if end_ctx + 8 <= 6144 else 0), eng.lib.zn_decode_path_detail(eng.h)
         o1b, l1b = _traced(model, c, pre, new, 1.0)
         o2, l2 = _traced(model, torch.cat([c, c], 0), pre, new, 2.0)
-        eng.call("zn_debug_tune", 8, 2)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 2)
         o3, l3 = _traced(model, c, pre, new, 1.0)
         assert eng.lib.zn_decode_path_detail(eng.h) == 0
-        eng.call("zn_debug_tune", 8, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1)
         assert o1.shape[-1] == prefix + new
         for o, l in ((o1b, l1b), (o2, l2), (o3, l3)):
             assert torch.equal(o, o1)
@@ -118,7 +118,7 @@ def test_full_dims_one_row_kernel_is_bit_identical(full, prefix, new):
         assert torch.equal(plain[0], o1) and torch.equal(plain[1], o1)
         assert eng.counters()["handoff_timeouts"] == t0
     finally:
-        eng.call("zn_debug_tune", 8, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1)
         eng.call("zn_debug_eos_bias", 0.0)
 
 

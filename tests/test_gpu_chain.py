@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from oracle import zonos_oracle as zo
-from zonos_amd import synth
+from zonos_amd import _lib, synth
 from zonos_amd.testing import build_model
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +20,7 @@ GREEDY = {"temperature": 0.0}
 
 def _run(model, cond, max_new, toks=None, chain=True, prefix=None):
     eng = model.engine(1)
-    eng.call("zn_debug_tune", 8, 1 if chain else 2)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1 if chain else 2)
     eng.call("zn_debug_eos_bias", float("-inf"))
     if toks is not None:
         tk = torch.from_numpy(toks.astype(np.int32)).to("cuda:0").contiguous()
@@ -32,7 +32,7 @@ def _run(model, cond, max_new, toks=None, chain=True, prefix=None):
     finally:
         eng.call("zn_debug_token_override", None, 0)
         eng.call("zn_debug_eos_bias", 0.0)
-        eng.call("zn_debug_tune", 8, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1)
     return out.cpu(), torch.stack(tr["logits"]).cpu(), path
 
 
@@ -65,19 +65,19 @@ def test_chain_generate_vs_oracle():
 
 @pytest.mark.parametrize("which", ["chain512", "full-chain", "full-step", "full-step-nopre"])
 def test_chain_is_bit_identical_to_the_launches_path(which):
-    """Free-running greedy generation through the persistent kernels and through the per-op launches (zn_debug_tune(8, 2)).  At the
+    """Free-running greedy generation through the persistent kernels and through the per-op launches (zn_debug_tune(ZN_TUNE_PERSISTENT, 2)).  At the
     Zonos-v0.1-transformer dimensions every path cuts every dot product the same way (fc2's K = 8192 in four quarters): equal
     codes and bit-equal logits at every step (200 steps: 8-step graphs, the fused attention arithmetic, hand-offs replayed
-    26 x 6 x 200 times), for one chain launch per block (zn_debug_tune(15, 2)), for the whole-step kernel (the default: block 0's in_proj
-    inside the launch, on the helper and communication waves) and for the whole-step kernel behind an in_proj launch (zn_debug_tune(18, 2)).  At
+    26 x 6 x 200 times), for one chain launch per block (zn_debug_tune(ZN_TUNE_WHOLE_STEP, 2)), for the whole-step kernel (the default: block 0's in_proj
+    inside the launch, on the helper and communication waves) and for the whole-step kernel behind an in_proj launch (zn_debug_tune(ZN_TUNE_STACK_PRE, 2)).  At
     d_model 512 the launches path keeps fc2's K = 2048 in one wave while the chain splits it in quarters - another summation
     order: equal codes, logits within one bf16 ulp of a hidden value."""
     cfg, seed, n = (synth.CHAIN_CFG, 55, 60) if which == "chain512" else (synth.FULL_CFG, 1234, 200)
     model, _ = build_model(cfg, seed, "cuda:0")
     eng = model.engine(1)
     cond = synth.conditioning(seed, "cond", 2, 24, cfg["d_model"])
-    eng.call("zn_debug_tune", 15, {"full-chain": 2}.get(which, 1))
-    eng.call("zn_debug_tune", 18, 2 if which == "full-step-nopre" else 1)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, {"full-chain": 2}.get(which, 1))
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_STACK_PRE, 2 if which == "full-step-nopre" else 1)
     try:
         a, la, pa = _run(model, cond, n, chain=True)
         b, lb, pb = _run(model, cond, n, chain=False)
@@ -97,13 +97,13 @@ def test_chain_is_bit_identical_to_the_launches_path(which):
         assert torch.equal(a, a2) and torch.equal(la.view(torch.int32), la2.view(torch.int32))
         assert eng.counters()["handoff_timeouts"] == 0
     finally:
-        eng.call("zn_debug_tune", 15, 1)
-        eng.call("zn_debug_tune", 18, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_STACK_PRE, 1)
 
 
 def test_whole_step_kernel_is_bit_identical_to_the_chain_path():
     """The whole-step kernel (csrc/zn_step_kernel.h: every block of the decode step in ONE launch; the default at batch 1) against one
-    attention launch (two beyond 512 keys) + one chain launch per block (zn_debug_tune(15, 2)) at the Zonos-v0.1-transformer dimensions:
+    attention launch (two beyond 512 keys) + one chain launch per block (zn_debug_tune(ZN_TUNE_WHOLE_STEP, 2)) at the Zonos-v0.1-transformer dimensions:
     free-running greedy codes equal and the logits of every step bit-equal, over single-step launches (trace mode, 40 steps) and over
     8-step graphs (300 steps: contexts 26 .. 333), with an audio prefix (contexts 426 .. 700, across the 512-key boundary where a second
     attention workgroup per (row, kv head) joins) and through the second and third block (contexts 650 .. 1050, logits of every step).  A hand-off timeout is an error (the bounded waits describe themselves: zn_last_error)."""
@@ -112,10 +112,10 @@ def test_whole_step_kernel_is_bit_identical_to_the_chain_path():
     eng = model.engine(1)
     cond = synth.conditioning(seed, "cond", 2, 24, cfg["d_model"])
     try:
-        eng.call("zn_debug_tune", 15, 2)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, 2)
         a, la, pa = _run(model, cond, 40)
         assert eng.lib.zn_decode_path_detail(eng.h) == 1
-        eng.call("zn_debug_tune", 15, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, 1)
         b, lb, pb = _run(model, cond, 40)
         assert eng.lib.zn_decode_path_detail(eng.h) == 2, "the whole-step kernel did not serve this configuration"
         assert torch.equal(a, b)
@@ -123,20 +123,20 @@ def test_whole_step_kernel_is_bit_identical_to_the_chain_path():
         eng.call("zn_debug_eos_bias", float("-inf"))
         outs = []
         for t15 in (2, 1):
-            eng.call("zn_debug_tune", 15, t15)
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, t15)
             outs.append(model.generate(cond.to("cuda:0"), max_new_tokens=300, sampling_params=GREEDY).cpu())
         assert torch.equal(outs[0], outs[1])
         pre = torch.from_numpy(synth.randint(seed, "prefix", (1, 9, 400), 1024)).to("cuda:0")
         outs = []
         for t15 in (2, 1):
-            eng.call("zn_debug_tune", 15, t15)
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, t15)
             outs.append(model.generate(cond.to("cuda:0"), audio_prefix_codes=pre, max_new_tokens=268, sampling_params=GREEDY).cpu())
             assert eng.lib.zn_decode_path_detail(eng.h) == (1 if t15 == 2 else 2)
         assert torch.equal(outs[0], outs[1])
         pre = torch.from_numpy(synth.randint(seed, "prefix2", (1, 9, 620), 1024)).to("cuda:0")
         outs = []
         for t15 in (2, 1):
-            eng.call("zn_debug_tune", 15, t15)
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, t15)
             tr = {"logits": []}
             o = model.generate(cond.to("cuda:0"), audio_prefix_codes=pre, max_new_tokens=400, sampling_params=GREEDY, _trace=tr)
             outs.append((o.cpu(), torch.stack(tr["logits"]).cpu()))
@@ -145,7 +145,7 @@ def test_whole_step_kernel_is_bit_identical_to_the_chain_path():
         assert torch.equal(outs[0][1].view(torch.int32), outs[1][1].view(torch.int32))
         assert eng.counters()["handoff_timeouts"] == 0
     finally:
-        eng.call("zn_debug_tune", 15, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, 1)
         eng.call("zn_debug_eos_bias", 0.0)
 
 
@@ -153,8 +153,8 @@ def test_whole_step_kernel_at_long_contexts_is_bit_identical_to_the_per_block_pa
     """Contexts beyond 1024 keys (the reference's default call is 30 s = 2.6 k keys, `zonos/model.py:359`; BASELINE config 5 runs at
     2.6 - 5.2 k): the whole-step kernel's attention role (one workgroup per (row, kv head, 512-key block), K and full-width V of
     the block in registers a block ahead, block maxima and partials exchanged as granules, the in-order combine of the split P.V pass)
-    against the per-block path (attn_scores_kernel + attn_block_kernel + one chain launch per block, zn_debug_tune(15, 2)) and, for
-    the traced steps, against the launches path (zn_debug_tune(8, 2)): equal codes over the whole run (8-step graphs; contexts 1025 ..
+    against the per-block path (attn_scores_kernel + attn_block_kernel + one chain launch per block, zn_debug_tune(ZN_TUNE_WHOLE_STEP, 2)) and, for
+    the traced steps, against the launches path (zn_debug_tune(ZN_TUNE_PERSISTENT, 2)): equal codes over the whole run (8-step graphs; contexts 1025 ..
     2725, 2585 .. 5225 = config 5, and across the 3072- and 4096-key changes of instantiation, up to the kernel's 6144-key limit and
     past it, where both runs take the per-block path) and bit-equal logits at every traced step."""
     cfg, seed = synth.FULL_CFG, 1234
@@ -171,15 +171,15 @@ def _long_context_case(model, eng, cond, seed, prefix, new, traced):
         eng.call("zn_debug_eos_bias", float("-inf"))
         outs = []
         for t15 in (2, 1):
-            eng.call("zn_debug_tune", 15, t15)
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, t15)
             outs.append(model.generate(cond, audio_prefix_codes=pre, max_new_tokens=new, sampling_params=GREEDY).cpu())
             want = 1 if (t15 == 2 or 24 + prefix + new + 8 > 6144) else 2
             assert eng.lib.zn_decode_path_detail(eng.h) == want, (t15, eng.lib.zn_decode_path_detail(eng.h))
         assert outs[0].shape[-1] == prefix + new and torch.equal(outs[0], outs[1])
         logs = []
         for t15, t8 in ((2, 1), (1, 1), (1, 2)):
-            eng.call("zn_debug_tune", 15, t15)
-            eng.call("zn_debug_tune", 8, t8)
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, t15)
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, t8)
             tr = {"logits": []}
             o = model.generate(cond, audio_prefix_codes=pre, max_new_tokens=traced, sampling_params=GREEDY, _trace=tr)
             logs.append((o.cpu(), torch.stack(tr["logits"]).cpu()))
@@ -188,8 +188,8 @@ def _long_context_case(model, eng, cond, seed, prefix, new, traced):
             assert torch.equal(lg.view(torch.int32), logs[0][1].view(torch.int32))
         assert eng.counters()["handoff_timeouts"] == 0
     finally:
-        eng.call("zn_debug_tune", 8, 1)
-        eng.call("zn_debug_tune", 15, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, 1)
         eng.call("zn_debug_eos_bias", 0.0)
 
 
@@ -222,7 +222,7 @@ def test_second_generation_on_the_device_takes_the_launches_path():
 
 def test_handoff_tags_restart_before_they_can_wrap():
     """The hand-off tags are 32-bit and advance by n_layer per decode step (about 41 hours of continuous batch-1 decoding).  Between two
-    generations, long before a wrap, zn_gen_begin restarts the epoch at 1 over zeroed granule buffers; zn_debug_tune(14, 7) makes the next
+    generations, long before a wrap, zn_gen_begin restarts the epoch at 1 over zeroed granule buffers; zn_debug_tune(ZN_TUNE_HOOK, ZN_HOOK_TAG_WRAP) makes the next
     zn_gen_begin take that branch: the generation after it must be unaffected (same codes, same logits, no stale tag accepted)."""
     cfg, seed = synth.FULL_CFG, 1234
     model, _ = build_model(cfg, seed, "cuda:0")
@@ -230,7 +230,7 @@ def test_handoff_tags_restart_before_they_can_wrap():
     cond = synth.conditioning(seed, "cond", 2, 24, cfg["d_model"])
     a, la, _ = _run(model, cond, 40)
     assert eng.lib.zn_decode_path_detail(eng.h) == 2
-    eng.call("zn_debug_tune", 14, 7)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_HOOK, _lib.ZN_HOOK_TAG_WRAP)
     b, lb, _ = _run(model, cond, 40)
     assert torch.equal(a, b) and torch.equal(la.view(torch.int32), lb.view(torch.int32))
     c, lc, _ = _run(model, cond, 40)                       # and the epoch counts on from 1 afterwards
@@ -240,9 +240,9 @@ def test_handoff_tags_restart_before_they_can_wrap():
 def test_a_reported_handoff_timeout_is_survived(capfd, monkeypatch):
     """A bounded hand-off wait that gives up voids the generation and demotes the handle to the launches path.  Under the test suite's
     setting (ZONOS_HIP_NO_TIMEOUT_RETRY=1, tests/conftest.py) `Zonos.generate` raises; without it - and when the caller has not seen any
-    frame yet - it repeats the generation on the launches path, says so on stderr and counts it.  zn_debug_tune(14, 9) sets the sticky
+    frame yet - it repeats the generation on the launches path, says so on stderr and counts it.  zn_debug_tune(ZN_TUNE_HOOK, ZN_HOOK_TIMEOUT_WORD) sets the sticky
     timeout word for the next generation (every wait gives up at once).  The demotion is visible (zn_get_counters) and temporary: four
-    clean generations on the launches path, or zn_debug_tune(8, 1), re-arm the persistent kernels."""
+    clean generations on the launches path, or zn_debug_tune(ZN_TUNE_PERSISTENT, 1), re-arm the persistent kernels."""
     cfg, seed = synth.FULL_CFG, 1234
     model, _ = build_model(cfg, seed, "cuda:0")
     eng = model.engine(1)
@@ -251,15 +251,15 @@ def test_a_reported_handoff_timeout_is_survived(capfd, monkeypatch):
     try:
         ref = model.generate(cond, max_new_tokens=40, sampling_params=GREEDY).cpu()
         assert eng.lib.zn_decode_path_detail(eng.h) == 2 and eng.counters()["handoff_timeouts"] == 0
-        eng.call("zn_debug_tune", 14, 9)                        # the suite's setting: the timeout is an error
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_HOOK, _lib.ZN_HOOK_TIMEOUT_WORD)                        # the suite's setting: the timeout is an error
         with pytest.raises(Exception, match="hand-off wait"):
             model.generate(cond, max_new_tokens=40, sampling_params=GREEDY)
         c = eng.counters()
         assert c["handoff_timeouts"] == 1 and c["demoted"] == 1 and model.handoff_counters()["repeated_generations"] == 0
-        eng.call("zn_debug_tune", 8, 1)                         # re-arm at once
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1)                         # re-arm at once
         assert eng.counters()["demoted"] == 0 and eng.counters()["rearms"] == 1
         monkeypatch.delenv("ZONOS_HIP_NO_TIMEOUT_RETRY")        # production behaviour: repeat once, loudly
-        eng.call("zn_debug_tune", 14, 9)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_HOOK, _lib.ZN_HOOK_TIMEOUT_WORD)
         out = model.generate(cond, max_new_tokens=40, sampling_params=GREEDY).cpu()
         err = capfd.readouterr().err
         assert "hand-off wait" in err and "repeating the generation" in err
@@ -273,14 +273,14 @@ def test_a_reported_handoff_timeout_is_survived(capfd, monkeypatch):
         again = model.generate(cond, max_new_tokens=40, sampling_params=GREEDY).cpu()     # the fifth: re-armed
         c = eng.counters()
         assert torch.equal(again, ref) and eng.lib.zn_decode_path_detail(eng.h) == 2 and c["demoted"] == 0 and c["rearms"] == 2 and c["fallback_generations"] == 4
-        eng.call("zn_debug_tune", 14, 9)                        # with a callback the caller has seen frames: the error is raised, not hidden
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_HOOK, _lib.ZN_HOOK_TIMEOUT_WORD)                        # with a callback the caller has seen frames: the error is raised, not hidden
         with pytest.raises(Exception, match="hand-off wait"):
             model.generate(cond, max_new_tokens=40, sampling_params=GREEDY, callback=lambda f, s_, m: True)
-        eng.call("zn_debug_tune", 8, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1)
         again = model.generate(cond, max_new_tokens=40, sampling_params=GREEDY).cpu()
         assert torch.equal(again, ref) and eng.lib.zn_decode_path_detail(eng.h) == 2
     finally:
-        eng.call("zn_debug_tune", 8, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1)
         eng.call("zn_debug_eos_bias", 0.0)
 
 
@@ -297,12 +297,12 @@ def test_two_concurrent_requests_on_one_model():
     eng = model.engine(1)
     solo = {}                                                   # zn_decode_path -> the solo codes of both requests
     try:
-        for path, t8 in ((1, 1), (0, 2)):                       # persistent kernels, then the launches path (zn_debug_tune(8, 2))
-            eng.call("zn_debug_tune", 8, t8)
+        for path, t8 in ((1, 1), (0, 2)):                       # persistent kernels, then the launches path (zn_debug_tune(ZN_TUNE_PERSISTENT, 2))
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, t8)
             solo[path] = [model.generate(c, max_new_tokens=120, sampling_params=GREEDY).cpu() for c in conds]
             assert eng.lib.zn_decode_path(eng.h) == path
     finally:
-        eng.call("zn_debug_tune", 8, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1)
     assert model._spare is None
     outs, errs = [None, None], []
     gate = threading.Barrier(2)
@@ -333,7 +333,7 @@ def test_two_concurrent_requests_on_one_model():
 
 def test_single_workgroup_sampler_matches_the_ticketed_sampler():
     """Batch 1: sample1_kernel (one workgroup: a wave per codebook, bookkeeping and the next embedding behind a barrier) against
-    sample_kernel + its ticketed tail (zn_debug_tune(16, 2)): same codes and same logits over greedy decoding, temperature + min_p
+    sample_kernel + its ticketed tail (zn_debug_tune(ZN_TUNE_SAMPLER, 2)): same codes and same logits over greedy decoding, temperature + min_p
     sampling with a repetition window, and a run that ends through the EOS bookkeeping (forced EOS: masks, remaining counters)."""
     cfg, seed = synth.FULL_CFG, 1234
     model, _ = build_model(cfg, seed, "cuda:0")
@@ -345,7 +345,7 @@ def test_single_workgroup_sampler_matches_the_ticketed_sampler():
         for sp, force in cases:
             outs = []
             for t16 in (2, 3):                              # 3: sample1_kernel also for the sampled cases (the default keeps it to greedy decoding)
-                eng.call("zn_debug_tune", 16, t16)
+                eng.call("zn_debug_tune", _lib.ZN_TUNE_SAMPLER, t16)
                 eng.call("zn_debug_eos_bias", float("-inf") if force is None else 0.0)
                 eng.call("zn_debug_force_eos", -1 if force is None else force)
                 tr = {"logits": []}
@@ -358,13 +358,13 @@ def test_single_workgroup_sampler_matches_the_ticketed_sampler():
             if force is not None:
                 assert outs[0][0].shape[-1] < 64, "the forced EOS did not end the generation"
     finally:
-        eng.call("zn_debug_tune", 16, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_SAMPLER, 1)
         eng.call("zn_debug_force_eos", -1)
         eng.call("zn_debug_eos_bias", 0.0)
 
 
 def test_a_device_pause_inside_the_attention_wait_is_survived(capfd):
-    """zn_debug_tune(14, 11): every whole-step launch of the next generation stops all its waves for 30 ms in block 2 - the attention
+    """zn_debug_tune(ZN_TUNE_HOOK, ZN_HOOK_PAUSE): every whole-step launch of the next generation stops all its waves for 30 ms in block 2 - the attention
     workgroups inside the wait their pacer measures, the streaming workgroups outside theirs - which is how a pause of the device
     (queue preemption) looks from inside the kernel.  The pacer must not turn the 30 ms "wait" into the next block's sleep (uncapped it
     did: the attention workgroups slept 22 ms while the streaming ones polled past the 20 ms / 4096-pass bound; the second record in
@@ -376,7 +376,7 @@ def test_a_device_pause_inside_the_attention_wait_is_survived(capfd):
     try:
         eng.call("zn_debug_eos_bias", float("-inf"))
         ref = model.generate(cond, max_new_tokens=12, sampling_params=GREEDY).cpu()
-        eng.call("zn_debug_tune", 14, 11)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_HOOK, _lib.ZN_HOOK_PAUSE)
         t0 = time.perf_counter()
         out = model.generate(cond, max_new_tokens=12, sampling_params=GREEDY).cpu()
         dt = time.perf_counter() - t0
@@ -393,5 +393,5 @@ def test_a_device_pause_inside_the_attention_wait_is_survived(capfd):
     # diagnostic words (zn_get_counters [6], [7]; tools/soak.py logs real pauses of the device this way)
     c = eng.counters()
     assert c["handoff_timeouts"] == 0 and c["longest_wait_us"] >= 29000 and c["waits_over_200us"] >= 8, c
-    eng.call("zn_debug_tune", 14, 13)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_HOOK, _lib.ZN_HOOK_RESET_WAIT_STATS)
     assert eng.counters()["longest_wait_us"] == 0

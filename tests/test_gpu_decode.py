@@ -212,7 +212,7 @@ def test_attention_decode_vs_cpu_sdpa(full, fused_limit):
     import torch.nn.functional as F
     model, _ = full
     eng = model.engine(1)
-    eng.call("zn_debug_tune", 5, fused_limit)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_ATTN_FUSED_MAX_KEYS, fused_limit)
     st = _lib.stream_ptr()
     gen = torch.Generator().manual_seed(0)
     for L in (1, 5, 16, 17, 31, 300, 512, 513, 530, 900, 1500):
@@ -231,7 +231,7 @@ def test_attention_decode_vs_cpu_sdpa(full, fused_limit):
         eq = float((got.view(torch.int16) == r.contiguous().view(torch.int16)).float().mean())
         print(f"\n[attn L={L}] bit-equal {eq:.5f} max|d| {(got.float() - r.float()).abs().max().item():.3g}")
         assert eq > 0.99, (L, eq)
-    eng.call("zn_debug_tune", 5, 512)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_ATTN_FUSED_MAX_KEYS, 512)
 
 
 def test_attention_long_context_split_pass_vs_cpu_sdpa(full):
@@ -263,7 +263,7 @@ def test_attention_long_context_split_pass_vs_cpu_sdpa(full):
 
 def test_attention_value_column_split_is_bit_identical(full):
     """Batches of 3..8 utterances launch TWO workgroups per (row, kv head[, 512-key block]), each with all the scores / P of the pair and
-    part of the value columns (attn_block_kernel<..., DS>; zn_debug_tune(19, 2) forces it, (19, 1) forbids it).  A column of P.V depends
+    part of the value columns (attn_block_kernel<..., DS>; zn_debug_tune(ZN_TUNE_ATTN_SPLIT_COLS, 2) forces it, (ZN_TUNE_ATTN_SPLIT_COLS, 1) forbids it).  A column of P.V depends
     on P and its own V column only, so the outputs must be the SAME BITS as the unsplit launches: 16 rows of ragged lengths (one block, the
     512 / 513 boundary, several blocks, a row of one key), both launch shapes, twice each (the split shape's tickets return to zero); one
     case against torch CPU SDPA as well, so that the common value is the right one."""
@@ -284,7 +284,7 @@ def test_attention_value_column_split_is_bit_identical(full):
             lengths = torch.tensor([l - 1 for l in lens], dtype=torch.int32, device="cuda:0")
             outs = {}
             for mode in (1, 2):
-                eng.call("zn_debug_tune", 19, mode)
+                eng.call("zn_debug_tune", _lib.ZN_TUNE_ATTN_SPLIT_COLS, mode)
                 out = torch.full((R, 2048), float("nan"), dtype=torch.bfloat16, device="cuda:0")
                 for rep in range(2):
                     eng.call("zn_op_attn_decode", qd.data_ptr(), kvd.data_ptr(), cap, lengths.data_ptr(), None, out.data_ptr(), R, st)
@@ -299,7 +299,7 @@ def test_attention_value_column_split_is_bit_identical(full):
             print(f"\n[attn value-column split, capacity {cap}] 16 rows bit-identical to the unsplit launches; row {r0} (L = {L}) vs CPU SDPA bit-equal {eq:.5f}")
             assert eq > 0.99
     finally:
-        eng.call("zn_debug_tune", 19, 3)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_ATTN_SPLIT_COLS, 3)
 
 
 @pytest.mark.parametrize("kernel", [1, 2], ids=["mfma", "valu"])
@@ -311,7 +311,7 @@ def test_attention_prefill_vs_cpu_sdpa(full, kernel):
     import torch.nn.functional as F
     model, _ = full
     eng = model.engine(1)
-    eng.call("zn_debug_tune", 10, kernel)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_PREFILL_ATTN_VALU, kernel)
     st = _lib.stream_ptr()
     gen = torch.Generator().manual_seed(2)
     try:
@@ -330,7 +330,7 @@ def test_attention_prefill_vs_cpu_sdpa(full, kernel):
             print(f"\n[prefill attn kernel={kernel} S={S}] bit-equal {eq:.5f} max|d| {(got.float() - ref.float()).abs().max().item():.3g}")
             assert eq > 0.99, (S, eq)
     finally:
-        eng.call("zn_debug_tune", 10, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PREFILL_ATTN_VALU, 1)
 
 
 @pytest.mark.parametrize("n_kv", [8, 4, 1], ids=["group1", "group2", "group8"])
@@ -364,13 +364,13 @@ def test_attention_other_group_sizes_vs_cpu_sdpa(n_kv):
         qd1 = q[:, :, -1].reshape(2, 1024).contiguous().to("cuda:0")
         lengths = torch.full((2,), S - 1, dtype=torch.int32, device="cuda:0")
         for fused_limit in (512, 1):                                     # S = 37, 300: the fused launch and the two passes; 700: two passes
-            eng.call("zn_debug_tune", 5, fused_limit)
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_ATTN_FUSED_MAX_KEYS, fused_limit)
             o1 = torch.empty(2, 1024, dtype=torch.bfloat16, device="cuda:0")
             eng.call("zn_op_attn_decode", qd1.data_ptr(), kvd.data_ptr(), cap, lengths.data_ptr(), None, o1.data_ptr(), 2, st)
             torch.cuda.synchronize()
             eqd = float((o1.cpu().view(2, 8, 128).view(torch.int16) == refd.contiguous().view(torch.int16)).float().mean())
             assert eqd > 0.99, (n_kv, S, fused_limit, eqd)
-    eng.call("zn_debug_tune", 5, 512)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_ATTN_FUSED_MAX_KEYS, 512)
 
 
 def test_layer0_decode_vs_reference_block(golden_dir, full):
@@ -521,10 +521,10 @@ def test_baseline_length_generation_properties(full):
         a = model.generate(cond, max_new_tokens=861, sampling_params=GREEDY)
         b = model.generate(cond, max_new_tokens=861, sampling_params=GREEDY)
         short = model.generate(cond, max_new_tokens=200, sampling_params=GREEDY)
-        eng.call("zn_debug_tune", 6, 1)                      # single-step launches only
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_GRAPH_RUNS, 1)                      # single-step launches only
         c = model.generate(cond, max_new_tokens=861, sampling_params=GREEDY)
     finally:
-        eng.call("zn_debug_tune", 6, 2)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_GRAPH_RUNS, 2)
         eng.call("zn_debug_eos_bias", 0.0)
     assert tuple(a.shape) == (1, 9, 861) and a.dtype == torch.int64
     assert int(a.min()) >= 0 and int(a.max()) <= 1023
@@ -580,11 +580,11 @@ def test_config5_longform_generation_properties(full):
     # whole-step kernel vs the per-op launches, same token stream
     toks = synth.randint(5, "c5.stream", (80, 1, 9), 1024).astype(np.int32)      # covers all 1 + 64 + 8 sampling calls
     out1, l1 = _override_generate(model, cond.cpu(), toks, 64, 1, prefix=pre)
-    eng.call("zn_debug_tune", 8, 2)                            # per-op launches
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 2)                            # per-op launches
     try:
         out2, l2 = _override_generate(model, cond.cpu(), toks, 64, 1, prefix=pre)
     finally:
-        eng.call("zn_debug_tune", 8, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1)
     assert torch.equal(out1, out2)
     d = max(float(np.abs(np.where(np.isfinite(x), x - y, 0.0)).max()) for x, y in zip(l1, l2))
     print(f"\n[config 5] whole-step kernel vs per-op launches over 73 calls at context 2.6 k: max |dlogit| {d:.4g}")
@@ -605,12 +605,12 @@ def test_rope_table_limit_full_dims_properties(full):
     try:
         a = model.generate(cond, audio_prefix_codes=pre, max_new_tokens=N, sampling_params=GREEDY)
         b = model.generate(cond, audio_prefix_codes=pre, max_new_tokens=N, sampling_params=GREEDY)
-        eng.call("zn_debug_tune", 6, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_GRAPH_RUNS, 1)
         c = model.generate(cond, audio_prefix_codes=pre, max_new_tokens=N, sampling_params=GREEDY)
         with pytest.raises(_lib.ZonosHipError, match="RoPE"):
             model.generate(cond, audio_prefix_codes=pre, max_new_tokens=N + 8, sampling_params=GREEDY)
     finally:
-        eng.call("zn_debug_tune", 6, 2)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_GRAPH_RUNS, 2)
         eng.call("zn_debug_eos_bias", 0.0)
     assert tuple(a.shape) == (1, 9, P + N) and torch.equal(a[..., :P], pre.to(torch.int64))
     assert torch.equal(a, b) and torch.equal(a, c)
@@ -1011,7 +1011,7 @@ def test_small_m_projections_match_the_gemv_path(full):
 def test_fc1_layernorm_from_handed_over_statistics(full, R):
     """Rows 5..16: fc1's nn.LayerNorm (_torch.py:325, `norm2`) is not a launch - the second out_proj's epilogue leaves {sum, centred second
     moment} per row and 16-column tile, fc1 adds the tiles in a fixed order and normalises its activation chunks while staging them
-    (gemm16s_kernel<EPI_SILU, ., true>).  Against the same block with layernorm_kernel in between (zn_debug_tune(9, 2)): the statistics are
+    (gemm16s_kernel<EPI_SILU, ., true>).  Against the same block with layernorm_kernel in between (zn_debug_tune(ZN_TUNE_FC1_LN_LAUNCH, 2)): the statistics are
     the same numbers summed in another order (tile-wise instead of lane-wise), so the normalised rows may differ by a bf16 ulp here and
     there; block output bit-equal > 0.98 and within 2^-6 of its scale, new K/V (produced before the change) bit-equal; ragged row counts
     (10, 5: clamped rows of the last group; 24: two row groups per launch pair) included.  The batch-8 tests above hold the path against the oracle."""
@@ -1026,14 +1026,14 @@ def test_fc1_layernorm_from_handed_over_statistics(full, R):
     outs = {}
     try:
         for mode in (1, 2):
-            eng.call("zn_debug_tune", 9, mode)
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_FC1_LN_LAUNCH, mode)
             xa, kva = x0.clone().to("cuda:0"), kv0.clone().to("cuda:0")
             for layer in (0, 11):
                 eng.call("zn_op_layer_decode", layer, xa.data_ptr(), kva.data_ptr(), max_len, lengths.data_ptr(), None, R, st)
             torch.cuda.synchronize()
             outs[mode] = (xa.cpu(), kva[:, L - 1].cpu())
     finally:
-        eng.call("zn_debug_tune", 9, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_FC1_LN_LAUNCH, 1)
     ya, yb = outs[1][0], outs[2][0]
     assert torch.isfinite(ya.float()).all()
     eq = float((ya.view(torch.int16) == yb.view(torch.int16)).float().mean())

@@ -1,7 +1,7 @@
 """Decode-step time vs context length for the two attention paths (GPU box).
 
     python tools/attnbench.py [steps=100] [L0,L0,...]
-tune[5] = fused-attention KV limit (1 disables the fused launch).
+ZN_TUNE_ATTN_FUSED_MAX_KEYS = fused-attention KV limit (1 disables the fused launch).
 """
 import ctypes as C
 import os
@@ -26,7 +26,7 @@ def main():
     st = _lib.stream_ptr()
     for L0 in Ls:
         for fused, multi in ((2048, 2), (1, 2)):
-            eng.call("zn_debug_tune", 5, fused); eng.call("zn_debug_tune", 6, multi)
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_ATTN_FUSED_MAX_KEYS, fused); eng.call("zn_debug_tune", _lib.ZN_TUNE_GRAPH_RUNS, multi)
             max_new = L0 + n + 64
             ip = model.setup_cache(2, L0 + n + 40)
             for i in ip.key_value_memory_dict:

@@ -7,7 +7,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zonos_amd import synth  # noqa: E402
+from zonos_amd import _lib, synth  # noqa: E402
 from zonos_amd.testing import build_model  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 861
@@ -17,7 +17,7 @@ eng.call("zn_debug_eos_bias", float("-inf"))
 cond = synth.conditioning(1234, "cond", 2, 24, 2048).to("cuda:0")
 outs = {}
 for name, v in (("launches", 2), ("chain", 1), ("launches", 2), ("chain", 1)):
-    eng.call("zn_debug_tune", 8, v)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, v)
     model.generate(cond, max_new_tokens=32, sampling_params={"temperature": 0.0})
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -31,7 +31,7 @@ print("codes identical:", torch.equal(outs["launches"], outs["chain"]))
 
 # timeline of workgroup 0's communication wave, one mid-stack layer of the last decode step
 stamps = torch.zeros(52, 32, dtype=torch.int64, device="cuda:0")
-eng.call("zn_debug_tune", 8, 1)
+eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1)
 eng.call("zn_debug_chain_stamps", stamps.data_ptr())
 model.generate(cond, max_new_tokens=64, sampling_params={"temperature": 0.0})
 torch.cuda.synchronize()

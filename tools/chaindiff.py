@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zonos_amd import synth  # noqa: E402
+from zonos_amd import _lib, synth  # noqa: E402
 from zonos_amd.testing import build_model  # noqa: E402
 
 CFG = synth.CHAIN_CFG if os.environ.get("ZN_DIFF_CFG") == "chain512" else synth.FULL_CFG
@@ -28,10 +28,10 @@ STACK = os.environ.get("ZN_DIFF_STACK") == "1"        # compare the whole-step k
 
 def run(chain):
     if STACK:
-        eng.call("zn_debug_tune", 15, 3 if chain else 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, 3 if chain else 1)
     else:
-        eng.call("zn_debug_tune", 8, 1 if chain else 2)
-    eng.call("zn_debug_tune", 6, 1)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 1 if chain else 2)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_GRAPH_RUNS, 1)
     tr = {"logits": [], "traces": []}
     tr["after_step"] = lambda step_idx, delayed, col: tr["traces"].append(trace.clone()) if step_idx >= 0 else None
     out = model.generate(cond, max_new_tokens=n, sampling_params={"temperature": 0.0}, _trace=tr)

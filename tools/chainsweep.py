@@ -6,7 +6,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zonos_amd import synth  # noqa: E402
+from zonos_amd import _lib, synth  # noqa: E402
 from zonos_amd.testing import build_model  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 400
@@ -14,7 +14,7 @@ model, _ = build_model(synth.FULL_CFG, 1234, "cuda:0")
 eng = model.engine(1)
 eng.call("zn_debug_eos_bias", float("-inf"))
 if os.environ.get("ZN_TUNE5"):
-    eng.call("zn_debug_tune", 5, int(os.environ["ZN_TUNE5"]))
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_ATTN_FUSED_MAX_KEYS, int(os.environ["ZN_TUNE5"]))
 for kv in os.environ.get("ZN_TUNE", "").split(","):          # e.g. ZN_TUNE=12:2,13:3
     if kv:
         eng.call("zn_debug_tune", int(kv.split(":")[0]), int(kv.split(":")[1]))

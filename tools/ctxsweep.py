@@ -3,8 +3,8 @@ random rows, `steps` steps from each starting context.
 
     python tools/ctxsweep.py [steps=160] [contexts=100,300,450,...] [modes=stack,chain,launches]
 
-modes: stack = the default (whole-step kernel); stack-nopre = the same with block 0's in_proj as a launch before it (zn_debug_tune(18, 2));
-chain = one chain launch per block (zn_debug_tune(15, 2)); launches = per-op launches.
+modes: stack = the default (whole-step kernel); stack-nopre = the same with block 0's in_proj as a launch before it (zn_debug_tune(ZN_TUNE_STACK_PRE, 2));
+chain = one chain launch per block (zn_debug_tune(ZN_TUNE_WHOLE_STEP, 2)); launches = per-op launches.
 Prints ms per decode step and the algorithmic HBM rate (SURVEY.md section 8d bytes at the middle context of the run)."""
 import ctypes as C
 import os
@@ -18,7 +18,8 @@ from zonos_amd.codebook_pattern import apply_delay_pattern  # noqa: E402
 from zonos_amd.model import _sampling_struct  # noqa: E402
 from zonos_amd.testing import build_model  # noqa: E402
 
-MODES = {"stack": {15: 1, 8: 1, 18: 1}, "stack-nopre": {15: 1, 8: 1, 18: 2}, "chain": {15: 2, 8: 1, 18: 1}, "launches": {15: 1, 8: 2, 18: 1}}
+WS, PE, PRE = _lib.ZN_TUNE_WHOLE_STEP, _lib.ZN_TUNE_PERSISTENT, _lib.ZN_TUNE_STACK_PRE
+MODES = {"stack": {WS: 1, PE: 1, PRE: 1}, "stack-nopre": {WS: 1, PE: 1, PRE: 2}, "chain": {WS: 2, PE: 1, PRE: 1}, "launches": {WS: 1, PE: 2, PRE: 1}}
 
 
 def main():
@@ -29,7 +30,7 @@ def main():
     model, _ = build_model(synth.FULL_CFG, 1234, dev)
     eng = model.engine(1)
     eng.call("zn_debug_eos_bias", float("-inf"))
-    extra = [tuple(int(v) for v in kv.split("=")) for kv in filter(None, os.environ.get("ZN_TUNE", "").split(","))]      # e.g. ZN_TUNE=17=4
+    extra = [tuple(int(v) for v in kv.split("=")) for kv in filter(None, os.environ.get("ZN_TUNE", "").split(","))]      # key=value by number, e.g. ZN_TUNE=6=1
     st = _lib.stream_ptr()
     sp = _sampling_struct({"temperature": 0.0}, 1)
     W = 3_200_290_816

@@ -72,7 +72,8 @@ def sweep():
     st = _lib.stream_ptr()
     t, by = C.c_float(0), C.c_double(0)
     only = sys.argv[2].split(",") if len(sys.argv) > 2 else None
-    for key, which, name in ((0, 4, "in_proj"), (2, 0, "fc1"), (3, 1, "fc2"), (1, 2, "out_proj"), (4, 3, "heads")):
+    for key, which, name in ((_lib.ZN_TUNE_WG_IN_PROJ, 4, "in_proj"), (_lib.ZN_TUNE_WG_FC1, 0, "fc1"), (_lib.ZN_TUNE_WG_FC2, 1, "fc2"), (_lib.ZN_TUNE_WG_OUT_PROJ, 2, "out_proj"),
+                             (_lib.ZN_TUNE_WG_HEADS, 3, "heads")):
         if only and name not in only:
             continue
         for tb in (96, 128, 192, 256, 384, 512, 768, 1024, 1536, 2048):

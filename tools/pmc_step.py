@@ -6,14 +6,14 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zonos_amd import synth  # noqa: E402
+from zonos_amd import _lib, synth  # noqa: E402
 from zonos_amd.testing import build_model  # noqa: E402
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 72
 model, _ = build_model(synth.FULL_CFG, 1234, "cuda:0")
 eng = model.engine(1)
 eng.call("zn_debug_eos_bias", float("-inf"))
-eng.call("zn_debug_tune", 6, 1)        # no multi-step graphs: rocprofv3 sees each kernel as its own dispatch either way
+eng.call("zn_debug_tune", _lib.ZN_TUNE_GRAPH_RUNS, 1)        # no multi-step graphs: rocprofv3 sees each kernel as its own dispatch either way
 cond = synth.conditioning(1234, "cond", 2, 24, 2048).to("cuda:0")
 out = model.generate(cond, max_new_tokens=steps - 8, sampling_params={"temperature": 0.0})
 torch.cuda.synchronize()

@@ -20,7 +20,7 @@ for S in sizes:
     kv = torch.randn(2, cap, 2, 4, 128, device=dev).to(torch.bfloat16)
     outs = []
     for kernel, name in ((1, "mfma"), (2, "valu")):
-        eng.call("zn_debug_tune", 10, kernel)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_PREFILL_ATTN_VALU, kernel)
         out = torch.empty(2, S, 2048, dtype=torch.bfloat16, device=dev)
         for _ in range(2):
             eng.call("zn_op_attn_prefill", q.data_ptr(), kv.data_ptr(), cap, out.data_ptr(), S, 2, st)
@@ -37,4 +37,4 @@ for S in sizes:
         outs.append(out)
     eq = float((outs[0].view(torch.int16) == outs[1].view(torch.int16)).float().mean())
     print(f"S={S}: mfma vs valu bit-equal {eq:.5f}, max|d| {(outs[0].float() - outs[1].float()).abs().max().item():.3g}", flush=True)
-eng.call("zn_debug_tune", 10, 1)
+eng.call("zn_debug_tune", _lib.ZN_TUNE_PREFILL_ATTN_VALU, 1)

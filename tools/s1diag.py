@@ -5,7 +5,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zonos_amd import synth  # noqa: E402
+from zonos_amd import _lib, synth  # noqa: E402
 from zonos_amd.testing import build_model  # noqa: E402
 
 model, _ = build_model(synth.FULL_CFG, 1234, "cuda:0")
@@ -16,8 +16,8 @@ G = {"temperature": 0.0}
 res = {}
 for t16 in (1, 2):
     for t6 in (2, 1):
-        eng.call("zn_debug_tune", 16, t16)
-        eng.call("zn_debug_tune", 6, t6)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_SAMPLER, t16)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_GRAPH_RUNS, t6)
         for rep in range(2):
             o = model.generate(cond, max_new_tokens=861, sampling_params=G).cpu()
             res[(t16, t6, rep)] = o

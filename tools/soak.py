@@ -11,7 +11,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zonos_amd import synth  # noqa: E402
+from zonos_amd import _lib, synth  # noqa: E402
 from zonos_amd.testing import build_model  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 50
@@ -51,7 +51,7 @@ for i in range(n):
         pauses.append((round(ta - t0, 2), i, c["longest_wait_us"], c["waits_over_200us"], round(dt * 1e3, 1)))
         print(f"  generation {i} at t = {ta - t0:.2f} s: longest in-kernel hand-off wait {c['longest_wait_us']} us ({c['waits_over_200us']} waits beyond 0.2 ms), "
               f"the generation took {dt * 1e3:.1f} ms", flush=True)
-        eng.call("zn_debug_tune", 14, 13)
+        eng.call("zn_debug_tune", _lib.ZN_TUNE_HOOK, _lib.ZN_HOOK_RESET_WAIT_STATS)
     path = eng.lib.zn_decode_path_detail(eng.h)
     if ref is None:
         ref = out.clone()

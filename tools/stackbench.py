@@ -8,7 +8,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zonos_amd import synth  # noqa: E402
+from zonos_amd import _lib, synth  # noqa: E402
 from zonos_amd.testing import build_model  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 400
@@ -18,8 +18,8 @@ eng.call("zn_debug_eos_bias", float("-inf"))
 cond = synth.conditioning(1234, "cond", 2, 24, 2048).to("cuda:0")
 outs = {}
 for name, t8, t15 in (("chain", 1, 2), ("stack", 1, 1), ("chain", 1, 2), ("stack", 1, 1), ("launches", 2, 1)):
-    eng.call("zn_debug_tune", 8, t8)
-    eng.call("zn_debug_tune", 15, t15)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, t8)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, t15)
     model.generate(cond, max_new_tokens=32, sampling_params={"temperature": 0.0})
     torch.cuda.synchronize()
     t0 = time.perf_counter()

@@ -5,7 +5,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zonos_amd import synth  # noqa: E402
+from zonos_amd import _lib, synth  # noqa: E402
 from zonos_amd.testing import build_model  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 24
@@ -15,7 +15,7 @@ eng.call("zn_debug_eos_bias", float("-inf"))
 cond = synth.conditioning(1234, "cond", 2, int(os.environ.get("ZN_LC", "24")), 2048).to("cuda:0")
 res = {}
 for name, t15 in (("chain", 2), ("stack", 1), ("stack2", 1), ("threerole", 4)):
-    eng.call("zn_debug_tune", 15, t15)
+    eng.call("zn_debug_tune", _lib.ZN_TUNE_WHOLE_STEP, t15)
     tr = {"logits": []}
     out = model.generate(cond, max_new_tokens=n, sampling_params={"temperature": 0.0}, _trace=tr)
     torch.cuda.synchronize()

@@ -14,6 +14,27 @@ LIB_PATH = os.environ.get("ZONOS_HIP_LIB") or os.path.join(_HERE, "libzonos_hip.
 
 ZN_ABI_VERSION = 8
 
+# zn_debug_tune keys (enum zn_tune_key of include/zonos_hip.h, which documents them; tests/test_abi.py keeps the two equal)
+ZN_TUNE_WG_IN_PROJ, ZN_TUNE_WG_OUT_PROJ, ZN_TUNE_WG_FC1, ZN_TUNE_WG_FC2, ZN_TUNE_WG_HEADS = 0, 1, 2, 3, 4
+ZN_TUNE_ATTN_FUSED_MAX_KEYS = 5
+ZN_TUNE_GRAPH_RUNS = 6
+ZN_TUNE_SMALL_M_LDS = 7
+ZN_TUNE_PERSISTENT = 8
+ZN_TUNE_FC1_LN_LAUNCH = 9
+ZN_TUNE_PREFILL_ATTN_VALU = 10
+ZN_TUNE_NO_SPLIT_SMALL_M = 11
+ZN_TUNE_NO_PREFILL_GEMM16K = 12
+ZN_TUNE_GEMM16K_MAX_TILES = 13
+ZN_TUNE_HOOK = 14
+ZN_TUNE_WHOLE_STEP = 15
+ZN_TUNE_SAMPLER = 16
+ZN_TUNE_RESERVED_17 = 17
+ZN_TUNE_STACK_PRE = 18
+ZN_TUNE_ATTN_SPLIT_COLS = 19
+ZN_TUNE_NKEYS = 20
+# values of ZN_TUNE_HOOK (enum zn_tune_hook)
+ZN_HOOK_TAG_WRAP, ZN_HOOK_TIMEOUT_WORD, ZN_HOOK_PAUSE, ZN_HOOK_RESET_WAIT_STATS = 7, 9, 11, 13
+
 
 class ZonosHipError(RuntimeError):
     pass

@@ -22,6 +22,16 @@ static thread_local std::string g_create_err;
 #define ZN_G16_MAX_GROUPS 1024
 #define ZN_REARM_AFTER 4
 
+// How the next decode steps run (plan_steps): the one record zn_decode_steps, enqueue_step and decode_blocks agree through.
+struct StepPlan {
+  enum Path { LAUNCHES, CHAIN, STACK } path = LAUNCHES;   // one launch per op; one chain launch per block; the whole-step kernel
+  int nbk = 0;              // STACK: key blocks (rows * Hkv attention workgroups each) of the launch
+  int attn_fused = 0;       // LAUNCHES, CHAIN: shape of the attention launches (attn_fused_for)
+  int run = 1;              // steps enqueued together: 1, or ZN_GRAPH_STEPS (one graph)
+  bool fused_tail = false;  // the step reads its embedding from x_emb and its sampler launch leaves the next step's
+  int graph_slot = 0;       // index into graph_exec (graph_slot_for)
+};
+
 struct zn_handle_s {
   zn_config cfg;
   int max_rows = 0, hd = 0, G = 0;
@@ -42,12 +52,10 @@ struct zn_handle_s {
   unsigned long long *ch_gy1 = nullptr, *ch_gx1 = nullptr, *ch_gx2 = nullptr, *ch_gm = nullptr;
   unsigned long long *ch_gqkv = nullptr, *ch_ga = nullptr;   // whole-step kernel: q | k | v of the next block, attention output
   unsigned long long *ch_gbmax = nullptr, *ch_gpart = nullptr;   // key-block attention role: per-block score maxima and P.V partials (zn_step_kernel.h)
-  int stack_nbk = 1;                         // key blocks (8 attention workgroups each) of the whole-step launches being enqueued
   bool stackv_ok[4] = {};                    // whole-step kernel instantiations 1 .. 3 that fit this model and device (stack_variant_ok)
   bool stackv1_ok[4] = {};                   // the same for the one-row kernel (step_r1_kernel: generations without guidance)
-  bool stack1_ok = false;
   StackLayer* stack_layers = nullptr;        // device table [n_layer], rebuilt by zn_gen_begin (it holds the KV cache pointers)
-  bool use_stack = false, stack_ok = false, stack_checked = false;   // use_stack: the steps being enqueued run the whole-step kernel
+  bool stack_ok = false, stack1_ok = false, stack_checked = false;   // two rows / one row: the whole-step kernel fits (stack_shapes_ok, asked once)
   unsigned* ch_epoch = nullptr;
   unsigned long long epoch_bound = 1;        // host-side upper bound of the device epoch (tags advance by one per block of every decode step enqueued)
   unsigned* ch_diag = nullptr;               // [16] words: [0..7] the first hand-off wait that timed out describes itself (sweep_granules); [8] the longest hand-off wait a whole-step launch measured (10 ns ticks), [9] waits beyond 0.2 ms (StepPacer::report)
@@ -57,11 +65,10 @@ struct zn_handle_s {
   bf16_t* x_emb = nullptr;                  // [max_rows][d] embedding of the column the next decode step consumes (written by the step's tail)
   int* tail_ticket = nullptr;               // arrival ticket of the sampler launch whose last workgroup runs the step's tail
   bool emb_valid = false;                   // x_emb holds the embedding of column st->offset
-  unsigned long long* at_stamps = nullptr;   // diagnostic: [n_layer][8] timeline of the fused attention launch (second half of the chain stamp buffer)
   unsigned long long* ch_stamps = nullptr;   // diagnostic: [n_layer][32] timeline stamps of workgroup 0 (zn_debug_chain_stamps)
   int device = 0;              // the HIP device the handle was created on
   // hand-off timeouts (zn_get_counters): a reported timeout demotes the handle to the launches path (no in-launch hand-offs) until ZN_REARM_AFTER
-  // generations in a row have completed there cleanly, or zn_debug_tune(8, 1) re-arms it at once
+  // generations in a row have completed there cleanly, or zn_debug_tune(ZN_TUNE_PERSISTENT, 1) re-arms it at once
   bool demoted = false;
   int clean_since_demotion = 0;
   long long n_timeouts = 0, n_generations = 0, n_fallback_generations = 0, n_rearms = 0;
@@ -85,7 +92,7 @@ struct zn_handle_s {
   int* fw_lengths = nullptr;   // [max_rows] positions of zn_op_backbone_forward's rows
   int* row_len = nullptr;      // [max_rows] valid positions per row of a right-padded prefill (zn_prefill_rows)
   std::vector<int> row_len_host;   // source of the copy into row_len (kept until the next zn_gen_begin has drained the stream)
-  bool rows_unequal2 = false;  // this generation's two unguided rows have different lengths: its steps run the launches path (persist_active)
+  bool rows_unequal2 = false;  // this generation's two unguided rows have different lengths: its steps run the launches path (persist_allowed)
   bf16_t* qkv_tmp = nullptr;   // [rows][(H + 2 Hkv) hd]: in_proj output of an attention layer whose RoPE / bias form the fused epilogue does not cover
   int prefill_mode = 1;     // 1 = batched (MFMA GEMMs + tiled attention), 0 = position by position through the decode kernels
   int lcap = 0;
@@ -105,20 +112,19 @@ struct zn_handle_s {
   int force_eos_step = -1;
   float eos_bias = 0.f;
   unsigned dbg_pause = 0;           // ChainArgs::dbg_pause of this generation's whole-step launches
-  int tune[20] = {256, 512, 512, 1024, 512, 512, 2, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // target workgroups: in_proj, out_proj, fc1, fc2, heads; [5] longest context of the fused attention launch (<= 512); [6] > 1: multi-step graphs; [7] > 1: LDS-staged small-M projections; [8] = 2: no persistent chain kernel (five launches per block instead); [9] = 2: fc1's LayerNorm as a launch of its own at 5..16 rows (default: statistics from out_proj's epilogue); [10] = 2: VALU prefill attention; [11] = 2: no in-workgroup-split small-M kernel
+  int tune[ZN_TUNE_NKEYS] = {};     // settings of zn_debug_tune by enum zn_tune_key (include/zonos_hip.h); defaults: zn_create.  0 = never set
+  int pending_hook = 0;             // zn_debug_tune(ZN_TUNE_HOOK, v): the one-shot test hook the next zn_gen_begin consumes (enum zn_tune_hook)
   const int* tok_override = nullptr;
   int tok_override_calls = 0;
   hipStream_t cap_stream = nullptr;
-  // captured decode steps per attention launch shape (k & 1: 1 = fused single launch, 0 = two passes) and per length
-  // (k >> 1: 0 = one step, 1 = ZN_GRAPH_STEPS consecutive steps: fewer graph launches on the chain)
-  // ... and, for the whole-step kernel, per key-block count of the attention role: slots 8 + nb (one step) and 8 + 13 + nb (ZN_GRAPH_STEPS steps).
-  // A count's graph is captured once per generation and kept to its end: no graph is destroyed while launches of it may still be queued.
+  // captured decode steps, one slot per launch shape and run length (graph_slot_for).  A slot's graph is captured once per generation and
+  // kept to its end: no graph is destroyed while launches of it may still be queued.
 #define ZN_NGRAPHS (8 + 2 * (ZN_SK_KB_MAXNB + 1))
   hipGraphExec_t graph_exec[ZN_NGRAPHS] = {};
   hipGraph_t graph[ZN_NGRAPHS] = {};
   bool graph_tried[ZN_NGRAPHS] = {};
   int len_hi = 0;            // host-side upper bound of the rows' KV lengths (keys already cached)
-  int attn_fused = 0;        // launch shape of the next run_attention (attn_fused_for)
+  StepPlan last_plan;        // of the decode steps enqueued last (zn_decode_path_detail)
   std::string err;
 };
 
@@ -182,6 +188,10 @@ extern "C" int zn_tenant_release(int32_t device, const void* owner) {
   g_tenant[device] = nullptr;
   return 1;
 }
+// While ANY thread of the process captures a stream (thread-local capture mode included) HIP refuses hipMemcpy / hipMemset on the null stream (hipErrorStreamCaptureImplicit): a handle
+// holds this lock from hipStreamBeginCapture to hipStreamEndCapture, and each such call that another handle's thread may make beside that generation holds it for the call alone.
+static std::mutex g_capture_mu;
+#define ZN_NOT_IN_CAPTURE(call) [&] { std::lock_guard<std::mutex> lk(g_capture_mu); return (call); }()
 
 extern "C" int zn_destroy(zn_handle h) {
   if (!h) return ZN_OK;
@@ -211,7 +221,6 @@ static bool chain_resident(int n_cus) {
 // Which instantiation of chain_kernel serves this model at batch 1 (0 = none: the launches path).
 static int chain_variant_for(const zn_config& c) {
   if (c.arch != 0 || !c.double_out_proj || c.d_ff != 4 * c.d_model) return 0;
-
   int dev = 0, n_cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
   const int G = ZN_CH_GRID, hd = c.d_model / c.n_heads, nqkv = (c.n_heads + 2 * c.n_heads_kv) * hd;
@@ -252,6 +261,8 @@ extern "C" int zn_create(const zn_config* cfg, const zn_weights* w, int32_t max_
   if (c.rope_mode < 0 || c.rope_mode > 2) ZN_FAIL((zn_handle) nullptr, ZN_ERR_ARG, "zn_create: rope_mode must be 0, 1 or 2");
   zn_handle h = new zn_handle_s();
   h->cfg = c; h->max_rows = max_rows; h->hd = hd; h->G = G;
+  h->tune[ZN_TUNE_WG_IN_PROJ] = 256; h->tune[ZN_TUNE_WG_OUT_PROJ] = 512; h->tune[ZN_TUNE_WG_FC1] = 512; h->tune[ZN_TUNE_WG_FC2] = 1024; h->tune[ZN_TUNE_WG_HEADS] = 512;
+  h->tune[ZN_TUNE_ATTN_FUSED_MAX_KEYS] = 512; h->tune[ZN_TUNE_GRAPH_RUNS] = 2; h->tune[ZN_TUNE_SMALL_M_LDS] = 2;      // every other key: unset
   if (hipGetDevice(&h->device) != hipSuccess) { (void)hipGetLastError(); h->device = 0; }
   if (c.arch == 1) {
     h->m_nheads = c.m_d_inner / c.m_headdim;
@@ -261,7 +272,7 @@ extern "C" int zn_create(const zn_config* cfg, const zn_weights* w, int32_t max_
   if (const char* e = getenv("ZN_PREFILL_MODE")) h->prefill_mode = atoi(e);
   h->layers.assign(w->layers, w->layers + c.n_layer);
   h->heads = w->heads; h->norm_f_w = w->norm_f_w; h->norm_f_b = w->norm_f_b; h->rope = w->rope_table;
-#define ZC(call) do { hipError_t _e = (call); if (_e != hipSuccess) { g_create_err = std::string(#call) + ": " + hipGetErrorString(_e); zn_destroy(h); return ZN_ERR_HIP; } } while (0)
+#define ZC(call) do { hipError_t _e = ZN_NOT_IN_CAPTURE(call); if (_e != hipSuccess) { g_create_err = std::string(#call) + ": " + hipGetErrorString(_e); zn_destroy(h); return ZN_ERR_HIP; } } while (0)
   ZC(hipMalloc(&h->emb_tables_dev, sizeof(void*) * c.n_codebooks));
   if (w->embeddings) ZC(hipMemcpy(h->emb_tables_dev, w->embeddings, sizeof(void*) * c.n_codebooks, hipMemcpyHostToDevice));
   h->has_io = (w->embeddings != nullptr && w->heads != nullptr);
@@ -302,8 +313,8 @@ extern "C" int zn_create(const zn_config* cfg, const zn_weights* w, int32_t max_
   { const unsigned one = 1; ZC(hipMemcpy(h->ch_epoch, &one, sizeof one, hipMemcpyHostToDevice)); }
   ZC(hipMalloc(&h->ch_x2, R * c.d_model * 2));
   h->ch_variant = chain_variant_for(c);
-  if (const char* e = getenv("ZN_CHAIN")) if (atoi(e) == 0) h->tune[8] = 2;
-  if (const char* e = getenv("ZN_STACK")) if (atoi(e) == 0) h->tune[15] = 2;
+  if (const char* e = getenv("ZN_CHAIN")) if (atoi(e) == 0) h->tune[ZN_TUNE_PERSISTENT] = 2;
+  if (const char* e = getenv("ZN_STACK")) if (atoi(e) == 0) h->tune[ZN_TUNE_WHOLE_STEP] = 2;
   {   // split-K partial tiles + tickets of the small-M projections (batches of 3..8 utterances; short-prompt prefill at any batch)
     ZC(hipMalloc(&h->x_emb, R * c.d_model * 2));
     ZC(hipMalloc(&h->tail_ticket, sizeof(int)));
@@ -393,12 +404,12 @@ static bool run_gemm16s(zn_handle h, GemvArgs g, hipStream_t s) {
 }
 
 // rows in (4, 16], K = 8 waves x 128 x {2, 4} and few weight rows (the LDS-staged kernel would have to split K over
-// workgroups): one 16-row tile per workgroup, K split over its waves, no cross-workgroup combine.  tune[11] = 2 disables.
+// workgroups): one 16-row tile per workgroup, K split over its waves, no cross-workgroup combine.  ZN_TUNE_NO_SPLIT_SMALL_M = 2 disables.
 static bool gemm16k_fits(zn_handle h, int epi, int N, int K) {
-  if (epi == EPI_SILU || h->tune[7] <= 1 || h->tune[11] == 2) return false;
+  if (epi == EPI_SILU || h->tune[ZN_TUNE_SMALL_M_LDS] <= 1 || h->tune[ZN_TUNE_NO_SPLIT_SMALL_M] == 2) return false;
   const int per = ZN_G16K_NKW * ZN_G16K_KCH, nch = K / per;
   if (K % per || (nch != 2 && nch != 4)) return false;
-  return (N + 15) / 16 < (h->tune[13] > 0 ? h->tune[13] : 1024);     // many rows: the 64-row workgroups fill the chip without a split (tune[13]: the tile count from which they take over)
+  return (N + 15) / 16 < (h->tune[ZN_TUNE_GEMM16K_MAX_TILES] > 0 ? h->tune[ZN_TUNE_GEMM16K_MAX_TILES] : 1024);     // many rows: the 64-row workgroups fill the chip without a split (ZN_TUNE_GEMM16K_MAX_TILES: the tile count from which they take over)
 }
 template <int PRO, int EPI>
 static void run_gemm16k(const GemvArgs& g, hipStream_t s) {
@@ -433,7 +444,7 @@ static int run_gemm16(zn_handle h, GemvArgs a, int rows, hipStream_t s) {
     const bool k16_ln = k16 && PRO == PRO_LN && tiles <= 256 && K == 2 * ZN_G16K_NKW * ZN_G16K_KCH;
     if constexpr (PRO == PRO_LN && EPI == EPI_SILU) {
       // the producer of these rows left LayerNorm statistics per 16-column tile (layer_post_attention): fc1 normalises while it stages
-      if (a.ln_part_in && !k16 && h->tune[7] > 1) {
+      if (a.ln_part_in && !k16 && h->tune[ZN_TUNE_SMALL_M_LDS] > 1) {
         GemvArgs gl = a;
         gl.nrows = nr; gl.x = a.x + (size_t)r0 * K; gl.ln_part_in = a.ln_part_in + (size_t)r0 * ZN_G16_LNT * 2;
         if (gl.out) gl.out += (size_t)r0 * (a.N / 2);
@@ -456,7 +467,7 @@ static int run_gemm16(zn_handle h, GemvArgs a, int rows, hipStream_t s) {
       if (k16_ln) run_gemm16k<PRO, EPI>(g, s); else run_gemm16k<PRO_NONE, EPI>(g, s);
       continue;
     }
-    if (h->tune[7] > 1 && run_gemm16s<EPI>(h, g, s)) continue;
+    if (h->tune[ZN_TUNE_SMALL_M_LDS] > 1 && run_gemm16s<EPI>(h, g, s)) continue;
     if constexpr (EPI != EPI_SILU) {
       if (tiles <= 192 && a.N % 8 == 0) {   // N = d_model: 8-row tiles so that every CU gets a workgroup
         const int t8 = a.N / 8;
@@ -512,14 +523,13 @@ static int run_gemv(zn_handle h, GemvArgs a, int rows, int target_blocks, hipStr
 // one summation order, P.V per 512-key block (the reference's block size) on the matrix cores in one order, the blocks' unnormalised partials
 // combined by the reference's recurrence acc = acc * f_j + pv_j in block order (attn_block_probs / attn_block_pv, shared by the launches and
 // by the attention role of zn_step_kernel.h).  The fused launch (scores + pass 2 + normalisation in one launch) serves contexts of one block:
-// tune[5] may lower that limit (tests), never raise it.
+// ZN_TUNE_ATTN_FUSED_MAX_KEYS may lower that limit (tests), never raise it.
 #define ZN_AFUSED_LIMIT 512
 // Launch shape of the decode attention for contexts of at most keys_upper_bound keys: 1 = the one-launch shape (one block), 0 = scores launch +
 // block launch.
-static bool attn_split_cols(zn_handle h, int rows) { return h->tune[19] == 2 || (h->tune[19] != 1 && rows > 4); }
-static int attn_fused_for(zn_handle h, int keys_upper_bound, int rows) {
-  (void)rows;
-  const int lim = h->tune[5] < ZN_AFUSED_LIMIT ? h->tune[5] : ZN_AFUSED_LIMIT;
+static bool attn_split_cols(zn_handle h, int rows) { return h->tune[ZN_TUNE_ATTN_SPLIT_COLS] == 2 || (h->tune[ZN_TUNE_ATTN_SPLIT_COLS] != 1 && rows > 4); }
+static int attn_fused_for(zn_handle h, int keys_upper_bound) {
+  const int lim = h->tune[ZN_TUNE_ATTN_FUSED_MAX_KEYS] < ZN_AFUSED_LIMIT ? h->tune[ZN_TUNE_ATTN_FUSED_MAX_KEYS] : ZN_AFUSED_LIMIT;
   return keys_upper_bound <= lim ? 1 : 0;
 }
 
@@ -563,13 +573,13 @@ static int ensure_attn_ws(zn_handle h, int max_len) {
   { const size_t groups = (size_t)h->max_rows * h->cfg.n_heads_kv;
     HIPCHK(h, hipMalloc(&h->pv_part, groups * (lcap / 512) * (size_t)(h->G * h->hd + 4 * h->G) * sizeof(float)));     // (up to four column parts, each with its e sums)
     HIPCHK(h, hipMalloc(&h->pv_tickets, 4 * groups * sizeof(int)));
-    HIPCHK(h, hipMemset(h->pv_tickets, 0, 4 * groups * sizeof(int))); }
+    HIPCHK(h, ZN_NOT_IN_CAPTURE(hipMemset(h->pv_tickets, 0, 4 * groups * sizeof(int)))); }
   h->lcap = lcap;
   return ZN_OK;
 }
 
 static int run_attention(zn_handle h, const bf16_t* q, const bf16_t* kv, int max_len, const int* lengths, const int* ext, int ext_scalar,
-                         bf16_t* out, int rows, hipStream_t s, unsigned long long* stamps = nullptr) {
+                         bf16_t* out, int rows, int fused, hipStream_t s, unsigned long long* stamps = nullptr) {
   const zn_config& c = h->cfg;
   if (max_len > h->lcap || rows > h->max_rows) ZN_FAIL(h, ZN_ERR_STATE, "attention workspace too small (max_len %d rows %d)", max_len, rows);
   AttnArgs a{};
@@ -578,12 +588,11 @@ static int run_attention(zn_handle h, const bf16_t* q, const bf16_t* kv, int max
   a.scores = h->scores; a.cmax = h->cmax; a.out = out; a.rows = rows; a.stamps = stamps;
   const int hd = h->hd;
   dim3 grid((max_len + ZN_ACHUNK - 1) / ZN_ACHUNK, c.n_heads_kv, rows);
-  // one fused launch for contexts of one 512-key block (the caller bounds the context: h->attn_fused); beyond: scores, then the P.V pass
+  // fused: one launch for contexts of one 512-key block (the caller bounds the context: attn_fused_for); else: scores, then the P.V pass
   // with one workgroup per (slice, kv head, row, 512-key block) and the ticketed in-order combine
-  const int fused = h->attn_fused;
   a.part = h->pv_part; a.tickets = h->pv_tickets; a.nbcap = (max_len + 511) / 512;
   if (a.nbcap > 32) ZN_FAIL(h, ZN_ERR_ARG, "attention: %d keys of capacity exceed the 32 blocks the split pass combines", max_len);
-  // batches of 3..8 utterances: two workgroups per (row, kv head[, block]), each with half of the value columns (tune[19] = 1: never, 2: always)
+  // batches of 3..8 utterances: two workgroups per (row, kv head[, block]), each with half of the value columns (ZN_TUNE_ATTN_SPLIT_COLS = 1: never, 2: always)
   const bool sc = attn_split_cols(h, rows);
   int r2 = hd == 128 ? launch_attn_g<128>(a, h->G, grid, fused, sc, s) : hd == 64 ? launch_attn_g<64>(a, h->G, grid, fused, sc, s)
                                                                                  : launch_attn_g<32>(a, h->G, grid, fused, sc, s);
@@ -601,7 +610,7 @@ static int layer_in_proj(zn_handle h, int li, bf16_t* x, bf16_t* kv, int max_len
   a.ln_w = (const bf16_t*)lw.norm_w; a.ln_b = (const bf16_t*)lw.norm_b; a.eps = c.norm_eps;
   a.lengths = lengths; a.hd = hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
   a.q_out = h->q; a.kv = kv; a.rope = h->rope; a.max_len = max_len; a.rope_positions = c.rope_positions;
-  return run_gemv<PRO_LN, EPI_ROPE_KV>(h, a, rows, h->tune[0], s);
+  return run_gemv<PRO_LN, EPI_ROPE_KV>(h, a, rows, h->tune[ZN_TUNE_WG_IN_PROJ], s);
 }
 
 // out_proj (-> out_proj again, _torch.py:419-420) -> residual -> LayerNorm -> fc1 -> y * silu(gate) -> fc2 -> residual
@@ -611,22 +620,22 @@ static int layer_post_attention(zn_handle h, int li, bf16_t* x, int rows, hipStr
   const int d = c.d_model, nq = c.n_heads * h->hd;
   int rc;
   // rows 5..16: the projection that completes the residual stream leaves LayerNorm statistics per 16-column tile and fc1 normalises its
-  // activation chunks from them - no LayerNorm launch in between (GemvArgs::ln_part_out).  tune[9] = 2: the launch.
-  const bool lnp = rows > 4 && h->tune[9] != 2 && h->ln_part && d == 16 * ZN_G16_LNT && gemm16k_fits(h, EPI_RESID, d, nq);
+  // activation chunks from them - no LayerNorm launch in between (GemvArgs::ln_part_out).  ZN_TUNE_FC1_LN_LAUNCH = 2: the launch.
+  const bool lnp = rows > 4 && h->tune[ZN_TUNE_FC1_LN_LAUNCH] != 2 && h->ln_part && d == 16 * ZN_G16_LNT && gemm16k_fits(h, EPI_RESID, d, nq);
   {
     GemvArgs a{};
     a.W = (const bf16_t*)lw.out_proj; a.N = d; a.K = nq; a.x = h->o1;
     if (c.double_out_proj) {
       a.out = h->q;   // q is dead after attention: reuse it for the intermediate projection
-      if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[1], s))) return rc;
+      if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s))) return rc;
       GemvArgs b{};
       b.W = (const bf16_t*)lw.out_proj; b.N = d; b.K = nq; b.x = h->q; b.resid = x; b.out = x;
       if (lnp) b.ln_part_out = h->ln_part;
-      if ((rc = run_gemv<PRO_NONE, EPI_RESID>(h, b, rows, h->tune[1], s))) return rc;
+      if ((rc = run_gemv<PRO_NONE, EPI_RESID>(h, b, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s))) return rc;
     } else {
       a.resid = x; a.out = x;
       if (lnp) a.ln_part_out = h->ln_part;
-      if ((rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[1], s))) return rc;
+      if ((rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s))) return rc;
     }
   }
   if (x1_copy) (void)hipMemcpyAsync(x1_copy, x, (size_t)rows * d * 2, hipMemcpyDeviceToDevice, s);      // diagnostic trace
@@ -635,37 +644,25 @@ static int layer_post_attention(zn_handle h, int li, bf16_t* x, int rows, hipStr
     a.W = (const bf16_t*)lw.fc1; a.N = 2 * c.d_ff; a.K = d; a.x = x;
     a.ln_w = (const bf16_t*)lw.norm2_w; a.ln_b = (const bf16_t*)lw.norm2_b; a.eps = c.norm_eps; a.out = h->mbuf;
     if (lnp) a.ln_part_in = h->ln_part;
-    if ((rc = run_gemv<PRO_LN, EPI_SILU>(h, a, rows, h->tune[2], s))) return rc;
+    if ((rc = run_gemv<PRO_LN, EPI_SILU>(h, a, rows, h->tune[ZN_TUNE_WG_FC1], s))) return rc;
   }
   {  // fc2 -> residual
     GemvArgs a{};
     a.W = (const bf16_t*)lw.fc2; a.N = d; a.K = c.d_ff; a.x = h->mbuf; a.resid = x; a.out = x;
-    if ((rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[3], s))) return rc;
+    if ((rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[ZN_TUNE_WG_FC2], s))) return rc;
   }
   return ZN_OK;
 }
 
 // One decode step of block `li` on x [rows][d] in place (_torch.py:307-328), as launches.
 static int layer_decode(zn_handle h, int li, bf16_t* x, bf16_t* kv, int max_len, const int* lengths, const int* ext,
-                        int ext_scalar, int rows, hipStream_t s) {
+                        int ext_scalar, int rows, int attn_fused, hipStream_t s) {
   int rc;
   if ((rc = layer_in_proj(h, li, x, kv, max_len, lengths, rows, s))) return rc;
   // KV-cached GQA attention over keys [0, lengths+1) (_torch.py:413-417) -> attention output in h->o1
-  if ((rc = run_attention(h, h->q, kv, max_len, lengths, ext, ext_scalar, h->o1, rows, s))) return rc;
+  if ((rc = run_attention(h, h->q, kv, max_len, lengths, ext, ext_scalar, h->o1, rows, attn_fused, s))) return rc;
   return layer_post_attention(h, li, x, rows, s);
 }
-
-// The persistent chain serves the step when the model fits an instantiation, at batch 1 (two rows), unless switched off
-// (zn_debug_tune(8, 2), or ZN_CHAIN=0 in the environment at zn_create): 1.07 vs 1.16 ms per decode step at the Zonos-v0.1 dimensions.
-// Two unguided rows of different lengths (zn_prefill_rows) stay off the persistent kernels: see persist_active.
-static bool chain_active(zn_handle h, int rows) { return h->ch_variant != 0 && rows == 2 && h->tune[8] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2; }
-// Row counts a persistent kernel can serve on this model: two (the per-block chain and step_kernel) or one (step_r1_kernel, the whole-step
-// kernel only: one row beyond its 6144-key bound, or with it switched off, runs the launches path).
-static bool persist_shape(zn_handle h, int rows) { return h->ch_variant != 0 && (rows == 2 || (rows == 1 && h->ch_variant == 1)); }
-// rows_unequal2: the two-row persistent kernels read lengths[r] per row, but their hand-off schedules, key-block counts and graph slots were
-// built and measured for the guided pair, whose rows advance in lockstep; two unguided utterances of different lengths run the launches
-// path, which is bit-identical by construction.
-static bool persist_active(zn_handle h, int rows) { return persist_shape(h, rows) && h->tune[8] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2; }
 
 // The chain never updates the residual stream in place (zn_chain_kernel.h): block li reads it from one buffer and leaves it
 // in the other.
@@ -719,7 +716,7 @@ static int launch_chain(zn_handle h, int li, const std::vector<const void*>& kv_
 }
 
 // Whole-step kernel (zn_step_kernel.h): batch 1 at the Zonos-v0.1 shapes: in_proj(0) + ONE launch per decode step.  The default at batch 1;
-// zn_debug_tune(15, 2) or ZN_STACK=0 in the environment at zn_create selects one chain launch per block.  Instantiations (static tile schedules
+// zn_debug_tune(ZN_TUNE_WHOLE_STEP, 2) or ZN_STACK=0 in the environment at zn_create selects one chain launch per block.  Instantiations (static tile schedules
 // for the streaming workgroups the attention role leaves):
 //   variant 1  <4, 2, 10, 5, 6, 6>   1 .. 6 key blocks  (8 .. 48 attention workgroups: contexts up to 3072 keys)
 //   variant 2  <4, 2, 11, 6, 7, 8>   7 .. 8 blocks   (up to 4096 keys)
@@ -755,27 +752,62 @@ static bool stack_shapes_ok(zn_handle h) {
   const zn_config& c = h->cfg;
   if (h->ch_variant != 1 || h->hd != 128 || c.n_heads_kv < 1 || c.n_heads != 4 * c.n_heads_kv) return false;
   const int npairs = 2 * c.n_heads_kv, nkvh = c.n_heads_kv;
-  h->stackv_ok[0] = false;
   h->stackv_ok[1] = stack_variant_ok<2, ZN_SK_T1>(h, npairs * 6);
   h->stackv_ok[2] = stack_variant_ok<2, ZN_SK_T2>(h, npairs * 8);
   h->stackv_ok[3] = stack_variant_ok<2, ZN_SK_T3>(h, npairs * ZN_SK_KB_MAXNB);
-  h->stackv1_ok[0] = false;
   h->stackv1_ok[1] = stack_variant_ok<1, ZN_SK_T1>(h, nkvh * 6);
   h->stackv1_ok[2] = stack_variant_ok<1, ZN_SK_T2>(h, nkvh * 8);
   h->stackv1_ok[3] = stack_variant_ok<1, ZN_SK_T3>(h, nkvh * ZN_SK_KB_MAXNB);
   h->stack1_ok = h->stackv1_ok[1];
   return h->stackv_ok[1];
 }
+// ------------------------------------------------------------------------------------------------ step plan: which kernels serve a decode step
+// The persistent kernels are allowed for this generation: not switched off (zn_debug_tune(ZN_TUNE_PERSISTENT, 2), or ZN_CHAIN=0 in the environment at zn_create), the handle not demoted by
+// a hand-off timeout, the device's tenancy held, and no two unguided rows of different lengths (zn_prefill_rows): the two-row persistent kernels read lengths[r] per row, but their hand-off
+// schedules, key-block counts and graph slots were built and measured for the guided pair, whose rows advance in lockstep; such rows run the launches path, bit-identical by construction.
+static bool persist_allowed(zn_handle h) { return h->tune[ZN_TUNE_PERSISTENT] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2; }
+// Row counts a persistent kernel can serve on this model: two (the per-block chain and step_kernel) or one (step_r1_kernel, the whole-step
+// kernel only: one row beyond its 6144-key bound, or with it switched off, runs the launches path).
+static bool persist_shape(zn_handle h, int rows) { return h->ch_variant != 0 && (rows == 2 || (rows == 1 && h->ch_variant == 1)); }
+static bool persist_active(zn_handle h, int rows) { return persist_shape(h, rows) && persist_allowed(h); }
 // The key blocks a whole-step launch covering `keys_upper_bound` keys needs: -1 = the whole-step kernel does not serve the step (the
-// per-block path does at two rows, the launches path at one), n >= 1 = rows * Hkv * n attention workgroups.
-static int stack_mode_for(zn_handle h, int rows, int keys_upper_bound) {
-  if (!persist_active(h, rows) || h->tune[15] == 2 || !(rows == 1 ? h->stack1_ok : h->stack_ok)) return -1;
+// per-block path does at two rows, the launches path at one), n >= 1 = rows * Hkv * n attention workgroups.  For rows that are persist_active.
+static int stack_blocks_for(zn_handle h, int rows, int keys_upper_bound) {
+  if (h->tune[ZN_TUNE_WHOLE_STEP] == 2 || !(rows == 1 ? h->stack1_ok : h->stack_ok)) return -1;
   const int nb = keys_upper_bound <= 512 ? 1 : (keys_upper_bound + 511) / 512;
-  if (nb > ZN_SK_KB_MAXNB) return -1;
-  return (rows == 1 ? h->stackv1_ok : h->stackv_ok)[stack_variant_of(nb)] ? nb : -1;
+  return nb <= ZN_SK_KB_MAXNB && (rows == 1 ? h->stackv1_ok : h->stackv_ok)[stack_variant_of(nb)] ? nb : -1;
 }
-static bool stack_pre(zn_handle h) { return h->tune[18] != 2; }
-static int launch_stack(zn_handle h, hipStream_t s, int rows) {
+// Launches path and chain path: slots 0..2 (one step) and 4..6 (a run), by attention launch shape.  Whole-step kernel: one slot per key-block
+// count of the attention role, 8 + nbk (one step) and 8 + (ZN_SK_KB_MAXNB + 1) + nbk (a run).
+static int graph_slot_for(const StepPlan& p) { return p.path == StepPlan::STACK ? 8 + (p.run > 1 ? ZN_SK_KB_MAXNB + 1 : 0) + p.nbk : p.attn_fused + (p.run > 1 ? 4 : 0); }
+// The per-block persistent chain serves two rows when the model fits an instantiation: 1.07 vs 1.16 ms per decode step at the Zonos-v0.1 dimensions.
+static bool chain_allowed(zn_handle h, int rows) { return h->ch_variant != 0 && rows == 2 && persist_allowed(h); }
+// One step of `rows` rows over at most `keys` keys off the whole-step kernel (a step of plan_steps, or of the position-by-position prefill).
+static StepPlan plan_blocks(zn_handle h, int rows, int keys) {
+  StepPlan p;
+  p.path = chain_allowed(h, rows) ? StepPlan::CHAIN : StepPlan::LAUNCHES; p.attn_fused = attn_fused_for(h, keys);
+  return p;
+}
+// The next decode steps of the generation, `steps_left` of them still asked for.  A step appends one key per row; a run of ZN_GRAPH_STEPS steps with one launch shape replays the long graph.
+// The whole-step kernel serves every step whose context fits one of its instantiations; a run takes the attention role its LAST step needs (workgroups of key blocks past a step's context leave
+// at once).  Fused tail: at batch 1 on a persistent kernel the step's tail (bookkeeping + next step's embedding) runs in the sampler launch's last workgroup.  Larger batches keep three launches
+// (one workgroup embedding 8 utterances in turn cost 31 us per step at batch 8), and so does the launches path (its first op reads h->x): one row has the fused tail only on whole-step steps.
+static StepPlan plan_steps(zn_handle h, int steps_left) {
+  const int rows = h->rows, keys = h->len_hi + 1, keys_run = h->len_hi + ZN_GRAPH_STEPS;
+  const bool want_run = steps_left >= ZN_GRAPH_STEPS && h->tune[ZN_TUNE_GRAPH_RUNS] > 1;
+  const bool tail_ok = h->cfg.arch == 0 && persist_active(h, rows) && h->batch <= 2;
+  const int nb_run = tail_ok && want_run ? stack_blocks_for(h, rows, keys_run) : -1;
+  const int nb_one = tail_ok ? stack_blocks_for(h, rows, keys) : -1;
+  StepPlan p = plan_blocks(h, rows, keys);
+  if (nb_run >= 0 || nb_one >= 0) {
+    p.path = StepPlan::STACK; p.nbk = nb_run >= 0 ? nb_run : nb_one; p.run = nb_run >= 0 ? ZN_GRAPH_STEPS : 1;
+  } else if (want_run && attn_fused_for(h, keys_run) == p.attn_fused) p.run = ZN_GRAPH_STEPS;
+  p.fused_tail = tail_ok && p.path != StepPlan::LAUNCHES;
+  p.graph_slot = graph_slot_for(p);
+  return p;
+}
+static bool stack_pre(zn_handle h) { return h->tune[ZN_TUNE_STACK_PRE] != 2; }
+static int launch_stack(zn_handle h, hipStream_t s, int rows, int nbk) {
   const zn_config& c = h->cfg;
   ChainArgs a{};
   a.eps = c.norm_eps; a.F = c.d_ff; a.nqkv = (c.n_heads + 2 * c.n_heads_kv) * h->hd;
@@ -789,9 +821,9 @@ static int launch_stack(zn_handle h, hipStream_t s, int rows) {
   a.rope_positions = c.rope_positions;
   a.layers = h->stack_layers; a.n_layer = c.n_layer; a.q0 = h->q; a.scale = (float)(1.0 / std::sqrt((double)h->hd));
   a.heads_rows = c.n_codebooks * c.vocab_head; a.heads_out = h->logits_raw; a.trace = h->dbg_trace;
-  const int mode = h->stack_nbk, npairs = rows * c.n_heads_kv;
+  const int mode = nbk, npairs = rows * c.n_heads_kv;
   a.natt = npairs * (mode < 1 ? 1 : mode);
-  if (stack_pre(h)) {       // block 0's LayerNorm + in_proj + RoPE + KV append inside the launch (zn_debug_tune(18, 2): as a launch before it)
+  if (stack_pre(h)) {       // block 0's LayerNorm + in_proj + RoPE + KV append inside the launch (ZN_TUNE_STACK_PRE = 2: as a launch before it)
     a.pre_W = (const bf16_t*)h->layers[0].in_proj; a.pre_ln_w = (const bf16_t*)h->layers[0].norm_w; a.pre_ln_b = (const bf16_t*)h->layers[0].norm_b;
     a.pre_kv = (bf16_t*)h->kv_layers[0];
   }
@@ -829,18 +861,18 @@ static int build_stack_table(zn_handle h) {
       L.W_in = (const bf16_t*)nx.in_proj; L.lnn_w = (const bf16_t*)nx.norm_w; L.lnn_b = (const bf16_t*)nx.norm_b; L.kv_next = (bf16_t*)h->kv_layers[li + 1];
     }
   }
-  HIPCHK(h, hipMemcpy(h->stack_layers, t.data(), t.size() * sizeof(StackLayer), hipMemcpyHostToDevice));
+  HIPCHK(h, ZN_NOT_IN_CAPTURE(hipMemcpy(h->stack_layers, t.data(), t.size() * sizeof(StackLayer), hipMemcpyHostToDevice)));
   return ZN_OK;
 }
 
-// All blocks of one decode step on h->x (transformer): launches per op, or in_proj(0) + (attention, chain) per block.
+// All blocks of one decode step on h->x (transformer): launches per op, or in_proj(0) + (attention, chain) per block, as the plan says.
 // x0 != NULL: the residual stream enters the first block from there (the decode step's embedding buffer) instead of h->x.
 // heads_done != NULL: the caller wants the logits too; set when the last block's chain launch has produced them.
-static int decode_blocks(zn_handle h, const int* ext, int ext_scalar, hipStream_t s, const bf16_t* x0 = nullptr, bool* heads_done = nullptr) {
+static int decode_blocks(zn_handle h, const StepPlan& p, const int* ext, int ext_scalar, hipStream_t s, const bf16_t* x0 = nullptr, bool* heads_done = nullptr) {
   const zn_config& c = h->cfg;
   int rc;
   const size_t tb = (size_t)h->rows * c.d_model * 2;
-  const bool chain = chain_active(h, h->rows);
+  const bool chain = p.path == StepPlan::CHAIN;
   if (x0 && !chain) ZN_FAIL(h, ZN_ERR_STATE, "decode_blocks: a separate input buffer is the chain path's");
   auto trace = [&](int li) {        // slots per block: x after the block, attention output, q, m (first d values per row pair), x after the attention half
     if (!h->dbg_trace) return;
@@ -851,13 +883,11 @@ static int decode_blocks(zn_handle h, const int* ext, int ext_scalar, hipStream_
   auto trace_q = [&](int li) {      // q of block li, as the attention launch reads it
     if (h->dbg_trace) (void)hipMemcpyAsync((char*)h->dbg_trace + (size_t)(8 * li + 2) * tb, h->q, tb, hipMemcpyDeviceToDevice, s);
   };
-  auto trace_x1 = [&]() {};
-  (void)trace_x1;
   if (!chain) {
     for (int li = 0; li < c.n_layer; ++li) {
       if ((rc = layer_in_proj(h, li, h->x, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, h->rows, s))) return rc;
       trace_q(li);
-      if ((rc = run_attention(h, h->q, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, ext, ext_scalar, h->o1, h->rows, s))) return rc;
+      if ((rc = run_attention(h, h->q, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, ext, ext_scalar, h->o1, h->rows, p.attn_fused, s))) return rc;
       if ((rc = layer_post_attention(h, li, h->x, h->rows, s, h->dbg_trace ? (bf16_t*)((char*)h->dbg_trace + (size_t)(8 * li + 7) * tb) : nullptr))) return rc;
       trace(li);
     }
@@ -867,7 +897,7 @@ static int decode_blocks(zn_handle h, const int* ext, int ext_scalar, hipStream_
   h->epoch_bound += c.n_layer;                             // one tag per chain launch (counted again by zn_decode_steps: the bound stays an upper bound)
   for (int li = 0; li < c.n_layer; ++li) {
     trace_q(li);
-    if ((rc = run_attention(h, h->q, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, ext, ext_scalar, h->o1, h->rows, s,
+    if ((rc = run_attention(h, h->q, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, ext, ext_scalar, h->o1, h->rows, p.attn_fused, s,
                             h->ch_stamps ? h->ch_stamps + (size_t)(c.n_layer + li) * 32 : nullptr))) return rc;
     const bool wh = heads_done && li + 1 == c.n_layer && chain_heads_fit(h);
     if ((rc = launch_chain(h, li, h->kv_layers, h->max_len, h->lengths, s, li == 0 ? x0 : nullptr, wh))) return rc;
@@ -883,7 +913,7 @@ static int heads_logits(zn_handle h, const bf16_t* x, int rows, hipStream_t s) {
   GemvArgs a{};
   a.W = (const bf16_t*)h->heads; a.N = c.n_codebooks * c.vocab_head; a.K = c.d_model; a.x = x;
   a.ln_w = (const bf16_t*)h->norm_f_w; a.ln_b = (const bf16_t*)h->norm_f_b; a.eps = c.norm_eps; a.out_f32 = h->logits_raw;
-  return run_gemv<PRO_LN, EPI_F32>(h, a, rows, h->tune[4], s);
+  return run_gemv<PRO_LN, EPI_F32>(h, a, rows, h->tune[ZN_TUNE_WG_HEADS], s);
 }
 
 // ------------------------------------------------------------------------------------------------ hybrid backbone
@@ -931,15 +961,15 @@ static int mamba_mixer(zn_handle h, int li, const bf16_t* n, void* state, bf16_t
   o.W = (const bf16_t*)lw.m_out_proj; o.N = c.d_model; o.K = c.m_d_inner; o.out = out;
   if (gated_pro) {
     o.gv = h->m_vg; o.ln_w = (const bf16_t*)lw.m_norm_w; o.eps = c.norm_eps;
-    return run_gemv<PRO_GATED, EPI_STORE>(h, o, rows, h->tune[3], s);
+    return run_gemv<PRO_GATED, EPI_STORE>(h, o, rows, h->tune[ZN_TUNE_WG_FC2], s);
   }
   hipLaunchKernelGGL(mamba_gated_norm_kernel, dim3(c.m_ngroups, rows), dim3(256), 0, s, m);
   o.x = h->m_g;
-  return run_gemv<PRO_NONE, EPI_STORE>(h, o, rows, h->tune[3], s);
+  return run_gemv<PRO_NONE, EPI_STORE>(h, o, rows, h->tune[ZN_TUNE_WG_FC2], s);
 }
 
 // One token through hybrid layer li (mamba_ssm Block, fused_add_norm): hidden h->x / residual h->res in, same out.
-static int hybrid_layer(zn_handle h, int li, void* cache, int max_len, const int* lengths, int rows, hipStream_t s) {
+static int hybrid_layer(zn_handle h, int li, void* cache, int max_len, const int* lengths, int rows, int attn_fused, hipStream_t s) {
   const zn_config& c = h->cfg;
   const zn_layer_weights& lw = h->layers[li];
   const int d = c.d_model, hd = h->hd, nq = c.n_heads * hd, nkv = c.n_heads_kv * hd;
@@ -953,53 +983,51 @@ static int hybrid_layer(zn_handle h, int li, void* cache, int max_len, const int
     a.W = (const bf16_t*)lw.in_proj; a.N = nq + 2 * nkv; a.K = d; a.x = h->hn;
     a.lengths = lengths; a.hd = hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
     a.q_out = h->q; a.kv = (bf16_t*)cache; a.rope = h->rope; a.max_len = max_len; a.rope_positions = c.rope_positions;
-    if ((rc = run_gemv<PRO_NONE, EPI_ROPE_KV>(h, a, rows, h->tune[0], s))) return rc;
+    if ((rc = run_gemv<PRO_NONE, EPI_ROPE_KV>(h, a, rows, h->tune[ZN_TUNE_WG_IN_PROJ], s))) return rc;
   } else {   // the other attn_cfg forms (half-split or no rotary, qkv bias): projection (+ bias), then rotation + KV append
     GemvArgs a{};
     a.W = (const bf16_t*)lw.in_proj; a.N = nq + 2 * nkv; a.K = d; a.x = h->hn; a.out = h->qkv_tmp; a.bias = (const bf16_t*)lw.in_proj_bias;
-    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[0], s))) return rc;
+    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[ZN_TUNE_WG_IN_PROJ], s))) return rc;
     hipLaunchKernelGGL(rope_kv_any_kernel, dim3(1, rows), dim3(256), 0, s, h->qkv_tmp, h->q, nq, (bf16_t*)cache, h->rope, 1, 0, lengths, max_len,
                        c.n_heads, c.n_heads_kv, hd, c.rope_positions, c.rope_mode);
   }
-  if ((rc = run_attention(h, h->q, (const bf16_t*)cache, max_len, lengths, nullptr, 0, h->o1, rows, s))) return rc;
+  if ((rc = run_attention(h, h->q, (const bf16_t*)cache, max_len, lengths, nullptr, 0, h->o1, rows, attn_fused, s))) return rc;
   {
     GemvArgs a{};
     a.W = (const bf16_t*)lw.out_proj; a.N = d; a.K = nq; a.x = h->o1; a.out = h->x; a.bias = (const bf16_t*)lw.out_proj_bias;
-    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[1], s))) return rc;
+    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s))) return rc;
   }
   launch_add_ln(h, h->x, h->res, 1, 1, lw.norm2_w, lw.norm2_b, h->hn, rows, s);
   {
     GemvArgs a{};
     a.W = (const bf16_t*)lw.fc1; a.N = 2 * c.d_ff; a.K = d; a.x = h->hn; a.out = h->mbuf;
-    if ((rc = run_gemv<PRO_NONE, EPI_SILU>(h, a, rows, h->tune[2], s))) return rc;
+    if ((rc = run_gemv<PRO_NONE, EPI_SILU>(h, a, rows, h->tune[ZN_TUNE_WG_FC1], s))) return rc;
   }
   {
     GemvArgs a{};
     a.W = (const bf16_t*)lw.fc2; a.N = d; a.K = c.d_ff; a.x = h->mbuf; a.out = h->x;
-    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[3], s))) return rc;
+    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[ZN_TUNE_WG_FC2], s))) return rc;
   }
   return ZN_OK;
 }
 
 // final add + norm (_mamba_ssm.py:111-119) of the token in h->x / h->res, then the heads
-static int hybrid_heads(zn_handle h, hipStream_t s);
-
-// All layers for the token in h->x, then the final add + LayerNorm and the heads.
-static int hybrid_token(zn_handle h, bool want_logits, hipStream_t s) {
-  const zn_config& c = h->cfg;
-  int rc;
-  for (int li = 0; li < c.n_layer; ++li)
-    if ((rc = hybrid_layer(h, li, (void*)h->kv_layers[li], h->max_len, h->lengths, h->rows, s))) return rc;
-  if (!want_logits) return ZN_OK;
-  return hybrid_heads(h, s);
-}
-
 static int hybrid_heads(zn_handle h, hipStream_t s) {
   const zn_config& c = h->cfg;
   launch_add_ln(h, h->x, h->res, 1, 0, h->norm_f_w, h->norm_f_b, h->hn, h->rows, s);
   GemvArgs a{};
   a.W = (const bf16_t*)h->heads; a.N = c.n_codebooks * c.vocab_head; a.K = c.d_model; a.x = h->hn; a.out_f32 = h->logits_raw;
-  return run_gemv<PRO_NONE, EPI_F32>(h, a, h->rows, h->tune[4], s);
+  return run_gemv<PRO_NONE, EPI_F32>(h, a, h->rows, h->tune[ZN_TUNE_WG_HEADS], s);
+}
+
+// All layers for the token in h->x, then the final add + LayerNorm and the heads.
+static int hybrid_token(zn_handle h, bool want_logits, int attn_fused, hipStream_t s) {
+  const zn_config& c = h->cfg;
+  int rc;
+  for (int li = 0; li < c.n_layer; ++li)
+    if ((rc = hybrid_layer(h, li, (void*)h->kv_layers[li], h->max_len, h->lengths, h->rows, attn_fused, s))) return rc;
+  if (!want_logits) return ZN_OK;
+  return hybrid_heads(h, s);
 }
 
 static SampleArgs make_sample_args(zn_handle h, const zn_sampling& sp) {
@@ -1024,33 +1052,27 @@ static EmbedArgs make_embed_args(zn_handle h) {
   return e;
 }
 
-// Batch 1 on the chain path: the step's tail (bookkeeping + next step's embedding) runs in the sampler launch's last workgroup.
-// Larger batches keep three launches (embed_kernel spreads the utterances over workgroups; one workgroup embedding 8 utterances
-// in turn cost 31 us per step at batch 8), and so does everything off the chain path (its first op reads h->x).  One row: only the
-// steps the whole-step kernel serves read the fused tail's embedding (enqueue_step, zn_decode_steps).
-static bool tail_fused(zn_handle h) { return h->cfg.arch == 0 && persist_active(h, h->rows) && h->batch <= 2; }
-
 // One iteration of model.py:467-502: embed -> 26 blocks -> heads -> CFG/bias/penalty/sample -> bookkeeping.  With the fused tail the
 // embedding of the current column is already in h->x_emb when the step starts (zn_decode_steps launches embed_kernel before the
 // first step of a run; every step's sampler launch leaves the next one's, SampleArgs::ticket).
-static int enqueue_step(zn_handle h, hipStream_t s) {
+static int enqueue_step(zn_handle h, const StepPlan& p, hipStream_t s) {
   const zn_config& c = h->cfg;
   int rc;
-  const bool fused = tail_fused(h) && (h->use_stack || chain_active(h, h->rows));
+  const bool fused = p.fused_tail;
   if (!fused) {
     EmbedArgs e = make_embed_args(h);
     e.out = h->x;
     hipLaunchKernelGGL(embed_kernel, dim3(h->batch), dim3(256), 0, s, e);
   }
   if (c.arch == 1) {
-    if ((rc = hybrid_token(h, true, s))) return rc;
+    if ((rc = hybrid_token(h, true, p.attn_fused, s))) return rc;
   } else {
     bool heads_done = false;
-    if (h->use_stack) {                                    // every block + the heads in one launch (in_proj of block 0 inside it, or as a launch before it)
+    if (p.path == StepPlan::STACK) {                                 // every block + the heads in one launch (in_proj of block 0 inside it, or as a launch before it)
       if (!stack_pre(h) && (rc = layer_in_proj(h, 0, h->x_emb, (bf16_t*)h->kv_layers[0], h->max_len, h->lengths, h->rows, s))) return rc;
-      if ((rc = launch_stack(h, s, h->rows))) return rc;
+      if ((rc = launch_stack(h, s, h->rows, p.nbk))) return rc;
       heads_done = true;
-    } else if ((rc = decode_blocks(h, nullptr, 0, s, fused ? h->x_emb : nullptr, &heads_done))) return rc;
+    } else if ((rc = decode_blocks(h, p, nullptr, 0, s, fused ? h->x_emb : nullptr, &heads_done))) return rc;
     if (!heads_done && (rc = heads_logits(h, h->x, h->rows, s))) return rc;
   }
   SampleArgs a = make_sample_args(h, h->sp);
@@ -1065,8 +1087,8 @@ static int enqueue_step(zn_handle h, hipStream_t s) {
   if (fused) { a.ticket = h->tail_ticket; a.em = make_embed_args(h); }
   // batch 1, greedy decoding: sampling, bookkeeping and the next embedding in one workgroup (sample1_kernel: 0.8337 -> 0.8312 ms per step).  With a
   // temperature its one wave per codebook carries 17 exp / log / hash evaluations per lane and the nine ticketed workgroups are ahead again (0.8396 vs
-  // 0.8415): they keep those steps.  tune[16] = 2: always the ticketed kernel; 3: the one-workgroup kernel for every parameter set it implements (tests).
-  const bool one_wg = fused && h->batch == 1 && h->tune[16] != 2 && (h->tune[16] == 3 || !(h->sp.temperature > 0.f)) && c.vocab_head <= 64 * ZN_S1_IT &&
+  // 0.8415): they keep those steps.  ZN_TUNE_SAMPLER = 2: always the ticketed kernel; 3: the one-workgroup kernel for every parameter set it implements (tests).
+  const bool one_wg = fused && h->batch == 1 && h->tune[ZN_TUNE_SAMPLER] != 2 && (h->tune[ZN_TUNE_SAMPLER] == 3 || !(h->sp.temperature > 0.f)) && c.vocab_head <= 64 * ZN_S1_IT &&
                       c.n_codebooks <= 16 && !(h->sp.top_p > 0.f) && h->sp.top_k <= 0 && !(h->sp.linear > 0.f) &&
                       (!a.use_penalty || h->sp.repetition_penalty_window <= 16) && h->rows <= 1024;
   if (one_wg) { hipLaunchKernelGGL(sample1_kernel, dim3(1), dim3(1024), 0, s, a); return ZN_OK; }
@@ -1099,7 +1121,7 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   h->lengths = lengths_dev; h->codes = delayed_codes_dev;
   // The hand-off tags are 32-bit and advance by n_layer per decode step (~41 hours of continuous batch-1 decoding): long before they
   // can wrap, between two generations, the epoch restarts at 1 over zeroed granule buffers (tag 0 is never a launch's epoch).
-  if (h->tune[14] == 7) { h->epoch_bound = 0x70000001ull; h->tune[14] = 0; }   // test hook (zn_debug_tune(14, 7)): behave as if the tags were about to wrap
+  if (h->pending_hook == ZN_HOOK_TAG_WRAP) { h->epoch_bound = 0x70000001ull; h->pending_hook = 0; }   // test hook: behave as if the tags were about to wrap
   if (h->epoch_bound > 0x70000000ull) {
     const size_t R = h->max_rows, nqkv = (size_t)(h->cfg.n_heads + 2 * h->cfg.n_heads_kv) * h->hd;
     for (unsigned long long* g : {h->ch_gy1, h->ch_gx1, h->ch_gx2, h->ch_ga}) HIPCHK(h, hipMemsetAsync(g, 0, R * (h->cfg.d_model / 2) * 8, s));
@@ -1118,7 +1140,7 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   h->n_generations++;
   if (h->demoted && h->clean_since_demotion >= ZN_REARM_AFTER) { h->demoted = false; h->clean_since_demotion = 0; h->n_rearms++; }
   const bool persist_rows = h->cfg.arch == 0 && persist_shape(h, rows);
-  if (h->demoted && persist_rows && h->tune[8] != 2) h->n_fallback_generations++;
+  if (h->demoted && persist_rows && h->tune[ZN_TUNE_PERSISTENT] != 2) h->n_fallback_generations++;
   // one or two rows on a model the persistent kernels serve: claim the device for them, or run this generation on the launches path
   h->persist_ok = !persist_rows || zn_tenant_try_claim(h->device, h) != 0;
   if (h->cfg.arch == 0 && h->ch_variant == 1) {
@@ -1128,8 +1150,8 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   GenState st{};
   st.offset = offset0; st.step = 0; st.all_done = 0; st.force_eos_step = h->force_eos_step; st.eos_bias = h->eos_bias;
   h->dbg_pause = 0;
-  if (h->tune[14] == 11) { h->dbg_pause = 3000000u; h->tune[14] = 0; }   // test hook (zn_debug_tune(14, 11)): every launch of this generation pauses all its waves for 30 ms in block 2
-  if (h->tune[14] == 9) { st.pad[0] = 1; h->tune[14] = 0; }   // test hook (zn_debug_tune(14, 9)): this generation's hand-off waits find the timeout word set
+  if (h->pending_hook == ZN_HOOK_PAUSE) { h->dbg_pause = 3000000u; h->pending_hook = 0; }   // test hook: every launch of this generation pauses all its waves for 30 ms in block 2
+  if (h->pending_hook == ZN_HOOK_TIMEOUT_WORD) { st.pad[0] = 1; h->pending_hook = 0; }   // test hook: this generation's hand-off waits find the timeout word set
   HIPCHK(h, hipMemcpyAsync(h->st, &st, sizeof st, hipMemcpyHostToDevice, s));
   std::vector<int> rem(batch, t_total - offset0), stop(batch, 0);   // model.py:439-441
   HIPCHK(h, hipMemcpyAsync(h->remaining, rem.data(), batch * sizeof(int), hipMemcpyHostToDevice, s));
@@ -1148,7 +1170,6 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   h->emb_valid = false;
   return ZN_OK;
 }
-
 
 static int ensure_prefill_ws(zn_handle h, size_t M) {
   if (M <= h->pf_rows) return ZN_OK;
@@ -1221,7 +1242,7 @@ static int prefill_attention(zn_handle h, const bf16_t* q, int ldq, const bf16_t
   pa.q = q; pa.ldq = ldq; pa.kv = kv; pa.out = out; pa.ldo = ldo; pa.S = S; pa.base = base; pa.max_len = max_len;
   pa.n_heads = c.n_heads; pa.n_heads_kv = c.n_heads_kv; pa.qsplit = qsplit(S); pa.scale = (float)(1.0 / std::sqrt((double)hd));
   pa.row_len = row_len;
-  const bool mfma = h->tune[10] != 2;   // tune[10] = 2: the VALU kernel at every head size
+  const bool mfma = h->tune[ZN_TUNE_PREFILL_ATTN_VALU] != 2;   // 2: the VALU kernel at every head size
   int r2 = hd == 128 ? launch_prefill_attn<128>(pa, h->G, R, mfma, s) : hd == 64 ? launch_prefill_attn<64>(pa, h->G, R, mfma, s) : launch_prefill_attn<32>(pa, h->G, R, mfma, s);
   if (r2) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "prefill attention: unsupported group %d", h->G);
   return ZN_OK;
@@ -1230,7 +1251,7 @@ static int prefill_attention(zn_handle h, const bf16_t* q, int ldq, const bf16_t
 // Projection of a short prompt (17..64 rows) through the weight-streaming 64-row kernel; false = shape not served.
 template <int EPI>
 static bool run_gemm64s(zn_handle h, const bf16_t* x, const void* W, int N, int K, bf16_t* out, const bf16_t* resid, int M, hipStream_t s) {
-  if (M > 64 || K % 256 || (EPI == EPI_SILU && (N / 2) % 32) || h->tune[7] <= 1) return false;
+  if (M > 64 || K % 256 || (EPI == EPI_SILU && (N / 2) % 32) || h->tune[ZN_TUNE_SMALL_M_LDS] <= 1) return false;
   const int groups = (EPI == EPI_SILU) ? (N / 2 + 31) / 32 : (N + 63) / 64;
   if (groups > ZN_G16_MAX_GROUPS) return false;
   int ks = 1;
@@ -1251,7 +1272,7 @@ static bool run_gemm64s(zn_handle h, const bf16_t* x, const void* W, int N, int 
 template <int PRO, int EPI>
 static bool run_gemm16k_rows(zn_handle h, const bf16_t* x, const void* ln_w, const void* ln_b, const void* W, int N, int K, bf16_t* out, const bf16_t* resid,
                              int M, hipStream_t s) {
-  if (M > 64 || !gemm16k_fits(h, EPI, N, K) || h->tune[12] == 2) return false;
+  if (M > 64 || !gemm16k_fits(h, EPI, N, K) || h->tune[ZN_TUNE_NO_PREFILL_GEMM16K] == 2) return false;
   const int nch = K / (ZN_G16K_NKW * ZN_G16K_KCH);
   if (PRO == PRO_LN && nch != 2) return false;
   GemvArgs g{};
@@ -1283,7 +1304,7 @@ static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, in
     hipLaunchKernelGGL(layernorm_kernel, dim3(M), dim3(64), 0, s, h->pf_x, (const bf16_t*)lw.norm_w, (const bf16_t*)lw.norm_b, h->pf_n, d, c.norm_eps);
     // short prompts: split, RoPE and the KV append in the projection's epilogue (q compact [M][Hq * hd] in pf_qkv), as in a decode step
     int ldq = nqkv;
-    if (M <= 64 && gemm16k_fits(h, EPI_ROPE_KV, nqkv, d) && d / (ZN_G16K_NKW * ZN_G16K_KCH) == 2 && h->tune[12] != 2) {
+    if (M <= 64 && gemm16k_fits(h, EPI_ROPE_KV, nqkv, d) && d / (ZN_G16K_NKW * ZN_G16K_KCH) == 2 && h->tune[ZN_TUNE_NO_PREFILL_GEMM16K] != 2) {
       GemvArgs g{};
       g.W = (const bf16_t*)lw.in_proj; g.N = nqkv; g.K = d; g.x = h->pf_n; g.nrows = M; g.eps = c.norm_eps;
       g.hd = hd; g.n_heads = c.n_heads; g.n_heads_kv = c.n_heads_kv; g.q_out = h->pf_qkv; g.kv = kv; g.rope = h->rope; g.max_len = max_len;
@@ -1337,7 +1358,7 @@ static int proj_rows(zn_handle h, const bf16_t* A, int lda, const void* W, const
     for (int m = 0; m < M; ++m) {
       GemvArgs g{};
       g.W = (const bf16_t*)W; g.N = N; g.K = K; g.x = A + (size_t)m * lda; g.out = out + (size_t)m * ldo; g.bias = (const bf16_t*)bias;
-      int rc = run_gemv<PRO_NONE, EPI_STORE>(h, g, 1, h->tune[1], s);
+      int rc = run_gemv<PRO_NONE, EPI_STORE>(h, g, 1, h->tune[ZN_TUNE_WG_OUT_PROJ], s);
       if (rc) return rc;
     }
     return ZN_OK;
@@ -1425,12 +1446,8 @@ static int prefill_impl(zn_handle h, const void* hidden_dev, int32_t S, const in
     for (int p = 0; p < S; ++p) {
       hipLaunchKernelGGL(gather_pos_kernel, dim3(h->rows), dim3(256), 0, s, (const bf16_t*)hidden_dev, h->x, S, p, c.d_model);
       int ext = (p / qb) * qb + qb; if (ext > S) ext = S;
-      h->attn_fused = attn_fused_for(h, ++h->len_hi, h->rows);
-      if (c.arch == 1) {
-        if ((rc = hybrid_token(h, p == S - 1, s))) return rc;
-      } else {
-        if ((rc = decode_blocks(h, nullptr, ext, s))) return rc;
-      }
+      const StepPlan plan = plan_blocks(h, h->rows, ++h->len_hi);
+      if ((rc = c.arch == 1 ? hybrid_token(h, p == S - 1, plan.attn_fused, s) : decode_blocks(h, plan, nullptr, ext, s))) return rc;
       hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > h->rows ? 64 : h->rows), 0, s, h->lengths, h->rows, 1);
     }
   }
@@ -1500,45 +1517,29 @@ extern "C" int zn_decode_steps(zn_handle h, int32_t n, zn_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   h->gen_stream = s;
   for (int i = 0; i < n;) {
-    // this step appends one key per row; a run of ZN_GRAPH_STEPS steps with one launch shape replays the long graph
-    const int fused = attn_fused_for(h, h->len_hi + 1, h->rows);
-    const bool want_run = n - i >= ZN_GRAPH_STEPS && h->tune[6] > 1;
-    // the whole-step kernel serves every step whose context fits one of its instantiations (stack_mode_for); a run of steps takes the
-    // attention role its LAST step needs (workgroups of key blocks past a step's context leave at once)
-    const bool st_ok = tail_fused(h);
-    const int mode_run = (st_ok && want_run) ? stack_mode_for(h, h->rows, h->len_hi + ZN_GRAPH_STEPS) : -1;
-    const int mode_one = st_ok ? stack_mode_for(h, h->rows, h->len_hi + 1) : -1;
-    const bool stack_run = mode_run >= 0, stack = stack_run || mode_one >= 0;
-    const int mode = stack_run ? mode_run : mode_one;
-    const int run = stack ? (stack_run ? ZN_GRAPH_STEPS : 1) : ((want_run && attn_fused_for(h, h->len_hi + ZN_GRAPH_STEPS, h->rows) == fused) ? ZN_GRAPH_STEPS : 1);
-    const int k = stack ? (8 + (run > 1 ? ZN_SK_KB_MAXNB + 1 : 0) + mode) : (fused + (run > 1 ? 4 : 0));      // launches path: slots 0..2 and 4..6
-    h->attn_fused = fused; h->use_stack = stack;
-    if (stack) h->stack_nbk = mode;
+    const StepPlan p = h->last_plan = plan_steps(h, n - i);
+    const int k = p.graph_slot, run = p.run;
     // steps with the fused tail read the embedding their predecessor's tail left: the first of them gets it from embed_kernel; steps
     // without it (one row off the whole-step kernel) embed into h->x themselves and leave x_emb stale
-    const bool tail = st_ok && (stack || chain_active(h, h->rows));
-    if (tail && !h->emb_valid) {
-      hipLaunchKernelGGL(embed_kernel, dim3(h->batch), dim3(256), 0, s, make_embed_args(h));
-      h->emb_valid = true;
-    }
-    if (!tail) h->emb_valid = false;
+    if (p.fused_tail && !h->emb_valid) hipLaunchKernelGGL(embed_kernel, dim3(h->batch), dim3(256), 0, s, make_embed_args(h));
+    h->emb_valid = p.fused_tail;
     if (!h->graph_exec[k] && !h->graph_tried[k] && n > 1) {
       // capture; every step-varying quantity (column, positions) is read from device memory
       h->graph_tried[k] = true;
       // capture on an internal stream: the caller's stream may be the legacy null stream, which cannot be captured
       if (!h->cap_stream) (void)hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking);
-      hipStream_t cs = h->cap_stream;
+      hipStream_t cs = h->cap_stream; std::unique_lock<std::mutex> capturing(g_capture_mu);
       if (cs && hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) == hipSuccess) {
         int rc = ZN_OK;
-        for (int j = 0; j < run && rc == ZN_OK; ++j) rc = enqueue_step(h, cs);
+        for (int j = 0; j < run && rc == ZN_OK; ++j) rc = enqueue_step(h, p, cs);
         hipGraph_t g = nullptr;
-        hipError_t e = hipStreamEndCapture(cs, &g);
+        hipError_t e = hipStreamEndCapture(cs, &g); capturing.unlock();
         if (rc == ZN_OK && e == hipSuccess && g && hipGraphInstantiate(&h->graph_exec[k], g, nullptr, nullptr, 0) == hipSuccess) h->graph[k] = g;
         else { if (g) (void)hipGraphDestroy(g); h->graph_exec[k] = nullptr; (void)hipGetLastError(); }
       } else (void)hipGetLastError();
     }
     if (h->graph_exec[k]) HIPCHK(h, hipGraphLaunch(h->graph_exec[k], s));
-    else for (int j = 0; j < run; ++j) { int rc = enqueue_step(h, s); if (rc) return rc; }
+    else for (int j = 0; j < run; ++j) { int rc = enqueue_step(h, p, s); if (rc) return rc; }
     i += run; h->len_hi += run; h->epoch_bound += (unsigned long long)run * (h->cfg.n_layer + 1);
   }
   HIPCHK(h, hipGetLastError());
@@ -1560,7 +1561,7 @@ extern "C" int zn_gen_end(zn_handle h) {
 extern "C" int zn_get_counters(zn_handle h, int64_t* out, int32_t n) {
   if (!h || !out || n < 0) return ZN_ERR_ARG;
   unsigned w[2] = {0, 0};
-  if (n > 6 && h->ch_diag) HIPCHK(h, hipMemcpy(w, h->ch_diag + 8, sizeof w, hipMemcpyDeviceToHost));
+  if (n > 6 && h->ch_diag) HIPCHK(h, ZN_NOT_IN_CAPTURE(hipMemcpy(w, h->ch_diag + 8, sizeof w, hipMemcpyDeviceToHost)));
   const long long v[8] = {h->n_timeouts, h->n_generations, h->n_fallback_generations, h->demoted ? 1 : 0, h->n_rearms, h->clean_since_demotion, (long long)(w[0] / 100u), (long long)w[1]};
   for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
   return ZN_OK;
@@ -1568,7 +1569,8 @@ extern "C" int zn_get_counters(zn_handle h, int64_t* out, int32_t n) {
 
 extern "C" int zn_decode_path_detail(zn_handle h) {
   if (!h || !h->gen_active || h->cfg.arch != 0 || !persist_active(h, h->rows)) return 0;
-  return h->use_stack ? 2 : chain_active(h, h->rows) ? 1 : 0;   // (one row: the whole-step kernel or the launches path)
+  // which persistent kernel: the last plan's; whether one is still allowed: asked now (a timeout reported since demotes at once).  One row: 2 or 0
+  return h->last_plan.path == StepPlan::STACK ? 2 : chain_allowed(h, h->rows) ? 1 : 0;
 }
 extern "C" int zn_decode_path(zn_handle h) { return zn_decode_path_detail(h) != 0 ? 1 : 0; }
 extern "C" int zn_graph_active(zn_handle h) {
@@ -1586,9 +1588,9 @@ static int handoff_timeout(zn_handle h, int count) {
   // it.  Drain the generation's stream before the diagnostic words are read and cleared and before the graphs those steps run from are
   // destroyed (on a non-blocking stream the null-stream copies below would not wait for them).
   if (h->gen_stream) (void)hipStreamSynchronize(h->gen_stream);
-  (void)hipMemcpy(h->diag_host, h->ch_diag, sizeof h->diag_host, hipMemcpyDeviceToHost);
-  (void)hipMemset(h->ch_diag, 0, 32);                   // (the wait statistics in words 8, 9 stay)
-  (void)hipMemset(&h->st->pad[0], 0, sizeof(int));
+  (void)ZN_NOT_IN_CAPTURE(hipMemcpy(h->diag_host, h->ch_diag, sizeof h->diag_host, hipMemcpyDeviceToHost));
+  (void)ZN_NOT_IN_CAPTURE(hipMemset(h->ch_diag, 0, 32));                   // (the wait statistics in words 8, 9 stay)
+  (void)ZN_NOT_IN_CAPTURE(hipMemset(&h->st->pad[0], 0, sizeof(int)));
   h->demoted = true; h->clean_since_demotion = 0; h->n_timeouts++; h->gen_timed_out = true;
   free_graph(h);
   const unsigned* d = h->diag_host;
@@ -1646,13 +1648,13 @@ extern "C" int zn_debug_token_override(zn_handle h, const int32_t* tokens_dev, i
   return ZN_OK;
 }
 extern "C" int zn_debug_tune(zn_handle h, int32_t key, int32_t value) {
-  if (!h || key < 0 || key >= 20 || value < 1) return ZN_ERR_ARG;
-  if (key == 14 && value == 13) {                        // observation hook: forget the wait statistics (zn_get_counters [6], [7]) gathered so far
-    if (h->ch_diag) { (void)hipDeviceSynchronize(); (void)hipMemset(h->ch_diag + 8, 0, 2 * sizeof(unsigned)); }
+  if (!h || key < 0 || key >= ZN_TUNE_NKEYS || value < 1) return ZN_ERR_ARG;
+  if (key == ZN_TUNE_HOOK && value == ZN_HOOK_RESET_WAIT_STATS) {   // observation hook: forget the wait statistics (zn_get_counters [6], [7]) gathered so far
+    if (h->ch_diag) { (void)hipDeviceSynchronize(); (void)ZN_NOT_IN_CAPTURE(hipMemset(h->ch_diag + 8, 0, 2 * sizeof(unsigned))); }
     return ZN_OK;
   }
-  h->tune[key] = value; free_graph(h); h->emb_valid = false;
-  if (key == 8 && value == 1 && h->demoted) { h->demoted = false; h->clean_since_demotion = 0; h->n_rearms++; }
+  (key == ZN_TUNE_HOOK ? h->pending_hook : h->tune[key]) = value; free_graph(h); h->emb_valid = false;      // (a hook waits for zn_gen_begin)
+  if (key == ZN_TUNE_PERSISTENT && value == 1 && h->demoted) { h->demoted = false; h->clean_since_demotion = 0; h->n_rearms++; }
   return ZN_OK;
 }
 extern "C" int zn_debug_trace(zn_handle h, void* trace_dev) {
@@ -1687,8 +1689,8 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   HIPCHK(h, hipMemsetAsync(h->mbuf, 0, (size_t)rows * c.d_ff * 2, s));
   HIPCHK(h, hipMemsetAsync(h->o1, 0, (size_t)rows * d * 2, s));
   const int hd = h->hd, nq = c.n_heads * hd, nkv = c.n_heads_kv * hd;
-  bf16_t* tkv = nullptr; int* tlen = nullptr;             // which == 4, 5: a scratch cache of 8 positions per row, all rows at position 0
-  if (which == 5 && !chain_active(h, rows)) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the persistent chain serves batch 1 (2 rows) of the transformer only");
+  bf16_t* tkv = nullptr; int* tlen = nullptr; int stack_nbk = -1;   // which == 4, 5: a scratch cache of 8 positions per row, all rows at position 0; which == 6: key blocks of the launch
+  if (which == 5 && !chain_allowed(h, rows)) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the persistent chain serves batch 1 (2 rows) of the transformer only");
   if (which == 4 || which == 5) {
     HIPCHK(h, hipMalloc(&tkv, (size_t)rows * 8 * 2 * nkv * 2));
     HIPCHK(h, hipMalloc(&tlen, (size_t)rows * sizeof(int)));
@@ -1703,12 +1705,11 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   if (which == 6) {
     if (!persist_active(h, rows)) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the whole-step kernel serves one or two rows of the transformer only");
     if (!h->stack_checked) { h->stack_ok = stack_shapes_ok(h); h->stack_checked = true; }
-    h->stack_nbk = stack_mode_for(h, rows, ctx + 1);
-    if (h->stack_nbk < 0) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the whole-step kernel does not serve this model / context");
+    if ((stack_nbk = stack_blocks_for(h, rows, ctx + 1)) < 0) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the whole-step kernel does not serve this model / context");
     const int cap = ctx + 8;
     std::vector<int> lens(rows, ctx);
     HIPCHK(h, hipMalloc(&tlen, (size_t)rows * sizeof(int)));
-    HIPCHK(h, hipMemcpy(tlen, lens.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, ZN_NOT_IN_CAPTURE(hipMemcpy(tlen, lens.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice)));
     skv.assign(c.n_layer, nullptr);
     h->kv_layers.assign(c.n_layer, nullptr);
     for (int li = 0; li < c.n_layer; ++li) {
@@ -1729,10 +1730,10 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   // which == 0 at 5..16 rows: the launch a decode step makes there - fc1 normalising from the statistics its producer left (layer_post_attention);
   // the producer runs once, outside the timed loop, on the zeroed rows
   bool fc1_lnp = false;
-  if (which == 0 && rows > 4 && h->tune[9] != 2 && h->ln_part && d == 16 * ZN_G16_LNT && gemm16k_fits(h, EPI_RESID, d, nq)) {
+  if (which == 0 && rows > 4 && h->tune[ZN_TUNE_FC1_LN_LAUNCH] != 2 && h->ln_part && d == 16 * ZN_G16_LNT && gemm16k_fits(h, EPI_RESID, d, nq)) {
     GemvArgs b{};
     b.W = (const bf16_t*)h->layers[0].out_proj; b.N = d; b.K = nq; b.x = h->o1; b.resid = h->x; b.out = h->x; b.eps = c.norm_eps; b.ln_part_out = h->ln_part;
-    rc = run_gemv<PRO_NONE, EPI_RESID>(h, b, rows, h->tune[1], s);
+    rc = run_gemv<PRO_NONE, EPI_RESID>(h, b, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s);
     fc1_lnp = rc == ZN_OK;
   }
   for (int pass = 0; pass < 2 && rc == ZN_OK; ++pass) {   // pass 0 = warm-up
@@ -1744,15 +1745,15 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
       if (which == 0) {
         a.W = (const bf16_t*)lw.fc1; a.N = 2 * c.d_ff; a.K = d; a.x = h->x; a.ln_w = (const bf16_t*)lw.norm2_w; a.ln_b = (const bf16_t*)lw.norm2_b; a.out = h->mbuf;
         if (fc1_lnp) a.ln_part_in = h->ln_part;
-        rc = run_gemv<PRO_LN, EPI_SILU>(h, a, rows, h->tune[2], s);
+        rc = run_gemv<PRO_LN, EPI_SILU>(h, a, rows, h->tune[ZN_TUNE_WG_FC1], s);
       } else if (which == 1) {
         a.W = (const bf16_t*)lw.fc2; a.N = d; a.K = c.d_ff; a.x = h->mbuf; a.resid = h->x; a.out = h->x;
-        rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[3], s);
+        rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[ZN_TUNE_WG_FC2], s);
       } else if (which == 2) {
         a.W = (const bf16_t*)lw.out_proj; a.N = d; a.K = c.n_heads * h->hd; a.x = h->o1; a.resid = h->x; a.out = h->x;
-        rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[1], s);
+        rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s);
       } else if (which == 6) {
-        rc = launch_stack(h, s, rows);
+        rc = launch_stack(h, s, rows, stack_nbk);
       } else if (which == 5) {
         if (i % c.n_layer == c.n_layer - 1) continue;       // the last block's launch has no in_proj: not the launch being priced
         rc = launch_chain(h, i % c.n_layer, std::vector<const void*>(c.n_layer, tkv), 8, tlen, s);
@@ -1760,7 +1761,7 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
         a.W = (const bf16_t*)lw.in_proj; a.N = nq + 2 * nkv; a.K = d; a.x = h->x; a.ln_w = (const bf16_t*)lw.norm_w; a.ln_b = (const bf16_t*)lw.norm_b;
         a.lengths = tlen; a.hd = hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
         a.q_out = h->q; a.kv = tkv; a.rope = h->rope; a.max_len = 8; a.rope_positions = c.rope_positions;
-        rc = run_gemv<PRO_LN, EPI_ROPE_KV>(h, a, rows, h->tune[0], s);
+        rc = run_gemv<PRO_LN, EPI_ROPE_KV>(h, a, rows, h->tune[ZN_TUNE_WG_IN_PROJ], s);
       } else {
         rc = heads_logits(h, h->x, rows, s);
       }
@@ -1779,7 +1780,7 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
     h->kv_layers = saved_kv; h->max_len = saved_max_len; h->lengths = saved_lengths;
     if (h->gen_active && (int)h->kv_layers.size() == c.n_layer) { int rcb = build_stack_table(h); if (rcb) return rcb; }
     int tmo = 0;
-    HIPCHK(h, hipMemcpy(&tmo, &h->st->pad[0], sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(h, ZN_NOT_IN_CAPTURE(hipMemcpy(&tmo, &h->st->pad[0], sizeof(int), hipMemcpyDeviceToHost)));
     if (tmo != 0) return handoff_timeout(h, tmo);
   }
   if (which == 5 || which == 6) h->epoch_bound += (unsigned long long)(iters + 8) * (c.n_layer + 1);
@@ -1876,8 +1877,8 @@ extern "C" int zn_op_layer_decode(zn_handle h, int32_t layer, void* x, void* kv,
     ZN_FAIL(h, ZN_ERR_ARG, "zn_op_layer_decode: bad argument");
   int rc = ensure_attn_ws(h, max_len);
   if (rc) return rc;
-  h->attn_fused = attn_fused_for(h, max_len, rows);   // lengths live on the device: bound the context by the capacity
-  rc = layer_decode(h, layer, (bf16_t*)x, (bf16_t*)kv, max_len, lengths, ext, 0, rows, (hipStream_t)stream);
+  // lengths live on the device: bound the context by the capacity
+  rc = layer_decode(h, layer, (bf16_t*)x, (bf16_t*)kv, max_len, lengths, ext, 0, rows, attn_fused_for(h, max_len), (hipStream_t)stream);
   if (rc) return rc;
   HIPCHK(h, hipGetLastError());
   return ZN_OK;
@@ -1917,10 +1918,10 @@ extern "C" int zn_op_backbone_forward(zn_handle h, const void* hidden_dev, void*
     hipLaunchKernelGGL(gather_pos_kernel, dim3(rows), dim3(256), 0, s, hid, h->x, S, p, d);
     hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64 > rows ? 64 : rows), 0, s, h->fw_lengths, rows, base + p);
     int ext = (p / qb) * qb + qb; if (ext > S) ext = S;
-    h->attn_fused = attn_fused_for(h, base + p + 1, rows);
+    const int attn_fused = attn_fused_for(h, base + p + 1);
     for (int li = 0; li < c.n_layer; ++li) {
-      if (c.arch == 1) rc = hybrid_layer(h, li, (void*)caches_dev[li], max_len, h->fw_lengths, rows, s);
-      else rc = layer_decode(h, li, h->x, (bf16_t*)caches_dev[li], max_len, h->fw_lengths, nullptr, S > 1 ? base + ext : 0, rows, s);
+      if (c.arch == 1) rc = hybrid_layer(h, li, (void*)caches_dev[li], max_len, h->fw_lengths, rows, attn_fused, s);
+      else rc = layer_decode(h, li, h->x, (bf16_t*)caches_dev[li], max_len, h->fw_lengths, nullptr, S > 1 ? base + ext : 0, rows, attn_fused, s);
       if (rc) return rc;
     }
     if (c.arch == 1) launch_add_ln(h, h->x, h->res, 1, 0, h->norm_f_w, h->norm_f_b, h->nbuf, rows, s);
@@ -1961,8 +1962,7 @@ extern "C" int zn_op_attn_decode(zn_handle h, const void* q, const void* kv, int
   if (rows > h->max_rows) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_decode: rows > max_rows");
   int rc = ensure_attn_ws(h, max_len);
   if (rc) return rc;
-  h->attn_fused = attn_fused_for(h, max_len, rows);
-  rc = run_attention(h, (const bf16_t*)q, (const bf16_t*)kv, max_len, lengths, ext, 0, (bf16_t*)out, rows, (hipStream_t)stream);
+  rc = run_attention(h, (const bf16_t*)q, (const bf16_t*)kv, max_len, lengths, ext, 0, (bf16_t*)out, rows, attn_fused_for(h, max_len), (hipStream_t)stream);
   if (rc) return rc;
   HIPCHK(h, hipGetLastError());
   return ZN_OK;
