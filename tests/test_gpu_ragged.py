@@ -68,7 +68,7 @@ def _same_bits(a, b):
 
 
 def _gemm_class(M):
-    """The prefill projections' kernel is chosen by M = R * S (zn_api.hip: run_gemm16k_rows / run_gemm64s up to 64 rows, launch_gemm's
+    """The prefill projections' kernel is chosen by M = R * S (zn_linear_plan.h: plan_linear's gemm16k / gemm64s kernels up to 64 rows, launch_gemm's
     plain kernel up to 255, its LDS-staged one from 256)."""
     return 0 if M <= 64 else 1 if M <= 255 else 2
 

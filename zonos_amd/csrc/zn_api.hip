@@ -19,7 +19,6 @@
 static thread_local std::string g_create_err;
 #define ZN_GRAPH_STEPS 8
 #define ZN_G16_PART_BYTES ((size_t)8 << 20)
-#define ZN_G16_MAX_GROUPS 1024
 #define ZN_REARM_AFTER 4
 
 // How the next decode steps run (plan_steps): the one record zn_decode_steps, enqueue_step and decode_blocks agree through.
@@ -369,154 +368,122 @@ static int launch_gemv_rows(const GemvArgs& a, int rgroup, int ks, int nch, int 
   return -1;
 }
 
-// Runs one fused GEMV over `rows` activation rows (groups of <= 4 rows per launch; weights are re-streamed per
-// group, so batches beyond 2 utterances pay extra HBM traffic until the MFMA small-M path lands).
-// rows in (4, 16]: one weight pass on the matrix cores (gemm16_kernel); LayerNorm, when fused in the GEMV, is a row-wise
-// launch here (amortised over the batch).
-// rows in (4, 16], K a multiple of 256: the LDS-staged kernel (coalesced weight stream); K is split over workgroups until
-// the grid has >= 512 of them, the partial tiles meet in a scratch buffer (allocated by zn_create when max_rows > 4).
-template <int EPI, bool LNP = false>
-static bool run_gemm16s(zn_handle h, GemvArgs g, hipStream_t s) {
-  const int K = g.K;
-  if (K % ZN_G16_KC || !h->g16_part) return false;
-  if (LNP && (K != 16 * ZN_G16_LNT || !g.ln_part_in)) return false;
-  const int nrows_w = (EPI == EPI_SILU) ? g.N / 2 : g.N;          // weight rows that define the grid
-  const int per64 = (EPI == EPI_SILU) ? 32 : 64;
-  // 64-row workgroups when that already gives >= 512 of them, else 32-row ones, else split K as well
-  int nwv = 4, groups = (nrows_w + per64 - 1) / per64;
-  if (groups < 512) { nwv = 2; groups = (nrows_w + per64 / 2 - 1) / (per64 / 2); }
-  if (groups > ZN_G16_MAX_GROUPS) return false;
-  int ks = 1;
-  while (groups * ks < 448 && ks < 16 && K % (2 * ks * ZN_G16_KC) == 0) ks *= 2;
-  // (fc2 at 16 rows, K = 8192 over 64 groups: 8 slices; 4: 1.690, 8: 1.681, 16: 1.746 ms per batch-8 step)
-  // (the Mamba2 in_proj, N = 8512 over 266 groups: 1 / 2 (default) / 4 slices: 1.933 / 1.937 / 1.945 ms per batch-8 hybrid step)
-  if (ks > 1 && K / ks < 512) {
-    // short slices: the combine costs more than the direct-fragment kernel's access pattern, unless a shallower split
-    // still fills the chip (in_proj, N = 3072: 96 groups x 4 slices of 512)
-    ks /= 2;
-    if (ks < 2 || K / ks < 512 || groups * ks < 320) return false;
+static void launch_gemm(const bf16_t* A, int lda, const bf16_t* W, bf16_t* out, int ldo, const bf16_t* resid, int M, int N, int K, hipStream_t s,
+                        const bf16_t* bias = nullptr) {
+  GemmArgs g{A, W, out, resid, M, N, K, lda, ldo, bias};
+  dim3 grid((N + 127) / 128, (M + 127) / 128);
+  if (M >= 256 && K % ZN_PG_KC == 0 && lda % 8 == 0) {   // long prompts: LDS-staged panels (coalesced row pieces)
+    if (resid) hipLaunchKernelGGL((gemm_bf16s_kernel<1>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((gemm_bf16s_kernel<0>), grid, dim3(256), 0, s, g);
+    return;
   }
-  if ((size_t)ks * 16 * groups * nwv * 16 * sizeof(float) > h->g16_part_bytes) return false;
-  g.part = h->g16_part; g.tickets = h->g16_tickets; g.ksplit = ks;
-  if (nwv == 4) hipLaunchKernelGGL((gemm16s_kernel<EPI, 4, LNP>), dim3(groups, ks), dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((gemm16s_kernel<EPI, 2, LNP>), dim3(groups, ks), dim3(128), 0, s, g);
-  return true;
+  if (resid) hipLaunchKernelGGL((gemm_bf16_kernel<1>), grid, dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((gemm_bf16_kernel<0>), grid, dim3(256), 0, s, g);
+}
+template <int NW, int EPI>
+static void launch_gemm16_t(const GemvArgs& g, int blocks, bool tile8, hipStream_t s) {
+  if constexpr (lin_has_tile8(EPI)) if (tile8) { hipLaunchKernelGGL((gemm16_kernel<NW, EPI, 8>), dim3(blocks), dim3(NW * 64), 0, s, g); return; }
+  hipLaunchKernelGGL((gemm16_kernel<NW, EPI>), dim3(blocks), dim3(NW * 64), 0, s, g);
+}
+template <int EPI, bool LNP>
+static void launch_gemm16s_t(const GemvArgs& g, const LinearPlan& p, hipStream_t s) {
+  if (p.nwv == 4) hipLaunchKernelGGL((gemm16s_kernel<EPI, 4, LNP>), dim3(p.groups, p.ksplit), dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((gemm16s_kernel<EPI, 2, LNP>), dim3(p.groups, p.ksplit), dim3(128), 0, s, g);
 }
 
-// rows in (4, 16], K = 8 waves x 128 x {2, 4} and few weight rows (the LDS-staged kernel would have to split K over
-// workgroups): one 16-row tile per workgroup, K split over its waves, no cross-workgroup combine.  ZN_TUNE_NO_SPLIT_SMALL_M = 2 disables.
-static bool gemm16k_fits(zn_handle h, int epi, int N, int K) {
-  if (epi == EPI_SILU || h->tune[ZN_TUNE_SMALL_M_LDS] <= 1 || h->tune[ZN_TUNE_NO_SPLIT_SMALL_M] == 2) return false;
-  const int per = ZN_G16K_NKW * ZN_G16K_KCH, nch = K / per;
-  if (K % per || (nch != 2 && nch != 4)) return false;
-  return (N + 15) / 16 < (h->tune[ZN_TUNE_GEMM16K_MAX_TILES] > 0 ? h->tune[ZN_TUNE_GEMM16K_MAX_TILES] : 1024);     // many rows: the 64-row workgroups fill the chip without a split (ZN_TUNE_GEMM16K_MAX_TILES: the tile count from which they take over)
+// Every decision about a linear of 1 .. 64 rows is plan_linear's (zn_linear_plan.h); what it may depend on:
+static LinearEnv linear_env(zn_handle h) {
+  LinearEnv e;
+  e.small_m_lds = h->tune[ZN_TUNE_SMALL_M_LDS]; e.no_split_small_m = h->tune[ZN_TUNE_NO_SPLIT_SMALL_M]; e.gemm16k_max_tiles = h->tune[ZN_TUNE_GEMM16K_MAX_TILES];
+  e.fc1_ln_launch = h->tune[ZN_TUNE_FC1_LN_LAUNCH]; e.no_prefill_gemm16k = h->tune[ZN_TUNE_NO_PREFILL_GEMM16K];
+  e.g16_part_bytes = h->g16_part_bytes; e.has_g16_part = h->g16_part != nullptr; e.has_ln_part = h->ln_part != nullptr;
+  return e;
 }
-template <int PRO, int EPI>
-static void run_gemm16k(const GemvArgs& g, hipStream_t s) {
-  if constexpr (EPI != EPI_SILU) {
-    const int tiles = (g.N + 15) / 16;
-    if (g.K / (ZN_G16K_NKW * ZN_G16K_KCH) == 2) hipLaunchKernelGGL((gemm16k_kernel<EPI, 2, PRO>), dim3(tiles), dim3(ZN_G16K_NKW * 64), 0, s, g);
-    else if constexpr (PRO == PRO_NONE) hipLaunchKernelGGL((gemm16k_kernel<EPI, 4, PRO>), dim3(tiles), dim3(ZN_G16K_NKW * 64), 0, s, g);   // (the LayerNorm prologue at K = 4096 would not fit the register file: the caller keeps it a launch)
-  }
+// g serves the row group [r0, r0 + nr) of the rows it described: every per-row pointer moves there.
+static void advance_rows(GemvArgs& g, int r0, int nr, int out_cols) {
+  g.nrows = nr;
+  if (g.x) g.x += (size_t)r0 * g.K;
+  if (g.gv) g.gv += (size_t)r0 * g.K;
+  if (g.out) g.out += (size_t)r0 * out_cols;
+  if (g.resid) g.resid += (size_t)r0 * g.N;
+  if (g.out_f32) g.out_f32 += (size_t)r0 * g.N;
+  if (g.lengths) g.lengths += r0;
+  if (g.q_out) g.q_out += (size_t)r0 * g.n_heads * g.hd;
+  if (g.kv) g.kv += (size_t)r0 * g.max_len * 2 * g.n_heads_kv * g.hd;
+  if (g.conv_state) { g.conv_state += (size_t)r0 * g.conv_dim * 4; g.xbc += (size_t)r0 * g.conv_dim; }
+  if (g.ln_part_out) g.ln_part_out += (size_t)r0 * ZN_G16_LNT * 2;
+  if (g.ln_part_in) g.ln_part_in += (size_t)r0 * ZN_G16_LNT * 2;
 }
-
+// Launches what the plan says over `rows` activation rows, group by group (weights are re-streamed per group): the template switches, and nothing that decides.
 template <int PRO, int EPI>
-static int run_gemm16(zn_handle h, GemvArgs a, int rows, hipStream_t s) {
-  if constexpr (PRO == PRO_GATED) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "gated-norm prologue: at most 4 rows (got %d)", rows);
-  else {
-  const int K = a.K;
-  // few weight-row tiles (N = d_model: 128 workgroups) -> more waves per workgroup so that every CU still keeps enough
-  // loads in flight
-  const int tiles_n = (EPI == EPI_SILU) ? (a.N / 2) / 16 : (a.N + 15) / 16;
-  int nw = 4;
-  if (tiles_n <= 256 && K % 256 == 0) nw = 8;
-  if (tiles_n <= 256 && K >= 8192 && K % 512 == 0) nw = 16;
-  if (K % (nw * 32)) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "gemm16: K=%d not a multiple of %d", K, nw * 32);
-  if (EPI == EPI_SILU && (a.N / 2) % 16) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "gemm16: d_ff must be a multiple of 16");
-  const int tiles = (EPI == EPI_SILU) ? (a.N / 2) / 16 : (a.N + 15) / 16;
-  for (int r0 = 0; r0 < rows; r0 += 16) {
+static int launch_linear(zn_handle h, const LinearPlan& p, GemvArgs a, int rows, hipStream_t s) {
+  if (p.err) ZN_FAIL(h, p.err, "%s", p.msg);
+  if (!linear_plan_launchable(p, PRO, EPI)) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "linear: no kernel %d for prologue %d / epilogue %d (ks=%d nch=%d)", (int)p.kernel, PRO, EPI, p.ks, p.nch);
+  if ((p.reads_ln_stats && !a.ln_part_in) || (p.writes_ln_stats && !a.ln_part_out)) ZN_FAIL(h, ZN_ERR_STATE, "linear: the plan hands over LayerNorm statistics, the call has no buffer for them");
+  if (!p.writes_ln_stats) a.ln_part_out = nullptr;
+  a.units = p.units; a.upw = p.upw;
+  if (p.ksplit) { a.part = h->g16_part; a.tickets = h->g16_tickets; a.ksplit = p.ksplit; }
+  const int per = p.rows_per_launch ? p.rows_per_launch : rows;
+  for (int r0 = 0; r0 < rows; r0 += per) {
     GemvArgs g = a;
-    const int nr = rows - r0 < 16 ? rows - r0 : 16;
-    g.nrows = nr;
-    const bool k16 = gemm16k_fits(h, EPI, a.N, K);
-    // that kernel normalises its rows itself when at most one workgroup per CU repeats the statistics (in_proj: 8.7 us vs
-    // 4.8 + 6.2; the heads' 577 tiles: 21.8 vs 5.0 + 11.9)
-    const bool k16_ln = k16 && PRO == PRO_LN && tiles <= 256 && K == 2 * ZN_G16K_NKW * ZN_G16K_KCH;
-    if constexpr (PRO == PRO_LN && EPI == EPI_SILU) {
-      // the producer of these rows left LayerNorm statistics per 16-column tile (layer_post_attention): fc1 normalises while it stages
-      if (a.ln_part_in && !k16 && h->tune[ZN_TUNE_SMALL_M_LDS] > 1) {
-        GemvArgs gl = a;
-        gl.nrows = nr; gl.x = a.x + (size_t)r0 * K; gl.ln_part_in = a.ln_part_in + (size_t)r0 * ZN_G16_LNT * 2;
-        if (gl.out) gl.out += (size_t)r0 * (a.N / 2);
-        if (run_gemm16s<EPI, true>(h, gl, s)) continue;
-      }
-    }
-    if (PRO == PRO_LN && !k16_ln) {
-      hipLaunchKernelGGL(layernorm_kernel, dim3(nr), dim3(64), 0, s, a.x + (size_t)r0 * K, a.ln_w, a.ln_b, h->nbuf, K, a.eps);
+    const int nr = rows - r0 < per ? rows - r0 : per;
+    advance_rows(g, r0, nr, EPI == EPI_SILU ? a.N / 2 : a.N);
+    if (p.ln_launch) {
+      hipLaunchKernelGGL(layernorm_kernel, dim3(nr), dim3(64), 0, s, g.x, a.ln_w, a.ln_b, h->nbuf, a.K, a.eps);
       g.x = h->nbuf;
-    } else g.x = a.x + (size_t)r0 * K;
-    if (g.out) g.out += (size_t)r0 * (EPI == EPI_SILU ? a.N / 2 : a.N);
-    if (g.resid) g.resid += (size_t)r0 * a.N;
-    if (g.out_f32) g.out_f32 += (size_t)r0 * a.N;
-    if (g.lengths) g.lengths += r0;
-    if (g.q_out) g.q_out += (size_t)r0 * a.n_heads * a.hd;
-    if (g.kv) g.kv += (size_t)r0 * a.max_len * 2 * a.n_heads_kv * a.hd;
-    if (g.conv_state) { g.conv_state += (size_t)r0 * a.conv_dim * 4; g.xbc += (size_t)r0 * a.conv_dim; }
-    if (g.ln_part_out) { if (k16 && EPI == EPI_RESID && a.N == 16 * ZN_G16_LNT) g.ln_part_out += (size_t)r0 * ZN_G16_LNT * 2; else g.ln_part_out = nullptr; }
-    if (k16) {
-      if (k16_ln) run_gemm16k<PRO, EPI>(g, s); else run_gemm16k<PRO_NONE, EPI>(g, s);
-      continue;
     }
-    if (h->tune[ZN_TUNE_SMALL_M_LDS] > 1 && run_gemm16s<EPI>(h, g, s)) continue;
-    if constexpr (EPI != EPI_SILU) {
-      if (tiles <= 192 && a.N % 8 == 0) {   // N = d_model: 8-row tiles so that every CU gets a workgroup
-        const int t8 = a.N / 8;
-        if (nw == 16) hipLaunchKernelGGL((gemm16_kernel<16, EPI, 8>), dim3(t8), dim3(1024), 0, s, g);
-        else if (nw == 8) hipLaunchKernelGGL((gemm16_kernel<8, EPI, 8>), dim3(t8), dim3(512), 0, s, g);
-        else hipLaunchKernelGGL((gemm16_kernel<4, EPI, 8>), dim3(t8), dim3(256), 0, s, g);
-        continue;
-      }
+    switch (p.kernel) {
+      case LinearPlan::GEMV:
+        (void)launch_gemv_rows<PRO, EPI>(g, nr, p.ks, p.nch, p.blocks, p.full, s);      // (its instantiations: linear_plan_launchable)
+        break;
+      case LinearPlan::GEMM16:
+        if constexpr (lin_has_gemm16(PRO)) {
+          if (p.nw == 16) launch_gemm16_t<16, EPI>(g, p.blocks, p.tile8, s);
+          else if (p.nw == 8) launch_gemm16_t<8, EPI>(g, p.blocks, p.tile8, s);
+          else launch_gemm16_t<4, EPI>(g, p.blocks, p.tile8, s);
+        }
+        break;
+      case LinearPlan::GEMM16S:
+        if constexpr (lin_has_lnp(PRO, EPI)) if (p.lnp) { launch_gemm16s_t<EPI, true>(g, p, s); break; }
+        if constexpr (lin_has_gemm16(PRO)) launch_gemm16s_t<EPI, false>(g, p, s);
+        break;
+      case LinearPlan::GEMM16K:   // decode: one 16-row group per launch; prefill: ceil(rows / 16) of them
+        if constexpr (lin_has_gemm16k(PRO, EPI)) {
+          const dim3 grid((a.N + 15) / 16, (nr + 15) / 16), block(ZN_G16K_NKW * 64);
+          if constexpr (lin_has_gemm16k_ln(PRO, 2)) if (p.ln_pro) { hipLaunchKernelGGL((gemm16k_kernel<EPI, 2, PRO_LN>), grid, block, 0, s, g); break; }
+          if (p.nch == 2) hipLaunchKernelGGL((gemm16k_kernel<EPI, 2, PRO_NONE>), grid, block, 0, s, g);
+          else hipLaunchKernelGGL((gemm16k_kernel<EPI, 4, PRO_NONE>), grid, block, 0, s, g);
+        }
+        break;
+      case LinearPlan::GEMM64S:
+        if constexpr (lin_has_prefill(PRO, EPI)) hipLaunchKernelGGL((gemm64s_kernel<EPI>), dim3(p.groups, p.ksplit), dim3(256), 0, s, g);
+        break;
+      case LinearPlan::GEMM_TILED:
+        if constexpr (lin_has_prefill(PRO, EPI) && EPI == EPI_SILU) {
+          launch_gemm(g.x, a.K, a.W, h->pf_u, a.N, nullptr, nr, a.N, a.K, s);
+          hipLaunchKernelGGL(silu_mul_rows_kernel, dim3(nr), dim3(256), 0, s, h->pf_u, g.out, a.N / 2);
+        } else if constexpr (lin_has_prefill(PRO, EPI)) launch_gemm(g.x, a.K, a.W, g.out, a.N, g.resid, nr, a.N, a.K, s);
+        break;
     }
-    if (nw == 16) hipLaunchKernelGGL((gemm16_kernel<16, EPI>), dim3(tiles), dim3(1024), 0, s, g);
-    else if (nw == 8) hipLaunchKernelGGL((gemm16_kernel<8, EPI>), dim3(tiles), dim3(512), 0, s, g);
-    else hipLaunchKernelGGL((gemm16_kernel<4, EPI>), dim3(tiles), dim3(256), 0, s, g);
   }
   return ZN_OK;
-  }
 }
-
 template <int PRO, int EPI>
-static int run_gemv(zn_handle h, GemvArgs a, int rows, int target_blocks, hipStream_t s) {
-  if (rows > 4) return run_gemm16<PRO, EPI>(h, a, rows, s);
-  const int K = a.K;
-  int ks = 1;
-  if ((PRO == PRO_NONE || PRO == PRO_GATED) && K >= 4096 && K % 2048 == 0) ks = 4;
-  const int kw = K / ks;
-  int nch = (kw + 511) / 512;
-  nch = nch <= 1 ? 1 : nch <= 2 ? 2 : nch <= 4 ? 4 : nch <= 8 ? 8 : 99;
-  if (nch > 8) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "gemv: K=%d too large for the register-resident activation path", K);
-  a.units = (EPI == EPI_SILU) ? a.N / 2 : (a.N + 1) / 2;
-  const int lanes_units = (ks == 1) ? 4 : 1;  // units in flight per block
-  int upw = (a.units + target_blocks * lanes_units - 1) / (target_blocks * lanes_units);
-  if (upw < 1) upw = 1;
-  a.upw = upw;
-  const int blocks = (a.units + upw * lanes_units - 1) / (upw * lanes_units);
-  const bool full = (kw == nch * 512) && (a.N % 2 == 0) && (a.units == blocks * lanes_units * upw);
-  for (int r0 = 0; r0 < rows; r0 += 4) {
-    GemvArgs g = a;
-    const int nr = rows - r0 < 4 ? rows - r0 : 4;
-    g.nrows = nr;
-    if (g.x) g.x += (size_t)r0 * K;
-    if (g.out) g.out += (size_t)r0 * (EPI == EPI_SILU ? a.N / 2 : a.N);
-    if (g.resid) g.resid += (size_t)r0 * a.N;
-    if (g.out_f32) g.out_f32 += (size_t)r0 * a.N;
-    if (g.lengths) g.lengths += r0;
-    if (g.q_out) g.q_out += (size_t)r0 * a.n_heads * a.hd;
-    if (g.kv) g.kv += (size_t)r0 * a.max_len * 2 * a.n_heads_kv * a.hd;
-    if (g.conv_state) { g.conv_state += (size_t)r0 * a.conv_dim * 4; g.xbc += (size_t)r0 * a.conv_dim; }
-    if (launch_gemv_rows<PRO, EPI>(g, nr, ks, nch, blocks, full, s) != 0) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "gemv: no kernel for ks=%d nch=%d", ks, nch);
+static int run_gemv(zn_handle h, const GemvArgs& a, int rows, int target_blocks, hipStream_t s) {
+  return launch_linear<PRO, EPI>(h, plan_linear(linear_env(h), PRO, EPI, rows, a.N, a.K, target_blocks, false, false, false), a, rows, s);
+}
+// A projection over the M rows of a batched prefill (x normalised by the caller): the small-M kernels up to 64 rows, else the tiled GEMM.
+// with_gemm16k = false: fc1 / fc2, which were measured on the 64-row kernel only.  EPI_ROPE_KV (in_proj): *rope_done tells whether split, RoPE and
+// the KV append ran in the epilogue (q compact [M][Hq * hd] in q_out) or rope_kv_rows_kernel still has to follow on out [M][N].
+template <int EPI>
+static int prefill_linear(zn_handle h, const GemvArgs& g, int M, hipStream_t s, bool with_gemm16k = true, bool* rope_done = nullptr) {
+  LinearEnv e = linear_env(h);
+  if (!with_gemm16k) e.no_prefill_gemm16k = 2;
+  const LinearPlan p = plan_linear(e, PRO_NONE, EPI, M, g.N, g.K, 0, true, false, false);
+  if constexpr (EPI == EPI_ROPE_KV) {
+    if (!(*rope_done = p.epi == EPI_ROPE_KV)) return launch_linear<PRO_NONE, EPI_STORE>(h, p, g, M, s);
   }
-  return ZN_OK;
+  return launch_linear<PRO_NONE, EPI>(h, p, g, M, s);
 }
 
 // ONE arithmetic for the decode attention on every path (launches, per-block chain, whole-step kernels): scores on the matrix cores in
@@ -600,58 +567,65 @@ static int run_attention(zn_handle h, const bf16_t* q, const bf16_t* kv, int max
   return ZN_OK;
 }
 
+// The arguments of a transformer block's projections and of the heads, shared by the decode step and by zn_bench_kernel (which prices the step's launches).
+static GemvArgs linear_args(zn_handle h, const void* W, int N, int K, const bf16_t* x, bf16_t* out, const bf16_t* resid = nullptr) {
+  GemvArgs a{};
+  a.W = (const bf16_t*)W; a.N = N; a.K = K; a.x = x; a.out = out; a.resid = resid; a.eps = h->cfg.norm_eps;
+  return a;
+}
+static GemvArgs in_proj_args(zn_handle h, const zn_layer_weights& lw, const bf16_t* x, bf16_t* kv, int max_len, const int* lengths) {
+  const zn_config& c = h->cfg;
+  GemvArgs a = linear_args(h, lw.in_proj, (c.n_heads + 2 * c.n_heads_kv) * h->hd, c.d_model, x, nullptr);
+  a.ln_w = (const bf16_t*)lw.norm_w; a.ln_b = (const bf16_t*)lw.norm_b; a.lengths = lengths; a.hd = h->hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
+  a.q_out = h->q; a.kv = kv; a.rope = h->rope; a.max_len = max_len; a.rope_positions = c.rope_positions;
+  return a;
+}
+static GemvArgs out_proj_args(zn_handle h, const zn_layer_weights& lw, const bf16_t* in, bf16_t* out, const bf16_t* resid) {
+  return linear_args(h, lw.out_proj, h->cfg.d_model, h->cfg.n_heads * h->hd, in, out, resid);
+}
+static GemvArgs fc1_args(zn_handle h, const zn_layer_weights& lw, const bf16_t* x, const float* ln_stats) {   // ln_stats: left by x's producer, or null
+  GemvArgs a = linear_args(h, lw.fc1, 2 * h->cfg.d_ff, h->cfg.d_model, x, h->mbuf);
+  a.ln_w = (const bf16_t*)lw.norm2_w; a.ln_b = (const bf16_t*)lw.norm2_b; a.ln_part_in = ln_stats;
+  return a;
+}
+static GemvArgs fc2_args(zn_handle h, const zn_layer_weights& lw, bf16_t* x) { return linear_args(h, lw.fc2, h->cfg.d_model, h->cfg.d_ff, h->mbuf, x, x); }
+static GemvArgs heads_args(zn_handle h, const bf16_t* x) {
+  GemvArgs a = linear_args(h, h->heads, h->cfg.n_codebooks * h->cfg.vocab_head, h->cfg.d_model, x, nullptr);
+  a.ln_w = (const bf16_t*)h->norm_f_w; a.ln_b = (const bf16_t*)h->norm_f_b; a.out_f32 = h->logits_raw;
+  return a;
+}
+// The projection that completes the residual stream (the second out_proj call under double_out_proj, else the single one) and fc1, planned
+// together: fc1 normalises from handed-over LayerNorm statistics exactly when that projection's plan writes them (rows 5..16).
+struct PostAttnPlans { LinearPlan out, fc1; };
+static PostAttnPlans plan_post_attention(zn_handle h, int rows) {
+  const zn_config& c = h->cfg;
+  const LinearEnv e = linear_env(h);
+  PostAttnPlans pp;
+  pp.out = plan_linear(e, PRO_NONE, EPI_RESID, rows, c.d_model, c.n_heads * h->hd, h->tune[ZN_TUNE_WG_OUT_PROJ], false, true, false);
+  pp.fc1 = plan_linear(e, PRO_LN, EPI_SILU, rows, 2 * c.d_ff, c.d_model, h->tune[ZN_TUNE_WG_FC1], false, false, pp.out.writes_ln_stats);
+  return pp;
+}
+
 // LayerNorm -> in_proj -> split -> RoPE(q,k) -> KV append of block `li` (q in h->q, k/v in the cache row lengths[r])
 static int layer_in_proj(zn_handle h, int li, bf16_t* x, bf16_t* kv, int max_len, const int* lengths, int rows, hipStream_t s) {
-  const zn_config& c = h->cfg;
-  const zn_layer_weights& lw = h->layers[li];
-  const int d = c.d_model, hd = h->hd, nq = c.n_heads * hd, nkv = c.n_heads_kv * hd;
-  GemvArgs a{};
-  a.W = (const bf16_t*)lw.in_proj; a.N = nq + 2 * nkv; a.K = d; a.x = x;
-  a.ln_w = (const bf16_t*)lw.norm_w; a.ln_b = (const bf16_t*)lw.norm_b; a.eps = c.norm_eps;
-  a.lengths = lengths; a.hd = hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
-  a.q_out = h->q; a.kv = kv; a.rope = h->rope; a.max_len = max_len; a.rope_positions = c.rope_positions;
-  return run_gemv<PRO_LN, EPI_ROPE_KV>(h, a, rows, h->tune[ZN_TUNE_WG_IN_PROJ], s);
+  return run_gemv<PRO_LN, EPI_ROPE_KV>(h, in_proj_args(h, h->layers[li], x, kv, max_len, lengths), rows, h->tune[ZN_TUNE_WG_IN_PROJ], s);
 }
 
 // out_proj (-> out_proj again, _torch.py:419-420) -> residual -> LayerNorm -> fc1 -> y * silu(gate) -> fc2 -> residual
 static int layer_post_attention(zn_handle h, int li, bf16_t* x, int rows, hipStream_t s, bf16_t* x1_copy = nullptr) {
-  const zn_config& c = h->cfg;
   const zn_layer_weights& lw = h->layers[li];
-  const int d = c.d_model, nq = c.n_heads * h->hd;
+  const PostAttnPlans pp = plan_post_attention(h, rows);
   int rc;
-  // rows 5..16: the projection that completes the residual stream leaves LayerNorm statistics per 16-column tile and fc1 normalises its
-  // activation chunks from them - no LayerNorm launch in between (GemvArgs::ln_part_out).  ZN_TUNE_FC1_LN_LAUNCH = 2: the launch.
-  const bool lnp = rows > 4 && h->tune[ZN_TUNE_FC1_LN_LAUNCH] != 2 && h->ln_part && d == 16 * ZN_G16_LNT && gemm16k_fits(h, EPI_RESID, d, nq);
-  {
-    GemvArgs a{};
-    a.W = (const bf16_t*)lw.out_proj; a.N = d; a.K = nq; a.x = h->o1;
-    if (c.double_out_proj) {
-      a.out = h->q;   // q is dead after attention: reuse it for the intermediate projection
-      if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s))) return rc;
-      GemvArgs b{};
-      b.W = (const bf16_t*)lw.out_proj; b.N = d; b.K = nq; b.x = h->q; b.resid = x; b.out = x;
-      if (lnp) b.ln_part_out = h->ln_part;
-      if ((rc = run_gemv<PRO_NONE, EPI_RESID>(h, b, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s))) return rc;
-    } else {
-      a.resid = x; a.out = x;
-      if (lnp) a.ln_part_out = h->ln_part;
-      if ((rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s))) return rc;
-    }
+  GemvArgs o = out_proj_args(h, lw, h->o1, x, x);
+  o.ln_part_out = h->ln_part;
+  if (h->cfg.double_out_proj) {   // q is dead after attention: reuse it for the intermediate projection
+    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, out_proj_args(h, lw, h->o1, h->q, nullptr), rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s))) return rc;
+    o.x = h->q;
   }
-  if (x1_copy) (void)hipMemcpyAsync(x1_copy, x, (size_t)rows * d * 2, hipMemcpyDeviceToDevice, s);      // diagnostic trace
-  {  // LayerNorm -> fc1 -> y * silu(gate)
-    GemvArgs a{};
-    a.W = (const bf16_t*)lw.fc1; a.N = 2 * c.d_ff; a.K = d; a.x = x;
-    a.ln_w = (const bf16_t*)lw.norm2_w; a.ln_b = (const bf16_t*)lw.norm2_b; a.eps = c.norm_eps; a.out = h->mbuf;
-    if (lnp) a.ln_part_in = h->ln_part;
-    if ((rc = run_gemv<PRO_LN, EPI_SILU>(h, a, rows, h->tune[ZN_TUNE_WG_FC1], s))) return rc;
-  }
-  {  // fc2 -> residual
-    GemvArgs a{};
-    a.W = (const bf16_t*)lw.fc2; a.N = d; a.K = c.d_ff; a.x = h->mbuf; a.resid = x; a.out = x;
-    if ((rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[ZN_TUNE_WG_FC2], s))) return rc;
-  }
-  return ZN_OK;
+  if ((rc = launch_linear<PRO_NONE, EPI_RESID>(h, pp.out, o, rows, s))) return rc;
+  if (x1_copy) (void)hipMemcpyAsync(x1_copy, x, (size_t)rows * h->cfg.d_model * 2, hipMemcpyDeviceToDevice, s);      // diagnostic trace
+  if ((rc = launch_linear<PRO_LN, EPI_SILU>(h, pp.fc1, fc1_args(h, lw, x, pp.out.writes_ln_stats ? h->ln_part : nullptr), rows, s))) return rc;
+  return run_gemv<PRO_NONE, EPI_RESID>(h, fc2_args(h, lw, x), rows, h->tune[ZN_TUNE_WG_FC2], s);
 }
 
 // One decode step of block `li` on x [rows][d] in place (_torch.py:307-328), as launches.
@@ -909,11 +883,7 @@ static int decode_blocks(zn_handle h, const StepPlan& p, const int* ext, int ext
 }
 
 static int heads_logits(zn_handle h, const bf16_t* x, int rows, hipStream_t s) {
-  const zn_config& c = h->cfg;
-  GemvArgs a{};
-  a.W = (const bf16_t*)h->heads; a.N = c.n_codebooks * c.vocab_head; a.K = c.d_model; a.x = x;
-  a.ln_w = (const bf16_t*)h->norm_f_w; a.ln_b = (const bf16_t*)h->norm_f_b; a.eps = c.norm_eps; a.out_f32 = h->logits_raw;
-  return run_gemv<PRO_LN, EPI_F32>(h, a, rows, h->tune[ZN_TUNE_WG_HEADS], s);
+  return run_gemv<PRO_LN, EPI_F32>(h, heads_args(h, x), rows, h->tune[ZN_TUNE_WG_HEADS], s);
 }
 
 // ------------------------------------------------------------------------------------------------ hybrid backbone
@@ -1195,19 +1165,6 @@ static int ensure_prefill_ws(zn_handle h, size_t M) {
   return ZN_OK;
 }
 
-static void launch_gemm(const bf16_t* A, int lda, const bf16_t* W, bf16_t* out, int ldo, const bf16_t* resid, int M, int N, int K, hipStream_t s,
-                        const bf16_t* bias = nullptr) {
-  GemmArgs g{A, W, out, resid, M, N, K, lda, ldo, bias};
-  dim3 grid((N + 127) / 128, (M + 127) / 128);
-  if (M >= 256 && K % ZN_PG_KC == 0 && lda % 8 == 0) {   // long prompts: LDS-staged panels (coalesced row pieces)
-    if (resid) hipLaunchKernelGGL((gemm_bf16s_kernel<1>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((gemm_bf16s_kernel<0>), grid, dim3(256), 0, s, g);
-    return;
-  }
-  if (resid) hipLaunchKernelGGL((gemm_bf16_kernel<1>), grid, dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((gemm_bf16_kernel<0>), grid, dim3(256), 0, s, g);
-}
-
 template <int HD>
 static int launch_prefill_attn(const PrefillAttnArgs& a, int G, int R, bool mfma, hipStream_t s) {
   if constexpr (HD == 128) {
@@ -1248,42 +1205,6 @@ static int prefill_attention(zn_handle h, const bf16_t* q, int ldq, const bf16_t
   return ZN_OK;
 }
 
-// Projection of a short prompt (17..64 rows) through the weight-streaming 64-row kernel; false = shape not served.
-template <int EPI>
-static bool run_gemm64s(zn_handle h, const bf16_t* x, const void* W, int N, int K, bf16_t* out, const bf16_t* resid, int M, hipStream_t s) {
-  if (M > 64 || K % 256 || (EPI == EPI_SILU && (N / 2) % 32) || h->tune[ZN_TUNE_SMALL_M_LDS] <= 1) return false;
-  const int groups = (EPI == EPI_SILU) ? (N / 2 + 31) / 32 : (N + 63) / 64;
-  if (groups > ZN_G16_MAX_GROUPS) return false;
-  int ks = 1;
-  while (groups * ks < 256 && ks < 16 && K % (2 * ks * 256) == 0) ks *= 2;
-  // (fc2, K = 8192: the split this picks, 8, against 4 / 16 / 2 forced: prefill 2.71 vs 2.90 / 2.77 / 3.13 ms)
-  if ((size_t)ks * 64 * groups * 64 * sizeof(float) > h->g16_part_bytes) return false;
-  GemvArgs g{};
-  g.W = (const bf16_t*)W; g.N = N; g.K = K; g.x = x; g.out = out; g.resid = resid; g.nrows = M;
-  g.part = h->g16_part; g.tickets = h->g16_tickets; g.ksplit = ks;
-  hipLaunchKernelGGL((gemm64s_kernel<EPI>), dim3(groups, ks), dim3(256), 0, s, g);
-  return true;
-}
-
-// Short prompts, contractions of 2048 or 4096 with few weight rows (in_proj, both out_proj calls): the decode side's gemm16k_kernel
-// (one 16-row weight tile per workgroup over the whole K, K split over its 8 waves: no cross-workgroup combine; LayerNorm as its
-// prologue) over ceil(M / 16) row groups in ONE launch, instead of gemm64s_kernel's 8-way split-K with a ticketed combine
-// (14.4 us for 8-13 MB) behind a LayerNorm launch.
-template <int PRO, int EPI>
-static bool run_gemm16k_rows(zn_handle h, const bf16_t* x, const void* ln_w, const void* ln_b, const void* W, int N, int K, bf16_t* out, const bf16_t* resid,
-                             int M, hipStream_t s) {
-  if (M > 64 || !gemm16k_fits(h, EPI, N, K) || h->tune[ZN_TUNE_NO_PREFILL_GEMM16K] == 2) return false;
-  const int nch = K / (ZN_G16K_NKW * ZN_G16K_KCH);
-  if (PRO == PRO_LN && nch != 2) return false;
-  GemvArgs g{};
-  g.W = (const bf16_t*)W; g.N = N; g.K = K; g.x = x; g.out = out; g.resid = resid; g.nrows = M; g.eps = h->cfg.norm_eps;
-  g.ln_w = (const bf16_t*)ln_w; g.ln_b = (const bf16_t*)ln_b;
-  const dim3 grid((N + 15) / 16, (M + 15) / 16), block(ZN_G16K_NKW * 64);
-  if (nch == 2) hipLaunchKernelGGL((gemm16k_kernel<EPI, 2, PRO>), grid, block, 0, s, g);
-  else if constexpr (PRO == PRO_NONE) hipLaunchKernelGGL((gemm16k_kernel<EPI, 4, PRO>), grid, block, 0, s, g);
-  return true;
-}
-
 // Transformer blocks over all S positions of R rows (hidden [R][S][d]) with `base` keys already cached per row: the
 // residual stream of every position ends in h->pf_x.  row_len (device, [R]; base 0 only): right-padded rows.  The row-wise kernels and the
 // projections run over all R * S positions (pad rows are computed and dropped: no op mixes positions except the attention, which bounds
@@ -1299,43 +1220,22 @@ static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, in
   for (int li = 0; li < c.n_layer; ++li) {
     const zn_layer_weights& lw = h->layers[li];
     bf16_t* kv = (bf16_t*)kv_layers[li];
-    // short prompts (<= 64 rows): every projection streams its weights through a small-M kernel (10.7 -> ~2.5 ms per prefill)
+    // short prompts (<= 64 rows): every projection streams its weights through a small-M kernel (10.7 -> ~2.5 ms per prefill); prefill_linear
     // (LayerNorm as gemm16k's prologue over four row groups: 22.0 us against 4.7 + 9 for the launch pair: 768 workgroups repeat the statistics)
     hipLaunchKernelGGL(layernorm_kernel, dim3(M), dim3(64), 0, s, h->pf_x, (const bf16_t*)lw.norm_w, (const bf16_t*)lw.norm_b, h->pf_n, d, c.norm_eps);
-    // short prompts: split, RoPE and the KV append in the projection's epilogue (q compact [M][Hq * hd] in pf_qkv), as in a decode step
-    int ldq = nqkv;
-    if (M <= 64 && gemm16k_fits(h, EPI_ROPE_KV, nqkv, d) && d / (ZN_G16K_NKW * ZN_G16K_KCH) == 2 && h->tune[ZN_TUNE_NO_PREFILL_GEMM16K] != 2) {
-      GemvArgs g{};
-      g.W = (const bf16_t*)lw.in_proj; g.N = nqkv; g.K = d; g.x = h->pf_n; g.nrows = M; g.eps = c.norm_eps;
-      g.hd = hd; g.n_heads = c.n_heads; g.n_heads_kv = c.n_heads_kv; g.q_out = h->pf_qkv; g.kv = kv; g.rope = h->rope; g.max_len = max_len;
-      g.rope_positions = c.rope_positions; g.pf_S = S; g.pf_base = base;
-      hipLaunchKernelGGL((gemm16k_kernel<EPI_ROPE_KV, 2, PRO_NONE>), dim3((nqkv + 15) / 16, (M + 15) / 16), dim3(ZN_G16K_NKW * 64), 0, s, g);
-      ldq = nq;
-    } else {
-      if (!run_gemm16k_rows<PRO_NONE, EPI_STORE>(h, h->pf_n, nullptr, nullptr, lw.in_proj, nqkv, d, h->pf_qkv, nullptr, M, s) &&
-          !run_gemm64s<EPI_STORE>(h, h->pf_n, lw.in_proj, nqkv, d, h->pf_qkv, nullptr, M, s))
-        launch_gemm(h->pf_n, d, (const bf16_t*)lw.in_proj, h->pf_qkv, nqkv, nullptr, M, nqkv, d, s);
-      hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(S, R), dim3(256), 0, s, h->pf_qkv, kv, h->rope, S, base, max_len, c.n_heads, c.n_heads_kv, hd, c.rope_positions);
-    }
-    rc = prefill_attention(h, h->pf_qkv, ldq, kv, max_len, h->pf_a, nq, S, R, s, base, row_len);
+    GemvArgs g = linear_args(h, lw.in_proj, nqkv, d, h->pf_n, h->pf_qkv, nullptr);
+    g.hd = hd; g.n_heads = c.n_heads; g.n_heads_kv = c.n_heads_kv; g.q_out = h->pf_qkv; g.kv = kv; g.rope = h->rope; g.max_len = max_len;
+    g.rope_positions = c.rope_positions; g.pf_S = S; g.pf_base = base;
+    bool rope_done = false;
+    if ((rc = prefill_linear<EPI_ROPE_KV>(h, g, M, s, true, &rope_done))) return rc;
+    if (!rope_done) hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(S, R), dim3(256), 0, s, h->pf_qkv, kv, h->rope, S, base, max_len, c.n_heads, c.n_heads_kv, hd, c.rope_positions);
+    rc = prefill_attention(h, h->pf_qkv, rope_done ? nq : nqkv, kv, max_len, h->pf_a, nq, S, R, s, base, row_len);
     if (rc) return rc;
-    if (c.double_out_proj) {
-      if (!run_gemm16k_rows<PRO_NONE, EPI_STORE>(h, h->pf_a, nullptr, nullptr, lw.out_proj, d, nq, h->pf_n, nullptr, M, s) &&
-          !run_gemm64s<EPI_STORE>(h, h->pf_a, lw.out_proj, d, nq, h->pf_n, nullptr, M, s))
-        launch_gemm(h->pf_a, nq, (const bf16_t*)lw.out_proj, h->pf_n, d, nullptr, M, d, nq, s);
-      if (!run_gemm16k_rows<PRO_NONE, EPI_RESID>(h, h->pf_n, nullptr, nullptr, lw.out_proj, d, nq, h->pf_x, h->pf_x, M, s) &&
-          !run_gemm64s<EPI_RESID>(h, h->pf_n, lw.out_proj, d, nq, h->pf_x, h->pf_x, M, s))
-        launch_gemm(h->pf_n, d, (const bf16_t*)lw.out_proj, h->pf_x, d, h->pf_x, M, d, nq, s);
-    } else if (!run_gemm16k_rows<PRO_NONE, EPI_RESID>(h, h->pf_a, nullptr, nullptr, lw.out_proj, d, nq, h->pf_x, h->pf_x, M, s) &&
-               !run_gemm64s<EPI_RESID>(h, h->pf_a, lw.out_proj, d, nq, h->pf_x, h->pf_x, M, s))
-      launch_gemm(h->pf_a, nq, (const bf16_t*)lw.out_proj, h->pf_x, d, h->pf_x, M, d, nq, s);
+    if (c.double_out_proj && (rc = prefill_linear<EPI_STORE>(h, linear_args(h, lw.out_proj, d, nq, h->pf_a, h->pf_n, nullptr), M, s))) return rc;
+    if ((rc = prefill_linear<EPI_RESID>(h, linear_args(h, lw.out_proj, d, nq, c.double_out_proj ? h->pf_n : h->pf_a, h->pf_x, h->pf_x), M, s))) return rc;
     hipLaunchKernelGGL(layernorm_kernel, dim3(M), dim3(64), 0, s, h->pf_x, (const bf16_t*)lw.norm2_w, (const bf16_t*)lw.norm2_b, h->pf_n, d, c.norm_eps);
-    if (!run_gemm64s<EPI_SILU>(h, h->pf_n, lw.fc1, 2 * F, d, h->pf_m, nullptr, M, s)) {
-      launch_gemm(h->pf_n, d, (const bf16_t*)lw.fc1, h->pf_u, 2 * F, nullptr, M, 2 * F, d, s);
-      hipLaunchKernelGGL(silu_mul_rows_kernel, dim3(M), dim3(256), 0, s, h->pf_u, h->pf_m, F);
-    }
-    if (!run_gemm64s<EPI_RESID>(h, h->pf_m, lw.fc2, d, F, h->pf_x, h->pf_x, M, s))
-      launch_gemm(h->pf_m, F, (const bf16_t*)lw.fc2, h->pf_x, d, h->pf_x, M, d, F, s);
+    if ((rc = prefill_linear<EPI_SILU>(h, linear_args(h, lw.fc1, 2 * F, d, h->pf_n, h->pf_m, nullptr), M, s, false))) return rc;
+    if ((rc = prefill_linear<EPI_RESID>(h, linear_args(h, lw.fc2, d, F, h->pf_m, h->pf_x, h->pf_x), M, s, false))) return rc;
   }
   return ZN_OK;
 }
@@ -1727,44 +1627,27 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   HIPCHK(h, hipEventCreate(&e0));
   HIPCHK(h, hipEventCreate(&e1));
   int rc = ZN_OK;
-  // which == 0 at 5..16 rows: the launch a decode step makes there - fc1 normalising from the statistics its producer left (layer_post_attention);
+  // which == 0 at 5..16 rows: the launch a decode step makes there - fc1 normalising from the statistics its producer left (plan_post_attention);
   // the producer runs once, outside the timed loop, on the zeroed rows
-  bool fc1_lnp = false;
-  if (which == 0 && rows > 4 && h->tune[ZN_TUNE_FC1_LN_LAUNCH] != 2 && h->ln_part && d == 16 * ZN_G16_LNT && gemm16k_fits(h, EPI_RESID, d, nq)) {
-    GemvArgs b{};
-    b.W = (const bf16_t*)h->layers[0].out_proj; b.N = d; b.K = nq; b.x = h->o1; b.resid = h->x; b.out = h->x; b.eps = c.norm_eps; b.ln_part_out = h->ln_part;
-    rc = run_gemv<PRO_NONE, EPI_RESID>(h, b, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s);
-    fc1_lnp = rc == ZN_OK;
+  const PostAttnPlans pp = plan_post_attention(h, rows);
+  if (which == 0 && pp.out.writes_ln_stats) {
+    GemvArgs b = out_proj_args(h, h->layers[0], h->o1, h->x, h->x);
+    b.ln_part_out = h->ln_part;
+    rc = launch_linear<PRO_NONE, EPI_RESID>(h, pp.out, b, rows, s);
   }
   for (int pass = 0; pass < 2 && rc == ZN_OK; ++pass) {   // pass 0 = warm-up
     if (pass == 1) HIPCHK(h, hipEventRecord(e0, s));
     for (int i = 0; i < (pass ? iters : (iters < 8 ? iters : 8)) && rc == ZN_OK; ++i) {
       const zn_layer_weights& lw = h->layers[same_layer ? 0 : i % c.n_layer];
-      GemvArgs a{};
-      a.eps = c.norm_eps;
-      if (which == 0) {
-        a.W = (const bf16_t*)lw.fc1; a.N = 2 * c.d_ff; a.K = d; a.x = h->x; a.ln_w = (const bf16_t*)lw.norm2_w; a.ln_b = (const bf16_t*)lw.norm2_b; a.out = h->mbuf;
-        if (fc1_lnp) a.ln_part_in = h->ln_part;
-        rc = run_gemv<PRO_LN, EPI_SILU>(h, a, rows, h->tune[ZN_TUNE_WG_FC1], s);
-      } else if (which == 1) {
-        a.W = (const bf16_t*)lw.fc2; a.N = d; a.K = c.d_ff; a.x = h->mbuf; a.resid = h->x; a.out = h->x;
-        rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[ZN_TUNE_WG_FC2], s);
-      } else if (which == 2) {
-        a.W = (const bf16_t*)lw.out_proj; a.N = d; a.K = c.n_heads * h->hd; a.x = h->o1; a.resid = h->x; a.out = h->x;
-        rc = run_gemv<PRO_NONE, EPI_RESID>(h, a, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s);
-      } else if (which == 6) {
-        rc = launch_stack(h, s, rows, stack_nbk);
-      } else if (which == 5) {
+      if (which == 0) rc = launch_linear<PRO_LN, EPI_SILU>(h, pp.fc1, fc1_args(h, lw, h->x, pp.out.writes_ln_stats ? h->ln_part : nullptr), rows, s);
+      else if (which == 1) rc = run_gemv<PRO_NONE, EPI_RESID>(h, fc2_args(h, lw, h->x), rows, h->tune[ZN_TUNE_WG_FC2], s);
+      else if (which == 2) rc = run_gemv<PRO_NONE, EPI_RESID>(h, out_proj_args(h, lw, h->o1, h->x, h->x), rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s);
+      else if (which == 6) rc = launch_stack(h, s, rows, stack_nbk);
+      else if (which == 5) {
         if (i % c.n_layer == c.n_layer - 1) continue;       // the last block's launch has no in_proj: not the launch being priced
         rc = launch_chain(h, i % c.n_layer, std::vector<const void*>(c.n_layer, tkv), 8, tlen, s);
-      } else if (which == 4) {
-        a.W = (const bf16_t*)lw.in_proj; a.N = nq + 2 * nkv; a.K = d; a.x = h->x; a.ln_w = (const bf16_t*)lw.norm_w; a.ln_b = (const bf16_t*)lw.norm_b;
-        a.lengths = tlen; a.hd = hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
-        a.q_out = h->q; a.kv = tkv; a.rope = h->rope; a.max_len = 8; a.rope_positions = c.rope_positions;
-        rc = run_gemv<PRO_LN, EPI_ROPE_KV>(h, a, rows, h->tune[ZN_TUNE_WG_IN_PROJ], s);
-      } else {
-        rc = heads_logits(h, h->x, rows, s);
-      }
+      } else if (which == 4) rc = run_gemv<PRO_LN, EPI_ROPE_KV>(h, in_proj_args(h, lw, h->x, tkv, 8, tlen), rows, h->tune[ZN_TUNE_WG_IN_PROJ], s);
+      else rc = heads_logits(h, h->x, rows, s);
     }
   }
   if (rc) return rc;
@@ -1805,8 +1688,7 @@ extern "C" int zn_op_linear(zn_handle h, const void* x, const void* ln_w, const 
                             int32_t N, int32_t K, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
   if (!x || !W || !out || rows < 1 || N < 1 || K < 8 || K % 8) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear: bad argument");
-  GemvArgs a{};
-  a.W = (const bf16_t*)W; a.N = N; a.K = K; a.x = (const bf16_t*)x; a.out = (bf16_t*)out; a.eps = h->cfg.norm_eps;
+  GemvArgs a = linear_args(h, W, N, K, (const bf16_t*)x, (bf16_t*)out);
   int rc;
   if (ln_w) {
     if (K > 4096) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_op_linear: fused LayerNorm needs K <= 4096");
@@ -1821,13 +1703,13 @@ extern "C" int zn_op_linear(zn_handle h, const void* x, const void* ln_w, const 
 extern "C" int zn_op_linear_bias(zn_handle h, const void* x, const void* W, const void* bias, void* out, int32_t rows, int32_t N, int32_t K, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
   if (!x || !W || !out || rows < 1 || N < 1 || K < 8 || K % 8) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_bias: bad argument");
-  GemvArgs a{};
-  a.W = (const bf16_t*)W; a.N = N; a.K = K; a.x = (const bf16_t*)x; a.out = (bf16_t*)out; a.bias = (const bf16_t*)bias; a.eps = h->cfg.norm_eps;
+  GemvArgs a = linear_args(h, W, N, K, (const bf16_t*)x, (bf16_t*)out);
+  a.bias = (const bf16_t*)bias;
   hipStream_t s = (hipStream_t)stream;
   for (int r0 = 0; r0 < rows; r0 += 4) {      // always the GEMV (its epilogue carries the bias); rows are few here
     GemvArgs g = a;
-    g.x = a.x + (size_t)r0 * K; g.out = a.out + (size_t)r0 * N;
-    int rc = run_gemv<PRO_NONE, EPI_STORE>(h, g, rows - r0 < 4 ? rows - r0 : 4, 1024, s);
+    advance_rows(g, r0, rows - r0 < 4 ? rows - r0 : 4, N);
+    int rc = run_gemv<PRO_NONE, EPI_STORE>(h, g, g.nrows, 1024, s);
     if (rc) return rc;
   }
   HIPCHK(h, hipGetLastError());

@@ -5,10 +5,9 @@
 // non-temporal loads, activations (a few KB) live in registers or LDS, reductions are wavefront shuffles.
 #pragma once
 #include "zn_common.h"
+#include "zn_linear_plan.h"   // PRO_* / EPI_*, ZN_G16_KC, ZN_G16_LNT, ZN_G16K_NKW, ZN_G16K_KCH
 
 // ------------------------------------------------------------------------------------------------ GEMV
-enum { PRO_NONE = 0, PRO_LN = 1, PRO_GATED = 2 };
-enum { EPI_STORE = 0, EPI_RESID = 1, EPI_SILU = 2, EPI_ROPE_KV = 3, EPI_F32 = 4, EPI_MAMBA = 5 };
 
 struct GemvArgs {
   const bf16_t* W;  // [N][K]
@@ -552,7 +551,6 @@ __global__ __launch_bounds__(NW * 64) void gemm16_kernel(GemvArgs a) {
 // MFMA tile per wave, and walks its K slice in chunks of KC = 256 with the next chunk's global loads in flight during
 // the MFMAs.  Small N (d_model rows) splits K over gridDim.y workgroups: fp32 partial tiles go to a scratch buffer and
 // the last workgroup to arrive (ticket, no waiting) adds them in slice order and runs the epilogue — deterministic.
-#define ZN_G16_KC 256
 ZN_DEVINL void st_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // write-through
 ZN_DEVINL float ld_wt(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // L2-bypassing
 // NWV = waves (16-row tiles) per workgroup: 4 (64 rows) or 2 (32 rows; more, smaller workgroups for mid-size N).
@@ -560,7 +558,6 @@ ZN_DEVINL float ld_wt(const float* p) { return __hip_atomic_load(p, __ATOMIC_REL
 // (GemvArgs::ln_part_in, ZN_G16_LNT tiles of 16 columns per row).  The workgroup adds them in a fixed order while its first weight chunk
 // is on the way and normalises every activation chunk as it stages it (the arithmetic of layernorm_kernel on each value; the statistics
 // are summed tile-wise instead of lane-wise) - no LayerNorm launch, no normalised copy of the rows in memory.
-#define ZN_G16_LNT 128
 template <int EPI, int NWV, bool LNP = false>
 __global__ __launch_bounds__(NWV * 64) void gemm16s_kernel(GemvArgs a) {
   constexpr int KC = ZN_G16_KC, LDW = KC + 8, NT = NWV * 64, TN = NWV * 16, HALF = TN / 2;
@@ -797,8 +794,6 @@ __global__ __launch_bounds__(NWV * 64) void gemm16s_kernel(GemvArgs a) {
 // eight partial tiles meet in LDS in wave order - one memory round trip, deterministic.  (K = 8192, fc2, in rounds of four
 // chunks per wave was measured 3 % slower per step than the split-K kernel: a 16-row tile re-reads the activations once
 // per 16 weight rows, which is as many bytes through the vector-memory pipe as the weights themselves.)
-#define ZN_G16K_NKW 8
-#define ZN_G16K_KCH 128
 // PRO_LN: the workgroup holds whole activation rows (as A fragments, spread over its waves), so nn.LayerNorm runs in
 // place on them - row sums through LDS in wave order, two statistics passes like layernorm_kernel - instead of as a
 // launch of its own in front (4.8 us at 16 rows).

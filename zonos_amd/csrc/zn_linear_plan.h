@@ -1,0 +1,172 @@
+// Plain C++ (no HIP): which kernel serves a linear of 1 .. 64 activation rows, decided as a VALUE (plan_linear -> LinearPlan) that the
+// launchers of zn_api.hip only follow (launch_linear) and that tests/test_linear_plan.py (tests/linear_plan_check.cpp, g++) walks on the CPU.
+#pragma once
+#include <cstddef>
+#include <cstdio>
+
+enum { PRO_NONE = 0, PRO_LN = 1, PRO_GATED = 2, ZN_NPRO = 3 };
+enum { EPI_STORE = 0, EPI_RESID = 1, EPI_SILU = 2, EPI_ROPE_KV = 3, EPI_F32 = 4, EPI_MAMBA = 5, ZN_NEPI = 6 };
+
+#define ZN_G16_KC 256          // gemm16s_kernel / gemm64s_kernel: K chunk staged in LDS
+#define ZN_G16_LNT 128         // 16-column tiles per row of the LayerNorm statistics (GemvArgs::ln_part_out / ln_part_in)
+#define ZN_G16_MAX_GROUPS 1024 // arrival tickets of the split-K combine
+#define ZN_G16K_NKW 8          // gemm16k_kernel: waves per workgroup ...
+#define ZN_G16K_KCH 128        // ... and K chunk per wave: K = 8 * 128 * {2, 4}
+
+// What a decision may depend on, and nothing else: the tune values (zn_debug_tune; 0 = never set) and the workspace of the handle.
+struct LinearEnv {
+  int small_m_lds = 2, no_split_small_m = 0, gemm16k_max_tiles = 0, fc1_ln_launch = 0, no_prefill_gemm16k = 0;
+  size_t g16_part_bytes = 0;      // split-K partial tiles
+  bool has_g16_part = false, has_ln_part = false;
+};
+
+struct LinearPlan {
+  enum Kernel { GEMV, GEMM16, GEMM16S, GEMM16K, GEMM64S, GEMM_TILED } kernel = GEMV;
+  int epi = 0;                // the epilogue the kernel carries: the one asked for, or (prefill, EPI_ROPE_KV not served) EPI_STORE: rope_kv_rows_kernel follows
+  int rows_per_launch = 0;    // 4 (GEMV), 16 (decode MFMA kernels), 0 = all rows in one launch (prefill)
+  bool ln_launch = false;     // a layernorm_kernel launch over the rows of each group runs first (into nbuf)
+  bool writes_ln_stats = false, reads_ln_stats = false;   // LayerNorm statistics per 16-column tile: left by this launch / normalised from
+  // GEMV: K slices per row pair, 512-wide chunks per slice, units (weight-row pairs) and units per wave (ks 1) or block (ks 4), grid, mask-free
+  int ks = 0, nch = 0, units = 0, upw = 0, blocks = 0;
+  bool full = false;
+  int nw = 0; bool tile8 = false;                  // GEMM16 (direct fragments): waves per workgroup, 8-row instead of 16-row weight tiles
+  int nwv = 0, groups = 0, ksplit = 0; bool lnp = false;   // GEMM16S / GEMM64S: 16-row tiles per workgroup, grid x, grid y; LayerNorm from handed-over statistics
+  bool ln_pro = false;        // GEMM16K (nch = 128-wide chunks per wave): LayerNorm as its prologue
+  int err = 0;                // shapes nobody serves: a ZN_ERR_* code (-4 = ZN_ERR_UNSUPPORTED) and its message
+  char msg[96] = {};
+};
+
+// ---------------------------------------------------------------------------- the instantiations launch_linear<PRO, EPI> holds: one table for
+// its `if constexpr` guards and for the CPU walk
+constexpr bool lin_has_gemv_ks4(int pro) { return pro == PRO_NONE || pro == PRO_GATED; }
+constexpr bool lin_has_gemm16(int pro) { return pro != PRO_GATED; }                         // GEMM16, GEMM16S, GEMM16K: no gated-norm prologue
+constexpr bool lin_has_tile8(int epi) { return epi != EPI_SILU; }
+constexpr bool lin_has_lnp(int pro, int epi) { return pro == PRO_LN && epi == EPI_SILU; }
+constexpr bool lin_has_gemm16k(int pro, int epi) { return lin_has_gemm16(pro) && epi != EPI_SILU; }   // row-pair epilogues only
+constexpr bool lin_has_gemm16k_ln(int pro, int nch) { return pro == PRO_LN && nch == 2; }  // (the LayerNorm prologue at K = 4096 would not fit the register file)
+constexpr bool lin_has_prefill(int pro, int epi) { return pro == PRO_NONE && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_SILU); }   // GEMM64S, GEMM_TILED
+inline bool linear_plan_launchable(const LinearPlan& p, int pro, int epi) {
+  switch (p.kernel) {
+    case LinearPlan::GEMV: return (p.ks == 1 || (p.ks == 4 && lin_has_gemv_ks4(pro))) && (p.nch == 1 || p.nch == 2 || p.nch == 4 || p.nch == 8);
+    case LinearPlan::GEMM16: return lin_has_gemm16(pro) && (p.nw == 4 || p.nw == 8 || p.nw == 16) && (!p.tile8 || lin_has_tile8(epi));
+    case LinearPlan::GEMM16S: return lin_has_gemm16(pro) && (p.nwv == 2 || p.nwv == 4) && (!p.lnp || lin_has_lnp(pro, epi));
+    case LinearPlan::GEMM16K: return lin_has_gemm16k(pro, epi) && (p.nch == 2 || p.nch == 4) && (!p.ln_pro || lin_has_gemm16k_ln(pro, p.nch));
+    case LinearPlan::GEMM64S: case LinearPlan::GEMM_TILED: return lin_has_prefill(pro, epi);
+  }
+  return false;
+}
+
+// ---------------------------------------------------------------------------- the decisions
+// rows in (4, 16] (and short prompts up to 64), K = 8 waves x 128 x {2, 4} and few weight rows (the LDS-staged kernel would have to split K over
+// workgroups): one 16-row tile per workgroup, K split over its waves, no cross-workgroup combine.  ZN_TUNE_NO_SPLIT_SMALL_M = 2 disables.
+inline bool gemm16k_fits(const LinearEnv& e, int epi, int N, int K) {
+  if (epi == EPI_SILU || e.small_m_lds <= 1 || e.no_split_small_m == 2) return false;
+  const int per = ZN_G16K_NKW * ZN_G16K_KCH, nch = K / per;
+  if (K % per || (nch != 2 && nch != 4)) return false;
+  return (N + 15) / 16 < (e.gemm16k_max_tiles > 0 ? e.gemm16k_max_tiles : 1024);     // many rows: the 64-row workgroups fill the chip without a split (ZN_TUNE_GEMM16K_MAX_TILES: the tile count from which they take over)
+}
+
+// rows in (4, 16], K a multiple of 256: the LDS-staged kernel (coalesced weight stream); K is split over workgroups until the grid has
+// >= 512 of them, the partial tiles meet in a scratch buffer.  false = shape not served.
+inline bool plan_gemm16s(const LinearEnv& e, int epi, int N, int K, bool lnp, LinearPlan& p) {
+  if (K % ZN_G16_KC || !e.has_g16_part) return false;
+  if (lnp && K != 16 * ZN_G16_LNT) return false;
+  const int nrows_w = (epi == EPI_SILU) ? N / 2 : N;          // weight rows that define the grid
+  const int per64 = (epi == EPI_SILU) ? 32 : 64;
+  // 64-row workgroups when that already gives >= 512 of them, else 32-row ones, else split K as well
+  int nwv = 4, groups = (nrows_w + per64 - 1) / per64;
+  if (groups < 512) { nwv = 2; groups = (nrows_w + per64 / 2 - 1) / (per64 / 2); }
+  if (groups > ZN_G16_MAX_GROUPS) return false;
+  int ks = 1;
+  while (groups * ks < 448 && ks < 16 && K % (2 * ks * ZN_G16_KC) == 0) ks *= 2;
+  // (fc2 at 16 rows, K = 8192 over 64 groups: 8 slices; 4: 1.690, 8: 1.681, 16: 1.746 ms per batch-8 step)
+  // (the Mamba2 in_proj, N = 8512 over 266 groups: 1 / 2 (default) / 4 slices: 1.933 / 1.937 / 1.945 ms per batch-8 hybrid step)
+  if (ks > 1 && K / ks < 512) {
+    // short slices: the combine costs more than the direct-fragment kernel's access pattern, unless a shallower split
+    // still fills the chip (in_proj, N = 3072: 96 groups x 4 slices of 512)
+    ks /= 2;
+    if (ks < 2 || K / ks < 512 || groups * ks < 320) return false;
+  }
+  if ((size_t)ks * 16 * groups * nwv * 16 * sizeof(float) > e.g16_part_bytes) return false;
+  p.kernel = LinearPlan::GEMM16S; p.nwv = nwv; p.groups = groups; p.ksplit = ks; p.lnp = lnp;
+  return true;
+}
+
+// Projection of a short prompt (17..64 rows) through the weight-streaming 64-row kernel; false = shape not served.
+inline bool plan_gemm64s(const LinearEnv& e, int epi, int rows, int N, int K, LinearPlan& p) {
+  if (rows > 64 || K % 256 || (epi == EPI_SILU && (N / 2) % 32) || e.small_m_lds <= 1) return false;
+  const int groups = (epi == EPI_SILU) ? (N / 2 + 31) / 32 : (N + 63) / 64;
+  if (groups > ZN_G16_MAX_GROUPS) return false;
+  int ks = 1;
+  while (groups * ks < 256 && ks < 16 && K % (2 * ks * 256) == 0) ks *= 2;
+  // (fc2, K = 8192: the split this picks, 8, against 4 / 16 / 2 forced: prefill 2.71 vs 2.90 / 2.77 / 3.13 ms)
+  if ((size_t)ks * 64 * groups * 64 * sizeof(float) > e.g16_part_bytes) return false;
+  p.kernel = LinearPlan::GEMM64S; p.nwv = 4; p.groups = groups; p.ksplit = ks;
+  return true;
+}
+
+// The plan of out [rows][N] = epi(pro(x [rows][K]) W^T).  Decode (prefill = false): rows <= 4 the fused GEMV (groups of <= 4 rows per launch),
+// rows in (4, 16] per group one weight pass on the matrix cores.  prefill = true: the rows of a prompt in one launch, normalised by the caller.
+// want_ln_stats_out: the caller would hand LayerNorm statistics of this projection's output to its consumer; have_ln_stats_in: the producer of
+// x left them (writes_ln_stats of its plan).  target_blocks: the GEMV's grid (ZN_TUNE_WG_*).
+inline LinearPlan plan_linear(const LinearEnv& e, int pro, int epi, int rows, int N, int K, int target_blocks, bool prefill, bool want_ln_stats_out,
+                              bool have_ln_stats_in) {
+  LinearPlan p;
+  p.epi = epi;
+#define ZN_PLAN_FAIL(...) do { p.err = -4; snprintf(p.msg, sizeof p.msg, __VA_ARGS__); return p; } while (0)
+  if (prefill) {
+    if (pro != PRO_NONE || !(lin_has_prefill(pro, epi) || epi == EPI_ROPE_KV)) ZN_PLAN_FAIL("prefill linear: prologue %d / epilogue %d not served", pro, epi);
+    // Short prompts (<= 64 rows), contractions of 2048 or 4096 with few weight rows (in_proj, both out_proj calls): the decode side's gemm16k_kernel
+    // over ceil(rows / 16) row groups in ONE launch, instead of gemm64s_kernel's 8-way split-K with a ticketed combine (14.4 us for 8-13 MB).
+    // in_proj at K = 2048: split, RoPE and the KV append in its epilogue, as in a decode step; else they follow as a launch.
+    const bool k16 = rows <= 64 && gemm16k_fits(e, epi, N, K) && e.no_prefill_gemm16k != 2;
+    if (epi == EPI_ROPE_KV && !(k16 && K / (ZN_G16K_NKW * ZN_G16K_KCH) == 2)) p.epi = epi = EPI_STORE;
+    if (k16) { p.kernel = LinearPlan::GEMM16K; p.nch = K / (ZN_G16K_NKW * ZN_G16K_KCH); return p; }
+    if (!plan_gemm64s(e, epi, rows, N, K, p)) p.kernel = LinearPlan::GEMM_TILED;
+    return p;
+  }
+  if (rows <= 4) {
+    p.kernel = LinearPlan::GEMV; p.rows_per_launch = 4;
+    p.ks = ((pro == PRO_NONE || pro == PRO_GATED) && K >= 4096 && K % 2048 == 0) ? 4 : 1;
+    const int kw = K / p.ks, nch = (kw + 511) / 512;
+    p.nch = nch <= 1 ? 1 : nch <= 2 ? 2 : nch <= 4 ? 4 : nch <= 8 ? 8 : 99;
+    if (p.nch > 8) ZN_PLAN_FAIL("gemv: K=%d too large for the register-resident activation path", K);
+    p.units = (epi == EPI_SILU) ? N / 2 : (N + 1) / 2;
+    const int lanes_units = (p.ks == 1) ? 4 : 1;  // units in flight per block
+    p.upw = (p.units + target_blocks * lanes_units - 1) / (target_blocks * lanes_units);
+    if (p.upw < 1) p.upw = 1;
+    p.blocks = (p.units + p.upw * lanes_units - 1) / (p.upw * lanes_units);
+    p.full = (kw == p.nch * 512) && (N % 2 == 0) && (p.units == p.blocks * lanes_units * p.upw);
+    return p;
+  }
+  // rows in (4, 16]: LayerNorm, when fused in the GEMV, is a row-wise launch here (amortised over the batch) unless a kernel below takes it in
+  if (pro == PRO_GATED) ZN_PLAN_FAIL("gated-norm prologue: at most 4 rows (got %d)", rows);
+  p.rows_per_launch = 16;
+  // few weight-row tiles (N = d_model: 128 workgroups) -> more waves per workgroup so that every CU still keeps enough loads in flight
+  const int tiles = (epi == EPI_SILU) ? (N / 2) / 16 : (N + 15) / 16;
+  p.nw = 4;
+  if (tiles <= 256 && K % 256 == 0) p.nw = 8;
+  if (tiles <= 256 && K >= 8192 && K % 512 == 0) p.nw = 16;
+  if (K % (p.nw * 32)) ZN_PLAN_FAIL("gemm16: K=%d not a multiple of %d", K, p.nw * 32);
+  if (epi == EPI_SILU && (N / 2) % 16) ZN_PLAN_FAIL("gemm16: d_ff must be a multiple of 16");
+  const bool k16 = gemm16k_fits(e, epi, N, K);
+  // the producer of these rows left LayerNorm statistics per 16-column tile (plan_post_attention): fc1 normalises while it stages
+  if (lin_has_lnp(pro, epi) && have_ln_stats_in && !k16 && e.small_m_lds > 1 && plan_gemm16s(e, epi, N, K, true, p)) { p.reads_ln_stats = true; return p; }
+  // gemm16k normalises its rows itself when at most one workgroup per CU repeats the statistics (in_proj: 8.7 us vs 4.8 + 6.2; the heads' 577
+  // tiles: 21.8 vs 5.0 + 11.9)
+  p.ln_pro = k16 && pro == PRO_LN && tiles <= 256 && K == 2 * ZN_G16K_NKW * ZN_G16K_KCH;
+  p.ln_launch = pro == PRO_LN && !p.ln_pro;
+  if (k16) {
+    // rows 5..16: the projection that completes the residual stream leaves LayerNorm statistics per 16-column tile and fc1 normalises its
+    // activation chunks from them - no LayerNorm launch in between.  ZN_TUNE_FC1_LN_LAUNCH = 2: the launch.
+    p.writes_ln_stats = want_ln_stats_out && e.fc1_ln_launch != 2 && e.has_ln_part && epi == EPI_RESID && N == 16 * ZN_G16_LNT;
+    p.kernel = LinearPlan::GEMM16K; p.nch = K / (ZN_G16K_NKW * ZN_G16K_KCH);
+    return p;
+  }
+  if (e.small_m_lds > 1 && plan_gemm16s(e, epi, N, K, false, p)) return p;
+  p.kernel = LinearPlan::GEMM16;
+  p.tile8 = lin_has_tile8(epi) && tiles <= 192 && N % 8 == 0;   // N = d_model: 8-row tiles so that every CU gets a workgroup
+  p.blocks = p.tile8 ? N / 8 : tiles;
+  return p;
+#undef ZN_PLAN_FAIL
+}
