@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define ZN_ABI_VERSION 8
+#define ZN_ABI_VERSION 9
 
 enum zn_status {
   ZN_OK = 0,
@@ -106,6 +106,17 @@ typedef struct zn_sampling {
   uint64_t seed;       /* device RNG stream for the Gumbel-max draw */
 } zn_sampling;
 
+/* ABI 9 - one utterance's settings in a batched generation (zn_gen_set_rows, zn_op_sample_rows): what zn_gen_begin takes once for the
+ * whole batch, per row.  ZN_ROW_PARAMS_BYTES = 64 bytes exactly, so that a sampler workgroup fetches its row with one aligned load. */
+#define ZN_ROW_PARAMS_BYTES 64
+typedef struct zn_row_params {
+  zn_sampling sp;           /* this utterance's sampling parameters; sp.seed seeds its own Gumbel stream */
+  float cfg_scale;          /* guidance strength of this utterance's [cond, uncond] pair; == 1 for every row or for none (the row layout
+                               is fixed by zn_gen_begin's cfg_scale) */
+  int32_t max_new_tokens;   /* this utterance's budget of frames, 1 .. zn_gen_begin's max_new_tokens */
+  int32_t reserved[2];      /* pads the entry to ZN_ROW_PARAMS_BYTES; set to 0 */
+} zn_row_params;
+
 /* ---------------------------------------------------------------- lifecycle */
 int zn_abi_version(void);
 /* Replaces Zonos.__init__/from_local weight binding (zonos/model.py:68-86,128-176).  Weights stay owned by the
@@ -138,6 +149,21 @@ int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_layers_dev, i
  * B conditional rows when cfg_scale == 1, conditioning concatenated with embed(delayed[..., :prefix+1]); fills KV positions
  * [0,S), lengths += S and leaves the fp32 logits [B, n_codebooks, vocab_head] (CFG-mixed with guidance) in the handle. */
 int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_stream stream);
+/* ABI 9 - per-utterance sampling parameters, seed, cfg_scale and length for the generation begun by zn_gen_begin.  rows_host: HOST array of
+ * n == batch entries, copied to a device table the handle owns; every sampler workgroup (cb, b) of this generation - zn_sample_first, the
+ * decode steps on every path, captured graphs included - then takes its parameters from entry b instead of zn_gen_begin's `sp` and
+ * `cfg_scale`: temperature, top_p, top_k, min_p, linear, conf, quad, repetition penalty and window, cfg_scale, and the penalty context
+ * min(max_new_tokens_b, 100).  Utterance b's Gumbel draw for (step, codebook cb, token t) is keyed by (sp.seed_b, draw + step, cb * V + t + 1)
+ * - the key of utterance 0 of a call seeded sp.seed_b: a request's random stream does not depend on the slot it occupies and equals the
+ * stream of a one-utterance generation with that seed.  remaining_steps of utterance b becomes max_new_tokens_b + n_codebooks - 1 (what a
+ * generation of that length starts with); an utterance whose budget is spent counts as stopped for zn_all_stopped*, and the columns it
+ * still receives beyond its own length are the caller's to cut.
+ * Legal only between zn_gen_begin and the generation's first zn_prefill / zn_prefill_rows (ZN_ERR_STATE otherwise; no graph has been
+ * captured yet).  ZN_ERR_ARG: n != batch, a repetition_penalty_window outside 0..64, max_new_tokens_b outside 1 .. zn_gen_begin's
+ * max_new_tokens, or cfg_scale_b == 1 on a generation begun with guidance (and the reverse): guided and unguided utterances do not share
+ * a call.  An error leaves the generation as it was.  Without this call every row uses zn_gen_begin's values (the same bits as ABI 8).
+ * Synchronises the generation's stream. */
+int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int32_t n);
 /* ABI 8 - zn_prefill for utterances of different prompt lengths.  hidden bf16 [R, S, d] is RIGHT-padded: row r holds row_len[r] valid
  * positions (its conditioning followed by the embedded audio prefix), then S - row_len[r] positions of padding whose contents are never
  * visible to a result: no valid query attends a pad key, no pad position reaches a logit, a Mamba2 state or a KV entry that is read
@@ -329,6 +355,11 @@ int zn_op_embed(zn_handle h, const int32_t* codes_dev, void* out_dev, int32_t ba
 int zn_op_sample(zn_handle h, const float* logits_dev, const int32_t* recent_dev, int32_t window,
                  const zn_sampling* sp, uint64_t draw_index, int32_t* tokens_dev, float* probs_out_dev,
                  int32_t batch, zn_stream stream);
+/* ABI 9 - zn_op_sample with a table: rows_dev is a DEVICE array of `batch` entries, row b sampled with rows_dev[b].sp (cfg_scale and
+ * max_new_tokens are not used: the logits are final) and the slot-independent key of zn_gen_set_rows.  Row b's tokens and probabilities
+ * equal zn_op_sample(batch = 1) on row b's logits and history with rows_dev[b].sp. */
+int zn_op_sample_rows(zn_handle h, const float* logits_dev, const int32_t* recent_dev, int32_t window, const zn_row_params* rows_dev,
+                      uint64_t draw_index, int32_t* tokens_dev, float* probs_out_dev, int32_t batch, zn_stream stream);
 
 /* ---------------------------------------------------------------- DAC decode (autoencoder.py:119-170) */
 typedef struct zn_dac_config { /* transformers DacConfig fields used by decode / encode */

@@ -12,7 +12,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ZONOS_HIP_LIB") or os.path.join(_HERE, "libzonos_hip.so")   # the override selects an experimental build (A/B runs)
 
-ZN_ABI_VERSION = 8
+ZN_ABI_VERSION = 9
 
 # zn_debug_tune keys (enum zn_tune_key of include/zonos_hip.h, which documents them; tests/test_abi.py keeps the two equal)
 ZN_TUNE_WG_IN_PROJ, ZN_TUNE_WG_OUT_PROJ, ZN_TUNE_WG_FC1, ZN_TUNE_WG_FC2, ZN_TUNE_WG_HEADS = 0, 1, 2, 3, 4
@@ -62,6 +62,14 @@ class zn_sampling(C.Structure):
                 ("repetition_penalty_window", C.c_int32), ("seed", C.c_uint64)]
 
 
+class zn_row_params(C.Structure):
+    """One utterance's settings in a batched generation (zn_gen_set_rows, zn_op_sample_rows): ZN_ROW_PARAMS_BYTES = 64 bytes."""
+    _fields_ = [("sp", zn_sampling), ("cfg_scale", C.c_float), ("max_new_tokens", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+ZN_ROW_PARAMS_BYTES = 64
+
+
 class zn_dac_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_codebooks", "codebook_size", "codebook_dim", "hidden_size", "decoder_hidden_size", "n_ratios")] + \
                [("ratios", C.c_int32 * 8), ("encoder_hidden_size", C.c_int32)]
@@ -83,6 +91,7 @@ SIGNATURES = {
                                C.c_int32, C.c_float, C.POINTER(zn_sampling), C.c_void_p]),
     "zn_prefill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "zn_prefill_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
+    "zn_gen_set_rows": (C.c_int, [C.c_void_p, C.POINTER(zn_row_params), C.c_int32]),
     "zn_sample_first": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zn_decode_steps": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "zn_graph_active": (C.c_int, [C.c_void_p]),
@@ -120,6 +129,8 @@ SIGNATURES = {
     "zn_op_mamba_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "zn_op_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(zn_sampling), C.c_uint64, C.c_void_p, C.c_void_p,
                                C.c_int32, C.c_void_p]),
+    "zn_op_sample_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                    C.c_int32, C.c_void_p]),
     "zn_dac_create": (C.c_int, [C.POINTER(zn_dac_config), C.POINTER(zn_dac_tensor), C.c_int32, C.POINTER(C.c_void_p)]),
     "zn_dac_destroy": (C.c_int, [C.c_void_p]),
     "zn_dac_last_error": (C.c_char_p, [C.c_void_p]),

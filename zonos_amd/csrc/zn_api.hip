@@ -97,6 +97,9 @@ struct zn_handle_s {
   int lcap = 0;
   GenState* st = nullptr;
   int *remaining = nullptr, *stopping = nullptr;
+  zn_row_params* row_tab = nullptr;   // [max_rows] per-utterance settings of this generation (zn_gen_set_rows)
+  bool rows_set = false;              // this generation's samplers read row_tab
+  bool gen_prefilled = false;         // zn_prefill / zn_prefill_rows has run since zn_gen_begin
   int* done_host = nullptr;  // pinned: [0..3] synchronous stop check, [4..7] asynchronous one
   hipEvent_t stop_event = nullptr;
   bool stop_pending = false;
@@ -196,7 +199,7 @@ extern "C" int zn_destroy(zn_handle h) {
   if (!h) return ZN_OK;
   (void)zn_tenant_release(h->device, h);
   free_graph(h);
-  void* ptrs[] = {h->emb_tables_dev, h->x, h->q, h->o1, h->mbuf, h->nbuf, h->logits_raw, h->last_logits, h->tok_raw, h->scores, h->cmax, h->pv_part, h->pv_tickets, h->pf_x, h->pf_n, h->pf_qkv, h->pf_a, h->pf_u, h->pf_m, h->pf_res, h->pf_zx, h->pf_xbc, h->pf_y, h->pf_g, h->qkv_tmp, h->fw_lengths, h->row_len, h->st, h->remaining, h->stopping, h->res, h->hn, h->m_zx, h->m_xbc, h->m_y, h->m_g, h->m_vg, h->g16_part, h->g16_tickets, h->ln_part, h->ch_gy1, h->ch_gx1, h->ch_gx2, h->ch_gm, h->ch_epoch, h->ch_x2, h->x_emb, h->tail_ticket, h->ch_gqkv, h->ch_ga, h->ch_gbmax, h->ch_gpart, h->stack_layers, h->ch_diag};
+  void* ptrs[] = {h->emb_tables_dev, h->x, h->q, h->o1, h->mbuf, h->nbuf, h->logits_raw, h->last_logits, h->tok_raw, h->scores, h->cmax, h->pv_part, h->pv_tickets, h->pf_x, h->pf_n, h->pf_qkv, h->pf_a, h->pf_u, h->pf_m, h->pf_res, h->pf_zx, h->pf_xbc, h->pf_y, h->pf_g, h->qkv_tmp, h->fw_lengths, h->row_len, h->st, h->remaining, h->stopping, h->row_tab, h->res, h->hn, h->m_zx, h->m_xbc, h->m_y, h->m_g, h->m_vg, h->g16_part, h->g16_tickets, h->ln_part, h->ch_gy1, h->ch_gx1, h->ch_gx2, h->ch_gm, h->ch_epoch, h->ch_x2, h->x_emb, h->tail_ticket, h->ch_gqkv, h->ch_ga, h->ch_gbmax, h->ch_gpart, h->stack_layers, h->ch_diag};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->done_host) (void)hipHostFree(h->done_host);
   if (h->stop_event) (void)hipEventDestroy(h->stop_event);
@@ -291,6 +294,7 @@ extern "C" int zn_create(const zn_config* cfg, const zn_weights* w, int32_t max_
   ZC(hipMemset(h->st, 0, sizeof(GenState)));
   ZC(hipMalloc(&h->remaining, R * sizeof(int)));
   ZC(hipMalloc(&h->stopping, R * sizeof(int)));
+  ZC(hipMalloc(&h->row_tab, R * sizeof(zn_row_params)));
   ZC(hipHostMalloc(&h->done_host, sizeof(int) * 8));
   ZC(hipEventCreateWithFlags(&h->stop_event, hipEventDisableTiming));
   for (unsigned long long** g : {&h->ch_gy1, &h->ch_gx1, &h->ch_gx2}) {
@@ -1010,6 +1014,7 @@ static SampleArgs make_sample_args(zn_handle h, const zn_sampling& sp) {
   a.seed = sp.seed;
   return a;
 }
+static_assert(sizeof(zn_row_params) == ZN_ROW_PARAMS_BYTES, "zn_row_params is one 64-byte entry per utterance");
 
 // With guidance every utterance has a conditional and an unconditional row (rows = 2 batch); cfg_scale == 1: one row per utterance.
 static bool guided(zn_handle h) { return h->rows == 2 * h->batch; }
@@ -1020,6 +1025,15 @@ static EmbedArgs make_embed_args(zn_handle h) {
   e.tables = h->emb_tables_dev; e.codes = h->codes; e.col_dev = &h->st->offset; e.sb = c.n_codebooks * h->t_total; e.si = h->t_total;
   e.col = 0; e.n_q = c.n_codebooks; e.d = c.d_model; e.batch = h->batch; e.vocab_embed = c.vocab_embed; e.out = h->x_emb; e.dup = guided(h) ? 1 : 0;
   return e;
+}
+
+// The sampler arguments of this generation's launches (first frame, decode steps of every path): the call-wide parameters, and the
+// per-utterance table once zn_gen_set_rows has filled it.
+static SampleArgs gen_sample_args(zn_handle h) {
+  SampleArgs a = make_sample_args(h, h->sp);
+  a.cfg_scale = h->cfg_scale; a.ctx = h->max_new < 100 ? h->max_new : 100;
+  a.rows = h->rows_set ? h->row_tab : nullptr;
+  return a;
 }
 
 // One iteration of model.py:467-502: embed -> 26 blocks -> heads -> CFG/bias/penalty/sample -> bookkeeping.  With the fused tail the
@@ -1045,10 +1059,10 @@ static int enqueue_step(zn_handle h, const StepPlan& p, hipStream_t s) {
     } else if ((rc = decode_blocks(h, p, nullptr, 0, s, fused ? h->x_emb : nullptr, &heads_done))) return rc;
     if (!heads_done && (rc = heads_logits(h, h->x, h->rows, s))) return rc;
   }
-  SampleArgs a = make_sample_args(h, h->sp);
-  a.raw = h->logits_raw; a.mix = guided(h) ? 1 : 0; a.cfg_scale = h->cfg_scale; a.apply_bias = 1; a.batch = h->batch;
-  a.codes = h->codes; a.t_total = h->t_total; a.ctx = h->max_new < 100 ? h->max_new : 100;
-  a.use_penalty = (h->sp.repetition_penalty != 1.0f); a.st = h->st; a.logits_out = h->last_logits; a.tokens = h->tok_raw;
+  SampleArgs a = gen_sample_args(h);
+  a.raw = h->logits_raw; a.mix = guided(h) ? 1 : 0; a.apply_bias = 1; a.batch = h->batch;
+  a.codes = h->codes; a.t_total = h->t_total;
+  a.use_penalty = h->rows_set || (h->sp.repetition_penalty != 1.0f); a.st = h->st; a.logits_out = h->last_logits; a.tokens = h->tok_raw;
   a.draw = 1;
   FrameArgs& f = a.fr;
   f.st = h->st; f.codes = h->codes; f.t_total = h->t_total; f.batch = h->batch; f.n_q = c.n_codebooks; f.eos_id = c.eos_id;
@@ -1058,7 +1072,7 @@ static int enqueue_step(zn_handle h, const StepPlan& p, hipStream_t s) {
   // batch 1, greedy decoding: sampling, bookkeeping and the next embedding in one workgroup (sample1_kernel: 0.8337 -> 0.8312 ms per step).  With a
   // temperature its one wave per codebook carries 17 exp / log / hash evaluations per lane and the nine ticketed workgroups are ahead again (0.8396 vs
   // 0.8415): they keep those steps.  ZN_TUNE_SAMPLER = 2: always the ticketed kernel; 3: the one-workgroup kernel for every parameter set it implements (tests).
-  const bool one_wg = fused && h->batch == 1 && h->tune[ZN_TUNE_SAMPLER] != 2 && (h->tune[ZN_TUNE_SAMPLER] == 3 || !(h->sp.temperature > 0.f)) && c.vocab_head <= 64 * ZN_S1_IT &&
+  const bool one_wg = fused && h->batch == 1 && !h->rows_set && h->tune[ZN_TUNE_SAMPLER] != 2 && (h->tune[ZN_TUNE_SAMPLER] == 3 || !(h->sp.temperature > 0.f)) && c.vocab_head <= 64 * ZN_S1_IT &&
                       c.n_codebooks <= 16 && !(h->sp.top_p > 0.f) && h->sp.top_k <= 0 && !(h->sp.linear > 0.f) &&
                       (!a.use_penalty || h->sp.repetition_penalty_window <= 16) && h->rows <= 1024;
   if (one_wg) { hipLaunchKernelGGL(sample1_kernel, dim3(1), dim3(1024), 0, s, a); return ZN_OK; }
@@ -1132,6 +1146,8 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   h->len_hi = 0;
   for (int v : len0) if (v > h->len_hi) h->len_hi = v;
   h->gen_active = true;
+  h->rows_set = false;
+  h->gen_prefilled = false;
   h->rows_unequal2 = false;
   h->gen_ended = false;
   h->gen_timed_out = false;
@@ -1360,6 +1376,7 @@ extern "C" int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_str
   if (!h) return ZN_ERR_ARG;
   if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill before zn_gen_begin");
   if (!hidden_dev || S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill: bad S=%d (max_len %d)", S, h->max_len);
+  h->gen_prefilled = true;
   return prefill_impl(h, hidden_dev, S, nullptr, (hipStream_t)stream);
 }
 
@@ -1381,6 +1398,7 @@ extern "C" int zn_prefill_rows(zn_handle h, const void* hidden_dev, int32_t S, c
       if (row_len[b] != row_len[B + b])
         ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: utterance %d has %d conditional and %d unconditional positions (a guided pair advances in lockstep)", b, row_len[b], row_len[B + b]);
   hipStream_t s = (hipStream_t)stream;
+  h->gen_prefilled = true;
   if (uniform) return prefill_impl(h, hidden_dev, S, nullptr, s);          // zn_prefill: the same launches, the same bits
   if (!prefill_all_at_once(h, S))
     ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_prefill_rows: rows of different lengths need the batched prefill; this handle prefills position by position "
@@ -1391,13 +1409,40 @@ extern "C" int zn_prefill_rows(zn_handle h, const void* hidden_dev, int32_t S, c
   return prefill_impl(h, hidden_dev, S, h->row_len, s);                     // len_hi += S: the bound of the longest row
 }
 
+extern "C" int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int32_t n) {
+  if (!h) return ZN_ERR_ARG;
+  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_rows before zn_gen_begin");
+  if (h->gen_prefilled) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_rows after zn_prefill: the table belongs between zn_gen_begin and the generation's prefill");
+  if (!rows_host) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: null argument");
+  if (n != h->batch) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: %d entries for a generation of %d utterances", n, h->batch);
+  const int nq = h->cfg.n_codebooks, budget = h->t_total - h->offset0 - nq + 1;   // zn_gen_begin's max_new_tokens (t_total = prefix + max_new_tokens + n_q)
+  std::vector<int> rem(n);
+  for (int b = 0; b < n; ++b) {
+    const zn_row_params& r = rows_host[b];
+    if (r.sp.repetition_penalty_window < 0 || r.sp.repetition_penalty_window > 64)
+      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d: repetition_penalty_window out of range", b);
+    if (r.max_new_tokens < 1 || r.max_new_tokens > budget)
+      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d: max_new_tokens %d not in 1..%d (the generation's own)", b, r.max_new_tokens, budget);
+    if ((r.cfg_scale == 1.0f) == guided(h))
+      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d has cfg_scale %g in a generation begun %s guidance (cfg_scale == 1 for every row or for none)", b,
+              (double)r.cfg_scale, guided(h) ? "with" : "without");
+    rem[b] = r.max_new_tokens + nq - 1;
+  }
+  hipStream_t s = h->gen_stream;
+  HIPCHK(h, hipMemcpyAsync(h->row_tab, rows_host, (size_t)n * sizeof(zn_row_params), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(h->remaining, rem.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipStreamSynchronize(s));  // the host arrays are the caller's / go out of scope
+  h->rows_set = true;
+  return ZN_OK;
+}
+
 extern "C" int zn_sample_first(zn_handle h, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
   if (!h->gen_active) ZN_FAIL(h, ZN_ERR_STATE, "zn_sample_first before zn_gen_begin");
   hipStream_t s = (hipStream_t)stream;
   const zn_config& c = h->cfg;
-  SampleArgs a = make_sample_args(h, h->sp);
-  a.raw = h->logits_raw; a.mix = guided(h) ? 1 : 0; a.cfg_scale = h->cfg_scale; a.apply_bias = 0; a.batch = h->batch;
+  SampleArgs a = gen_sample_args(h);
+  a.raw = h->logits_raw; a.mix = guided(h) ? 1 : 0; a.apply_bias = 0; a.batch = h->batch;
   a.use_penalty = 0; a.st = h->st; a.logits_out = h->last_logits; a.tokens = h->tok_raw; a.draw = 0;
   hipLaunchKernelGGL(sample_kernel, dim3(c.n_codebooks, h->batch), dim3(256), 0, s, a);
   FrameArgs f{};
@@ -1870,6 +1915,18 @@ extern "C" int zn_op_embed(zn_handle h, const int32_t* codes, void* out, int32_t
   e.tables = h->emb_tables_dev; e.codes = codes; e.sb = c.n_codebooks; e.si = 1; e.col = 0; e.n_q = c.n_codebooks; e.d = c.d_model;
   e.batch = batch; e.vocab_embed = c.vocab_embed; e.out = (bf16_t*)out; e.dup = 0;
   hipLaunchKernelGGL(embed_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, e);
+  HIPCHK(h, hipGetLastError());
+  return ZN_OK;
+}
+
+extern "C" int zn_op_sample_rows(zn_handle h, const float* logits, const int32_t* recent, int32_t window, const zn_row_params* rows_dev,
+                                 uint64_t draw_index, int32_t* tokens, float* probs_out, int32_t batch, zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  if (!logits || !rows_dev || !tokens || batch < 1 || (recent && window < 1)) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_sample_rows: bad argument");
+  SampleArgs a = make_sample_args(h, zn_sampling{});
+  a.raw = logits; a.mix = 0; a.apply_bias = 0; a.batch = batch; a.recent = recent; a.window = window; a.rows = rows_dev;
+  a.use_penalty = recent != nullptr; a.tokens = tokens; a.probs_out = probs_out; a.draw = draw_index;
+  hipLaunchKernelGGL(sample_kernel, dim3(h->cfg.n_codebooks, batch), dim3(256), 0, (hipStream_t)stream, a);
   HIPCHK(h, hipGetLastError());
   return ZN_OK;
 }

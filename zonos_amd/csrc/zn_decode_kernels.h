@@ -5,6 +5,7 @@
 // non-temporal loads, activations (a few KB) live in registers or LDS, reductions are wavefront shuffles.
 #pragma once
 #include "zn_common.h"
+#include "../../include/zonos_hip.h"   // zn_row_params (the per-utterance table of sample_kernel)
 #include "zn_linear_plan.h"   // PRO_* / EPI_*, ZN_G16_KC, ZN_G16_LNT, ZN_G16K_NKW, ZN_G16K_KCH
 
 // ------------------------------------------------------------------------------------------------ GEMV
@@ -1572,6 +1573,11 @@ struct SampleArgs {
   int use_penalty; float penalty; int pen_window;
   float temperature, top_p; int top_k; float min_p, linear, conf, quad;
   unsigned long long seed, draw;
+  // Per-utterance table (zn_gen_set_rows, zn_op_sample_rows), NULL = every row uses the values above.  With a table, workgroup (cb, b)
+  // takes temperature .. quad, the penalty and its window, the seed, cfg_scale and ctx = min(max_new_tokens, 100) from rows[b]; the penalty
+  // applies where use_penalty is set AND rows[b]'s penalty != 1; and the Gumbel key's utterance index is 0 (a request's stream does not
+  // depend on its slot).  sample1_kernel does not read it: zn_api.hip never gives a table to a step that kernel serves.
+  const zn_row_params* rows;
   GenState* st;            // may be NULL (op mode)
   float* logits_out;       // [B][n_q][V] logits as consumed by the sampler (after bias), may be NULL
   float* probs_out;        // optional filtered probabilities
@@ -1693,6 +1699,23 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   const int o = a.st ? a.st->offset : 0;
   const float st_bias = a.st ? a.st->eos_bias : 0.f;
   const bool st_force = a.st ? (a.st->force_eos_step == a.st->step) : false;
+  // the utterance's own settings: one 64-byte entry at a workgroup-uniform address, requested with the loads above and below (every
+  // branch on these values is uniform across the workgroup, as it is on the launch-wide ones)
+  float temperature = a.temperature, top_p = a.top_p, min_p = a.min_p, linear = a.linear, conf = a.conf, quad = a.quad;
+  float penalty = a.penalty, cfg_scale = a.cfg_scale;
+  int top_k = a.top_k, pen_window = a.pen_window, ctx = a.ctx, use_penalty = a.use_penalty;
+  unsigned long long seed = a.seed;
+  size_t key_b = (size_t)b;
+  if (a.rows) {
+    const zn_row_params rp = a.rows[b];
+    temperature = rp.sp.temperature; top_p = rp.sp.top_p; top_k = rp.sp.top_k; min_p = rp.sp.min_p;
+    linear = rp.sp.linear; conf = rp.sp.conf; quad = rp.sp.quad;
+    penalty = rp.sp.repetition_penalty; pen_window = rp.sp.repetition_penalty_window;
+    seed = rp.sp.seed; cfg_scale = rp.cfg_scale;
+    ctx = rp.max_new_tokens < 100 ? rp.max_new_tokens : 100;
+    use_penalty = a.use_penalty && penalty != 1.0f;
+    key_b = 0;
+  }
   constexpr int IT = ZN_SAMPLE_MAXV / 256;
   float cc[IT], uu[IT];
   const float* rc = a.raw + ((size_t)b * a.n_q + cb) * V;
@@ -1708,7 +1731,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   for (int it = 0; it < IT; ++it) {
     const int i = tid + it * 256;
     if (i < V) {
-      float l = a.mix ? __fadd_rn(uu[it], __fmul_rn(__fsub_rn(cc[it], uu[it]), a.cfg_scale)) : cc[it];
+      float l = a.mix ? __fadd_rn(uu[it], __fmul_rn(__fsub_rn(cc[it], uu[it]), cfg_scale)) : cc[it];
       if (a.apply_bias && i == a.eos_id) {
         if (cb == 0) {
           l = __fadd_rn(l, -0.6931471824645996f);  // -log(2) in fp32
@@ -1724,13 +1747,13 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   }
   __syncthreads();
   // ---- repetition penalty (sampling.py:159-163): factor = penalty^(#occurrences in the last `window` tokens)
-  if (a.use_penalty) {
+  if (use_penalty) {
     int nw = 0;
     const int* hist = nullptr;
-    if (a.recent) { nw = a.window < a.pen_window ? a.window : a.pen_window; hist = a.recent + ((size_t)b * a.n_q + cb) * a.window + (a.window - nw); }
+    if (a.recent) { nw = a.window < pen_window ? a.window : pen_window; hist = a.recent + ((size_t)b * a.n_q + cb) * a.window + (a.window - nw); }
     else if (a.codes) {
-      int avail = o + 1 < a.ctx ? o + 1 : a.ctx;   // columns [max(0,o+1-ctx), o]
-      nw = avail < a.pen_window ? avail : a.pen_window;
+      int avail = o + 1 < ctx ? o + 1 : ctx;   // columns [max(0,o+1-ctx), o]
+      nw = avail < pen_window ? avail : pen_window;
       hist = a.codes + ((size_t)b * a.n_q + cb) * a.t_total + (o + 1 - nw);
     }
     // the window's tokens are fetched once, together, into LDS (the default window is 2); longer windows re-read memory
@@ -1748,7 +1771,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         for (int w2 = 0; w2 < w; ++w2) if (tokat(w2) == g) seen = true;
         if (seen) continue;
         float f = 1.f;
-        for (int w2 = w; w2 < nw; ++w2) if (tokat(w2) == g) f = __fmul_rn(f, a.penalty);
+        for (int w2 = w; w2 < nw; ++w2) if (tokat(w2) == g) f = __fmul_rn(f, penalty);
         const float l = sp[g];
         sp[g] = (l <= 0.f) ? __fmul_rn(l, f) : __fdiv_rn(l, f);
       }
@@ -1756,7 +1779,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     __syncthreads();
   }
   int tok;
-  if (!(a.temperature > 0.f)) {
+  if (!(temperature > 0.f)) {
     float bv = -INFINITY; int bi = 0x7fffffff;
     for (int i = tid; i < V; i += 256) { const float v = sp[i]; if (v > bv) { bv = v; bi = i; } }
     float rv; int ri;
@@ -1765,21 +1788,21 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   } else {
     // ---- softmax(logits / T) (sampling.py:217)
     float mx = -INFINITY;
-    for (int i = tid; i < V; i += 256) { sp[i] = sp[i] / a.temperature; mx = fmaxf(mx, sp[i]); }
+    for (int i = tid; i < V; i += 256) { sp[i] = sp[i] / temperature; mx = fmaxf(mx, sp[i]); }
     mx = block_max(mx, sv);
     float s = 0.f;
     for (int i = tid; i < V; i += 256) { const float e = expf(sp[i] - mx); sp[i] = e; s += e; }
     s = block_sum(s, sv);
     for (int i = tid; i < V; i += 256) sp[i] = sp[i] / s;
     __syncthreads();
-    if (a.linear > 0.f) {  // apply_unified (sampling.py:60-63)
+    if (linear > 0.f) {  // apply_unified (sampling.py:60-63)
       float ent = 0.f;
       for (int i = tid; i < V; i += 256) { const float lp = logf(fmaxf(sp[i], 1e-20f)); ent += sp[i] * lp; }
       ent = -block_sum(ent, sv);
       float m2 = -INFINITY;
       for (int i = tid; i < V; i += 256) {
         const float lp = logf(fmaxf(sp[i], 1e-20f));
-        const float raw = lp * (a.linear + ent * a.conf) - lp * lp * a.quad;
+        const float raw = lp * (linear + ent * conf) - lp * lp * quad;
         sp[i] = raw; m2 = fmaxf(m2, raw);
       }
       m2 = block_max(m2, sv);
@@ -1789,7 +1812,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       for (int i = tid; i < V; i += 256) sp[i] = sp[i] / s2;
       __syncthreads();
     }
-    if (a.top_p > 0.f || a.top_k > 0) {
+    if (top_p > 0.f || top_k > 0) {
       // descending bitonic sort of (prob, index) padded to 2048 (sampling.py:93 torch.sort, :77 topk)
       for (int i = tid; i < ZN_SAMPLE_MAXV; i += 256) { sidx[i] = i; if (i >= V) sp[i] = -1.f; }
       __syncthreads();
@@ -1808,10 +1831,10 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
           __syncthreads();
         }
       }
-      if (a.top_p > 0.f) {  // apply_top_p (sampling.py:93-99): sequential fp32 cumsum like torch.cumsum on CPU
+      if (top_p > 0.f) {  // apply_top_p (sampling.py:93-99): sequential fp32 cumsum like torch.cumsum on CPU
         if (tid == 0) {
           float cum = 0.f;
-          for (int i = 0; i < V; ++i) { const float p = sp[i]; cum += p; if (cum - p > a.top_p) sp[i] = 0.f; }
+          for (int i = 0; i < V; ++i) { const float p = sp[i]; cum += p; if (cum - p > top_p) sp[i] = 0.f; }
         }
         __syncthreads();
         float s3 = 0.f;
@@ -1820,8 +1843,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         for (int i = tid; i < V; i += 256) sp[i] = sp[i] / s3;
         __syncthreads();
       }
-      if (a.top_k > 0) {  // apply_top_k (sampling.py:77-81): still sorted descending (zeros sink consistently)
-        const int kk = a.top_k < V ? a.top_k : V;
+      if (top_k > 0) {  // apply_top_k (sampling.py:77-81): still sorted descending (zeros sink consistently)
+        const int kk = top_k < V ? top_k : V;
         // after top_p the array is no longer strictly sorted only among zeros; the k-th largest is sp[kk-1]
         const float pivot = sp[kk - 1];
         __syncthreads();
@@ -1835,12 +1858,12 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       for (int i = tid; i < V; i += 256) sidx[i] = i;
       __syncthreads();
     }
-    if (a.min_p > 0.f) {  // apply_min_p (sampling.py:123-127)
+    if (min_p > 0.f) {  // apply_min_p (sampling.py:123-127)
       float m3 = 0.f;
       for (int i = tid; i < V; i += 256) m3 = fmaxf(m3, sp[i]);
       m3 = block_max(m3, sv);
       float s5 = 0.f;
-      for (int i = tid; i < V; i += 256) { if (sp[i] < a.min_p * m3) sp[i] = 0.f; s5 += sp[i]; }
+      for (int i = tid; i < V; i += 256) { if (sp[i] < min_p * m3) sp[i] = 0.f; s5 += sp[i]; }
       s5 = block_sum(s5, sv);
       for (int i = tid; i < V; i += 256) sp[i] = sp[i] / s5;
       __syncthreads();
@@ -1850,8 +1873,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     float bv = -1.f; int bi = 0x7fffffff;
     for (int i = tid; i < V; i += 256) {
       const int tokid = sidx[i];
-      unsigned long long h = zn_mix64(a.seed ^ zn_mix64(a.draw + (a.st ? (unsigned long long)a.st->step : 0ull)));
-      h = zn_mix64(h + 0x9E3779B97F4A7C15ull * (unsigned long long)(((size_t)b * a.n_q + cb) * V + tokid + 1));
+      unsigned long long h = zn_mix64(seed ^ zn_mix64(a.draw + (a.st ? (unsigned long long)a.st->step : 0ull)));
+      h = zn_mix64(h + 0x9E3779B97F4A7C15ull * (unsigned long long)((key_b * a.n_q + cb) * V + tokid + 1));
       const float uu = ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
       const float q = -logf(uu);
       const float v = sp[i] / q;

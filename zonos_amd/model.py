@@ -12,6 +12,7 @@ import os
 import sys
 import threading
 import json
+from dataclasses import dataclass, field
 from typing import Callable, Iterator, NamedTuple, Sequence
 
 import torch
@@ -21,7 +22,7 @@ from . import _lib
 from .autoencoder import DACAutoencoder
 from .backbone import BACKBONES, HipEngine
 from .codebook_pattern import apply_delay_pattern, revert_delay_pattern
-from .conditioning import ConditioningCache, PrefixConditioner, prepare_conditioning_with_cache
+from .conditioning import ConditioningCache, PrefixConditioner, pad_conditionings, prepare_conditioning_with_cache
 from .config import InferenceParams, ZonosConfig
 from .utils import DEFAULT_DEVICE, find_multiple
 
@@ -74,6 +75,78 @@ def release_limit(offset: int, nq: int, eos_frame: int | None) -> int:
     the stop frame itself).  What the end keeps beyond that, `finalise_codes` decides."""
     limit = max(0, offset - nq + 1)
     return limit if eos_frame is None else min(limit, eos_frame)
+
+
+def stop_check_at(step_idx: int, batch_size: int) -> bool:
+    """The reference's stop-check cadence (tensor_ops.py:90-103) as `_decode_loop` runs it: is the stop flag read after loop step
+    `step_idx` (0-based) of a call of `batch_size` utterances?"""
+    return step_idx % 16 == 15 or (step_idx % 8 == 7 and max(0, batch_size * 10 - (step_idx + 1)) < 5)
+
+
+def row_end_offset(offset0: int, t_total: int, batch_size: int, nq: int, eos_column: int | None) -> int:
+    """The column at which the decode loop of a call of `batch_size` utterances would have ended had it watched one row alone
+    (`generate_batch`: every request is cut and finalised for itself, while the call runs on to its last row).  The row starts at column
+    `offset0` (audio prefix + 1) with its own `t_total` = prefix + max_new_tokens + nq columns and remaining_steps = t_total - offset0;
+    `eos_column` is the first column beyond offset0 whose codebook 0 holds EOS (None: there is none below t_total).  Loop step i writes
+    column offset0 + i + 1; a step that samples EOS in codebook 0 caps remaining_steps at nq; every step takes one off (tensor_ops.py:87,
+    155-211).  The loop leaves at the first check of the call's cadence (`stop_check_at`) at which remaining_steps <= 0 - the deferred
+    read-back of `_decode_loop` rolls back to that same check - or at t_total when the row's budget ends before any such check."""
+    remaining, offset = t_total - offset0, offset0
+    for step_idx in range(t_total - offset0):
+        offset += 1
+        if offset >= t_total:
+            break
+        if eos_column is not None and offset == eos_column:
+            remaining = min(remaining, nq)
+        remaining -= 1
+        if stop_check_at(step_idx, batch_size) and remaining <= 0:
+            return offset
+    return t_total
+
+
+@dataclass
+class GenRequest:
+    """One utterance of `Zonos.generate_batch`: `generate()`'s per-call arguments, per request.  `conditioning` is what
+    `prepare_conditioning` returns for the utterance: [2, L, d] = [cond ‖ uncond], or [1, L, d] when cfg_scale == 1."""
+    conditioning: torch.Tensor
+    sampling_params: dict = field(default_factory=lambda: dict(min_p=0.1))
+    seed: int | None = None
+    cfg_scale: float = 2.0
+    max_new_tokens: int = 86 * 30
+    audio_prefix_codes: torch.Tensor | None = None
+
+
+MAX_BATCH_REQUESTS = 64       # utterances of one generate_batch() call: the batch the sampler tail's tables are sized for (ZN_TAIL_MAXB)
+
+
+def check_requests(requests: Sequence[GenRequest], nq: int, d_model: int) -> tuple[bool, int]:
+    """What `generate_batch` refuses before any launch (ValueError); returns (guided, audio prefix length) of the call."""
+    n = len(requests)
+    if n == 0:
+        raise ValueError("generate_batch: no requests")
+    if n > MAX_BATCH_REQUESTS:
+        raise ValueError(f"generate_batch: {n} requests, one call holds at most {MAX_BATCH_REQUESTS}")
+    guided = {float(r.cfg_scale) != 1.0 for r in requests}
+    if len(guided) > 1:
+        raise ValueError("generate_batch: requests with cfg_scale == 1 and with guidance cannot share a call (the batch's row layout "
+                         f"differs): cfg_scale = {[float(r.cfg_scale) for r in requests]}")
+    prefixes = {0 if r.audio_prefix_codes is None else int(r.audio_prefix_codes.shape[-1]) for r in requests}
+    if len(prefixes) > 1:
+        raise ValueError(f"generate_batch: audio prefixes of different lengths {sorted(prefixes)} in one call are not supported "
+                         "(the audio prefix length is shared by the batch)")
+    halves = 2 if guided.pop() else 1
+    for i, r in enumerate(requests):
+        c = r.conditioning
+        if c.dim() != 3 or c.shape[0] != halves or c.shape[1] < 1 or c.shape[2] != d_model:
+            raise ValueError(f"generate_batch: request {i}: conditioning of shape {tuple(c.shape)}, expected [{halves}, L >= 1, {d_model}] at "
+                             f"cfg_scale={r.cfg_scale}")
+        if int(r.max_new_tokens) != r.max_new_tokens or int(r.max_new_tokens) < 1:
+            raise ValueError(f"generate_batch: request {i}: max_new_tokens must be a positive integer, got {r.max_new_tokens}")
+        a = r.audio_prefix_codes
+        if a is not None and (a.dim() != 3 or a.shape[0] != 1 or a.shape[1] != nq):
+            raise ValueError(f"generate_batch: request {i}: audio_prefix_codes of shape {tuple(a.shape)}, expected [1, {nq}, P]")
+        _sampling_struct(r.sampling_params, 0)             # unknown sampling keys: TypeError, as in generate()
+    return halves == 2, prefixes.pop()
 
 
 def _drain(gen):
@@ -309,6 +382,46 @@ class Zonos(nn.Module):
             raise _lib.ZonosHipError("zonos_amd runs on MI355X only: move the model to a cuda device (no CPU fallback)")
         return n
 
+    @torch.inference_mode()
+    def generate_batch(self, requests: Sequence[GenRequest], _trace: dict | None = None) -> list[torch.Tensor]:
+        """One generation for several requests, each with its own sampling parameters, seed, cfg_scale and max_new_tokens (and its own
+        prompt length); returns, per request, int64 [1, 9, T_b] as `generate()` returns it, cut and finalised for that request alone.
+
+        The conditionings are right-padded (`pad_conditionings`) and prefilled as `conditioning_lengths` does; the call runs max_b
+        max_new_tokens frames at most and ends at the first stop check after every request has stopped or spent its budget.  Request b is
+        sampled with the random stream of a one-utterance `generate(seed=seed_b)`, whatever slot it takes; its codes are
+        its row's first prefix + max_new_tokens_b + 9 delayed columns, finalised at `row_end_offset`.  ValueError, before any launch: an
+        empty list, more than MAX_BATCH_REQUESTS requests, guided and cfg_scale == 1 requests together, audio prefixes of different
+        lengths.  A single request is `generate()` with its arguments."""
+        reqs = list(requests)
+        nq = self.config.codebook_dimension
+        guided, P = check_requests(reqs, nq, self.config.backbone.d_model)
+        if len(reqs) == 1:
+            r = reqs[0]
+            return [self.generate(r.conditioning, r.audio_prefix_codes, int(r.max_new_tokens), r.cfg_scale, 1, r.sampling_params, seed=r.seed,
+                                  _trace=_trace)]
+        B, dev = len(reqs), self.device
+        cond, lengths = pad_conditionings([r.conditioning.to(dev) for r in reqs], 2.0 if guided else 1.0)
+        self._check_rows(cond, 2.0 if guided else 1.0, B, lengths)
+        prefix = None if P == 0 else torch.cat([r.audio_prefix_codes.to(dev) for r in reqs], 0)
+        table = (_lib.zn_row_params * B)()
+        for b, r in enumerate(reqs):
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if r.seed is None else r.seed
+            table[b].sp = _sampling_struct(r.sampling_params, seed)
+            table[b].cfg_scale, table[b].max_new_tokens = float(r.cfg_scale), int(r.max_new_tokens)
+        max_new = max(int(r.max_new_tokens) for r in reqs)
+        eng = self._acquire_engine((cond.shape[0] + 1) // 2)
+        try:
+            with torch.cuda.device(dev):
+                # zn_gen_begin's own cfg_scale and sampling parameters only fix the row layout: every sampler reads the table
+                run = lambda: _drain(self._generation(eng, cond, prefix, max_new, 2.0 if guided else 1.0, B, reqs[0].sampling_params, None, 0, _trace,
+                                                      torch.cuda.current_stream(dev), None, lengths, table))
+                outs = self._with_timeout_policy(run, caller_saw_frames=_trace is not None)
+            return [o.to(dev) for o in outs]
+        finally:
+            eng.generating = False
+            eng.lock.release()
+
     def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor = None, max_new_tokens: int = 86 * 30,
                cfg_scale: float = 2.0, sampling_params: dict = dict(min_p=0.1), seed: int | None = None, chunk_frames: int = 16,
                batch_size: int = 1) -> Iterator[StreamChunk]:
@@ -414,9 +527,10 @@ class Zonos(nn.Module):
                                        seed, _trace, torch.cuda.current_stream(self.device), None, cond_lengths)).to(self.device)
 
     def _generation(self, eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params, callback, seed,
-                    _trace, ts, chunk, cond_lengths=None):
+                    _trace, ts, chunk, cond_lengths=None, row_table=None):
         """One generation on `eng` (its lock held by the caller), with every launch on torch stream `ts`.  A generator: with `chunk` it yields
-        (delayed codes, last column written) every `chunk` decode steps (Zonos.stream), and it returns the final codes on the host."""
+        (delayed codes, last column written) every `chunk` decode steps (Zonos.stream), and it returns the final codes on the host.  With
+        `row_table` (zn_row_params per utterance, generate_batch) it returns one tensor per utterance."""
         dev = self.device
         B, nq = batch_size, self.config.codebook_dimension
         R = prefix_conditioning.shape[0]                          # 2B with guidance, B when cfg_scale == 1 (checked by generate)
@@ -428,6 +542,11 @@ class Zonos(nn.Module):
         codes = torch.full((B, nq, audio_len), -1, dtype=torch.int32, device=dev)
         if audio_prefix_codes is not None:
             codes[..., :P] = audio_prefix_codes.to(device=dev, dtype=torch.int32)
+        if row_table is not None:
+            # a row's cells beyond its own budget hold the mask token, as the delay pattern of a generation of that length leaves them:
+            # they are never written, and the steps that run past the row's end embed what its own generation would have embedded
+            for b in range(B):
+                codes[b, :, P + int(row_table[b].max_new_tokens):] = self.masked_token_id
         delayed = apply_delay_pattern(codes, self.masked_token_id).contiguous()       # [B, nq, audio_len + nq]
         t_total = delayed.shape[2]
         offset = P + 1
@@ -437,13 +556,29 @@ class Zonos(nn.Module):
         eng.call("zn_gen_begin", B, kv_ptrs, ip.max_seqlen, ip.lengths_per_sample.data_ptr(), delayed.data_ptr(), t_total, offset,
                  max_new_tokens, float(cfg_scale), C.byref(sp), st)
         try:
+            if row_table is not None:
+                eng.call("zn_gen_set_rows", row_table, B)
             offset = yield from self._decode_loop(eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk, cond_lengths)
         finally:
             # the device's persistent-kernel tenancy goes back once this generation's kernels have drained (include/zonos_hip.h)
             ts.synchronize()
             eng.call("zn_gen_end")
+        if row_table is not None:
+            return self._finalise_rows(delayed.cpu(), row_table, P, B, nq)       # the same one device->host copy
         out = revert_delay_pattern(delayed.to(torch.int64)).cpu()     # one device->host copy (model.py:511)
         return finalise_codes(out, offset, nq, self.eos_token_id)
+
+    def _finalise_rows(self, delayed: torch.Tensor, row_table, P: int, B: int, nq: int) -> list[torch.Tensor]:
+        """generate_batch's results from the call's delayed codes (host): row b keeps its own P + max_new_tokens_b + nq columns and is
+        finalised at the column its own loop would have ended at (`row_end_offset`, from its first codebook-0 EOS)."""
+        outs, offset0 = [], P + 1
+        for b in range(B):
+            t_b = P + int(row_table[b].max_new_tokens) + nq
+            row = delayed[b:b + 1, :, :t_b].to(torch.int64)
+            hit = (row[0, 0, offset0 + 1:] == self.eos_token_id).nonzero()
+            eos_column = offset0 + 1 + int(hit[0, 0]) if len(hit) else None
+            outs.append(finalise_codes(revert_delay_pattern(row), row_end_offset(offset0, t_b, B, nq, eos_column), nq, self.eos_token_id))
+        return outs
 
     def _decode_loop(self, eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk=None, cond_lengths=None):
         """Prefill, first frame and the hot loop (model.py:421-509); a generator that returns the final column offset.  With `chunk`, the
@@ -494,7 +629,7 @@ class Zonos(nn.Module):
                 break
             pending += 1
             ip.seqlen_offset += 1
-            check = (step_idx % 16 == 15) or (step_idx % 8 == 7 and max(0, B * 10 - cpu_step_counter) < 5)
+            check = stop_check_at(step_idx, B)
             hook = chunk is not None and step_idx % chunk == chunk - 1
             if check or hook or callback is not None or _trace is not None:
                 eng.call("zn_decode_steps", pending, st)
