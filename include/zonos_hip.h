@@ -164,6 +164,20 @@ int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_stream stream)
  * a call.  An error leaves the generation as it was.  Without this call every row uses zn_gen_begin's values (the same bits as ABI 8).
  * Synchronises the generation's stream. */
 int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int32_t n);
+/* An audio prefix of its own length per utterance of the generation begun by zn_gen_begin (a column shift per row of the code buffer).  The
+ * caller begins the generation for the LONGEST prefix: offset0 = P_call + 1 and t_total = P_call + max_b max_new_tokens_b + n_codebooks with
+ * P_call = max_b P_b, and lays utterance b out left-aligned in its own buffer row: P_b prefix frames, its unknown cells, then the mask
+ * token, under the delay pattern.  prefix_len_host: HOST array of n == batch lengths P_b; the library stores shift[b] = P_b - P_call (<= 0) in
+ * a device array of its own, and at loop state `offset` utterance b's column is offset + shift[b]: zn_sample_first writes it there, every
+ * decode step embeds that column, writes the next one and takes its repetition-penalty history from the columns ending there (clamped at the
+ * row's own column 0, never reaching another row) - what a generation with a shared prefix of P_b frames does for that utterance.  The
+ * prefill rows are the caller's (zn_prefill_rows with row_len[r] = L_b + P_b + 1; zn_op_assemble_prefill builds them).
+ * Legal exactly where zn_gen_set_rows is: after zn_gen_begin, before the generation's prefill, before any graph is captured (ZN_ERR_STATE
+ * otherwise).  ZN_ERR_ARG: n != batch, a length outside 0 .. P_call, or no length equal to P_call.  An error leaves the generation as it
+ * was.  Without this call, or with every length equal, every shift is 0, the kernels receive a NULL array and compute what they computed
+ * before.  A generation with a shift never runs the persistent kernels (zn_decode_path_detail reports 0), whose samplers do not read it -
+ * two unguided utterances whose lengths advance in lockstep included.  Synchronises the generation's stream. */
+int zn_gen_set_prefix_rows(zn_handle h, const int32_t* prefix_len_host, int32_t n);
 /* ABI 8 - zn_prefill for utterances of different prompt lengths.  hidden bf16 [R, S, d] is RIGHT-padded: row r holds row_len[r] valid
  * positions (its conditioning followed by the embedded audio prefix), then S - row_len[r] positions of padding whose contents are never
  * visible to a result: no valid query attends a pad key, no pad position reaches a logit, a Mamba2 state or a KV entry that is read
@@ -355,6 +369,15 @@ int zn_op_embed(zn_handle h, const int32_t* codes_dev, void* out_dev, int32_t ba
 int zn_op_sample(zn_handle h, const float* logits_dev, const int32_t* recent_dev, int32_t window,
                  const zn_sampling* sp, uint64_t draw_index, int32_t* tokens_dev, float* probs_out_dev,
                  int32_t batch, zn_stream stream);
+/* The right-padded prefill rows of utterances with conditionings and audio prefixes of their own lengths, in one launch: for the `rows`
+ * rows (rows == batch, or 2 * batch = [cond ‖ uncond]; b = r mod batch) hidden bf16 [rows, S, d] receives
+ * [cond_dev[r, :L_b] ‖ embed(delayed_codes_dev[b, :, 0 : P_b + 1]) ‖ zeros] and row_len_dev[r] = L_b + P_b + 1.  cond_dev bf16
+ * [rows, L_c, d]; cond_len_dev, prefix_len_dev int32 [batch] (DEVICE; clamped to L_c and t_total - 1); delayed_codes_dev int32
+ * [batch, n_codebooks, t_total]; S >= max_b (L_b + P_b + 1) is the caller's to ensure (positions at or beyond S are not written).  The
+ * embedded positions carry the bits of zn_op_embed. */
+int zn_op_assemble_prefill(zn_handle h, const void* cond_dev, int32_t L_c, const int32_t* cond_len_dev, const int32_t* delayed_codes_dev,
+                           int32_t t_total, const int32_t* prefix_len_dev, int32_t batch, int32_t rows, void* hidden_dev, int32_t S,
+                           int32_t* row_len_dev, zn_stream stream);
 /* ABI 9 - zn_op_sample with a table: rows_dev is a DEVICE array of `batch` entries, row b sampled with rows_dev[b].sp (cfg_scale and
  * max_new_tokens are not used: the logits are final) and the slot-independent key of zn_gen_set_rows.  Row b's tokens and probabilities
  * equal zn_op_sample(batch = 1) on row b's logits and history with rows_dev[b].sp. */

@@ -92,6 +92,7 @@ SIGNATURES = {
     "zn_prefill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "zn_prefill_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
     "zn_gen_set_rows": (C.c_int, [C.c_void_p, C.POINTER(zn_row_params), C.c_int32]),
+    "zn_gen_set_prefix_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "zn_sample_first": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zn_decode_steps": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "zn_graph_active": (C.c_int, [C.c_void_p]),
@@ -129,6 +130,8 @@ SIGNATURES = {
     "zn_op_mamba_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "zn_op_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(zn_sampling), C.c_uint64, C.c_void_p, C.c_void_p,
                                C.c_int32, C.c_void_p]),
+    "zn_op_assemble_prefill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "zn_op_sample_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                     C.c_int32, C.c_void_p]),
     "zn_dac_create": (C.c_int, [C.POINTER(zn_dac_config), C.POINTER(zn_dac_tensor), C.c_int32, C.POINTER(C.c_void_p)]),

@@ -99,6 +99,8 @@ struct zn_handle_s {
   int *remaining = nullptr, *stopping = nullptr;
   zn_row_params* row_tab = nullptr;   // [max_rows] per-utterance settings of this generation (zn_gen_set_rows)
   bool rows_set = false;              // this generation's samplers read row_tab
+  int* prefix_shift = nullptr;        // [max_rows] column shift per utterance of this generation, <= 0 (zn_gen_set_prefix_rows)
+  bool prefix_set = false;            // some shift is not 0: this generation's embedding, sampler and bookkeeping launches read prefix_shift
   bool gen_prefilled = false;         // zn_prefill / zn_prefill_rows has run since zn_gen_begin
   int* done_host = nullptr;  // pinned: [0..3] synchronous stop check, [4..7] asynchronous one
   hipEvent_t stop_event = nullptr;
@@ -199,7 +201,7 @@ extern "C" int zn_destroy(zn_handle h) {
   if (!h) return ZN_OK;
   (void)zn_tenant_release(h->device, h);
   free_graph(h);
-  void* ptrs[] = {h->emb_tables_dev, h->x, h->q, h->o1, h->mbuf, h->nbuf, h->logits_raw, h->last_logits, h->tok_raw, h->scores, h->cmax, h->pv_part, h->pv_tickets, h->pf_x, h->pf_n, h->pf_qkv, h->pf_a, h->pf_u, h->pf_m, h->pf_res, h->pf_zx, h->pf_xbc, h->pf_y, h->pf_g, h->qkv_tmp, h->fw_lengths, h->row_len, h->st, h->remaining, h->stopping, h->row_tab, h->res, h->hn, h->m_zx, h->m_xbc, h->m_y, h->m_g, h->m_vg, h->g16_part, h->g16_tickets, h->ln_part, h->ch_gy1, h->ch_gx1, h->ch_gx2, h->ch_gm, h->ch_epoch, h->ch_x2, h->x_emb, h->tail_ticket, h->ch_gqkv, h->ch_ga, h->ch_gbmax, h->ch_gpart, h->stack_layers, h->ch_diag};
+  void* ptrs[] = {h->emb_tables_dev, h->x, h->q, h->o1, h->mbuf, h->nbuf, h->logits_raw, h->last_logits, h->tok_raw, h->scores, h->cmax, h->pv_part, h->pv_tickets, h->pf_x, h->pf_n, h->pf_qkv, h->pf_a, h->pf_u, h->pf_m, h->pf_res, h->pf_zx, h->pf_xbc, h->pf_y, h->pf_g, h->qkv_tmp, h->fw_lengths, h->row_len, h->st, h->remaining, h->stopping, h->row_tab, h->prefix_shift, h->res, h->hn, h->m_zx, h->m_xbc, h->m_y, h->m_g, h->m_vg, h->g16_part, h->g16_tickets, h->ln_part, h->ch_gy1, h->ch_gx1, h->ch_gx2, h->ch_gm, h->ch_epoch, h->ch_x2, h->x_emb, h->tail_ticket, h->ch_gqkv, h->ch_ga, h->ch_gbmax, h->ch_gpart, h->stack_layers, h->ch_diag};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->done_host) (void)hipHostFree(h->done_host);
   if (h->stop_event) (void)hipEventDestroy(h->stop_event);
@@ -295,6 +297,7 @@ extern "C" int zn_create(const zn_config* cfg, const zn_weights* w, int32_t max_
   ZC(hipMalloc(&h->remaining, R * sizeof(int)));
   ZC(hipMalloc(&h->stopping, R * sizeof(int)));
   ZC(hipMalloc(&h->row_tab, R * sizeof(zn_row_params)));
+  ZC(hipMalloc(&h->prefix_shift, R * sizeof(int)));
   ZC(hipHostMalloc(&h->done_host, sizeof(int) * 8));
   ZC(hipEventCreateWithFlags(&h->stop_event, hipEventDisableTiming));
   for (unsigned long long** g : {&h->ch_gy1, &h->ch_gx1, &h->ch_gx2}) {
@@ -743,7 +746,9 @@ static bool stack_shapes_ok(zn_handle h) {
 // The persistent kernels are allowed for this generation: not switched off (zn_debug_tune(ZN_TUNE_PERSISTENT, 2), or ZN_CHAIN=0 in the environment at zn_create), the handle not demoted by
 // a hand-off timeout, the device's tenancy held, and no two unguided rows of different lengths (zn_prefill_rows): the two-row persistent kernels read lengths[r] per row, but their hand-off
 // schedules, key-block counts and graph slots were built and measured for the guided pair, whose rows advance in lockstep; such rows run the launches path, bit-identical by construction.
-static bool persist_allowed(zn_handle h) { return h->tune[ZN_TUNE_PERSISTENT] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2; }
+// Nor a column shift per utterance (zn_gen_set_prefix_rows): the fused tail's sampler and sample1_kernel do not read it, so two unguided rows whose audio prefixes differ run the launches
+// path even when their lengths advance in lockstep.
+static bool persist_allowed(zn_handle h) { return h->tune[ZN_TUNE_PERSISTENT] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2 && !h->prefix_set; }
 // Row counts a persistent kernel can serve on this model: two (the per-block chain and step_kernel) or one (step_r1_kernel, the whole-step
 // kernel only: one row beyond its 6144-key bound, or with it switched off, runs the launches path).
 static bool persist_shape(zn_handle h, int rows) { return h->ch_variant != 0 && (rows == 2 || (rows == 1 && h->ch_variant == 1)); }
@@ -1024,15 +1029,17 @@ static EmbedArgs make_embed_args(zn_handle h) {
   EmbedArgs e{};
   e.tables = h->emb_tables_dev; e.codes = h->codes; e.col_dev = &h->st->offset; e.sb = c.n_codebooks * h->t_total; e.si = h->t_total;
   e.col = 0; e.n_q = c.n_codebooks; e.d = c.d_model; e.batch = h->batch; e.vocab_embed = c.vocab_embed; e.out = h->x_emb; e.dup = guided(h) ? 1 : 0;
+  e.shift = h->prefix_set ? h->prefix_shift : nullptr;
   return e;
 }
 
 // The sampler arguments of this generation's launches (first frame, decode steps of every path): the call-wide parameters, and the
-// per-utterance table once zn_gen_set_rows has filled it.
+// per-utterance table once zn_gen_set_rows has filled it, the column shifts once zn_gen_set_prefix_rows has.
 static SampleArgs gen_sample_args(zn_handle h) {
   SampleArgs a = make_sample_args(h, h->sp);
   a.cfg_scale = h->cfg_scale; a.ctx = h->max_new < 100 ? h->max_new : 100;
   a.rows = h->rows_set ? h->row_tab : nullptr;
+  a.shift = h->prefix_set ? h->prefix_shift : nullptr;
   return a;
 }
 
@@ -1067,7 +1074,7 @@ static int enqueue_step(zn_handle h, const StepPlan& p, hipStream_t s) {
   FrameArgs& f = a.fr;
   f.st = h->st; f.codes = h->codes; f.t_total = h->t_total; f.batch = h->batch; f.n_q = c.n_codebooks; f.eos_id = c.eos_id;
   f.mask_id = c.mask_id; f.tokens = h->tok_raw; f.remaining = h->remaining; f.stopping = h->stopping; f.lengths = h->lengths;
-  f.rows = h->rows; f.first = 0; f.override = h->tok_override; f.override_calls = h->tok_override_calls;
+  f.rows = h->rows; f.first = 0; f.override = h->tok_override; f.override_calls = h->tok_override_calls; f.shift = a.shift;
   if (fused) { a.ticket = h->tail_ticket; a.em = make_embed_args(h); }
   // batch 1, greedy decoding: sampling, bookkeeping and the next embedding in one workgroup (sample1_kernel: 0.8337 -> 0.8312 ms per step).  With a
   // temperature its one wave per codebook carries 17 exp / log / hash evaluations per lane and the nine ticketed workgroups are ahead again (0.8396 vs
@@ -1147,6 +1154,7 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   for (int v : len0) if (v > h->len_hi) h->len_hi = v;
   h->gen_active = true;
   h->rows_set = false;
+  h->prefix_set = false;
   h->gen_prefilled = false;
   h->rows_unequal2 = false;
   h->gen_ended = false;
@@ -1436,6 +1444,31 @@ extern "C" int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int3
   return ZN_OK;
 }
 
+extern "C" int zn_gen_set_prefix_rows(zn_handle h, const int32_t* prefix_len_host, int32_t n) {
+  if (!h) return ZN_ERR_ARG;
+  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_prefix_rows before zn_gen_begin");
+  if (h->gen_prefilled) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_prefix_rows after zn_prefill: the prefix lengths belong between zn_gen_begin and the generation's prefill");
+  if (!prefix_len_host) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_prefix_rows: null argument");
+  if (n != h->batch) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_prefix_rows: %d entries for a generation of %d utterances", n, h->batch);
+  const int p_call = h->offset0 - 1;        // zn_gen_begin's offset0 = the longest prefix + 1
+  std::vector<int> shift(n);
+  bool longest = false, any = false;
+  for (int b = 0; b < n; ++b) {
+    const int p = prefix_len_host[b];
+    if (p < 0 || p > p_call) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_prefix_rows: utterance %d: prefix length %d not in 0..%d (zn_gen_begin's offset0 - 1)", b, p, p_call);
+    shift[b] = p - p_call;
+    longest = longest || p == p_call; any = any || p != p_call;
+  }
+  if (!longest) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_prefix_rows: no utterance has the %d prefix frames zn_gen_begin's offset0 stands for", p_call);
+  if (any) {
+    hipStream_t s = h->gen_stream;
+    HIPCHK(h, hipMemcpyAsync(h->prefix_shift, shift.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));  // the host vector goes out of scope
+  }
+  h->prefix_set = any;                  // every shift 0: the kernels keep their NULL branch (the same launches, the same bits)
+  return ZN_OK;
+}
+
 extern "C" int zn_sample_first(zn_handle h, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
   if (!h->gen_active) ZN_FAIL(h, ZN_ERR_STATE, "zn_sample_first before zn_gen_begin");
@@ -1448,7 +1481,7 @@ extern "C" int zn_sample_first(zn_handle h, zn_stream stream) {
   FrameArgs f{};
   f.st = h->st; f.codes = h->codes; f.t_total = h->t_total; f.batch = h->batch; f.n_q = c.n_codebooks; f.eos_id = c.eos_id;
   f.mask_id = c.mask_id; f.tokens = h->tok_raw; f.remaining = h->remaining; f.stopping = h->stopping; f.lengths = h->lengths;
-  f.rows = h->rows; f.first = 1; f.override = h->tok_override; f.override_calls = h->tok_override_calls;
+  f.rows = h->rows; f.first = 1; f.override = h->tok_override; f.override_calls = h->tok_override_calls; f.shift = a.shift;
   hipLaunchKernelGGL(frame_update_kernel, dim3(1), dim3(256), 0, s, f);
   h->emb_valid = false;
   HIPCHK(h, hipGetLastError());
@@ -1915,6 +1948,24 @@ extern "C" int zn_op_embed(zn_handle h, const int32_t* codes, void* out, int32_t
   e.tables = h->emb_tables_dev; e.codes = codes; e.sb = c.n_codebooks; e.si = 1; e.col = 0; e.n_q = c.n_codebooks; e.d = c.d_model;
   e.batch = batch; e.vocab_embed = c.vocab_embed; e.out = (bf16_t*)out; e.dup = 0;
   hipLaunchKernelGGL(embed_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, e);
+  HIPCHK(h, hipGetLastError());
+  return ZN_OK;
+}
+
+extern "C" int zn_op_assemble_prefill(zn_handle h, const void* cond_dev, int32_t L_c, const int32_t* cond_len_dev, const int32_t* delayed_codes_dev,
+                                      int32_t t_total, const int32_t* prefix_len_dev, int32_t batch, int32_t rows, void* hidden_dev, int32_t S, int32_t* row_len_dev,
+                                      zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  if (!cond_dev || !cond_len_dev || !delayed_codes_dev || !prefix_len_dev || !hidden_dev || !row_len_dev || L_c < 1 || t_total < 1 || S < 1 || batch < 1 ||
+      (rows != batch && rows != 2 * batch))
+    ZN_FAIL(h, ZN_ERR_ARG, "zn_op_assemble_prefill: null argument, a non-positive size, or rows %d not batch %d or twice it", rows, batch);
+  if (!h->has_io) ZN_FAIL(h, ZN_ERR_STATE, "zn_op_assemble_prefill: handle was created without embeddings");
+  const zn_config& c = h->cfg;
+  AssembleArgs a{};
+  a.cond = (const bf16_t*)cond_dev; a.cond_len = cond_len_dev; a.codes = delayed_codes_dev; a.prefix_len = prefix_len_dev;
+  a.hidden = (bf16_t*)hidden_dev; a.row_len = row_len_dev; a.L_c = L_c; a.t_total = t_total; a.S = S; a.batch = batch;
+  a.em.tables = h->emb_tables_dev; a.em.n_q = c.n_codebooks; a.em.d = c.d_model; a.em.vocab_embed = c.vocab_embed;
+  hipLaunchKernelGGL(assemble_prefill_kernel, dim3(S, rows), dim3(256), 0, (hipStream_t)stream, a);
   HIPCHK(h, hipGetLastError());
   return ZN_OK;
 }

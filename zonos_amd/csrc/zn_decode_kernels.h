@@ -1445,6 +1445,7 @@ struct EmbedArgs {
   int sb, si, col, n_q, d, batch, vocab_embed;
   bf16_t* out;                  // [2*batch or batch][d]
   int dup;                      // 1: also write row b + batch (CFG duplicate, generation_utils.py:192)
+  const int* shift;             // optional device array [batch] added to utterance b's column (zn_gen_set_prefix_rows), NULL = none
 };
 #define ZN_EMBED_MAXQ 16
 // Sum of the n_q codebook embeddings of utterance b (codes clamped into the table) -> out rows b (and b + batch).
@@ -1470,7 +1471,7 @@ ZN_DEVINL void embed_row(const EmbedArgs& a, int b, const int (&code)[ZN_EMBED_M
 }
 __global__ __launch_bounds__(256) void embed_kernel(EmbedArgs a) {
   const int b = blockIdx.x;
-  const int col = a.col_dev ? *a.col_dev : a.col;
+  const int col = (a.col_dev ? *a.col_dev : a.col) + (a.shift ? a.shift[b] : 0);
   // all codes, then all table rows, are requested before the first add (three memory round trips on the step's
   // launch-bound tail instead of one per codebook); indices past n_q repeat the last codebook and are not added
   int code[ZN_EMBED_MAXQ];
@@ -1559,6 +1560,7 @@ struct FrameArgs {
   int first;           // 1: model.py:423-431 (first frame after prefill: plain write-where-unknown)
   const int* override; // test hook: raw tokens [calls][B][n_q] replacing the sampled ones (call 0 = first frame)
   int override_calls;
+  const int* shift;    // [B] column shift per utterance, <= 0 (zn_gen_set_prefix_rows): utterance b writes column offset + shift[b]; NULL = none
 };
 #define ZN_FRAME_MAXQ 16
 #define ZN_TAIL_MAXB 64
@@ -1578,6 +1580,9 @@ struct SampleArgs {
   // applies where use_penalty is set AND rows[b]'s penalty != 1; and the Gumbel key's utterance index is 0 (a request's stream does not
   // depend on its slot).  sample1_kernel does not read it: zn_api.hip never gives a table to a step that kernel serves.
   const zn_row_params* rows;
+  // Column shift per utterance (zn_gen_set_prefix_rows), NULL = every row reads the penalty history ending at column st->offset.  With it,
+  // utterance b's history ends at column st->offset + shift[b] and clamps at the row's own column 0.  sample1_kernel does not read it either.
+  const int* shift;
   GenState* st;            // may be NULL (op mode)
   float* logits_out;       // [B][n_q][V] logits as consumed by the sampler (after bias), may be NULL
   float* probs_out;        // optional filtered probabilities
@@ -1640,19 +1645,23 @@ ZN_DEVINL void frame_update_body(const FrameArgs& a, int (*s_code)[ZN_FRAME_MAXQ
   // of the reference becomes one memory round trip); lanes of one utterance share a wave, so all of them have read the
   // counters before lane 0 of the group rewrites them.  n_q <= 16 is checked by zn_create.
   const int o = a.st->offset, stp = a.st->step;
+  // (the utterance's column shift is requested with the loop state, before the barrier: the cell's address waits for both at once)
+  const int b0 = threadIdx.x / ZN_FRAME_MAXQ;
+  int sh = (a.shift && b0 < a.batch) ? a.shift[b0] : 0;
   __shared__ int s_done;
   if (threadIdx.x == 0) s_done = 1;
   __syncthreads();
   const int cb = threadIdx.x & (ZN_FRAME_MAXQ - 1);
-  for (int b = threadIdx.x / ZN_FRAME_MAXQ; b < a.batch; b += blockDim.x / ZN_FRAME_MAXQ) {
+  for (int b = b0; b < a.batch; b += blockDim.x / ZN_FRAME_MAXQ) {
+    if (a.shift && b != b0) sh = a.shift[b];
     const int* tk = a.tokens + b * a.n_q;
     const int call = a.first ? 0 : stp + 1;
     const bool ovr = a.override && call < a.override_calls;
     if (ovr) tk = a.override + ((size_t)call * a.batch + b) * a.n_q;
     const int cbc = min(cb, a.n_q - 1);
-    const int col = a.first ? o : o + 1;
-    const bool in_range = cb < a.n_q && col < a.t_total;
-    int* cell = a.codes + ((size_t)b * a.n_q + cbc) * a.t_total + min(col, a.t_total - 1);
+    const int col = (a.first ? o : o + 1) + sh;            // sh <= 0, and never below the row's own column 1 (zn_gen_set_prefix_rows)
+    const bool in_range = cb < a.n_q && col >= 0 && col < a.t_total;
+    int* cell = a.codes + ((size_t)b * a.n_q + cbc) * a.t_total + max(0, min(col, a.t_total - 1));
     int tok, tok0;
     if (TAIL && !ovr) {
       tok = __hip_atomic_load(tk + cbc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1696,7 +1705,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   __shared__ int si[4];
   // every input is requested before the first use (clamped indices, masked use): the kernel sits on the step's
   // launch-bound tail, where one memory round trip per loop iteration used to cost several microseconds
-  const int o = a.st ? a.st->offset : 0;
+  const int o = (a.st ? a.st->offset : 0) + (a.shift ? a.shift[b] : 0);   // the utterance's own column (workgroup-uniform, requested with the loop state)
   const float st_bias = a.st ? a.st->eos_bias : 0.f;
   const bool st_force = a.st ? (a.st->force_eos_step == a.st->step) : false;
   // the utterance's own settings: one 64-byte entry at a workgroup-uniform address, requested with the loads above and below (every

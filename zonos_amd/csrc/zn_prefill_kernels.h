@@ -4,6 +4,7 @@
 // (512-key blocks, running max, fexp_u20 / libm exp split governed by the query block's key span, bf16 P).
 #pragma once
 #include "zn_common.h"
+#include "zn_decode_kernels.h"   // embed_row (assemble_prefill_kernel sums the codebook embeddings as the decode step does)
 
 typedef __attribute__((ext_vector_type(8))) __bf16 zn_bf16x8p;
 
@@ -728,5 +729,44 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(PrefillAttnArgs 
     u32x4 ov;
     ov.x = pack2(o[0], o[1]); ov.y = pack2(o[2], o[3]); ov.z = pack2(o[4], o[5]); ov.w = pack2(o[6], o[7]);
     *(u32x4*)(a.out + ((size_t)r * a.S + s) * a.ldo + (size_t)(kvh * G + g) * HD + 8 * pc) = ov;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ ragged prefill rows, assembled on the device
+// hidden[r] = [cond_r[:L_b] ‖ embed(delayed_b[:, 0 : P_b + 1]) ‖ zeros] for the R rows of a call whose B utterances (b = r mod B) bring
+// conditionings and audio prefixes of their own lengths; row_len[r] = L_b + P_b + 1.  One workgroup per (position, row): a conditioning
+// position is a 16-byte copy, an audio position is embed_kernel's body (codes clamped into the table, all table rows requested before the
+// first add, sequential bf16 adds: the bits of zn_op_embed), a pad position is zeroed.  Lengths are clamped into the buffers they index.
+struct AssembleArgs {
+  const bf16_t* cond;           // [R][L_c][d] right-padded conditioning
+  const int* cond_len;          // [B] valid conditioning positions
+  const int* codes;             // [B][n_q][t_total] delayed codes
+  const int* prefix_len;        // [B] audio prefix frames
+  bf16_t* hidden;               // [R][S][d]
+  int* row_len;                 // [R]
+  int L_c, t_total, S, batch;
+  EmbedArgs em;                 // tables, n_q, d, vocab_embed (codes / col / out / batch / dup are set per workgroup)
+};
+__global__ __launch_bounds__(256) void assemble_prefill_kernel(AssembleArgs a) {
+  const int pos = blockIdx.x, r = blockIdx.y, b = r % a.batch, d = a.em.d;
+  const int L = max(0, min(a.cond_len[b], a.L_c)), P = max(0, min(a.prefix_len[b], a.t_total - 1));
+  if (pos == 0 && threadIdx.x == 0) a.row_len[r] = L + P + 1;
+  bf16_t* out = a.hidden + ((size_t)r * a.S + pos) * d;
+  if (pos < L) {
+    const bf16_t* src = a.cond + ((size_t)r * a.L_c + pos) * d;
+    for (int k = threadIdx.x * 8; k < d; k += 256 * 8) *(u32x4*)(out + k) = ld16(src + k);
+  } else if (pos <= L + P) {
+    const int col = pos - L;
+    int code[ZN_EMBED_MAXQ];
+#pragma unroll
+    for (int i = 0; i < ZN_EMBED_MAXQ; ++i) {
+      const int c = a.codes[((size_t)b * a.em.n_q + min(i, a.em.n_q - 1)) * a.t_total + col];
+      code[i] = c < 0 ? 0 : (c >= a.em.vocab_embed ? a.em.vocab_embed - 1 : c);
+    }
+    EmbedArgs e = a.em;
+    e.out = out; e.dup = 0;
+    embed_row(e, 0, code);
+  } else {
+    for (int k = threadIdx.x * 8; k < d; k += 256 * 8) *(u32x4*)(out + k) = u32x4{0u, 0u, 0u, 0u};
   }
 }

@@ -119,8 +119,9 @@ class GenRequest:
 MAX_BATCH_REQUESTS = 64       # utterances of one generate_batch() call: the batch the sampler tail's tables are sized for (ZN_TAIL_MAXB)
 
 
-def check_requests(requests: Sequence[GenRequest], nq: int, d_model: int) -> tuple[bool, int]:
-    """What `generate_batch` refuses before any launch (ValueError); returns (guided, audio prefix length) of the call."""
+def check_requests(requests: Sequence[GenRequest], nq: int, d_model: int, ragged_prefix: bool = False) -> tuple[bool, int | list[int]]:
+    """What `generate_batch` refuses before any launch (ValueError); returns (guided, audio prefix length) of the call.  With `ragged_prefix`
+    the requests may bring audio prefixes of different lengths, and the second value is the list of their lengths (0 for None)."""
     n = len(requests)
     if n == 0:
         raise ValueError("generate_batch: no requests")
@@ -130,8 +131,9 @@ def check_requests(requests: Sequence[GenRequest], nq: int, d_model: int) -> tup
     if len(guided) > 1:
         raise ValueError("generate_batch: requests with cfg_scale == 1 and with guidance cannot share a call (the batch's row layout "
                          f"differs): cfg_scale = {[float(r.cfg_scale) for r in requests]}")
-    prefixes = {0 if r.audio_prefix_codes is None else int(r.audio_prefix_codes.shape[-1]) for r in requests}
-    if len(prefixes) > 1:
+    prefix_lens = [0 if r.audio_prefix_codes is None else int(r.audio_prefix_codes.shape[-1]) for r in requests]
+    prefixes = set(prefix_lens)
+    if len(prefixes) > 1 and not ragged_prefix:
         raise ValueError(f"generate_batch: audio prefixes of different lengths {sorted(prefixes)} in one call are not supported "
                          "(the audio prefix length is shared by the batch)")
     halves = 2 if guided.pop() else 1
@@ -146,7 +148,7 @@ def check_requests(requests: Sequence[GenRequest], nq: int, d_model: int) -> tup
         if a is not None and (a.dim() != 3 or a.shape[0] != 1 or a.shape[1] != nq):
             raise ValueError(f"generate_batch: request {i}: audio_prefix_codes of shape {tuple(a.shape)}, expected [1, {nq}, P]")
         _sampling_struct(r.sampling_params, 0)             # unknown sampling keys: TypeError, as in generate()
-    return halves == 2, prefixes.pop()
+    return halves == 2, (prefix_lens if ragged_prefix else prefixes.pop())
 
 
 def _drain(gen):
@@ -383,7 +385,7 @@ class Zonos(nn.Module):
         return n
 
     @torch.inference_mode()
-    def generate_batch(self, requests: Sequence[GenRequest], _trace: dict | None = None) -> list[torch.Tensor]:
+    def generate_batch(self, requests: Sequence[GenRequest], ragged_prefix: bool = False, _trace: dict | None = None) -> list[torch.Tensor]:
         """One generation for several requests, each with its own sampling parameters, seed, cfg_scale and max_new_tokens (and its own
         prompt length); returns, per request, int64 [1, 9, T_b] as `generate()` returns it, cut and finalised for that request alone.
 
@@ -392,10 +394,18 @@ class Zonos(nn.Module):
         sampled with the random stream of a one-utterance `generate(seed=seed_b)`, whatever slot it takes; its codes are
         its row's first prefix + max_new_tokens_b + 9 delayed columns, finalised at `row_end_offset`.  ValueError, before any launch: an
         empty list, more than MAX_BATCH_REQUESTS requests, guided and cfg_scale == 1 requests together, audio prefixes of different
-        lengths.  A single request is `generate()` with its arguments."""
+        lengths.  A single request is `generate()` with its arguments.
+
+        `ragged_prefix=True` lifts the last refusal: request b continues its own `audio_prefix_codes` of P_b frames (None: 0) and gets the
+        codes it would get in a call whose requests all bring P_b frames.  Row b of the code buffer is left-aligned: its
+        prefix, its max_new_tokens_b unknown cells, then the mask token; the device shifts the row's column by P_b - max_b P_b
+        (zn_gen_set_prefix_rows), and the right-padded prefill rows are assembled by one kernel (zn_op_assemble_prefill)."""
         reqs = list(requests)
         nq = self.config.codebook_dimension
-        guided, P = check_requests(reqs, nq, self.config.backbone.d_model)
+        guided, P = check_requests(reqs, nq, self.config.backbone.d_model, ragged_prefix)
+        prefix_lens = None
+        if ragged_prefix:
+            prefix_lens, P = P, max(P)
         if len(reqs) == 1:
             r = reqs[0]
             return [self.generate(r.conditioning, r.audio_prefix_codes, int(r.max_new_tokens), r.cfg_scale, 1, r.sampling_params, seed=r.seed,
@@ -403,7 +413,10 @@ class Zonos(nn.Module):
         B, dev = len(reqs), self.device
         cond, lengths = pad_conditionings([r.conditioning.to(dev) for r in reqs], 2.0 if guided else 1.0)
         self._check_rows(cond, 2.0 if guided else 1.0, B, lengths)
-        prefix = None if P == 0 else torch.cat([r.audio_prefix_codes.to(dev) for r in reqs], 0)
+        if prefix_lens is not None:
+            prefix = [r.audio_prefix_codes for r in reqs]          # per request, None or [1, nq, P_b]
+        else:
+            prefix = None if P == 0 else torch.cat([r.audio_prefix_codes.to(dev) for r in reqs], 0)
         table = (_lib.zn_row_params * B)()
         for b, r in enumerate(reqs):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if r.seed is None else r.seed
@@ -415,7 +428,7 @@ class Zonos(nn.Module):
             with torch.cuda.device(dev):
                 # zn_gen_begin's own cfg_scale and sampling parameters only fix the row layout: every sampler reads the table
                 run = lambda: _drain(self._generation(eng, cond, prefix, max_new, 2.0 if guided else 1.0, B, reqs[0].sampling_params, None, 0, _trace,
-                                                      torch.cuda.current_stream(dev), None, lengths, table))
+                                                      torch.cuda.current_stream(dev), None, lengths, table, prefix_lens))
                 outs = self._with_timeout_policy(run, caller_saw_frames=_trace is not None)
             return [o.to(dev) for o in outs]
         finally:
@@ -527,26 +540,37 @@ class Zonos(nn.Module):
                                        seed, _trace, torch.cuda.current_stream(self.device), None, cond_lengths)).to(self.device)
 
     def _generation(self, eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params, callback, seed,
-                    _trace, ts, chunk, cond_lengths=None, row_table=None):
+                    _trace, ts, chunk, cond_lengths=None, row_table=None, prefix_lens=None):
         """One generation on `eng` (its lock held by the caller), with every launch on torch stream `ts`.  A generator: with `chunk` it yields
         (delayed codes, last column written) every `chunk` decode steps (Zonos.stream), and it returns the final codes on the host.  With
-        `row_table` (zn_row_params per utterance, generate_batch) it returns one tensor per utterance."""
+        `row_table` (zn_row_params per utterance, generate_batch) it returns one tensor per utterance.  With `prefix_lens` (generate_batch's
+        ragged_prefix; needs `row_table` and `cond_lengths`) `audio_prefix_codes` is a list of per-utterance prefixes (None or [1, nq, P_b])."""
         dev = self.device
         B, nq = batch_size, self.config.codebook_dimension
         R = prefix_conditioning.shape[0]                          # 2B with guidance, B when cfg_scale == 1 (checked by generate)
-        P = 0 if audio_prefix_codes is None else audio_prefix_codes.shape[2]
-        L_c = prefix_conditioning.shape[1] if cond_lengths is None else max(cond_lengths)      # the KV capacity follows the longest VALID row
+        if prefix_lens is not None:
+            P = max(prefix_lens)
+            # every row runs every step of the call: the KV capacity follows the longest prefilled row plus the call's steps
+            L_c = max(L + p for L, p in zip(cond_lengths, prefix_lens)) - P
+        else:
+            P = 0 if audio_prefix_codes is None else audio_prefix_codes.shape[2]
+            L_c = prefix_conditioning.shape[1] if cond_lengths is None else max(cond_lengths)      # the KV capacity follows the longest VALID row
         audio_len = P + max_new_tokens
         seq_len = L_c + audio_len + nq
         ip = self.setup_cache(batch_size=R, max_seqlen=seq_len)
         codes = torch.full((B, nq, audio_len), -1, dtype=torch.int32, device=dev)
-        if audio_prefix_codes is not None:
+        if prefix_lens is not None:
+            # row b is left-aligned in its own buffer row: its P_b prefix frames, its unknown cells (below), the mask token up to the width
+            for b, a in enumerate(audio_prefix_codes):
+                if prefix_lens[b]:
+                    codes[b, :, :prefix_lens[b]] = a[0].to(device=dev, dtype=torch.int32)
+        elif audio_prefix_codes is not None:
             codes[..., :P] = audio_prefix_codes.to(device=dev, dtype=torch.int32)
         if row_table is not None:
             # a row's cells beyond its own budget hold the mask token, as the delay pattern of a generation of that length leaves them:
             # they are never written, and the steps that run past the row's end embed what its own generation would have embedded
             for b in range(B):
-                codes[b, :, P + int(row_table[b].max_new_tokens):] = self.masked_token_id
+                codes[b, :, (P if prefix_lens is None else prefix_lens[b]) + int(row_table[b].max_new_tokens):] = self.masked_token_id
         delayed = apply_delay_pattern(codes, self.masked_token_id).contiguous()       # [B, nq, audio_len + nq]
         t_total = delayed.shape[2]
         offset = P + 1
@@ -558,31 +582,62 @@ class Zonos(nn.Module):
         try:
             if row_table is not None:
                 eng.call("zn_gen_set_rows", row_table, B)
-            offset = yield from self._decode_loop(eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk, cond_lengths)
+            if prefix_lens is not None:
+                eng.call("zn_gen_set_prefix_rows", (C.c_int32 * B)(*prefix_lens), B)
+            offset = yield from self._decode_loop(eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk, cond_lengths,
+                                                  prefix_lens)
         finally:
             # the device's persistent-kernel tenancy goes back once this generation's kernels have drained (include/zonos_hip.h)
             ts.synchronize()
             eng.call("zn_gen_end")
         if row_table is not None:
-            return self._finalise_rows(delayed.cpu(), row_table, P, B, nq)       # the same one device->host copy
+            return self._finalise_rows(delayed.cpu(), row_table, P if prefix_lens is None else prefix_lens, B, nq)       # the same one device->host copy
         out = revert_delay_pattern(delayed.to(torch.int64)).cpu()     # one device->host copy (model.py:511)
         return finalise_codes(out, offset, nq, self.eos_token_id)
 
-    def _finalise_rows(self, delayed: torch.Tensor, row_table, P: int, B: int, nq: int) -> list[torch.Tensor]:
-        """generate_batch's results from the call's delayed codes (host): row b keeps its own P + max_new_tokens_b + nq columns and is
-        finalised at the column its own loop would have ended at (`row_end_offset`, from its first codebook-0 EOS)."""
-        outs, offset0 = [], P + 1
+    def _finalise_rows(self, delayed: torch.Tensor, row_table, P: int | Sequence[int], B: int, nq: int) -> list[torch.Tensor]:
+        """generate_batch's results from the call's delayed codes (host): row b keeps its own P_b + max_new_tokens_b + nq columns and is
+        finalised at the column its own loop would have ended at (`row_end_offset`, from its first codebook-0 EOS).  `P`: the call's audio
+        prefix length, or one per row (ragged_prefix: a row's step index does not depend on its prefix, only its columns do)."""
+        outs = []
         for b in range(B):
-            t_b = P + int(row_table[b].max_new_tokens) + nq
+            P_b = P if isinstance(P, int) else int(P[b])
+            offset0 = P_b + 1
+            t_b = P_b + int(row_table[b].max_new_tokens) + nq
             row = delayed[b:b + 1, :, :t_b].to(torch.int64)
             hit = (row[0, 0, offset0 + 1:] == self.eos_token_id).nonzero()
             eos_column = offset0 + 1 + int(hit[0, 0]) if len(hit) else None
             outs.append(finalise_codes(revert_delay_pattern(row), row_end_offset(offset0, t_b, B, nq, eos_column), nq, self.eos_token_id))
         return outs
 
-    def _decode_loop(self, eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk=None, cond_lengths=None):
+    def _decode_loop(self, eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk=None, cond_lengths=None,
+                     prefix_lens=None):
         """Prefill, first frame and the hot loop (model.py:421-509); a generator that returns the final column offset.  With `chunk`, the
         steps are enqueued at least every `chunk` steps and it yields (delayed, column offset written last) there."""
+        if prefix_lens is not None:
+            S = self._prefill_ragged(eng, delayed, prefix_conditioning, t_total, B, st, cond_lengths, prefix_lens)
+        else:
+            S = self._prefill_shared(eng, delayed, prefix_conditioning, offset, B, st, cond_lengths)
+        return (yield from self._loop_after_prefill(eng, ip, delayed, S, offset, t_total, B, nq, callback, _trace, st, chunk))
+
+    def _prefill_ragged(self, eng, delayed, prefix_conditioning, t_total, B, st, cond_lengths, prefix_lens) -> int:
+        """generate_batch(ragged_prefix=True): row r = [cond_r[:L_b] ‖ embed(delayed_b[:, :P_b + 1]) ‖ zeros], b = r mod B, built for all rows
+        by one kernel (zn_op_assemble_prefill); returns S, the longest row."""
+        dev = self.device
+        cond = prefix_conditioning.to(device=dev, dtype=torch.bfloat16).contiguous()
+        R, L_c, d = cond.shape
+        row_lens = [cond_lengths[r % B] + prefix_lens[r % B] + 1 for r in range(R)]
+        S = max(row_lens)
+        meta = torch.tensor([list(cond_lengths), list(prefix_lens)], dtype=torch.int32).to(dev)      # one host->device copy for both arrays
+        hidden = torch.empty(R, S, d, dtype=torch.bfloat16, device=dev)
+        row_len_dev = torch.empty(R, dtype=torch.int32, device=dev)
+        eng.call("zn_op_assemble_prefill", cond.data_ptr(), L_c, meta[0].data_ptr(), delayed.data_ptr(), t_total, meta[1].data_ptr(), B, R,
+                 hidden.data_ptr(), S, row_len_dev.data_ptr(), st)
+        eng.call("zn_prefill_rows", hidden.data_ptr(), S, (C.c_int32 * R)(*row_lens), st)
+        return S
+
+    def _prefill_shared(self, eng, delayed, prefix_conditioning, offset, B, st, cond_lengths) -> int:
+        """The prefill of a call whose utterances share one audio prefix length; returns S, the longest row."""
         dev = self.device
         # prefill (generation_utils.py:236-244): [cond ‖ uncond] conditioning + embed(delayed[..., :P+1]) for both halves; without
         # guidance the B conditional rows and the embedding once (generation_utils.py:237)
@@ -606,6 +661,10 @@ class Zonos(nn.Module):
             hidden = hidden[:, :S].contiguous()
             row_len = (C.c_int32 * hidden.shape[0])(*[cond_lengths[r % B] + E for r in range(hidden.shape[0])])
             eng.call("zn_prefill_rows", hidden.data_ptr(), S, row_len, st)
+        return S
+
+    def _loop_after_prefill(self, eng, ip, delayed, S, offset, t_total, B, nq, callback, _trace, st, chunk):
+        """First frame and the hot loop (model.py:423-509), the prefill of S positions done."""
         eng.call("zn_sample_first", st)
         ip.seqlen_offset += S
         if _trace is not None:
