@@ -704,9 +704,19 @@ static int launch_chain(zn_handle h, int li, const std::vector<const void*>& kv_
 //   variant 3  <4, 2, 13, 7, 8, 12>  9 .. 12 blocks  (up to 6144 keys); longer contexts take the per-block path
 // One row (step_r1_kernel, cfg_scale == 1) uses the same three instantiations with Hkv * NBK attention workgroups: the streaming workgroups
 // grow from 256 - 8 NBK to 256 - 4 NBK, and their fullest share of every matrix never exceeds the two-row launch's.
+// The T_* are tiles per compute wave, so they follow ZN_SK_CW.  With 208 / 192 / 160 streaming workgroups the fullest workgroup has 5 / 6 / 7 row pairs
+// of out_proj (four K-quarter tiles each in fc2), 40 / 44 / 52 rows of fc1, 8 / 8 / 10 row pairs of in_proj and 23 / 25 / 29 of the heads; six compute
+// waves (-DZN_SK_CW=6) cover them with
+//   variant 1  <4, 1, 7, 4, 4, 6>    variant 2  <4, 1, 8, 4, 5, 8>    variant 3  <4, 2, 9, 5, 5, 12>
+#if ZN_SK_CW == 6
+#define ZN_SK_T1 4, 1, 7, 4, 4, 6
+#define ZN_SK_T2 4, 1, 8, 4, 5, 8
+#define ZN_SK_T3 4, 2, 9, 5, 5, 12
+#else
 #define ZN_SK_T1 4, 2, 10, 5, 6, 6
 #define ZN_SK_T2 4, 2, 11, 6, 7, 8
 #define ZN_SK_T3 4, 2, 13, 7, 8, 12
+#endif
 static int stack_variant_of(int mode) { return mode <= 6 ? 1 : mode <= 8 ? 2 : 3; }
 template <int R, int NCH, int T_OUT, int T_FC1, int T_FC2, int T_IN, int NBV>
 static bool stack_variant_ok(zn_handle h, int natt) {
@@ -716,8 +726,8 @@ static bool stack_variant_ok(zn_handle h, int natt) {
   auto most = [&](int units) { return (units + nsw - 1) / nsw; };                     // units of the fullest streaming workgroup
   const int nqkv = (c.n_heads + 2 * c.n_heads_kv) * h->hd;
   const int p_out = most(c.d_model / 2), p_fc1 = 2 * most(c.d_ff / 2), p_qkv = most((nqkv + 1) / 2), p_hd = most((c.n_codebooks * c.vocab_head + 1) / 2);
-  if (p_out > ZN_SK_CW * T_OUT || p_out > T_FC2 || p_fc1 > ZN_SK_CW * T_FC1 || p_qkv > ZN_SK_CW * T_IN || p_hd > ZN_SK_CW * T_IN) return false;   // the static schedule
-  if (p_qkv > 10) return false;                                                                                                   // the pre-block: five row pairs per helper wave
+  if (p_out > ZN_SK_CW * T_OUT || 4 * p_out > ZN_SK_CW * T_FC2 || p_fc1 > ZN_SK_CW * T_FC1 || p_qkv > ZN_SK_CW * T_IN || p_hd > ZN_SK_CW * T_IN) return false;   // the static schedule
+  if (p_qkv > 10) return false;                                                                                                   // the pre-block: five row pairs per helper wave, or two per compute wave when there are six
   if (p_out * 2 > 64 || p_out * 4 > 64 || p_fc1 > 64 || p_qkv * 2 > 64 || p_hd * 2 > 64 || nqkv % 2) return false;              // one epilogue lane per (unit, row); s_res slots
   // every workgroup of the grid must be resident at once (the hand-offs wait on all of them): one per CU by its LDS, no scratch
   const void* fn = R == 1 ? (const void*)step_r1_kernel<NCH, T_OUT, T_FC1, T_FC2, T_IN, NBV> : (const void*)step_kernel<NCH, T_OUT, T_FC1, T_FC2, T_IN, NBV>;

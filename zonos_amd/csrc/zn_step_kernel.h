@@ -12,6 +12,10 @@
 //    ZN_SK_PARK tiles of the block through its register buffers into LDS ("parked" tiles, 128 KB per CU) and leaves ZN_SK_NBUF more
 //    in flight in registers - 7 of its ~17 tiles (~50 MB chip-wide, ~40 % of the block's weights) are on chip before op 0's input
 //    exists.  (_torch.py:307-328)
+//    The compute-wave count is ZN_SK_CW.  With -DZN_SK_CW=6 the two communication waves are waves 6, 7 and there are no idle waves: each
+//    compute wave parks 2 tiles (96 KB per CU) and keeps 3 in flight (240 KB on chip before op 0), the pre-block's row pairs and the
+//    block's LayerNorm parameters are the compute waves' work, and fc2's input (four K quarters, six waves) reaches them through LDS
+//    behind one more workgroup barrier.  Which wave contracts a tile does not enter its arithmetic: the results are the same bits.
 //
 // Hand-offs are chain_kernel's tagged granules (tag = epoch + block).  Reuse of a granule buffer block after block is safe
 // because every streaming workgroup publishes in every op 0-3 and every sweep covers the whole vector: a workgroup can publish
@@ -32,12 +36,16 @@
 #include "zn_step_sched.h"
 
 #define ZN_SK_THREADS 512
-#define ZN_SK_CW 4                                          // compute waves of a streaming workgroup (waves 4, 5: communication; 6, 7: idle)
+#ifndef ZN_SK_CW
+#define ZN_SK_CW 6                                          // compute waves of a streaming workgroup: 6 (waves 6, 7: communication; no helper waves: the compute waves stage the
+#endif                                                      // LayerNorm parameters and contract the pre-block) or 4 (waves 4, 5: communication; 6, 7: helpers).  Alternated on one device,
+                                                            // ms per step at 300 / 600 / 1600 / 3800 keys (profiles/step_waves_ctxsweep.txt): 4: .830 .848 .871 .979; 6: .802 .836 .840 .937
+#define ZN_SK_HELPERS (8 - (ZN_SK_CW + 2))                  // waves behind the two communication waves
 #ifndef ZN_SK_NBUF
 #define ZN_SK_NBUF 3                                        // register tile buffers per compute wave
 #endif
 #ifndef ZN_SK_PARK
-#define ZN_SK_PARK 4                                        // tiles per compute wave parked in LDS during the attention (>= T_OUT); 3: 0.8743 vs 0.8694 ms per step
+#define ZN_SK_PARK (ZN_SK_CW == 4 ? 4 : 2)                                      // tiles per compute wave parked in LDS during the attention (>= T_OUT); 3: 0.8743 vs 0.8694 ms per step
 #endif
 #ifndef ZN_SK_HELP
 #define ZN_SK_HELP 0                                        // tiles per compute wave that a helper wave (6, 7) holds in ITS registers during the attention and
@@ -58,7 +66,11 @@
 #endif                                                      // (two sweep passes in flight per wave, a new one every half round trip: 0.891 vs 0.869 ms per step - more polling loads the fabric).
                                                             // With the key-block attention role, ms per step at contexts 300 / 600 / 1600 / 3800 (profiles/r04_sweep_delay.txt): 20: .852 .879
                                                             // .902 .976; 24: .844 .866 .886 .973; 28: .834 .853 .868 .975; 32: .835 .852 .867 .980; 40: .834 .856 .875 .990; 48: .834 .862 .881 1.001
-#define ZN_SK_DYN_LDS (ZN_SK_CW * ZN_SK_PARK * 8192)        // parked tiles (streaming role) / StepKbLds (attention role)
+#define ZN_SK_DYN_LDS (ZN_SK_CW * ZN_SK_PARK * 8192)        // parked tiles (streaming role; with 6 compute waves also fc2's input while op 3 runs) / StepKbLds (attention role).
+static_assert(ZN_SK_CW == 4 || ZN_SK_CW == 6, "4 compute waves + 2 helper waves, or 6 compute waves");
+// With 6 compute waves 2 parked tiles per wave are 96 KB; 3 would be 144 KB, which beside the streaming role's 26 KB of static LDS (s_act, s_res, s_ln) exceeds the CU's 160 KB.
+static_assert(ZN_SK_DYN_LDS + 26 * 1024 <= 160 * 1024, "parked tiles + the streaming role's static LDS fit a CU");
+static_assert(ZN_SK_CW == 4 || ZN_SK_DYN_LDS >= 2 * 4 * 2048 * 2, "fc2's input [2][4 d_model] is staged in the parked tiles' LDS");
 #ifndef ZN_SK_APOLL
 #define ZN_SK_APOLL 1                                       // sweep passes an attention workgroup keeps in flight while it waits for a hand-off.  Its CU streams nothing, and
 #endif                                                      // still: 2 / 3 passes in flight cost 0.914 / 0.940 ms per step at 600 keys against 0.861 with one (polling loads the fabric)
@@ -486,14 +498,17 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
   int n_qkv, s_qkv, n_hd, s_hd;
   split((a.nqkv + 1) / 2, n_qkv, s_qkv);
   split((a.heads_rows + 1) / 2, n_hd, s_hd);
-  constexpr int NBAR = 14;                                    // workgroup barriers per block (every wave of a streaming workgroup runs them all)
+  constexpr bool MLDS = CW != 4;                              // fc2's input reaches the compute waves through LDS (below, op 3) instead of each wave sweeping its own K quarter
+  constexpr int NBAR = 14 + (MLDS ? 1 : 0);                   // workgroup barriers per block (every wave of a streaming workgroup runs them all)
   // ---- pre-block (a.pre_W): LayerNorm + in_proj + RoPE + KV append of block 0 from the step's embedding, by the waves that have nothing to
   // do at the start of a launch - the two communication waves normalise a row each, the two helper waves hold the workgroup's <= 10 weight
   // row pairs (requested at kernel entry) and contract them, communication wave 0 runs the epilogue and publishes q | k | v under tag0 - while
   // the compute waves park block 0's tiles as in every block.  The four waves meet through two counters in LDS, not through workgroup
   // barriers (the compute waves would have to join those).  Same arithmetic as gemv_kernel<PRO_LN, EPI_ROPE_KV> / the op-4 path of a block.
-  __shared__ int s_pf[2];                                                   // [0] rows normalised (R), [1] helper waves done (2)
-  constexpr int NPT = 5;                                                    // pre-block row pairs per helper wave (host-checked: <= 10 per workgroup)
+  // With 6 compute waves there are no helper waves: the compute waves take the row pairs (two each) and contract them before they park block 0's tiles.
+  __shared__ int s_pf[2];                                                   // [0] rows normalised (R), [1] contracting waves done (NPW)
+  constexpr int NPW = ZN_SK_HELPERS > 0 ? ZN_SK_HELPERS : CW;               // waves that contract the pre-block
+  constexpr int NPT = (10 + NPW - 1) / NPW;                                 // pre-block row pairs per such wave (host-checked: <= 10 per workgroup)
   const bool pre = a.pre_W != nullptr;
   if (tid < 2) s_pf[tid] = 0;
   __syncthreads();
@@ -509,6 +524,7 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
   constexpr int L_F2 = SC::L_F2;                              // first load of fc2
   constexpr int NH = ZN_SK_HELP;
   static_assert(NH >= 0 && NH <= T_OUT && NH < T_FC1 - (P - T_OUT), "helper tiles take the slots of op 0's tiles");
+  static_assert(NH == 0 || ZN_SK_HELPERS == 2, "helper tiles need the two helper waves");
   constexpr int NREG = SC::NREG;
   auto slot_of_load = [](int l) constexpr { return SC::slot_of_load(l); };
   struct WT { u32x4 a[NCH], b[NCH]; };
@@ -516,8 +532,8 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
   struct LW { const bf16_t *out, *fc1, *fc2, *in; };           // the block's weight matrices, read from the layer table ONCE per block (SGPRs)
   auto tile_of = [&](const LW& Lr, int rows_in, int n_in, int s_in, int s, int w, bool& ok, const bf16_t*& pa, const bf16_t*& pb, int& ridx) {
     const int op = op_of(s), t = s - first_of(op);
-    if (op == 3) {
-      const int qt = w, j = t;
+    if (op == 3) {                                             // fc2: (row pair j, K quarter qt) in turn over the compute waves; with 4 of them wave w keeps quarter w
+      const int i = w + CW * t, qt = i & 3, j = i >> 2;
       ok = j < n_out;
       const int u = s_out + (ok ? j : 0);
       pa = Lr.fc2 + (size_t)(2 * u) * (4 * D) + qt * D + lane * 8;
@@ -537,49 +553,52 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
   };
   auto park_of = [&](int w) { return reinterpret_cast<u32x4*>(zn_dyn_lds) + (size_t)w * (P * 2 * NCH * 64) + lane; };
 
-  if (wave >= CW + 2) {
+  // the pre-block's contraction by wave pw of the NPW that share it
+  auto pre_contract = [&](int pw) {
+    WT pt[NPT];
+#pragma unroll
+    for (int t = 0; t < NPT; ++t) {
+      const int j = pw + NPW * t;
+      if (j < n_qkv) {                                      // wave-uniform
+        const int u = s_qkv + j;
+        const bf16_t* pa = a.pre_W + (size_t)(2 * u) * D + lane * 8;
+        const bf16_t* pb = (2 * u + 1 < a.nqkv) ? pa + D : pa;
+#pragma unroll
+        for (int c2 = 0; c2 < NCH; ++c2) { pt[t].a[c2] = ld_nt16(pa + c2 * 512); pt[t].b[c2] = ld_nt16(pb + c2 * 512); }
+      }
+    }
+    while (__hip_atomic_load(&s_pf[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < R) __builtin_amdgcn_s_sleep(1);
+    u32x4 xr[NCH][R];
+#pragma unroll
+    for (int c2 = 0; c2 < NCH; ++c2)
+#pragma unroll
+      for (int r = 0; r < R; ++r) xr[c2][r] = *(const u32x4*)&s_act[r * D + (c2 * 64 + lane) * 8];
+#pragma unroll
+    for (int t = 0; t < NPT; ++t) {
+      const int j = pw + NPW * t;
+      if (j < n_qkv) {
+        float accA[R] = {}, accB[R] = {};
+#pragma unroll
+        for (int c2 = 0; c2 < NCH; ++c2) {
+#pragma unroll
+          for (int r = 0; r < R; ++r) { accA[r] = dot8(pt[t].a[c2], xr[c2][r], accA[r]); accB[r] = dot8(pt[t].b[c2], xr[c2][r], accB[r]); }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) { accA[r] = wave_sum(accA[r]); accB[r] = wave_sum(accB[r]); }
+        if (lane == 0) {
+#pragma unroll
+          for (int r = 0; r < R; ++r) { s_res[0][j][0][r] = accA[r]; s_res[0][j][1][r] = accB[r]; }
+        }
+      }
+    }
+    if (lane == 0) __hip_atomic_fetch_add(&s_pf[1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  };
+
+  if (ZN_SK_HELPERS > 0 && wave >= CW + 2) {
     // ------------------------------------------------------------------------------------ helper waves
     const int hw = wave - (CW + 2);                           // serves compute waves 2 hw and 2 hw + 1
     WT hb[2 * (NH > 0 ? NH : 1)];
-    if (pre) {
-      WT pt[NPT];
-#pragma unroll
-      for (int t = 0; t < NPT; ++t) {
-        const int j = hw + 2 * t;
-        if (j < n_qkv) {                                      // wave-uniform
-          const int u = s_qkv + j;
-          const bf16_t* pa = a.pre_W + (size_t)(2 * u) * D + lane * 8;
-          const bf16_t* pb = (2 * u + 1 < a.nqkv) ? pa + D : pa;
-#pragma unroll
-          for (int c2 = 0; c2 < NCH; ++c2) { pt[t].a[c2] = ld_nt16(pa + c2 * 512); pt[t].b[c2] = ld_nt16(pb + c2 * 512); }
-        }
-      }
-      while (__hip_atomic_load(&s_pf[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < R) __builtin_amdgcn_s_sleep(1);
-      u32x4 xr[NCH][R];
-#pragma unroll
-      for (int c2 = 0; c2 < NCH; ++c2)
-#pragma unroll
-        for (int r = 0; r < R; ++r) xr[c2][r] = *(const u32x4*)&s_act[r * D + (c2 * 64 + lane) * 8];
-#pragma unroll
-      for (int t = 0; t < NPT; ++t) {
-        const int j = hw + 2 * t;
-        if (j < n_qkv) {
-          float accA[R] = {}, accB[R] = {};
-#pragma unroll
-          for (int c2 = 0; c2 < NCH; ++c2) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) { accA[r] = dot8(pt[t].a[c2], xr[c2][r], accA[r]); accB[r] = dot8(pt[t].b[c2], xr[c2][r], accB[r]); }
-          }
-#pragma unroll
-          for (int r = 0; r < R; ++r) { accA[r] = wave_sum(accA[r]); accB[r] = wave_sum(accB[r]); }
-          if (lane == 0) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) { s_res[0][j][0][r] = accA[r]; s_res[0][j][1][r] = accB[r]; }
-          }
-        }
-      }
-      if (lane == 0) __hip_atomic_fetch_add(&s_pf[1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
+    if (pre) pre_contract(hw);
 #pragma unroll 1
     for (int li = 0; li < a.n_layer; ++li) {
       const LW Lr{a.layers[li].W_out, a.layers[li].W_fc1, a.layers[li].W_fc2, a.layers[li].W_in};
@@ -636,7 +655,7 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
     // ------------------------------------------------------------------------------------ compute waves
     WT bufs[NB];                                           // every index below is a compile-time constant: the buffers live in registers
     u32x4* park = park_of(wave);
-    static_assert(CW == 4, "fc2 splits K over the four compute waves");
+    if constexpr (ZN_SK_HELPERS == 0) { if (pre) pre_contract(wave); }
     const bool st_on = a.stamps && sc == 0 && wave == 0 && lane == 0;
 #pragma unroll 1
     for (int li = 0; li < a.n_layer; ++li) {
@@ -672,10 +691,20 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
         if constexpr (k >= 0 && k < NREG) load_into(std::integral_constant<int, SC::nth_reg(k >= 0 && k < NREG ? k : 0)>{}, std::integral_constant<int, ((k >= 0 ? k : 0) + P) % NB>{});
       };
       u32x4 xr[NCH][R];
+      auto m_lds = [&](int qt) { return reinterpret_cast<u32x4*>(zn_dyn_lds) + (size_t)qt * (NCH * R * 64) + lane; };      // fc2's input, K quarter qt [chunk][row][lane]
       auto process = [&](int s, const WT& w) {
         bool ok; const bf16_t *pa, *pb; int ridx;
         tile(s, ok, pa, pb, ridx);
         if (!ok) return;
+        if constexpr (MLDS) {
+          if (op_of(s) == 3) {                                // this tile's K quarter of fc2's input (ridx = 4 j + quarter)
+            const u32x4* mq = m_lds(ridx & 3);
+#pragma unroll
+            for (int c2 = 0; c2 < NCH; ++c2)
+#pragma unroll
+              for (int r = 0; r < R; ++r) xr[c2][r] = mq[(c2 * R + r) * 64];
+          }
+        }
         float accA[R] = {}, accB[R] = {};
 #pragma unroll
         for (int c2 = 0; c2 < NCH; ++c2) {
@@ -692,11 +721,27 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
       };
       // ---- prefetch while the attention runs: loads 0 .. P-1 through the register buffers into LDS, then the first NB REG loads stay in flight
       cstamp(0);
+      // No helper waves: compute waves 0 .. 3 stage one of the block's four LayerNorm parameter vectors each (the previous block's were last read
+      // before its B(4)), requested ahead of the tiles so that the store below waits for nothing else
+      u32x4 lnp[NCH];
+      if constexpr (ZN_SK_HELPERS == 0) {
+        if (wave < 4) {
+          const bf16_t* lp = wave == 0 ? a.layers[li].ln2_w : wave == 1 ? a.layers[li].ln2_b : wave == 2 ? a.layers[li].lnn_w : a.layers[li].lnn_b;
+#pragma unroll
+          for (int c2 = 0; c2 < NCH; ++c2) lnp[c2] = ld16g(lp + (c2 * 64 + lane) * 8);
+        }
+      }
       zn_static_for<0, NB>([&](auto IC) {
         constexpr int i = decltype(IC)::value;
         if constexpr (i < P) load_into(std::integral_constant<int, i>{}, std::integral_constant<int, i % NB>{});
         else reg_req(std::integral_constant<int, i - P>{});
       });
+      if constexpr (ZN_SK_HELPERS == 0) {
+        if (wave < 4) {
+#pragma unroll
+          for (int c2 = 0; c2 < NCH; ++c2) *(u32x4*)&s_ln[wave * D + (c2 * 64 + lane) * 8] = lnp[c2];
+        }
+      }
       zn_static_for<0, P>([&](auto LC) {
         constexpr int l = decltype(LC)::value;
         bool ok; const bf16_t *pa, *pb; int ridx;
@@ -725,15 +770,23 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
           }
           if constexpr (op == 3) {
             // fc2's input m [2][4 d]: this wave's K quarter straight from the granules (no LDS, no barrier)
-            u32x4 dat[NCH * R];
-            const int mbase = (wave * (D / 2) + lane * 4) * 8;
-            if constexpr (ZN_SK_MSWEEP_DELAY > 0) __builtin_amdgcn_s_sleep(ZN_SK_MSWEEP_DELAY);
-            sweep_granules_at<NCH * R>(zn_rsrc(a.g_m), [&](int i) { return mbase + ((i % R) * (2 * D) + (i / R) * 256) * 8; }, tag, dat, a.tmo, lane,
-                                       SweepWho{(3u << 8) | (unsigned)li, a.diag});
+            // Six compute waves: waves 0 .. 3 sweep a quarter each as above and leave it in the parked tiles' LDS (every parked tile was read
+            // before A(2), the next block's arrive after P(4)); behind B(3) each wave reads the quarter of its tile there (process_fc2).
+            if (!MLDS || wave < 4) {
+              u32x4 dat[NCH * R];
+              const int mbase = (wave * (D / 2) + lane * 4) * 8;
+              if constexpr (ZN_SK_MSWEEP_DELAY > 0) __builtin_amdgcn_s_sleep(ZN_SK_MSWEEP_DELAY);
+              sweep_granules_at<NCH * R>(zn_rsrc(a.g_m), [&](int i) { return mbase + ((i % R) * (2 * D) + (i / R) * 256) * 8; }, tag, dat, a.tmo, lane,
+                                         SweepWho{(3u << 8) | (unsigned)li, a.diag});
 #pragma unroll
-            for (int c2 = 0; c2 < NCH; ++c2)
+              for (int c2 = 0; c2 < NCH; ++c2)
 #pragma unroll
-              for (int r = 0; r < R; ++r) xr[c2][r] = dat[c2 * R + r];
+                for (int r = 0; r < R; ++r) {
+                  if constexpr (MLDS) m_lds(wave)[(c2 * R + r) * 64] = dat[c2 * R + r];
+                  else xr[c2][r] = dat[c2 * R + r];
+                }
+            }
+            if constexpr (MLDS) __syncthreads();              // B(3): fc2's input is in LDS
           } else {
             __syncthreads();                                // B(op): the op's input vector is in LDS
 #pragma unroll
@@ -817,8 +870,8 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
 #pragma unroll
     for (int c2 = 0; c2 < NCH; ++c2) *(u32x4*)&s_act[myr * D + (c2 * 64 + lane) * 8] = g[c2];
     if (lane == 0) __hip_atomic_fetch_add(&s_pf[0], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    // both communication waves wait for the helper waves: s_act and s_res are theirs again only then
-    while (__hip_atomic_load(&s_pf[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < 2) __builtin_amdgcn_s_sleep(1);
+    // both communication waves wait for the contracting waves: s_act and s_res are theirs again only then
+    while (__hip_atomic_load(&s_pf[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < NPW) __builtin_amdgcn_s_sleep(1);
     if (it_qkv) {                                            // EPI_ROPE_KV (gemv_epilogue) of block 0, q | k | v also as granules under tag0
       const int rowA = 2 * u_qkv;
       const float x0 = bfround(s_res[0][ij][0][ir]), x1 = bfround(s_res[0][ij][1][ir]);
@@ -932,7 +985,10 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
 #pragma unroll
           for (int c2 = 0; c2 < NCH; ++c2) *(u32x4*)&s_act[myr * D + (c2 * 64 + lane) * 8] = g[c2];
           __syncthreads();                                 // B(op + 1)
-        } else stamp();
+        } else {
+          if constexpr (MLDS) __syncthreads();               // B(3): the compute waves stage fc2's input
+          stamp();
+        }
         stamp();
       }
     });
