@@ -580,7 +580,8 @@ def dac_decode(dw: dict, codes: torch.Tensor, ratios=(8, 8, 4, 2), collect: dict
         if collect is not None:
             collect[f"block{bi}"] = h
     h = F.conv1d(snake(h, dw["decoder.snake1.alpha"]), dw["decoder.conv2.weight"], dw["decoder.conv2.bias"], padding=3)
-    return torch.tanh(h).float()
+    wav = torch.tanh(h)
+    return wav if wav.dtype == torch.float64 else wav.float()      # (float64 weights: the float64 reference of the pointwise tests)
 
 
 def dac_decode_to_int16(dw: dict, codes: torch.Tensor) -> torch.Tensor:

@@ -8,6 +8,7 @@ import torch
 from oracle import zonos_oracle as zo
 from zonos_amd import synth
 from zonos_amd.autoencoder import DACAutoencoder
+from zonos_amd.testing import DAC_SMALL, DAC_SMALL_CODEBOOK, build_small_dac, dac_oracle_pair, dac_pointwise
 
 pytestmark = pytest.mark.gpu
 RMS_TOL = 1e-4
@@ -148,3 +149,122 @@ def test_clip_beyond_the_32_bit_offsets_takes_the_fp32_kernels(dac):
     tail = ae.decode(codes[..., -200:])
     a, b = long[0, 0, -160 * 512:].cpu().numpy(), tail[0, 0, -160 * 512:].cpu().numpy()
     assert _rms(a, b) <= 1e-5
+
+
+# ------------------------------------------------------------------------------------------------ pointwise bars, small configurations
+# Every case below is held to a single-sample bar against the float64 oracle (zonos_amd.testing.dac_pointwise: max|gpu - oracle64| <=
+# 8 x max|oracle32 - oracle64|), on both kernel families: the three-term kernels (default) and the fp32 kernels (ZONOS_DAC_CONV=fp32 when the
+# handle is created).  Small configurations (zonos_amd.testing.DAC_SMALL) reach what the 44.1 kHz one never does: Cout below a tile,
+# the NT = 2 / 3 / 4 variants and the pad-to-128 branch of the fp32 family, strides 6 and 10, frames of 6 ... 120 rows against 128-row tiles.
+
+FULL_RATIOS = (8, 8, 4, 2)
+FAMILIES = ("three_term", "fp32")
+SMALL_CASES = [(1, 1), (1, 2), (2, 23), (3, 70)]
+POINTWISE_CASES = [(n, b, t) for n in DAC_SMALL for (b, t) in SMALL_CASES] + [("FULL", 1, 24), ("FULL", 2, 40)]
+
+
+class _Handles:
+    """One DACAutoencoder per (configuration, kernel family) and one oracle pair per case, made on first use and shared by the tests below."""
+
+    def __init__(self):
+        self.ae, self.refs = {}, {}
+
+    def get(self, name, family):
+        if (name, family) not in self.ae:
+            if name == "FULL":
+                dw = synth.dac_state_dict(4321, encoder=False)
+                ae, ratios, size = DACAutoencoder(dw, device="cuda:0"), FULL_RATIOS, 1024
+            else:
+                ae, dw, ratios = build_small_dac(name)
+                size = DAC_SMALL_CODEBOOK
+            with pytest.MonkeyPatch.context() as mp:       # zn_dac_create reads the variable: set only around the handle's creation
+                if family == "fp32":
+                    mp.setenv("ZONOS_DAC_CONV", "fp32")
+                else:
+                    mp.delenv("ZONOS_DAC_CONV", raising=False)
+                ae._handle()
+            self.ae[name, family] = (ae, dw, ratios, size)
+        return self.ae[name, family]
+
+    def oracle(self, key, dw, codes, ratios):
+        if key not in self.refs:
+            self.refs[key] = dac_oracle_pair(dw, codes, ratios)
+        return self.refs[key]
+
+
+@pytest.fixture(scope="module")
+def handles():
+    return _Handles()
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("name,B,T", POINTWISE_CASES, ids=[f"{n}-B{b}-T{t}" for n, b, t in POINTWISE_CASES])
+def test_dac_pointwise_vs_float64_oracle(handles, name, B, T, family):
+    ae, dw, ratios, size = handles.get(name, family)
+    codes = torch.from_numpy(synth.randint(31, f"pw.{name}.{B}.{T}", (B, 9, T), size))
+    wav = ae.decode(codes.to("cuda:0")).cpu()
+    hop = int(np.prod(ratios))
+    assert wav.shape == (B, 1, hop * T) and wav.dtype == torch.float32
+    assert bool(torch.isfinite(wav).all()) and float(wav.abs().max()) <= 1.0
+    res = dac_pointwise(wav, dw, codes, ratios, f"{name} {family} B={B} T={T}", refs=handles.oracle((name, B, T), dw, codes, ratios))
+    assert res.ok, res.line(f"{name} {family} B={B} T={T}", hop)
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("name,B,T", [("S2", 3, 70), ("FULL", 4, 40)])
+def test_dac_batch_rows_equal_solo_decodes(handles, name, B, T, family):
+    """Every row of a batch, decoded alone, is that row of the batch bit for bit.  At FULL the solo decode takes the 128-row tile kernel at
+    the last block and the batch the 256-row one (zn_conv3_launch: `big`); an output's accumulation order does not depend on the tile height."""
+    ae, _, ratios, size = handles.get(name, family)
+    codes = torch.from_numpy(synth.randint(37, f"rows.{name}", (B, 9, T), size)).to("cuda:0")
+    batch = ae.decode(codes)
+    assert batch.shape == (B, 1, int(np.prod(ratios)) * T)
+    for b in range(B):
+        solo = ae.decode(codes[b:b + 1])
+        assert torch.equal(solo[0], batch[b]), (name, family, b, (solo[0] - batch[b]).abs().max().item())
+
+
+def _constant_codes(name, B, T, size):
+    col = torch.from_numpy(synth.randint(41, f"period.{name}", (B, 9, 1), size))          # a different column per batch row
+    assert all(not torch.equal(col[0], col[b]) for b in range(1, B))
+    return col.expand(B, 9, T).contiguous()
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("name", ["S1", "S2", "FULL"])
+def test_dac_constant_codes_give_bit_periodic_frames(handles, name, family):
+    """The same code column in every frame: away from the clip's ends every layer's activations are periodic in time with the layer's
+    cumulative stride, and an output element's arithmetic order does not depend on where it sits in a tile (K chunk, then tap, then the six
+    products in dac_conv3_kernel; tap, then channel in dac_final_kernel), so the interior frames of the waveform are bit-identical: a row
+    staged or read wrongly at a tile seam breaks that, with no tolerance involved.  The interior comes from the reference alone: the frames
+    whose float64-oracle output equals the middle frame's within 1e-12 (S1, S2: at least 40 of the 96 frames, required here; FULL: the fixed
+    [12, 36) of 48 frames, B = 4, so that blocks 2 and 3 run the 256-row kernels)."""
+    ae, dw, ratios, size = handles.get(name, family)
+    hop = int(np.prod(ratios))
+    if name == "FULL":
+        B, T, lo, hi = 4, 48, 12, 36
+        codes = _constant_codes(name, B, T, size)
+    else:
+        B, T = 2, 96
+        codes = _constant_codes(name, B, T, size)
+        _, ref64 = handles.oracle((name, "period"), dw, codes, ratios)
+        f = ref64.view(B, T, hop)
+        same = ((f - f[:, T // 2:T // 2 + 1]).abs().amax(dim=(0, 2)) <= 1e-12).tolist()
+        lo = hi = T // 2
+        while lo > 0 and same[lo - 1]:
+            lo -= 1
+        while hi < T and same[hi]:
+            hi += 1
+        print(f"\n[dac periodic {name}] oracle interior frames [{lo}, {hi})")
+        assert hi - lo >= 40, (name, lo, hi)
+    wav = ae.decode(codes.to("cuda:0")).cpu()
+    assert wav.shape == (B, 1, hop * T)
+    frames = wav.view(B, T, hop)
+    want = frames[:, lo:lo + 1].expand(B, hi - lo, hop)
+    if not torch.equal(frames[:, lo:hi], want):
+        bad = (frames[:, lo:hi] != want).nonzero()
+        b, fr, s = (int(v) for v in bad[0])
+        pos = (lo + fr) * hop + s
+        raise AssertionError(f"{name} {family}: {len(bad)} samples of the interior differ from frame {lo}; first at row {b} sample {pos} "
+                             f"(mod 128 = {pos % 128}, mod 256 = {pos % 256}), |d| {float((frames[b, lo + fr, s] - frames[b, lo, s]).abs()):.3g}")
+    assert float(frames[:, lo].abs().max()) > 1e-3         # not a silent waveform

@@ -5,7 +5,7 @@ import torch
 
 from zonos_amd import synth
 from zonos_amd.autoencoder import DACAutoencoder
-from zonos_amd.testing import build_model
+from zonos_amd.testing import DAC_SMALL_CODEBOOK, build_model, build_small_dac
 
 pytestmark = pytest.mark.gpu
 GREEDY = {"temperature": 0.0}
@@ -47,6 +47,36 @@ def test_dac_stream_equals_decode(dac, B, T):
         assert torch.equal(got, ref), (name, T, B, (got - ref).abs().max().item())
         if T >= 40 and name != "all":
             assert sum(p.shape[2] for p in parts[:-1]) > 0, name            # audio before the end
+
+
+@pytest.fixture(scope="module")
+def small_dacs():
+    return {name: build_small_dac(name, device=DEV)[0] for name in ("S1", "S2")}
+
+
+@pytest.mark.parametrize("B", [1, 2])
+@pytest.mark.parametrize("T", [1, 3, 30, 96])
+@pytest.mark.parametrize("name", ["S1", "S2"])
+def test_dac_stream_equals_decode_small_ratios(small_dacs, name, B, T):
+    """The span windows' device side (launch_conv3_win, the ioff / Tin arguments of dac_final_kernel) at ratios (6, 2) and (2, 6, 10): frames
+    of 12 and 120 samples, strides 6 and 10, output channels below a tile."""
+    ae = small_dacs[name]
+    codes = torch.from_numpy(synth.randint(23 + T, f"stream.{name}.codes{B}", (B, 9, T), DAC_SMALL_CODEBOOK)).to(DEV)
+    ref = ae.decode(codes)
+    assert ref.shape == (B, 1, ae.hop * T)
+    for cname, sizes in _chunkings(T).items():
+        st = ae.stream()
+        parts, k = [], 0
+        for n in sizes:
+            parts.append(st.push(codes[..., k:k + n]))
+            k += n
+        parts.append(st.flush())
+        assert all(p.shape[:2] == (B, 1) for p in parts)
+        got = torch.cat(parts, dim=2)
+        assert got.shape == ref.shape, (name, cname, got.shape, ref.shape)
+        assert torch.equal(got, ref), (name, cname, T, B, (got - ref).abs().max().item())
+        if T >= 96 and cname != "all":
+            assert sum(p.shape[2] for p in parts[:-1]) > 0, cname            # audio before the end
 
 
 def _cond(cfg, seed, cfg_scale):
