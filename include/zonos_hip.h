@@ -117,6 +117,15 @@ typedef struct zn_row_params {
   int32_t reserved[2];      /* pads the entry to ZN_ROW_PARAMS_BYTES; set to 0 */
 } zn_row_params;
 
+/* Slotted sessions (additive to ABI 9: new entry points only, no existing layout or call changes) - one request admitted into a slot of a slotted session (zn_gen_admit). */
+typedef struct zn_admit {
+  int32_t slot;             /* 0 .. batch - 1, idle */
+  int32_t row_len;          /* valid positions of the request's prefill rows: L_b + P_b + 1 (conditioning, audio prefix, the column that starts the loop) */
+  int32_t prefix_len;       /* P_b audio prefix frames at the left of the slot's row of the code buffer */
+  int32_t reserved;         /* set to 0 */
+  zn_row_params params;     /* as for zn_gen_set_rows */
+} zn_admit;
+
 /* ---------------------------------------------------------------- lifecycle */
 int zn_abi_version(void);
 /* Replaces Zonos.__init__/from_local weight binding (zonos/model.py:68-86,128-176).  Weights stay owned by the
@@ -178,6 +187,44 @@ int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int32_t n);
  * before.  A generation with a shift never runs the persistent kernels (zn_decode_path_detail reports 0), whose samplers do not read it -
  * two unguided utterances whose lengths advance in lockstep included.  Synchronises the generation's stream. */
 int zn_gen_set_prefix_rows(zn_handle h, const int32_t* prefix_len_host, int32_t n);
+/* A slotted session: requests join the running generation as slots free up.  zn_gen_open_slots turns the generation begun by
+ * zn_gen_begin into a session of `batch` slots, all idle; zn_gen_begin's max_len, t_total (the width W of a row of the code buffer),
+ * cfg_scale (guided or not) and batch fix the KV capacity per row, the code-buffer width, the row layout and the slot count, and its
+ * lengths array must be zero.  `slack` >= 0 is the number of decode steps a request may run beyond its own end (max_new_tokens + n_codebooks
+ * - 1 steps) before the caller retires it; the caller's scheduling cadence decides it (zonos_amd/serving.py: 16 + sched_every).  Legal where
+ * zn_gen_set_rows is (ZN_ERR_STATE otherwise), instead of zn_gen_set_rows / zn_gen_set_prefix_rows / zn_prefill*.  The session's loop is
+ *   zn_gen_admit ... | zn_decode_steps(k) | zn_gen_row_state | zn_gen_retire ... | zn_gen_admit ... | zn_decode_steps(k) | ...
+ * Every slot has its own length (lengths[r]), stop state, parameter entry, column shift and step origin on the device; the rows of an idle slot
+ * keep running through the steps' kernels at length 0 (each step rewrites position 0 of their own cache rows, their lengths do not advance,
+ * their code cells - the caller fills an idle slot's row with anything but -1 - are not written) and nothing they compute reaches another row.
+ * A session never runs the persistent kernels (zn_decode_path_detail reports 0, one and two rows included).  zn_debug_force_eos,
+ * zn_debug_eos_bias and zn_debug_token_override stay call-wide, indexed by the SESSION's step (the decode steps enqueued since zn_gen_begin),
+ * not by a request's own.  zn_decode_steps returns ZN_ERR_STATE when a step would take a busy slot's rows past max_len. */
+int zn_gen_open_slots(zn_handle h, int32_t slack);
+/* Admits n >= 1 requests into idle slots between two zn_decode_steps calls.  hidden bf16 [n * halves, S, d] (halves = 2 in a guided session:
+ * [cond_0..cond_{n-1} ‖ uncond_0..uncond_{n-1}]) is right-padded as for zn_prefill_rows, request j holding a[j].row_len valid positions in
+ * each of its rows.  Before the call the caller has written slot b's row of the code buffer (stream-ordered): P_b prefix frames,
+ * max_new_tokens_b unknown cells (-1), the mask token up to W, under the delay pattern.  The rows are prefilled as ONE batch of n * halves
+ * rows - the launches zn_prefill_rows makes for such a batch - into a scratch cache the handle owns, and one kernel moves them into the
+ * slots' rows.  For every admitted slot b: KV positions [0, row_len) of cache rows b and batch + b (Mamba2: the conv and SSM states of those
+ * rows), lengths = row_len, remaining_steps = max_new_tokens_b + n_codebooks - 1, stopping = 0, the parameter entry, the column shift
+ * (P_b + 1 - the loop's current column: either sign) and the slot's step origin = the session's step.  The slot's first frame is then sampled
+ * as zn_sample_first samples it (draw index 0 of the slot's own seed, no penalty, no logit bias) into column P_b + 1 of its row, and its
+ * logits go to row b of zn_get_step_outputs.  From then on the slot's Gumbel draw at session step t is keyed by (seed_b, 1 + t - origin_b, ...):
+ * the stream of a generation of that request alone.  Nothing of another slot is written: no KV position, length, logit, counter, token or
+ * code cell.
+ * ZN_ERR_ARG: a slot out of range or named twice, a row_len outside 1..S or none equal to S, a prefix_len outside 0 .. row_len - 2, a request
+ * that does not fit (row_len - 1 + max_new_tokens + n_codebooks + slack > max_len, or prefix_len + max_new_tokens + n_codebooks + slack > W),
+ * cfg_scale == 1 in a guided session or the reverse, a repetition_penalty_window outside 0..64.  ZN_ERR_STATE: no session, a busy slot, steps
+ * still owed to zn_all_stopped_end.  ZN_ERR_UNSUPPORTED: the position-by-position prefill (zn_debug_prefill_mode 0).  An error leaves the
+ * session as it was.  The call does not synchronise (it waits for the previous admission's staged arguments to have been consumed). */
+int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const void* hidden_dev, int32_t S, zn_stream stream);
+/* Marks a busy slot idle: its rows' lengths and its remaining_steps become 0 (an idle slot counts as stopped for zn_all_stopped*) on the
+ * session's stream.  ZN_ERR_STATE: no session, or the slot is idle already. */
+int zn_gen_retire(zn_handle h, int32_t slot);
+/* remaining_steps[0 .. batch) and every slot's own step count (session step - step origin; -1 for an idle slot) to HOST arrays (either may be
+ * NULL), as of the steps enqueued so far.  Synchronises the stream; surfaces a hand-off timeout word as zn_all_stopped does. */
+int zn_gen_row_state(zn_handle h, int32_t* remaining_host, int32_t* steps_host, zn_stream stream);
 /* ABI 8 - zn_prefill for utterances of different prompt lengths.  hidden bf16 [R, S, d] is RIGHT-padded: row r holds row_len[r] valid
  * positions (its conditioning followed by the embedded audio prefix), then S - row_len[r] positions of padding whose contents are never
  * visible to a result: no valid query attends a pad key, no pad position reaches a logit, a Mamba2 state or a KV entry that is read

@@ -70,6 +70,11 @@ class zn_row_params(C.Structure):
 ZN_ROW_PARAMS_BYTES = 64
 
 
+class zn_admit(C.Structure):
+    """One request admitted into a slot of a slotted session (zn_gen_admit)."""
+    _fields_ = [("slot", C.c_int32), ("row_len", C.c_int32), ("prefix_len", C.c_int32), ("reserved", C.c_int32), ("params", zn_row_params)]
+
+
 class zn_dac_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_codebooks", "codebook_size", "codebook_dim", "hidden_size", "decoder_hidden_size", "n_ratios")] + \
                [("ratios", C.c_int32 * 8), ("encoder_hidden_size", C.c_int32)]
@@ -93,6 +98,10 @@ SIGNATURES = {
     "zn_prefill_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
     "zn_gen_set_rows": (C.c_int, [C.c_void_p, C.POINTER(zn_row_params), C.c_int32]),
     "zn_gen_set_prefix_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
+    "zn_gen_open_slots": (C.c_int, [C.c_void_p, C.c_int32]),
+    "zn_gen_admit": (C.c_int, [C.c_void_p, C.POINTER(zn_admit), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "zn_gen_retire": (C.c_int, [C.c_void_p, C.c_int32]),
+    "zn_gen_row_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
     "zn_sample_first": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zn_decode_steps": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "zn_graph_active": (C.c_int, [C.c_void_p]),

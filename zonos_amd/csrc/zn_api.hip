@@ -99,9 +99,24 @@ struct zn_handle_s {
   int *remaining = nullptr, *stopping = nullptr;
   zn_row_params* row_tab = nullptr;   // [max_rows] per-utterance settings of this generation (zn_gen_set_rows)
   bool rows_set = false;              // this generation's samplers read row_tab
-  int* prefix_shift = nullptr;        // [max_rows] column shift per utterance of this generation, <= 0 (zn_gen_set_prefix_rows)
+  int* prefix_shift = nullptr;        // [max_rows] column shift per utterance of this generation (zn_gen_set_prefix_rows: <= 0; zn_gen_admit: either sign)
   bool prefix_set = false;            // some shift is not 0: this generation's embedding, sampler and bookkeeping launches read prefix_shift
   bool gen_prefilled = false;         // zn_prefill / zn_prefill_rows has run since zn_gen_begin
+  // slotted session (zn_gen_open_slots): requests join the running generation slot by slot
+  bool slots_open = false;
+  int slot_slack = 0;                 // steps a request may run past its own end before it is retired
+  int* step0 = nullptr;               // [max_rows] device: session step at which slot b's request was admitted, -1 = idle
+  std::vector<int> slot_len;          // [batch] host mirror of a busy slot's lengths[b] (they advance by one per step), 0 = idle
+  std::vector<char> slot_busy;
+  void* adm_cache = nullptr;          // scratch cache of an admission's prefill: n_layer buffers of adm_layer_bytes
+  size_t adm_layer_bytes = 0;
+  int adm_cap_S = 0;                  // positions per row the scratch cache holds (max_rows rows)
+  AdmitLayer* adm_layers = nullptr;   // device table [n_layer] (scratch buffer, session buffer, kind) of admit_rows_kernel
+  std::vector<const void*> adm_caches;
+  char* adm_stage = nullptr;          // pinned: an admission's slots, prefixes, remaining steps, row lengths ([max_rows] ints each) and parameter entries
+  char* adm_dev = nullptr;            // its device copy
+  hipEvent_t adm_event = nullptr;     // the copy of adm_stage has been consumed
+  bool adm_pending = false;
   int* done_host = nullptr;  // pinned: [0..3] synchronous stop check, [4..7] asynchronous one
   hipEvent_t stop_event = nullptr;
   bool stop_pending = false;
@@ -201,9 +216,11 @@ extern "C" int zn_destroy(zn_handle h) {
   if (!h) return ZN_OK;
   (void)zn_tenant_release(h->device, h);
   free_graph(h);
-  void* ptrs[] = {h->emb_tables_dev, h->x, h->q, h->o1, h->mbuf, h->nbuf, h->logits_raw, h->last_logits, h->tok_raw, h->scores, h->cmax, h->pv_part, h->pv_tickets, h->pf_x, h->pf_n, h->pf_qkv, h->pf_a, h->pf_u, h->pf_m, h->pf_res, h->pf_zx, h->pf_xbc, h->pf_y, h->pf_g, h->qkv_tmp, h->fw_lengths, h->row_len, h->st, h->remaining, h->stopping, h->row_tab, h->prefix_shift, h->res, h->hn, h->m_zx, h->m_xbc, h->m_y, h->m_g, h->m_vg, h->g16_part, h->g16_tickets, h->ln_part, h->ch_gy1, h->ch_gx1, h->ch_gx2, h->ch_gm, h->ch_epoch, h->ch_x2, h->x_emb, h->tail_ticket, h->ch_gqkv, h->ch_ga, h->ch_gbmax, h->ch_gpart, h->stack_layers, h->ch_diag};
+  void* ptrs[] = {h->emb_tables_dev, h->x, h->q, h->o1, h->mbuf, h->nbuf, h->logits_raw, h->last_logits, h->tok_raw, h->scores, h->cmax, h->pv_part, h->pv_tickets, h->pf_x, h->pf_n, h->pf_qkv, h->pf_a, h->pf_u, h->pf_m, h->pf_res, h->pf_zx, h->pf_xbc, h->pf_y, h->pf_g, h->qkv_tmp, h->fw_lengths, h->row_len, h->st, h->remaining, h->stopping, h->row_tab, h->prefix_shift, h->step0, h->adm_cache, h->adm_layers, h->adm_dev, h->res, h->hn, h->m_zx, h->m_xbc, h->m_y, h->m_g, h->m_vg, h->g16_part, h->g16_tickets, h->ln_part, h->ch_gy1, h->ch_gx1, h->ch_gx2, h->ch_gm, h->ch_epoch, h->ch_x2, h->x_emb, h->tail_ticket, h->ch_gqkv, h->ch_ga, h->ch_gbmax, h->ch_gpart, h->stack_layers, h->ch_diag};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->done_host) (void)hipHostFree(h->done_host);
+  if (h->adm_stage) (void)hipHostFree(h->adm_stage);
+  if (h->adm_event) (void)hipEventDestroy(h->adm_event);
   if (h->stop_event) (void)hipEventDestroy(h->stop_event);
   if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
   delete h;
@@ -758,7 +775,8 @@ static bool stack_shapes_ok(zn_handle h) {
 // schedules, key-block counts and graph slots were built and measured for the guided pair, whose rows advance in lockstep; such rows run the launches path, bit-identical by construction.
 // Nor a column shift per utterance (zn_gen_set_prefix_rows): the fused tail's sampler and sample1_kernel do not read it, so two unguided rows whose audio prefixes differ run the launches
 // path even when their lengths advance in lockstep.
-static bool persist_allowed(zn_handle h) { return h->tune[ZN_TUNE_PERSISTENT] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2 && !h->prefix_set; }
+// Nor a slotted session (zn_gen_open_slots): its samplers read the row table, the shifts and the slots' step origins.
+static bool persist_allowed(zn_handle h) { return h->tune[ZN_TUNE_PERSISTENT] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2 && !h->prefix_set && !h->slots_open; }
 // Row counts a persistent kernel can serve on this model: two (the per-block chain and step_kernel) or one (step_r1_kernel, the whole-step
 // kernel only: one row beyond its 6144-key bound, or with it switched off, runs the launches path).
 static bool persist_shape(zn_handle h, int rows) { return h->ch_variant != 0 && (rows == 2 || (rows == 1 && h->ch_variant == 1)); }
@@ -1040,6 +1058,7 @@ static EmbedArgs make_embed_args(zn_handle h) {
   e.tables = h->emb_tables_dev; e.codes = h->codes; e.col_dev = &h->st->offset; e.sb = c.n_codebooks * h->t_total; e.si = h->t_total;
   e.col = 0; e.n_q = c.n_codebooks; e.d = c.d_model; e.batch = h->batch; e.vocab_embed = c.vocab_embed; e.out = h->x_emb; e.dup = guided(h) ? 1 : 0;
   e.shift = h->prefix_set ? h->prefix_shift : nullptr;
+  e.step0 = h->slots_open ? h->step0 : nullptr;
   return e;
 }
 
@@ -1050,6 +1069,7 @@ static SampleArgs gen_sample_args(zn_handle h) {
   a.cfg_scale = h->cfg_scale; a.ctx = h->max_new < 100 ? h->max_new : 100;
   a.rows = h->rows_set ? h->row_tab : nullptr;
   a.shift = h->prefix_set ? h->prefix_shift : nullptr;
+  a.step0 = h->slots_open ? h->step0 : nullptr;
   return a;
 }
 
@@ -1084,7 +1104,7 @@ static int enqueue_step(zn_handle h, const StepPlan& p, hipStream_t s) {
   FrameArgs& f = a.fr;
   f.st = h->st; f.codes = h->codes; f.t_total = h->t_total; f.batch = h->batch; f.n_q = c.n_codebooks; f.eos_id = c.eos_id;
   f.mask_id = c.mask_id; f.tokens = h->tok_raw; f.remaining = h->remaining; f.stopping = h->stopping; f.lengths = h->lengths;
-  f.rows = h->rows; f.first = 0; f.override = h->tok_override; f.override_calls = h->tok_override_calls; f.shift = a.shift;
+  f.rows = h->rows; f.first = 0; f.override = h->tok_override; f.override_calls = h->tok_override_calls; f.shift = a.shift; f.step0 = a.step0;
   if (fused) { a.ticket = h->tail_ticket; a.em = make_embed_args(h); }
   // batch 1, greedy decoding: sampling, bookkeeping and the next embedding in one workgroup (sample1_kernel: 0.8337 -> 0.8312 ms per step).  With a
   // temperature its one wave per codebook carries 17 exp / log / hash evaluations per lane and the nine ticketed workgroups are ahead again (0.8396 vs
@@ -1165,6 +1185,7 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   h->gen_active = true;
   h->rows_set = false;
   h->prefix_set = false;
+  h->slots_open = false;
   h->gen_prefilled = false;
   h->rows_unequal2 = false;
   h->gen_ended = false;
@@ -1393,6 +1414,7 @@ static int prefill_impl(zn_handle h, const void* hidden_dev, int32_t S, const in
 extern "C" int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
   if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill before zn_gen_begin");
+  if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill in a slotted session: zn_gen_admit fills the slots");
   if (!hidden_dev || S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill: bad S=%d (max_len %d)", S, h->max_len);
   h->gen_prefilled = true;
   return prefill_impl(h, hidden_dev, S, nullptr, (hipStream_t)stream);
@@ -1401,6 +1423,7 @@ extern "C" int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_str
 extern "C" int zn_prefill_rows(zn_handle h, const void* hidden_dev, int32_t S, const int32_t* row_len, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
   if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill_rows before zn_gen_begin");
+  if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill_rows in a slotted session: zn_gen_admit fills the slots");
   if (!hidden_dev || !row_len || S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: null argument or bad S=%d (max_len %d)", S, h->max_len);
   const int R = h->rows, B = h->batch;
   int hi = 0;
@@ -1430,6 +1453,7 @@ extern "C" int zn_prefill_rows(zn_handle h, const void* hidden_dev, int32_t S, c
 extern "C" int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int32_t n) {
   if (!h) return ZN_ERR_ARG;
   if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_rows before zn_gen_begin");
+  if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_rows in a slotted session: zn_gen_admit fills the slots");
   if (h->gen_prefilled) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_rows after zn_prefill: the table belongs between zn_gen_begin and the generation's prefill");
   if (!rows_host) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: null argument");
   if (n != h->batch) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: %d entries for a generation of %d utterances", n, h->batch);
@@ -1457,6 +1481,7 @@ extern "C" int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int3
 extern "C" int zn_gen_set_prefix_rows(zn_handle h, const int32_t* prefix_len_host, int32_t n) {
   if (!h) return ZN_ERR_ARG;
   if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_prefix_rows before zn_gen_begin");
+  if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_prefix_rows in a slotted session: zn_gen_admit fills the slots");
   if (h->gen_prefilled) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_prefix_rows after zn_prefill: the prefix lengths belong between zn_gen_begin and the generation's prefill");
   if (!prefix_len_host) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_prefix_rows: null argument");
   if (n != h->batch) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_prefix_rows: %d entries for a generation of %d utterances", n, h->batch);
@@ -1479,9 +1504,207 @@ extern "C" int zn_gen_set_prefix_rows(zn_handle h, const int32_t* prefix_len_hos
   return ZN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ slotted session
+static int handoff_timeout(zn_handle h, int count);
+// The host bound of the rows' KV lengths in a session: the longest busy slot (an idle slot's rows stay at 0).
+static void slots_len_hi(zn_handle h) {
+  h->len_hi = 0;
+  for (int b = 0; b < h->batch; ++b) if (h->slot_busy[b] && h->slot_len[b] > h->len_hi) h->len_hi = h->slot_len[b];
+}
+#define ZN_SESSION_CHECK(h, fn)                                                                              \
+  do {                                                                                                       \
+    if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, fn " before zn_gen_begin");                 \
+    if (!h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, fn ": the generation is not a slotted session (zn_gen_open_slots)"); \
+  } while (0)
+
+extern "C" int zn_gen_open_slots(zn_handle h, int32_t slack) {
+  if (!h) return ZN_ERR_ARG;
+  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_open_slots before zn_gen_begin");
+  if (h->gen_prefilled) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_open_slots after zn_prefill: a session is opened between zn_gen_begin and the generation's first prefill");
+  if (h->slots_open || h->rows_set || h->prefix_set) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_open_slots: the generation already has a row table, column shifts or slots");
+  if (slack < 0) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_open_slots: slack %d < 0", slack);
+  if (h->len_hi != 0) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_open_slots: the session's lengths array must be zero (every slot begins idle)");
+  const size_t R = h->max_rows;
+  if (!h->step0) HIPCHK(h, hipMalloc(&h->step0, R * sizeof(int)));
+  if (!h->adm_stage) HIPCHK(h, hipHostMalloc(&h->adm_stage, R * (4 * sizeof(int) + sizeof(zn_row_params))));
+  if (!h->adm_dev) HIPCHK(h, hipMalloc(&h->adm_dev, R * (4 * sizeof(int) + sizeof(zn_row_params))));
+  if (!h->adm_layers) HIPCHK(h, hipMalloc(&h->adm_layers, (size_t)h->cfg.n_layer * sizeof(AdmitLayer)));
+  if (!h->adm_event) HIPCHK(h, hipEventCreateWithFlags(&h->adm_event, hipEventDisableTiming));
+  hipStream_t s = h->gen_stream;
+  const int B = h->batch;
+  HIPCHK(h, hipMemsetAsync(h->remaining, 0, B * sizeof(int), s));
+  HIPCHK(h, hipMemsetAsync(h->stopping, 0, B * sizeof(int), s));
+  HIPCHK(h, hipMemsetAsync(h->prefix_shift, 0, B * sizeof(int), s));
+  HIPCHK(h, hipMemsetAsync(h->step0, 0xFF, B * sizeof(int), s));                     // -1: idle
+  HIPCHK(h, hipMemsetAsync(h->row_tab, 0, (size_t)B * sizeof(zn_row_params), s));    // an idle slot samples greedily, without a penalty
+  h->slot_len.assign(B, 0); h->slot_busy.assign(B, 0);
+  h->slot_slack = slack;
+  h->adm_cap_S = 0;                        // the pointer table names this generation's caches: rebuilt by the first admission
+  h->rows_set = h->prefix_set = h->slots_open = true;
+  return ZN_OK;
+}
+
+// The scratch cache of an admission: n_layer buffers for max_rows rows of S positions (attention) or of Mamba2 state, and the table that pairs
+// each with the session's buffer.  Grows with S; the stream is drained before a buffer an earlier admission may still read is freed.
+static int ensure_admit_cache(zn_handle h, int S, hipStream_t s) {
+  if (S <= h->adm_cap_S) return ZN_OK;
+  const zn_config& c = h->cfg;
+  const int cap = ((S + 63) / 64) * 64;
+  const size_t attn = zn_kv_bytes_per_layer(&c, h->max_rows, cap), mamba = zn_mamba_state_bytes_per_layer(&c, h->max_rows, nullptr);
+  const size_t per = ((attn > mamba ? attn : mamba) + 255) / 256 * 256;
+  if (per > h->adm_layer_bytes) {
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (h->adm_cache) { (void)hipFree(h->adm_cache); h->adm_cache = nullptr; h->adm_layer_bytes = 0; }
+    HIPCHK(h, hipMalloc(&h->adm_cache, per * c.n_layer));
+    h->adm_layer_bytes = per;
+  }
+  std::vector<AdmitLayer> tab(c.n_layer);
+  h->adm_caches.resize(c.n_layer);
+  for (int li = 0; li < c.n_layer; ++li) {
+    h->adm_caches[li] = (char*)h->adm_cache + (size_t)li * h->adm_layer_bytes;
+    tab[li] = AdmitLayer{h->adm_caches[li], const_cast<void*>(h->kv_layers[li]), (c.arch == 1 && h->layers[li].kind == 1) ? 1 : 0, 0};
+  }
+  HIPCHK(h, hipMemcpyAsync(h->adm_layers, tab.data(), tab.size() * sizeof(AdmitLayer), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipStreamSynchronize(s));      // the host vector goes out of scope
+  h->adm_cap_S = cap;
+  return ZN_OK;
+}
+
+extern "C" int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const void* hidden_dev, int32_t S, zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  ZN_SESSION_CHECK(h, "zn_gen_admit");
+  const zn_config& c = h->cfg;
+  const int B = h->batch, halves = guided(h) ? 2 : 1, nq = c.n_codebooks, MR = h->max_rows;
+  if (!a || !hidden_dev || n < 1 || n > B) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: null argument or %d requests for a session of %d slots", n, B);
+  if (S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: bad S=%d (max_len %d)", S, h->max_len);
+  if (h->stop_pending) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_admit: steps are still owed to a deferred stop read-back (zn_all_stopped_end first)");
+  bool longest = false;
+  for (int j = 0; j < n; ++j) {
+    const zn_admit& q = a[j];
+    if (q.slot < 0 || q.slot >= B) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d out of range 0..%d", q.slot, B - 1);
+    for (int k = 0; k < j; ++k) if (a[k].slot == q.slot) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d named twice in one call", q.slot);
+    if (h->slot_busy[q.slot]) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_admit: slot %d is busy (zn_gen_retire first)", q.slot);
+    if (q.row_len < 1 || q.row_len > S) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: %d positions, not in 1..%d", q.slot, q.row_len, S);
+    if (q.prefix_len < 0 || q.prefix_len > q.row_len - 2)
+      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: prefix length %d not in 0..%d (row_len = conditioning + prefix + 1)", q.slot, q.prefix_len, q.row_len - 2);
+    const zn_row_params& r = q.params;
+    if (r.sp.repetition_penalty_window < 0 || r.sp.repetition_penalty_window > 64) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: repetition_penalty_window out of range", q.slot);
+    if (r.max_new_tokens < 1) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: max_new_tokens %d < 1", q.slot, r.max_new_tokens);
+    if ((long long)q.row_len - 1 + r.max_new_tokens + nq + h->slot_slack > h->max_len)
+      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: %d positions + %d frames + %d + slack %d exceed the session's max_len %d", q.slot, q.row_len - 1, r.max_new_tokens, nq,
+              h->slot_slack, h->max_len);
+    if ((long long)q.prefix_len + r.max_new_tokens + nq + h->slot_slack > h->t_total)
+      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: %d prefix frames + %d frames + %d + slack %d exceed the code buffer's width %d", q.slot, q.prefix_len, r.max_new_tokens, nq,
+              h->slot_slack, h->t_total);
+    if ((r.cfg_scale == 1.0f) == guided(h))
+      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d has cfg_scale %g in a session begun %s guidance", q.slot, (double)r.cfg_scale, guided(h) ? "with" : "without");
+    longest = longest || q.row_len == S;
+  }
+  if (!longest) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: no request holds S = %d positions (no row may be all padding at its end)", S);
+  if (!prefill_all_at_once(h, S))
+    ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_gen_admit needs the batched prefill; this handle prefills position by position (zn_debug_prefill_mode 0, S = 1, or dimensions that are not multiples of 32)");
+  hipStream_t s = (hipStream_t)stream;
+  h->gen_stream = s;
+  int rc = ensure_admit_cache(h, S, s);
+  if (rc) return rc;
+  // stage the admission's arguments: one pinned buffer, one copy
+  if (h->adm_pending) { HIPCHK(h, hipEventSynchronize(h->adm_event)); h->adm_pending = false; }
+  const int Rs = n * halves;
+  int* w = (int*)h->adm_stage;
+  zn_row_params* pw = (zn_row_params*)(h->adm_stage + (size_t)MR * 4 * sizeof(int));
+  bool uniform = true;
+  for (int j = 0; j < n; ++j) {
+    w[j] = a[j].slot; w[MR + j] = a[j].prefix_len; w[2 * MR + j] = a[j].params.max_new_tokens + nq - 1;
+    for (int hf = 0; hf < halves; ++hf) w[3 * MR + hf * n + j] = a[j].row_len;
+    pw[j] = a[j].params;
+    uniform = uniform && a[j].row_len == S;
+  }
+  HIPCHK(h, hipMemcpyAsync(h->adm_dev, h->adm_stage, (size_t)MR * (4 * sizeof(int) + sizeof(zn_row_params)), hipMemcpyHostToDevice, s));
+  const int* dv = (const int*)h->adm_dev;
+  const int* row_len_dev = uniform ? nullptr : dv + 3 * MR;           // every length S: zn_prefill's launches, as zn_prefill_rows makes them
+  h->gen_prefilled = true;
+  size_t conv_src = 0, conv_dst = 0;
+  if (c.arch == 1) {
+    (void)zn_mamba_state_bytes_per_layer(&c, Rs, &conv_src);
+    const size_t state = zn_mamba_state_bytes_per_layer(&c, h->rows, &conv_dst);
+    (void)state;
+    const size_t zb = zn_mamba_state_bytes_per_layer(&c, Rs, nullptr);
+    for (int li = 0; li < c.n_layer; ++li)                               // a prefill continues the state it finds: the scratch rows begin at zero
+      if (h->layers[li].kind == 1) HIPCHK(h, hipMemsetAsync(const_cast<void*>(h->adm_caches[li]), 0, zb, s));
+    if ((rc = hybrid_prefill_core(h, (const bf16_t*)hidden_dev, S, Rs, h->adm_caches.data(), S, 0, h->prefill_mode == 2, s, row_len_dev))) return rc;
+  } else if ((rc = transformer_prefill_core(h, (const bf16_t*)hidden_dev, S, Rs, h->adm_caches.data(), S, 0, s, row_len_dev))) return rc;
+  AdmitArgs m{};
+  m.layers = h->adm_layers; m.n_layer = c.n_layer; m.n = n; m.halves = halves; m.B = B; m.S = S; m.max_len = h->max_len;
+  m.kv_row_bytes = 2 * c.n_heads_kv * h->hd * 2;
+  if (c.arch == 1) {
+    m.conv_row_bytes = h->m_conv_dim * c.m_d_conv * 2; m.ssm_row_bytes = c.m_d_inner * c.m_d_state * 2; m.ssm_off_src = conv_src; m.ssm_off_dst = conv_dst;
+    m.pf_res = h->pf_res; m.res = h->res; m.res_row_bytes = c.d_model * (c.residual_in_fp32 ? 4 : 2);
+  }
+  m.slot = dv; m.prefix = dv + MR; m.rem = dv + 2 * MR; m.row_len = dv + 3 * MR; m.params = (const zn_row_params*)(h->adm_dev + (size_t)MR * 4 * sizeof(int));
+  m.pf_x = h->pf_x; m.x = h->x; m.d = c.d_model; m.st = h->st;
+  m.lengths = h->lengths; m.remaining = h->remaining; m.stopping = h->stopping; m.shift = h->prefix_shift; m.step0 = h->step0; m.rows = h->row_tab;
+  hipLaunchKernelGGL(admit_rows_kernel, dim3(Rs, c.n_layer + 1, ZN_ADMIT_PARTS), dim3(256), 0, s, m);
+  HIPCHK(h, hipEventRecord(h->adm_event, s));
+  h->adm_pending = true;
+  // the heads over every row of h->x, as a prefill of the whole batch runs them (the logits of the rows not admitted are workspace: the next
+  // step's heads rewrite them before any sampler reads them), then the first frame of each admitted slot alone
+  if ((rc = c.arch == 1 ? hybrid_heads(h, s) : heads_logits(h, h->x, h->rows, s))) return rc;
+  for (int j = 0; j < n; ++j) {
+    SampleArgs sa = gen_sample_args(h);
+    sa.raw = h->logits_raw; sa.mix = guided(h) ? 1 : 0; sa.apply_bias = 0; sa.batch = B;
+    sa.use_penalty = 0; sa.st = h->st; sa.logits_out = h->last_logits; sa.tokens = h->tok_raw; sa.draw = 0; sa.slot_base = a[j].slot;
+    hipLaunchKernelGGL(sample_kernel, dim3(nq, 1), dim3(256), 0, s, sa);
+    FrameArgs f{};
+    f.st = h->st; f.codes = h->codes; f.t_total = h->t_total; f.batch = B; f.n_q = nq; f.eos_id = c.eos_id;
+    f.mask_id = c.mask_id; f.tokens = h->tok_raw; f.remaining = h->remaining; f.stopping = h->stopping; f.lengths = h->lengths;
+    f.rows = h->rows; f.first = 1; f.shift = sa.shift; f.step0 = sa.step0; f.slot_base = a[j].slot; f.slot_count = 1;
+    hipLaunchKernelGGL(frame_update_kernel, dim3(1), dim3(256), 0, s, f);
+  }
+  for (int j = 0; j < n; ++j) { h->slot_busy[a[j].slot] = 1; h->slot_len[a[j].slot] = a[j].row_len; }
+  slots_len_hi(h);
+  h->emb_valid = false;
+  HIPCHK(h, hipGetLastError());
+  return ZN_OK;
+}
+
+extern "C" int zn_gen_retire(zn_handle h, int32_t slot) {
+  if (!h) return ZN_ERR_ARG;
+  ZN_SESSION_CHECK(h, "zn_gen_retire");
+  if (slot < 0 || slot >= h->batch) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_retire: slot %d out of range 0..%d", slot, h->batch - 1);
+  if (!h->slot_busy[slot]) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_retire: slot %d is idle already", slot);
+  hipStream_t s = h->gen_stream;
+  HIPCHK(h, hipMemsetAsync(h->lengths + slot, 0, sizeof(int), s));
+  if (guided(h)) HIPCHK(h, hipMemsetAsync(h->lengths + h->batch + slot, 0, sizeof(int), s));
+  HIPCHK(h, hipMemsetAsync(h->remaining + slot, 0, sizeof(int), s));
+  HIPCHK(h, hipMemsetAsync(h->step0 + slot, 0xFF, sizeof(int), s));
+  h->slot_busy[slot] = 0; h->slot_len[slot] = 0;
+  slots_len_hi(h);
+  return ZN_OK;
+}
+
+extern "C" int zn_gen_row_state(zn_handle h, int32_t* remaining_host, int32_t* steps_host, zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  ZN_SESSION_CHECK(h, "zn_gen_row_state");
+  hipStream_t s = (hipStream_t)stream;
+  const int B = h->batch;
+  std::vector<int> rem(B), s0(B);
+  GenState st{};
+  HIPCHK(h, hipMemcpyAsync(rem.data(), h->remaining, B * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(s0.data(), h->step0, B * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(&st, h->st, sizeof st, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  for (int b = 0; b < B; ++b) {
+    if (remaining_host) remaining_host[b] = rem[b];
+    if (steps_host) steps_host[b] = s0[b] < 0 ? -1 : st.step - s0[b];
+  }
+  if (st.pad[0] != 0) return handoff_timeout(h, st.pad[0]);
+  return ZN_OK;
+}
+
 extern "C" int zn_sample_first(zn_handle h, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
   if (!h->gen_active) ZN_FAIL(h, ZN_ERR_STATE, "zn_sample_first before zn_gen_begin");
+  if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_sample_first in a slotted session: zn_gen_admit samples each slot's first frame");
   hipStream_t s = (hipStream_t)stream;
   const zn_config& c = h->cfg;
   SampleArgs a = gen_sample_args(h);
@@ -1504,6 +1727,10 @@ extern "C" int zn_decode_steps(zn_handle h, int32_t n, zn_stream stream) {
   if (n < 0) ZN_FAIL(h, ZN_ERR_ARG, "n < 0");
   hipStream_t s = (hipStream_t)stream;
   h->gen_stream = s;
+  if (h->slots_open)
+    for (int b = 0; b < h->batch; ++b)
+      if (h->slot_busy[b] && h->slot_len[b] + n > h->max_len)
+        ZN_FAIL(h, ZN_ERR_STATE, "zn_decode_steps: %d steps would take slot %d (%d positions) past max_len %d: retire it first", n, b, h->slot_len[b], h->max_len);
   for (int i = 0; i < n;) {
     const StepPlan p = h->last_plan = plan_steps(h, n - i);
     const int k = p.graph_slot, run = p.run;
@@ -1529,6 +1756,10 @@ extern "C" int zn_decode_steps(zn_handle h, int32_t n, zn_stream stream) {
     if (h->graph_exec[k]) HIPCHK(h, hipGraphLaunch(h->graph_exec[k], s));
     else for (int j = 0; j < run; ++j) { int rc = enqueue_step(h, p, s); if (rc) return rc; }
     i += run; h->len_hi += run; h->epoch_bound += (unsigned long long)run * (h->cfg.n_layer + 1);
+  }
+  if (h->slots_open) {
+    for (int b = 0; b < h->batch; ++b) if (h->slot_busy[b]) h->slot_len[b] += n;
+    slots_len_hi(h);
   }
   HIPCHK(h, hipGetLastError());
   return ZN_OK;

@@ -1446,6 +1446,8 @@ struct EmbedArgs {
   bf16_t* out;                  // [2*batch or batch][d]
   int dup;                      // 1: also write row b + batch (CFG duplicate, generation_utils.py:192)
   const int* shift;             // optional device array [batch] added to utterance b's column (zn_gen_set_prefix_rows), NULL = none
+  const int* step0;             // slotted session (zn_gen_open_slots), NULL = none: the column is clamped into the row (si columns): an idle or
+                                // overrunning slot's column may lie anywhere, and what it embeds is never used
 };
 #define ZN_EMBED_MAXQ 16
 // Sum of the n_q codebook embeddings of utterance b (codes clamped into the table) -> out rows b (and b + batch).
@@ -1471,7 +1473,8 @@ ZN_DEVINL void embed_row(const EmbedArgs& a, int b, const int (&code)[ZN_EMBED_M
 }
 __global__ __launch_bounds__(256) void embed_kernel(EmbedArgs a) {
   const int b = blockIdx.x;
-  const int col = (a.col_dev ? *a.col_dev : a.col) + (a.shift ? a.shift[b] : 0);
+  int col = (a.col_dev ? *a.col_dev : a.col) + (a.shift ? a.shift[b] : 0);
+  if (a.step0) col = max(0, min(col, a.si - 1));
   // all codes, then all table rows, are requested before the first add (three memory round trips on the step's
   // launch-bound tail instead of one per codebook); indices past n_q repeat the last codebook and are not added
   int code[ZN_EMBED_MAXQ];
@@ -1560,7 +1563,11 @@ struct FrameArgs {
   int first;           // 1: model.py:423-431 (first frame after prefill: plain write-where-unknown)
   const int* override; // test hook: raw tokens [calls][B][n_q] replacing the sampled ones (call 0 = first frame)
   int override_calls;
-  const int* shift;    // [B] column shift per utterance, <= 0 (zn_gen_set_prefix_rows): utterance b writes column offset + shift[b]; NULL = none
+  const int* shift;    // [B] column shift per utterance (zn_gen_set_prefix_rows: <= 0; a slotted session: either sign): utterance b writes column offset + shift[b]; NULL = none
+  // Slotted session (zn_gen_open_slots), NULL = none: step0[b] = the session step at which slot b's request was admitted, < 0 while the slot is
+  // idle.  The rows of an idle slot do not advance their lengths: they keep appending to position 0 of their own cache rows.
+  const int* step0;
+  int slot_base, slot_count;   // slot_count > 0: the launch serves slots [slot_base, slot_base + slot_count) only (zn_gen_admit's first frame); 0 = all
 };
 #define ZN_FRAME_MAXQ 16
 #define ZN_TAIL_MAXB 64
@@ -1593,6 +1600,10 @@ struct SampleArgs {
   int* ticket;
   FrameArgs fr;
   EmbedArgs em;            // codes/col fields unused: the codes come from the bookkeeping just done
+  // Slotted session (zn_gen_open_slots), NULL = none: utterance b's draw is keyed by its own step count st->step - step0[b] instead of the
+  // session's, and its history column is clamped into its buffer row.  sample1_kernel does not read it.
+  const int* step0;
+  int slot_base;           // workgroup (cb, y) serves utterance slot_base + y (zn_gen_admit's first frame); 0 = the whole batch
 };
 
 ZN_DEVINL void block_argmax(float v, int i, float* sv, int* si, float& bv, int& bi) {
@@ -1646,20 +1657,21 @@ ZN_DEVINL void frame_update_body(const FrameArgs& a, int (*s_code)[ZN_FRAME_MAXQ
   // counters before lane 0 of the group rewrites them.  n_q <= 16 is checked by zn_create.
   const int o = a.st->offset, stp = a.st->step;
   // (the utterance's column shift is requested with the loop state, before the barrier: the cell's address waits for both at once)
-  const int b0 = threadIdx.x / ZN_FRAME_MAXQ;
+  const int b_end = a.slot_count > 0 ? a.slot_base + a.slot_count : a.batch;
+  const int b0 = threadIdx.x / ZN_FRAME_MAXQ + a.slot_base;
   int sh = (a.shift && b0 < a.batch) ? a.shift[b0] : 0;
   __shared__ int s_done;
   if (threadIdx.x == 0) s_done = 1;
   __syncthreads();
   const int cb = threadIdx.x & (ZN_FRAME_MAXQ - 1);
-  for (int b = b0; b < a.batch; b += blockDim.x / ZN_FRAME_MAXQ) {
+  for (int b = b0; b < b_end; b += blockDim.x / ZN_FRAME_MAXQ) {
     if (a.shift && b != b0) sh = a.shift[b];
     const int* tk = a.tokens + b * a.n_q;
     const int call = a.first ? 0 : stp + 1;
     const bool ovr = a.override && call < a.override_calls;
     if (ovr) tk = a.override + ((size_t)call * a.batch + b) * a.n_q;
     const int cbc = min(cb, a.n_q - 1);
-    const int col = (a.first ? o : o + 1) + sh;            // sh <= 0, and never below the row's own column 1 (zn_gen_set_prefix_rows)
+    const int col = (a.first ? o : o + 1) + sh;            // never below the row's own column 1 (zn_gen_set_prefix_rows, zn_gen_admit); elsewhere: in_range
     const bool in_range = cb < a.n_q && col >= 0 && col < a.t_total;
     int* cell = a.codes + ((size_t)b * a.n_q + cbc) * a.t_total + max(0, min(col, a.t_total - 1));
     int tok, tok0;
@@ -1689,7 +1701,8 @@ ZN_DEVINL void frame_update_body(const FrameArgs& a, int (*s_code)[ZN_FRAME_MAXQ
   }
   __syncthreads();
   if (!a.first) {
-    for (int r = threadIdx.x; r < a.rows; r += blockDim.x) a.lengths[r] += 1;   // tensor_ops.py:85-86
+    for (int r = threadIdx.x; r < a.rows; r += blockDim.x)
+      if (!a.step0 || a.step0[r % a.batch] >= 0) a.lengths[r] += 1;             // tensor_ops.py:85-86 (an idle slot's rows stay at 0)
     if (threadIdx.x == 0) { a.st->offset = o + 1; a.st->step = stp + 1; a.st->all_done = s_done; }
   }
 }
@@ -1697,7 +1710,7 @@ __global__ __launch_bounds__(256) void frame_update_kernel(FrameArgs a) { frame_
 
 #define ZN_SAMPLE_MAXV 2048
 __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
-  const int cb = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int cb = blockIdx.x, b = blockIdx.y + a.slot_base, tid = threadIdx.x;
   const int V = a.V;
   __shared__ float sp[ZN_SAMPLE_MAXV];
   __shared__ int sidx[ZN_SAMPLE_MAXV];
@@ -1705,7 +1718,9 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   __shared__ int si[4];
   // every input is requested before the first use (clamped indices, masked use): the kernel sits on the step's
   // launch-bound tail, where one memory round trip per loop iteration used to cost several microseconds
-  const int o = (a.st ? a.st->offset : 0) + (a.shift ? a.shift[b] : 0);   // the utterance's own column (workgroup-uniform, requested with the loop state)
+  int o = (a.st ? a.st->offset : 0) + (a.shift ? a.shift[b] : 0);   // the utterance's own column (workgroup-uniform, requested with the loop state)
+  const int step_b0 = a.step0 ? a.step0[b] : 0;                     // slotted session: the session step the slot's request began at
+  if (a.step0 && a.codes) o = max(0, min(o, a.t_total - 1));        // (an idle slot's column: its history stays inside its own buffer row)
   const float st_bias = a.st ? a.st->eos_bias : 0.f;
   const bool st_force = a.st ? (a.st->force_eos_step == a.st->step) : false;
   // the utterance's own settings: one 64-byte entry at a workgroup-uniform address, requested with the loads above and below (every
@@ -1882,7 +1897,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     float bv = -1.f; int bi = 0x7fffffff;
     for (int i = tid; i < V; i += 256) {
       const int tokid = sidx[i];
-      unsigned long long h = zn_mix64(seed ^ zn_mix64(a.draw + (a.st ? (unsigned long long)a.st->step : 0ull)));
+      unsigned long long h = zn_mix64(seed ^ zn_mix64(a.draw + (a.st ? (unsigned long long)(a.st->step - step_b0) : 0ull)));
       h = zn_mix64(h + 0x9E3779B97F4A7C15ull * (unsigned long long)((key_b * a.n_q + cb) * V + tokid + 1));
       const float uu = ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);
       const float q = -logf(uu);

@@ -770,3 +770,62 @@ __global__ __launch_bounds__(256) void assemble_prefill_kernel(AssembleArgs a) {
     for (int k = threadIdx.x * 8; k < d; k += 256 * 8) *(u32x4*)(out + k) = u32x4{0u, 0u, 0u, 0u};
   }
 }
+
+// ------------------------------------------------------------------------------------------------ slotted session: rows admitted between two decode steps
+// zn_gen_admit prefills its n requests into a scratch cache of n * halves rows ([cond_0..cond_{n-1} ‖ uncond_0..uncond_{n-1}], S positions per
+// row) and this kernel moves every row into the slot it was admitted to: for scratch row i = half * n + j, session row r = half * B + slot[j],
+//   attention layers: KV positions [0, row_len) of the row; Mamba2 layers: its conv window and SSM state;
+//   the hidden state of its last valid position (and the hybrid residual) into row r of x / res;
+//   lengths[r] = row_len; and, once per slot, remaining, stopping, the 64-byte parameter entry, the column shift (P + 1 - st->offset: the
+//   slot's column of the code buffer at the session's current loop state) and step0 = st->step.
+// Grid (n * halves, n_layer + 1, ZN_ADMIT_PARTS): workgroup (i, li, z) copies every ZN_ADMIT_PARTS-th 16-byte piece of layer li's bytes; the plane
+// y == n_layer gathers and writes the words.  Nothing of a row that is not named is touched.
+#define ZN_ADMIT_PARTS 4
+struct AdmitLayer { const void* src; void* dst; int kind; int pad; };       // kind 0: KV cache, 1: Mamba2 conv + SSM state buffer
+struct AdmitArgs {
+  const AdmitLayer* layers; int n_layer;
+  int n, halves, B;                        // requests of this admission, rows per request, slots of the session
+  int S, max_len;                          // positions per row of the scratch cache / of the session's
+  int kv_row_bytes;                        // one position of an attention layer's cache: 2 * Hkv * hd bf16
+  int conv_row_bytes, ssm_row_bytes;       // one row's Mamba2 conv window / SSM state
+  size_t ssm_off_src, ssm_off_dst;         // offset of the SSM states in a scratch / session state buffer (rows * conv_row_bytes)
+  const int *slot, *prefix, *rem;          // [n] staged by the host
+  const int* row_len;                      // [n * halves]
+  const zn_row_params* params;             // [n]
+  const bf16_t* pf_x; bf16_t* x; int d;    // [n * halves][S][d] -> [rows][d]
+  const void* pf_res; void* res; int res_row_bytes;   // hybrid residual stream (NULL: none)
+  const GenState* st;
+  int *lengths, *remaining, *stopping, *shift, *step0;
+  zn_row_params* rows;
+};
+ZN_DEVINL void admit_copy(const void* src, void* dst, size_t bytes, int part, int parts) {
+  const u32x4* sp = (const u32x4*)src;
+  u32x4* dp = (u32x4*)dst;
+  for (size_t k = (size_t)part * 256 + threadIdx.x; k < bytes / 16; k += (size_t)parts * 256) dp[k] = sp[k];
+}
+__global__ __launch_bounds__(256) void admit_rows_kernel(AdmitArgs a) {
+  const int i = blockIdx.x, li = blockIdx.y, z = blockIdx.z, j = i % a.n, half = i / a.n;
+  const int b = a.slot[j], r = half * a.B + b, len = a.row_len[i];
+  if (li < a.n_layer) {
+    const AdmitLayer L = a.layers[li];
+    if (L.kind == 0) {
+      admit_copy((const char*)L.src + (size_t)i * a.S * a.kv_row_bytes, (char*)L.dst + (size_t)r * a.max_len * a.kv_row_bytes, (size_t)len * a.kv_row_bytes, z, ZN_ADMIT_PARTS);
+    } else {
+      admit_copy((const char*)L.src + (size_t)i * a.conv_row_bytes, (char*)L.dst + (size_t)r * a.conv_row_bytes, a.conv_row_bytes, z, ZN_ADMIT_PARTS);
+      admit_copy((const char*)L.src + a.ssm_off_src + (size_t)i * a.ssm_row_bytes, (char*)L.dst + a.ssm_off_dst + (size_t)r * a.ssm_row_bytes, a.ssm_row_bytes, z, ZN_ADMIT_PARTS);
+    }
+    return;
+  }
+  if (z) return;
+  const size_t last = (size_t)i * a.S + (len - 1);
+  admit_copy(a.pf_x + last * a.d, a.x + (size_t)r * a.d, (size_t)a.d * 2, 0, 1);
+  if (a.pf_res) admit_copy((const char*)a.pf_res + last * a.res_row_bytes, (char*)a.res + (size_t)r * a.res_row_bytes, a.res_row_bytes, 0, 1);
+  if (threadIdx.x == 0) a.lengths[r] = len;
+  if (half) return;
+  if (threadIdx.x < ZN_ROW_PARAMS_BYTES / 4) ((int*)(a.rows + b))[threadIdx.x] = ((const int*)(a.params + j))[threadIdx.x];
+  if (threadIdx.x == 0) {
+    a.remaining[b] = a.rem[j]; a.stopping[b] = 0;
+    a.shift[b] = a.prefix[j] + 1 - a.st->offset;
+    a.step0[b] = a.st->step;
+  }
+}

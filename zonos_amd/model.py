@@ -11,6 +11,7 @@ import ctypes as C
 import os
 import sys
 import threading
+import time
 import json
 from dataclasses import dataclass, field
 from typing import Callable, Iterator, NamedTuple, Sequence
@@ -24,6 +25,7 @@ from .backbone import BACKBONES, HipEngine
 from .codebook_pattern import apply_delay_pattern, revert_delay_pattern
 from .conditioning import ConditioningCache, PrefixConditioner, pad_conditionings, prepare_conditioning_with_cache
 from .config import InferenceParams, ZonosConfig
+from .serving import ServeResult, SlotScheduler, check_serve_request, row_end_offset, serve_slack, stop_check_at  # noqa: F401  (row_end_offset, stop_check_at: defined there, used and re-exported here)
 from .utils import DEFAULT_DEVICE, find_multiple
 
 DEFAULT_BACKBONE_CLS = next(iter(BACKBONES.values()))
@@ -75,33 +77,6 @@ def release_limit(offset: int, nq: int, eos_frame: int | None) -> int:
     the stop frame itself).  What the end keeps beyond that, `finalise_codes` decides."""
     limit = max(0, offset - nq + 1)
     return limit if eos_frame is None else min(limit, eos_frame)
-
-
-def stop_check_at(step_idx: int, batch_size: int) -> bool:
-    """The reference's stop-check cadence (tensor_ops.py:90-103) as `_decode_loop` runs it: is the stop flag read after loop step
-    `step_idx` (0-based) of a call of `batch_size` utterances?"""
-    return step_idx % 16 == 15 or (step_idx % 8 == 7 and max(0, batch_size * 10 - (step_idx + 1)) < 5)
-
-
-def row_end_offset(offset0: int, t_total: int, batch_size: int, nq: int, eos_column: int | None) -> int:
-    """The column at which the decode loop of a call of `batch_size` utterances would have ended had it watched one row alone
-    (`generate_batch`: every request is cut and finalised for itself, while the call runs on to its last row).  The row starts at column
-    `offset0` (audio prefix + 1) with its own `t_total` = prefix + max_new_tokens + nq columns and remaining_steps = t_total - offset0;
-    `eos_column` is the first column beyond offset0 whose codebook 0 holds EOS (None: there is none below t_total).  Loop step i writes
-    column offset0 + i + 1; a step that samples EOS in codebook 0 caps remaining_steps at nq; every step takes one off (tensor_ops.py:87,
-    155-211).  The loop leaves at the first check of the call's cadence (`stop_check_at`) at which remaining_steps <= 0 - the deferred
-    read-back of `_decode_loop` rolls back to that same check - or at t_total when the row's budget ends before any such check."""
-    remaining, offset = t_total - offset0, offset0
-    for step_idx in range(t_total - offset0):
-        offset += 1
-        if offset >= t_total:
-            break
-        if eos_column is not None and offset == eos_column:
-            remaining = min(remaining, nq)
-        remaining -= 1
-        if stop_check_at(step_idx, batch_size) and remaining <= 0:
-            return offset
-    return t_total
 
 
 @dataclass
@@ -435,6 +410,167 @@ class Zonos(nn.Module):
             eng.generating = False
             eng.lock.release()
 
+    def serve(self, requests, slots: int = 8, max_prompt: int = 64, max_new_tokens: int = 86 * 30, guided: bool = True, sched_every: int = 8,
+              _trace: dict | None = None, _stats: dict | None = None) -> Iterator[ServeResult]:
+        """Requests join a running batch as slots free up: a generator of `ServeResult(index, codes, error)` in order of completion.
+
+        `requests` is any iterable of `GenRequest`, pulled lazily: an item is taken only when a slot is free at a scheduling point (every
+        `sched_every` decode steps, enqueued in one call), and an item that is None means that nothing is waiting right now.  `index`
+        counts the requests pulled (None items do not count).  A request is prefilled into its slot while the other rows keep their state
+        (zn_gen_admit), decodes there with its own parameters, seed, guidance strength, budget and audio prefix, and is retired at the
+        first scheduling point at which a `generate_batch()` call of `slots` requests would have stopped watching it: its codes are the
+        codes of its row in such a call.  `max_prompt` (conditioning positions + audio prefix frames of the longest
+        request) and `max_new_tokens` size the KV cache and the code buffer once; a request that does not fit them, whose guidance differs
+        from the session's (`guided`: cfg_scale != 1) or that is malformed yields ServeResult(index, None, ValueError) and takes no slot.
+
+        The engine and the stream current at the call are held while the generator is alive; `close()`, leaving the loop early or garbage
+        collection releases them.  A session runs no persistent kernel, so no hand-off timeout can occur; any library error raises.
+        `_trace`: one step per enqueue; "logits" receives [slots, 9, 1025] per admission and per step, "slots" a (kind, session step,
+        request index per slot) record for each of them (an admission's record names the admitted slots only).  `_stats` (tools/servebench.py)
+        receives the session's decode steps and admissions, and with _stats["time_admissions"] set the seconds spent in admissions, each
+        bracketed by a synchronisation."""
+        slots, sched_every, max_prompt, max_new_tokens = int(slots), int(sched_every), int(max_prompt), int(max_new_tokens)
+        if not 1 <= slots <= MAX_BATCH_REQUESTS:
+            raise ValueError(f"serve: slots must lie in 1..{MAX_BATCH_REQUESTS}, got {slots}")
+        if sched_every < 1 or max_prompt < 1 or max_new_tokens < 1:
+            raise ValueError(f"serve: sched_every={sched_every}, max_prompt={max_prompt}, max_new_tokens={max_new_tokens} must all be >= 1")
+        if self.device.type != "cuda":
+            raise _lib.ZonosHipError("zonos_amd runs on MI355X only: move the model to a cuda device (no CPU fallback)")
+        dev = self.device
+        return self._serve_gen(dev, torch.cuda.current_stream(dev), iter(requests), slots, max_prompt, max_new_tokens, bool(guided), sched_every, _trace, _stats)
+
+    def _serve_gen(self, dev, ts, source, slots, max_prompt, max_new_tokens, guided, sched_every, _trace, _stats=None):
+        nq, d, mask = self.config.codebook_dimension, self.config.backbone.d_model, self.masked_token_id
+        halves = 2 if guided else 1
+        R = slots * halves
+        slack = serve_slack(sched_every)
+        width = max_prompt + max_new_tokens + nq + slack              # columns of a slot's row of the code buffer
+        sched = SlotScheduler(slots, nq, sched_every)
+        eng = self._acquire_engine((R + 1) // 2)
+        begun = False
+        st = ts.cuda_stream
+        try:
+            with torch.inference_mode(), torch.cuda.device(dev), torch.cuda.stream(ts):
+                ip = self.setup_cache(batch_size=R, max_seqlen=max_prompt + max_new_tokens + nq + slack)
+                max_len = ip.max_seqlen
+                delayed = torch.full((slots, nq, width), mask, dtype=torch.int32, device=dev)      # an idle slot's cells are never -1
+                n_layer = self.config.backbone.n_layer
+                kv_ptrs = (C.c_void_p * n_layer)(*[ip.key_value_memory_dict[i][0].data_ptr() for i in range(n_layer)])
+                sp = _sampling_struct({}, 0)                           # (every sampler of a session reads its slot's entry)
+                eng.call("zn_gen_begin", slots, kv_ptrs, max_len, ip.lengths_per_sample.data_ptr(), delayed.data_ptr(), width, 1, max_new_tokens,
+                         2.0 if guided else 1.0, C.byref(sp), st)
+                begun = True
+                eng.call("zn_gen_open_slots", slack)
+
+            def accept(r):
+                if not isinstance(r, GenRequest):
+                    raise ValueError(f"serve: expected a GenRequest or None, got {type(r).__name__}")
+                c, a = r.conditioning, r.audio_prefix_codes
+                if not hasattr(c, "shape") or (a is not None and not hasattr(a, "shape")):
+                    raise ValueError("serve: conditioning and audio_prefix_codes must be tensors")
+                L, P = check_serve_request(c.shape, None if a is None else a.shape, r.max_new_tokens, r.cfg_scale, nq=nq, d_model=d, guided=guided,
+                                           max_len=max_len, width=width, slack=slack)
+                try:
+                    _sampling_struct(r.sampling_params, 0)
+                except TypeError as e:
+                    raise ValueError(f"serve: {e}") from None
+                return P, int(r.max_new_tokens)
+
+            def record(kind, holders):
+                if _trace is not None:
+                    _trace.setdefault("logits", []).append(self._step_logits(eng, slots, nq))
+                    _trace.setdefault("slots", []).append((kind, sched.step, list(holders)))
+
+            def admit(admitted):
+                n = len(admitted)
+                reqs = [r for _, _, r in admitted]
+                Ls = [int(r.conditioning.shape[1]) for r in reqs]
+                Ps = [0 if r.audio_prefix_codes is None else int(r.audio_prefix_codes.shape[2]) for r in reqs]
+                cond, _ = pad_conditionings([r.conditioning.to(dev) for r in reqs], 2.0 if guided else 1.0)
+                cond = cond.to(device=dev, dtype=torch.bfloat16).contiguous()
+                codes = torch.full((n, nq, width - nq), mask, dtype=torch.int32, device=dev)
+                for j, r in enumerate(reqs):                          # a slot's row: its prefix, its unknown cells, the mask token up to the width
+                    if Ps[j]:
+                        codes[j, :, :Ps[j]] = r.audio_prefix_codes[0].to(device=dev, dtype=torch.int32)
+                    codes[j, :, Ps[j]:Ps[j] + int(r.max_new_tokens)] = -1
+                rows = apply_delay_pattern(codes, mask).contiguous()  # [n, nq, width]
+                adm = (_lib.zn_admit * n)()
+                for j, (slot, _, r) in enumerate(admitted):
+                    delayed[slot].copy_(rows[j])
+                    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if r.seed is None else r.seed
+                    adm[j].slot, adm[j].row_len, adm[j].prefix_len = slot, Ls[j] + Ps[j] + 1, Ps[j]
+                    adm[j].params.sp = _sampling_struct(r.sampling_params, seed)
+                    adm[j].params.cfg_scale, adm[j].params.max_new_tokens = float(r.cfg_scale), int(r.max_new_tokens)
+                S = max(L + P + 1 for L, P in zip(Ls, Ps))
+                meta = torch.tensor([Ls, Ps], dtype=torch.int32).to(dev)
+                hidden = torch.empty(halves * n, S, d, dtype=torch.bfloat16, device=dev)
+                row_len_dev = torch.empty(halves * n, dtype=torch.int32, device=dev)
+                eng.call("zn_op_assemble_prefill", cond.data_ptr(), cond.shape[1], meta[0].data_ptr(), rows.data_ptr(), width, meta[1].data_ptr(), n,
+                         halves * n, hidden.data_ptr(), S, row_len_dev.data_ptr(), st)
+                eng.call("zn_gen_admit", adm, n, hidden.data_ptr(), S, st)
+                held = [None] * slots
+                for slot, index, _ in admitted:
+                    held[slot] = index
+                record("admit", held)
+
+            rem, own = (C.c_int32 * slots)(), (C.c_int32 * slots)()
+            while True:
+                out = []
+                with torch.inference_mode(), torch.cuda.device(dev), torch.cuda.stream(ts):
+                    admitted, refused = sched.pull(source, accept)
+                    out += [ServeResult(index, None, err) for index, err in refused]
+                    if admitted:
+                        timed = _stats is not None and _stats.get("time_admissions")
+                        if timed:
+                            ts.synchronize()
+                            t0 = time.perf_counter()
+                        admit(admitted)
+                        if timed:
+                            ts.synchronize()
+                            _stats["admit_seconds"] = _stats.get("admit_seconds", 0.0) + time.perf_counter() - t0
+                        if _stats is not None:
+                            _stats["admissions"] = _stats.get("admissions", 0) + 1
+                            _stats["admitted"] = _stats.get("admitted", 0) + len(admitted)
+                    stop = sched.finished()
+                    if not stop and not sched.all_idle():
+                        if _trace is None:
+                            eng.call("zn_decode_steps", sched_every, st)
+                            sched.advance()
+                        else:
+                            for _ in range(sched_every):
+                                eng.call("zn_decode_steps", 1, st)
+                                sched.advance(1)
+                                record("step", sched.holders())
+                        if _stats is not None:
+                            _stats["steps"] = sched.step
+                        eng.call("zn_gen_row_state", rem, own, st)
+                        if [own[b] for b in range(slots)] != [sched.own_steps(b) for b in range(slots)]:
+                            raise _lib.ZonosHipError(f"serve: the device counts {list(own)} steps per slot, the scheduler {[sched.own_steps(b) for b in range(slots)]}")
+                        rows_host = {}
+                        for b in sched.wants_eos(rem):
+                            rows_host[b] = delayed[b:b + 1].cpu()
+                            r = sched.rows[b]
+                            sched.set_eos(b, self._finalise_row(rows_host[b], r.prefix_len, r.max_new_tokens, slots, nq)[1])
+                        known = {b: sched.rows[b] for b in range(slots) if sched.rows[b] is not None}
+                        for b, index, end in sched.due():
+                            row = rows_host[b] if b in rows_host else delayed[b:b + 1].cpu()
+                            codes, _, end_b = self._finalise_row(row, known[b].prefix_len, known[b].max_new_tokens, slots, nq)
+                            assert end_b == end, (end_b, end)
+                            eng.call("zn_gen_retire", b)
+                            out.append(ServeResult(index, codes.to(dev), None))
+                for res in out:
+                    yield res
+                if stop:
+                    break
+        finally:
+            try:
+                if begun:
+                    ts.synchronize()
+                    eng.call("zn_gen_end")
+            finally:
+                eng.generating = False
+                eng.lock.release()
+
     def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor = None, max_new_tokens: int = 86 * 30,
                cfg_scale: float = 2.0, sampling_params: dict = dict(min_p=0.1), seed: int | None = None, chunk_frames: int = 16,
                batch_size: int = 1) -> Iterator[StreamChunk]:
@@ -599,16 +735,18 @@ class Zonos(nn.Module):
         """generate_batch's results from the call's delayed codes (host): row b keeps its own P_b + max_new_tokens_b + nq columns and is
         finalised at the column its own loop would have ended at (`row_end_offset`, from its first codebook-0 EOS).  `P`: the call's audio
         prefix length, or one per row (ragged_prefix: a row's step index does not depend on its prefix, only its columns do)."""
-        outs = []
-        for b in range(B):
-            P_b = P if isinstance(P, int) else int(P[b])
-            offset0 = P_b + 1
-            t_b = P_b + int(row_table[b].max_new_tokens) + nq
-            row = delayed[b:b + 1, :, :t_b].to(torch.int64)
-            hit = (row[0, 0, offset0 + 1:] == self.eos_token_id).nonzero()
-            eos_column = offset0 + 1 + int(hit[0, 0]) if len(hit) else None
-            outs.append(finalise_codes(revert_delay_pattern(row), row_end_offset(offset0, t_b, B, nq, eos_column), nq, self.eos_token_id))
-        return outs
+        return [self._finalise_row(delayed[b:b + 1], P if isinstance(P, int) else int(P[b]), int(row_table[b].max_new_tokens), B, nq)[0] for b in range(B)]
+
+    def _finalise_row(self, delayed_row: torch.Tensor, P_b: int, max_new_tokens: int, B: int, nq: int):
+        """One row [1, nq, >= t_b] of a call of B utterances (or of a session of B slots): (its final codes, its first codebook-0 EOS column
+        or None, the column its own loop ends at)."""
+        offset0 = P_b + 1
+        t_b = P_b + max_new_tokens + nq
+        row = delayed_row[:, :, :t_b].to(torch.int64)
+        hit = (row[0, 0, offset0 + 1:] == self.eos_token_id).nonzero()
+        eos_column = offset0 + 1 + int(hit[0, 0]) if len(hit) else None
+        end = row_end_offset(offset0, t_b, B, nq, eos_column)
+        return finalise_codes(revert_delay_pattern(row), end, nq, self.eos_token_id), eos_column, end
 
     def _decode_loop(self, eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk=None, cond_lengths=None,
                      prefix_lens=None):

@@ -1,0 +1,185 @@
+"""The host side of `Zonos.serve()`: which request holds which slot of a running batch, and when it leaves.
+
+Pure Python: no torch device, no library.  A session has `slots` rows that step together; a request joins at a scheduling point (every
+`sched_every` decode steps), runs its own decode loop inside its slot - the device keeps the slot's length, stop state, parameters, column
+and step origin per row - and is retired at the first scheduling point at which a `generate_batch()` call of `slots` requests would have
+stopped watching it (`row_end_offset`).  Its codes are then cut and finalised exactly as `_finalise_rows` does for that call.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, Iterator, NamedTuple, Sequence
+
+STOP_CHECK_SPAN = 16          # a row whose remaining_steps reached 0 leaves at the next check of its own cadence: at most 16 steps on
+
+
+def stop_check_at(step_idx: int, batch_size: int) -> bool:
+    """The reference's stop-check cadence (tensor_ops.py:90-103) as `_decode_loop` runs it: is the stop flag read after loop step
+    `step_idx` (0-based) of a call of `batch_size` utterances?"""
+    return step_idx % 16 == 15 or (step_idx % 8 == 7 and max(0, batch_size * 10 - (step_idx + 1)) < 5)
+
+
+def row_end_offset(offset0: int, t_total: int, batch_size: int, nq: int, eos_column: int | None) -> int:
+    """The column at which the decode loop of a call of `batch_size` utterances would have ended had it watched one row alone
+    (`generate_batch`: every request is cut and finalised for itself, while the call runs on to its last row).  The row starts at column
+    `offset0` (audio prefix + 1) with its own `t_total` = prefix + max_new_tokens + nq columns and remaining_steps = t_total - offset0;
+    `eos_column` is the first column beyond offset0 whose codebook 0 holds EOS (None: there is none below t_total).  Loop step i writes
+    column offset0 + i + 1; a step that samples EOS in codebook 0 caps remaining_steps at nq; every step takes one off (tensor_ops.py:87,
+    155-211).  The loop leaves at the first check of the call's cadence (`stop_check_at`) at which remaining_steps <= 0 - the deferred
+    read-back of `_decode_loop` rolls back to that same check - or at t_total when the row's budget ends before any such check."""
+    remaining, offset = t_total - offset0, offset0
+    for step_idx in range(t_total - offset0):
+        offset += 1
+        if offset >= t_total:
+            break
+        if eos_column is not None and offset == eos_column:
+            remaining = min(remaining, nq)
+        remaining -= 1
+        if stop_check_at(step_idx, batch_size) and remaining <= 0:
+            return offset
+    return t_total
+
+
+def serve_slack(sched_every: int) -> int:
+    """The furthest a row can run past its own end before it is retired: to the next check of its own cadence, then to the next
+    scheduling point."""
+    return STOP_CHECK_SPAN + int(sched_every)
+
+
+def check_serve_request(cond_shape: Sequence[int], prefix_shape: Sequence[int] | None, max_new_tokens, cfg_scale: float, *, nq: int,
+                        d_model: int, guided: bool, max_len: int, width: int, slack: int) -> tuple[int, int]:
+    """What a session refuses (ValueError) before the request takes a slot; returns (L, P), its conditioning positions and audio prefix
+    frames.  `max_len`: KV positions per row of the session; `width`: columns of a row of its code buffer.  A request fits when its
+    prompt, its own steps and the slack stay inside both: L + P + max_new_tokens + nq + slack <= max_len (the last append of an
+    overrunning row) and P + max_new_tokens + nq + slack <= width (its penalty history stays in its own buffer row)."""
+    halves = 2 if guided else 1
+    if (float(cfg_scale) != 1.0) != guided:
+        raise ValueError(f"serve: cfg_scale={cfg_scale} in a session {'with' if guided else 'without'} guidance (guided and cfg_scale == 1 "
+                         "requests cannot share a session: the row layout differs)")
+    c = tuple(cond_shape)
+    if len(c) != 3 or c[0] != halves or c[1] < 1 or c[2] != d_model:
+        raise ValueError(f"serve: conditioning of shape {c}, expected [{halves}, L >= 1, {d_model}] at cfg_scale={cfg_scale}")
+    if int(max_new_tokens) != max_new_tokens or int(max_new_tokens) < 1:
+        raise ValueError(f"serve: max_new_tokens must be a positive integer, got {max_new_tokens}")
+    P = 0
+    if prefix_shape is not None:
+        a = tuple(prefix_shape)
+        if len(a) != 3 or a[0] != 1 or a[1] != nq:
+            raise ValueError(f"serve: audio_prefix_codes of shape {a}, expected [1, {nq}, P]")
+        P = int(a[2])
+    L, n = int(c[1]), int(max_new_tokens)
+    if L + P + n + nq + slack > max_len:
+        raise ValueError(f"serve: {L} conditioning positions + {P} prefix frames + {n} frames + {nq} + slack {slack} exceed the session's "
+                         f"{max_len} KV positions per row (max_prompt / max_new_tokens of serve())")
+    if P + n + nq + slack > width:
+        raise ValueError(f"serve: {P} prefix frames + {n} frames + {nq} + slack {slack} exceed the session's code buffer width {width}")
+    return L, P
+
+
+class ServeResult(NamedTuple):
+    """One request of `Zonos.serve()`: its pull index, and either its codes (int64 [1, 9, P + T], as `generate_batch` returns them) or
+    the ValueError that refused it."""
+    index: int
+    codes: object
+    error: Exception | None = None
+
+
+@dataclass
+class _Row:
+    index: int                  # the request's pull index
+    prefix_len: int
+    max_new_tokens: int
+    step0: int                  # the session step at which it was admitted
+    eos_known: bool = False
+    eos_column: int | None = None
+
+
+class SlotScheduler:
+    """Admits requests FIFO into free slots, retires rows, and says when the session ends.  The caller drives it at every scheduling
+    point: `pull` (admissions), `advance` (the steps it enqueued), `wants_eos` / `set_eos` (the codebook-0 cells of the rows whose
+    remaining_steps reached 0), `due` (the rows to retire)."""
+
+    def __init__(self, slots: int, nq: int, sched_every: int):
+        if int(slots) < 1 or int(sched_every) < 1 or int(nq) < 1:
+            raise ValueError(f"SlotScheduler: slots={slots}, nq={nq}, sched_every={sched_every} must all be >= 1")
+        self.slots, self.nq, self.sched_every = int(slots), int(nq), int(sched_every)
+        self.slack = serve_slack(sched_every)
+        self.step = 0                                  # decode steps of the session so far
+        self.rows: list[_Row | None] = [None] * self.slots
+        self.pulled = 0                                # items that were requests (an index each)
+        self.exhausted = False
+
+    # ---------------------------------------------------------------- admission
+    def free_slots(self) -> list[int]:
+        return [b for b, r in enumerate(self.rows) if r is None]
+
+    def pull(self, source: Iterator, accept: Callable) -> tuple[list, list]:
+        """One scheduling point's admissions: while a slot is free, take the next item of `source` - lazily, one item per free slot.
+        None: nothing is waiting right now.  `accept(request)` returns (prefix_len, max_new_tokens) or raises ValueError: a refused
+        request takes no slot.  Returns ([(slot, index, request)], [(index, error)])."""
+        admitted, refused = [], []
+        for slot in self.free_slots():
+            while not self.exhausted:
+                try:
+                    item = next(source)
+                except StopIteration:
+                    self.exhausted = True
+                    break
+                if item is None:
+                    return admitted, refused
+                index, self.pulled = self.pulled, self.pulled + 1
+                try:
+                    prefix_len, max_new = accept(item)
+                except ValueError as e:
+                    refused.append((index, e))
+                    continue
+                self.rows[slot] = _Row(index, int(prefix_len), int(max_new), self.step)
+                admitted.append((slot, index, item))
+                break
+            if self.exhausted:
+                break
+        return admitted, refused
+
+    # ---------------------------------------------------------------- the steps
+    def advance(self, steps: int | None = None) -> None:
+        self.step += self.sched_every if steps is None else int(steps)
+
+    def own_steps(self, slot: int) -> int:
+        r = self.rows[slot]
+        return -1 if r is None else self.step - r.step0
+
+    def holders(self) -> list[int | None]:
+        return [None if r is None else r.index for r in self.rows]
+
+    # ---------------------------------------------------------------- retirement
+    def wants_eos(self, remaining: Sequence[int]) -> list[int]:
+        """The busy slots whose remaining_steps reached 0 (stopped, or budget spent) and whose first codebook-0 EOS column is not known
+        yet: every column that decides it has been written."""
+        return [b for b, r in enumerate(self.rows) if r is not None and not r.eos_known and remaining[b] <= 0]
+
+    def set_eos(self, slot: int, eos_column: int | None) -> None:
+        r = self.rows[slot]
+        r.eos_known, r.eos_column = True, eos_column
+
+    def end_offset(self, slot: int) -> int:
+        r = self.rows[slot]
+        offset0 = r.prefix_len + 1
+        return row_end_offset(offset0, r.prefix_len + r.max_new_tokens + self.nq, self.slots, self.nq, r.eos_column)
+
+    def due(self) -> list[tuple[int, int, int]]:
+        """(slot, index, end offset) of every row whose own loop has left by now; the slots become idle."""
+        out = []
+        for b, r in enumerate(self.rows):
+            if r is None or not r.eos_known:
+                continue
+            end = self.end_offset(b)
+            if self.step - r.step0 >= end - (r.prefix_len + 1):
+                out.append((b, r.index, end))
+                self.rows[b] = None
+        return out
+
+    def all_idle(self) -> bool:
+        return all(r is None for r in self.rows)
+
+    def finished(self) -> bool:
+        return self.exhausted and self.all_idle()
