@@ -457,6 +457,15 @@ int zn_dac_span(const zn_dac_config* cfg, int32_t c0, int32_t n, int32_t at_end,
  * handle built with ZONOS_DAC_CONV=fp32; ZN_ERR_ARG when the range is empty. */
 int zn_dac_decode_span(zn_dac d, const int32_t* codes_dev, int32_t batch, int32_t c0, int32_t n, int32_t at_end, float* wav_dev,
                        zn_stream stream);
+/* Ragged span decode (Zonos.serve_stream): one pass over the decoder's layers for `rows` windows, each with its own place in its own
+ * sequence (1 <= rows <= 64).  ZN_ERR_ARG, naming the row and launching nothing, when a row's span is empty, n_r > n_max or
+ * s1_r - s0_r > t_max; ZN_ERR_UNSUPPORTED on a ZONOS_DAC_CONV=fp32 handle or when one row's window passes zn_dac_decode_span's limit. */
+typedef struct zn_dac_span_row { int32_t c0, n, at_end; } zn_dac_span_row;   /* HOST array */
+/* codes int32 [rows, n_codebooks, n_max]: row r holds frames [c0_r, c0_r + n_r) in its first n_r columns (cells beyond n_r are never
+ * read); wav fp32 [rows, t_max]: row r receives samples [s0_r, s1_r) of zn_dac_span(c0_r, n_r, at_end_r) in its first s1_r - s0_r
+ * entries (entries beyond are never written).  Row r's samples carry the bits of zn_dac_decode_span(batch = 1) on row r alone. */
+int zn_dac_decode_spans(zn_dac d, const int32_t* codes_dev, int32_t n_max, const zn_dac_span_row* rows_host, int32_t rows,
+                        float* wav_dev, int64_t t_max, zn_stream stream);
 /* DACAutoencoder.encode (zonos/autoencoder.py:103-117 -> DacModel.encode): wav fp32 [B, T] at the codec rate, T a
  * positive multiple of the hop (preprocess pads) -> codes int32 [B, n_codebooks, T / hop].  Needs the encoder.* and
  * quantizer.quantizers.{i}.in_proj tensors at zn_dac_create. */

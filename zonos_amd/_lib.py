@@ -84,6 +84,11 @@ class zn_dac_tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data_dev", C.c_void_p), ("numel", C.c_int64)]
 
 
+class zn_dac_span_row(C.Structure):
+    """One row of zn_dac_decode_spans: frames [c0, c0 + n) of the row's own sequence, `at_end` when they end it."""
+    _fields_ = [("c0", C.c_int32), ("n", C.c_int32), ("at_end", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/zonos_hip.h declares
 SIGNATURES = {
     "zn_abi_version": (C.c_int, []),
@@ -150,6 +155,7 @@ SIGNATURES = {
     "zn_dac_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "zn_dac_span": (C.c_int, [C.POINTER(zn_dac_config), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "zn_dac_decode_span": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "zn_dac_decode_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(zn_dac_span_row), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "zn_spk_create": (C.c_int, [C.POINTER(zn_dac_tensor), C.c_int32, C.POINTER(C.c_void_p)]),
     "zn_spk_destroy": (C.c_int, [C.c_void_p]),
     "zn_spk_last_error": (C.c_char_p, [C.c_void_p]),

@@ -9,6 +9,7 @@ that step is unpinned, identity at 44.1 kHz input).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 
@@ -139,6 +140,12 @@ class DACAutoencoder:
         kernels).  `stream`: the torch stream every launch goes to (default: the current stream of each call)."""
         return DACStream(self, stream)
 
+    def stream_set(self, stream: "torch.cuda.Stream | None" = None) -> "DACStreamSet":
+        """Any number of independent incremental decodes, by key, served together: `push({key: codes [1, 9, k]}, end=keys)` decodes the
+        windows of all keys that have something to emit in one ragged pass (zn_dac_decode_spans).  Per key, the concatenated outputs
+        equal `decode(all codes of the key)` bit for bit, as with `stream()`."""
+        return DACStreamSet(self, stream)
+
     def preprocess(self, wav: torch.Tensor, sr: int) -> torch.Tensor:
         """autoencoder.py:80-101: resample to 44.1 kHz, zero-pad on the LEFT to a multiple of 512 samples."""
         wav = sinc_resample(wav, sr, self.sampling_rate)
@@ -184,6 +191,27 @@ class DACAutoencoder:
         return torch.clamp(wav * 32767.0, -32767.0, 32767.0).to(torch.int16).squeeze(0).unsqueeze(1)
 
 
+def span_lead(ae: DACAutoencoder) -> int:
+    """Frames [c, ...) determine the samples from c * hop + lead on (c >= 1; the receptive field is shift-invariant by one hop per frame)."""
+    return ae.span(1, 1 << 12, True)[0] - ae.hop
+
+
+def window_step(span, hop: int, lead: int, c0: int, n: int, emitted: int, at_end: bool):
+    """The arithmetic of one rolling-window decode, shared by `DACStream` and `DACStreamSet`.  The window holds frames [c0, c0 + n) and
+    `emitted` samples have been returned; `span` is `DACAutoencoder.span`.  None when the window completes no new sample; otherwise
+    (s0, s1, skip, keep_from): decode samples [s0, s1) of the window, return them from index `skip` on, and afterwards keep the frames
+    from `keep_from` (>= c0) on - the earlier ones are read by no sample from s1 on."""
+    if n == 0:
+        return None
+    s0, s1 = span(c0, n, at_end)
+    if s1 <= emitted:
+        return None
+    if s0 > emitted:
+        raise RuntimeError(f"DAC stream: window from frame {c0} starts at sample {s0}, past {emitted}")
+    c = (s1 - lead) // hop if s1 >= hop + lead else 0
+    return s0, s1, emitted - s0, max(c, c0)
+
+
 class DACStream:
     """Rolling decode over `zn_dac_decode_span`: keeps on the device only the code frames that samples not yet returned still read
     (the decoder's receptive field, ~10 frames on each side at the 44.1 kHz ratios), and no activations: every call decodes its window
@@ -195,11 +223,17 @@ class DACStream:
         self._c0 = 0
         self._emitted = 0                         # samples returned so far
         self._closed = False
-        # frames [c, ...) determine the samples from c * hop + lead on (c >= 1; the receptive field is shift-invariant by one hop per frame)
-        self._lead = ae.span(1, 1 << 12, True)[0] - ae.hop
+        self._lead = span_lead(ae)
 
     def _torch_stream(self):
         return self._stream if self._stream is not None else torch.cuda.current_stream(self.ae.device)
+
+    def _ctx(self):
+        """The device and the stream of every launch of a call."""
+        st = contextlib.ExitStack()
+        st.enter_context(torch.cuda.device(self.ae.device))
+        st.enter_context(torch.cuda.stream(self._torch_stream()))
+        return st
 
     @torch.inference_mode()
     def push(self, codes: torch.Tensor) -> torch.Tensor:
@@ -211,7 +245,7 @@ class DACStream:
             raise ValueError(f"expected {self.ae.num_codebooks} codebooks, got {nq}")
         if self._win is not None and B != self._win.shape[0]:
             raise ValueError(f"batch size changed from {self._win.shape[0]} to {B}")
-        with torch.cuda.device(self.ae.device), torch.cuda.stream(self._torch_stream()):
+        with self._ctx():
             c32 = codes.to(device=self.ae.device, dtype=torch.int32)
             self._win = c32.contiguous() if self._win is None else torch.cat([self._win, c32], dim=2)
             return self._emit(False)
@@ -224,34 +258,122 @@ class DACStream:
         self._closed = True
         if self._win is None:
             return torch.empty(0, 1, 0, dtype=torch.float32, device=self.ae.device)
-        with torch.cuda.device(self.ae.device), torch.cuda.stream(self._torch_stream()):
+        with self._ctx():
             out = self._emit(True)
         self._win = None
         return out
 
+    def _decode(self, win: torch.Tensor, c0: int, at_end: bool, m: int) -> torch.Tensor:
+        """The device call: the m samples of the span of window `win` = frames [c0, c0 + n)."""
+        ae = self.ae
+        h = ae._handle()
+        wav = torch.empty(win.shape[0], 1, m, dtype=torch.float32, device=ae.device)
+        with ae._lock:
+            _lib.check_dac(_lib.load().zn_dac_decode_span(h, win.data_ptr(), win.shape[0], c0, win.shape[2], int(at_end), wav.data_ptr(),
+                                                          torch.cuda.current_stream(ae.device).cuda_stream), h, "zn_dac_decode_span")
+        return wav
+
     def _emit(self, at_end: bool) -> torch.Tensor:
         ae, win = self.ae, self._win
         B, n = win.shape[0], win.shape[2]
-        if n == 0:
+        step = window_step(ae.span, ae.hop, self._lead, self._c0, n, self._emitted, at_end)
+        if step is None:
             return torch.empty(B, 1, 0, dtype=torch.float32, device=ae.device)
-        s0, s1 = ae.span(self._c0, n, at_end)
-        if s1 <= self._emitted:
-            return torch.empty(B, 1, 0, dtype=torch.float32, device=ae.device)
-        if s0 > self._emitted:
-            raise RuntimeError(f"DACStream: window from frame {self._c0} starts at sample {s0}, past {self._emitted}")
-        h = ae._handle()
-        wav = torch.empty(B, 1, s1 - s0, dtype=torch.float32, device=ae.device)
-        with ae._lock:
-            _lib.check_dac(_lib.load().zn_dac_decode_span(h, win.data_ptr(), B, self._c0, n, int(at_end), wav.data_ptr(),
-                                                          torch.cuda.current_stream(ae.device).cuda_stream), h, "zn_dac_decode_span")
-        out = wav[..., self._emitted - s0:]
+        s0, s1, skip, keep = step
+        out = self._decode(win, self._c0, at_end, s1 - s0)[..., skip:]
         self._emitted = s1
-        # drop the frames that no sample from s1 on reads
-        c = (s1 - self._lead) // ae.hop if s1 >= ae.hop + self._lead else 0
-        if c > self._c0:
-            self._win = win[..., c - self._c0:].contiguous()
-            self._c0 = c
+        if keep > self._c0:                        # drop the frames that no sample from s1 on reads
+            self._win = win[..., keep - self._c0:].contiguous()
+            self._c0 = keep
         return out
+
+
+class _Window:
+    """One key of a DACStreamSet: frames [c0, c0 + n) as int32 [1, 9, n], and the samples returned so far."""
+    __slots__ = ("win", "c0", "emitted")
+
+    def __init__(self):
+        self.win, self.c0, self.emitted = None, 0, 0
+
+
+class DACStreamSet:
+    """Independent rolling windows by key (the slots of a `Zonos.serve_stream` session), decoded together: a `push` pads the windows of
+    all keys that complete a sample into one [rows, 9, n_max] tensor and makes ONE `zn_dac_decode_spans` call, in which every row has its
+    own place in its own sequence (frame 0, interior, or its end).  Per key the arithmetic is `DACStream`'s (`window_step`)."""
+
+    def __init__(self, ae: DACAutoencoder, stream=None):
+        self.ae, self._stream = ae, stream
+        self._keys: dict = {}
+        self._lead = span_lead(ae)
+
+    _torch_stream = DACStream._torch_stream
+    _ctx = DACStream._ctx
+
+    def __len__(self):
+        return len(self._keys)
+
+    def __contains__(self, key):
+        return key in self._keys
+
+    def _decode_rows(self, codes: torch.Tensor, rows: list[tuple[int, int, bool]], t_max: int) -> torch.Tensor:
+        """The device call: codes int32 [rows, 9, n_max], rows = [(c0, n, at_end)] -> float32 [rows, t_max], row r's span in front."""
+        ae = self.ae
+        h = ae._handle()
+        wav = torch.empty(len(rows), t_max, dtype=torch.float32, device=ae.device)
+        arr = (_lib.zn_dac_span_row * len(rows))(*[_lib.zn_dac_span_row(c0, n, int(e)) for c0, n, e in rows])
+        with ae._lock:
+            _lib.check_dac(_lib.load().zn_dac_decode_spans(h, codes.data_ptr(), codes.shape[2], arr, len(rows), wav.data_ptr(), t_max,
+                                                           torch.cuda.current_stream(ae.device).cuda_stream), h, "zn_dac_decode_spans")
+        return wav
+
+    @torch.inference_mode()
+    def push(self, chunks: dict, end=()) -> dict:
+        """chunks {key: codes [1, 9, k]} (the key's next k frames; a new key starts a stream) -> {key: float32 [1, 1, m]} for every key
+        of `chunks` and of `end`: the samples that became final.  Keys in `end` are flushed - their frames so far end their sequence -
+        and forgotten.  A key whose window completes no sample takes no row of the call and gets m = 0."""
+        ae, nq = self.ae, self.ae.num_codebooks
+        end = set(end)
+        for key, codes in chunks.items():
+            if codes.dim() != 3 or codes.shape[0] != 1 or codes.shape[1] != nq:
+                raise ValueError(f"key {key!r}: expected codes [1, {nq}, k], got {tuple(codes.shape)}")
+        out, plan = {}, []
+        with self._ctx():
+            for key in list(chunks) + [k for k in end if k not in chunks]:
+                w = self._keys.get(key)
+                if key in chunks:
+                    if w is None:
+                        w = self._keys[key] = _Window()
+                    c32 = chunks[key].to(device=ae.device, dtype=torch.int32)
+                    w.win = c32.contiguous() if w.win is None else torch.cat([w.win, c32], dim=2)
+                out[key] = torch.empty(1, 1, 0, dtype=torch.float32, device=ae.device)
+                if w is None or w.win is None:
+                    continue
+                step = window_step(ae.span, ae.hop, self._lead, w.c0, w.win.shape[2], w.emitted, key in end)
+                if step is not None:
+                    plan.append((key, w, step))
+            if plan:
+                n_max = max(w.win.shape[2] for _, w, _ in plan)
+                t_max = max(s1 - s0 for _, _, (s0, s1, _, _) in plan)
+                if len(plan) == 1:
+                    codes = plan[0][1].win
+                else:                                 # (the cells beyond a row's n are never read: any valid code will do)
+                    codes = torch.zeros(len(plan), nq, n_max, dtype=torch.int32, device=ae.device)
+                    for r, (_, w, _) in enumerate(plan):
+                        codes[r, :, :w.win.shape[2]] = w.win[0]
+                wav = self._decode_rows(codes, [(w.c0, w.win.shape[2], key in end) for key, w, _ in plan], t_max)
+                for r, (key, w, (s0, s1, skip, keep)) in enumerate(plan):
+                    out[key] = wav[r:r + 1, None, skip:s1 - s0]
+                    w.emitted = s1
+                    if keep > w.c0:
+                        w.win = w.win[..., keep - w.c0:].contiguous()
+                        w.c0 = keep
+            for key in end:
+                self._keys.pop(key, None)
+        return out
+
+    def drop(self, key) -> None:
+        """Forget a key without decoding its tail (an abandoned request)."""
+        self._keys.pop(key, None)
 
 
 _GLOBAL_DAC_AUTOENCODER = None

@@ -76,8 +76,10 @@ ZN_DEVINL float c3_sin2(float a) {
 // RB: 32-row blocks per wave (workgroup = RB * 128 output times); MAXT: taps the launch may have (7: the dilated 7-tap layers, halo
 // of up to 54 rows; 2: the two taps of a transposed convolution's phase; 1: the pointwise layers - small staging, several workgroups
 // per CU hide one another's per-stage latency).
+// The body of a workgroup: batch element b's input starts at row b * in_rows of a.in and its outputs at row b * out_rows (a whole-launch
+// geometry: in_rows = a.Tin, out_rows = a.Tout; dac_conv3_rows_kernel: the per-layer maxima over rows, a.Tin / a.Tout being row b's own).
 template <int RB, int MAXT>
-__global__ __launch_bounds__(256, 2) void dac_conv3_kernel(Conv3Args a) {
+ZN_DEVINL void dac_conv3_body(const Conv3Args& a, const int in_rows, const int out_rows) {
   constexpr int TM = RB * 128, NT = C3_TN / 32, HALO = MAXT == 7 ? 54 : (MAXT == 2 ? 1 : 0), MAXROWS = TM + HALO;
   extern __shared__ __attribute__((aligned(16))) unsigned char c3_smem[];
   unsigned char* s_in = c3_smem;                            // [MAXROWS][96]
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(256, 2) void dac_conv3_kernel(Conv3Args a) {
   const int offmin = a.off0 < offlast ? a.off0 : offlast, offmax = a.off0 < offlast ? offlast : a.off0;
   const int nrows = TM + offmax - offmin;
   const int nck = a.Cin / C3_KC;
-  const float* inb = a.in + (size_t)b * a.Tin * a.Cin;
+  const float* inb = a.in + (size_t)b * in_rows * a.Cin;
   const bf16_t* wp = a.w + (size_t)phase * nck * a.taps * a.CoutPad * 48;
   f32x16 acc[RB][NT];
 #pragma unroll
@@ -195,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void dac_conv3_kernel(Conv3Args a) {
         const int m = m0 + wave * (32 * RB) + rb * 32 + rowi;
         const int to = m * a.ostride + a.ooff + phase;
         if (m >= a.M || to < 0 || to >= a.Tout) continue;
-        const size_t o = ((size_t)b * a.Tout + to) * a.Cout + co;
+        const size_t o = ((size_t)b * out_rows + to) * a.Cout + co;
         float v = acc[rb][nt][reg] + bv;
         if (a.skip) v = a.skip[o] + v;
         if (a.out32) a.out32[o] = v;
@@ -203,6 +205,27 @@ __global__ __launch_bounds__(256, 2) void dac_conv3_kernel(Conv3Args a) {
       }
     }
   }
+}
+
+template <int RB, int MAXT>
+__global__ __launch_bounds__(256, 2) void dac_conv3_kernel(Conv3Args a) {
+  dac_conv3_body<RB, MAXT>(a, a.Tin, a.Tout);
+}
+
+// Rows with their own windows (zn_dac_decode_spans): one launch, the five integers of the geometry per batch element.  The table travels
+// by value in the kernel arguments (64 x 20 bytes) and is indexed with the workgroup-uniform b: scalar loads, no device table to fill.
+// Row b's buffers start at row b * in_rows / b * out_rows (the maxima over rows); its own Tin bounds its buffer resource, so rows outside
+// [0, Tin_b) read as the zero padding, and its own Tout bounds the stores.  A workgroup past row b's tiles leaves before it issues a load
+// or meets a barrier (m0 and M_b are uniform over the workgroup).
+#define C3_MAX_ROWS 64
+struct Conv3Row { int Tin, Tout, M, off0, ooff; };
+struct Conv3Rows { Conv3Row r[C3_MAX_ROWS]; int in_rows, out_rows; };
+template <int RB, int MAXT>
+__global__ __launch_bounds__(256, 2) void dac_conv3_rows_kernel(Conv3Args a, Conv3Rows g) {
+  const Conv3Row r = g.r[blockIdx.z / a.phases];
+  if ((int)(C3_NFAST ? blockIdx.y : blockIdx.x) * (RB * 128) >= r.M) return;
+  a.Tin = r.Tin; a.Tout = r.Tout; a.M = r.M; a.off0 = r.off0; a.ooff = r.ooff;
+  dac_conv3_body<RB, MAXT>(a, g.in_rows, g.out_rows);
 }
 
 // conv weight [Cout][Cin][K] -> W3 [Cin/16][K][CoutPad][3][16]
@@ -232,7 +255,9 @@ template <int RB, int MAXT> static inline size_t zn_conv3_lds() {
   return (size_t)(RB * 128 + (MAXT == 7 ? 54 : (MAXT == 2 ? 1 : 0))) * C3_ROW + (size_t)MAXT * C3_TN * C3_ROW;
 }
 template <int RB, int MAXT> static inline hipError_t zn_conv3_attr() {
-  return hipFuncSetAttribute((const void*)dac_conv3_kernel<RB, MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)zn_conv3_lds<RB, MAXT>());
+  hipError_t e = hipFuncSetAttribute((const void*)dac_conv3_kernel<RB, MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)zn_conv3_lds<RB, MAXT>());
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute((const void*)dac_conv3_rows_kernel<RB, MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)zn_conv3_lds<RB, MAXT>());
 }
 static inline hipError_t zn_conv3_set_attrs() {
   hipError_t e;
@@ -254,4 +279,22 @@ static inline void zn_conv3_launch(const Conv3Args& a, int B, hipStream_t s) {
   const bool big = (long)((a.M + 255) / 256) * (a.CoutPad / C3_TN) * B * a.phases >= 512;
   if (a.taps == 2) { if (big) zn_conv3_go<2, 2>(a, B, s); else zn_conv3_go<1, 2>(a, B, s); return; }
   if (big) zn_conv3_go<2, 7>(a, B, s); else zn_conv3_go<1, 7>(a, B, s);
+}
+// The rows form: a.Tin / Tout / M / off0 / ooff are not read (every row brings its own in g); the grid spans the longest row's tiles, and
+// `big` counts the live tiles of all rows.
+template <int RB, int MAXT> static inline void zn_conv3_rows_go(const Conv3Args& a, const Conv3Rows& g, int rows, hipStream_t s) {
+  int mt = 1;
+  for (int r = 0; r < rows; ++r) mt = std::max(mt, (g.r[r].M + RB * 128 - 1) / (RB * 128));
+  const int ntile = a.CoutPad / C3_TN;
+  const dim3 grid = C3_NFAST ? dim3(ntile, mt, rows * a.phases) : dim3(mt, ntile, rows * a.phases);
+  const size_t lds = zn_conv3_lds<RB, MAXT>();
+  hipLaunchKernelGGL((dac_conv3_rows_kernel<RB, MAXT>), grid, dim3(256), lds, s, a, g);
+}
+static inline void zn_conv3_rows_launch(const Conv3Args& a, const Conv3Rows& g, int rows, hipStream_t s) {
+  if (a.taps == 1) return zn_conv3_rows_go<C3_K1_RB, 1>(a, g, rows, s);
+  long live = 0;
+  for (int r = 0; r < rows; ++r) live += (long)((g.r[r].M + 255) / 256) * (a.CoutPad / C3_TN) * a.phases;
+  const bool big = live >= 512;
+  if (a.taps == 2) { if (big) zn_conv3_rows_go<2, 2>(a, g, rows, s); else zn_conv3_rows_go<1, 2>(a, g, rows, s); return; }
+  if (big) zn_conv3_rows_go<2, 7>(a, g, rows, s); else zn_conv3_rows_go<1, 7>(a, g, rows, s);
 }

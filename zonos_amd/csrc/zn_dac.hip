@@ -74,15 +74,16 @@ __global__ void dac_wconvt_kernel(const float* w, float* o, int Cin, int Cout, i
 // and meet through one DPP add.
 #define DAC_FIN_T 128
 #define DAC_FIN_MAXP 16
-__global__ __launch_bounds__(256) void dac_final_kernel(const float* in, const float* alpha, const float* w /*[1][C][7]*/, const float* bias,
-                                                        float* out, int T, int C, int Tin, int ioff) {
+// (the body of a workgroup: batch element b's input rows start at row b * in_rows of `in`, its samples at out + b * out_stride)
+ZN_DEVINL void dac_final_body(const float* in, const float* alpha, const float* w /*[1][C][7]*/, const float* bias, float* out, const int T,
+                              const int C, const int Tin, const int ioff, const int in_rows, const int64_t out_stride) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* s_x = smem;                         // [DAC_FIN_T + 6][C + 1]
   float* s_w = smem + (DAC_FIN_T + 6) * (C + 1);   // [7][C]
   // output time t reads input rows t + ioff - 3 .. t + ioff + 3 of the [Tin]-row input; rows outside [0, Tin) are the zero padding (a whole
   // clip: Tin = T, ioff = 0; a span: the window's buffer, which reaches past its ends only where the sequence ends)
   const int t0 = blockIdx.x * DAC_FIN_T, b = blockIdx.y, tid = threadIdx.x;
-  const float* inb = in + (size_t)b * Tin * C;
+  const float* inb = in + (size_t)b * in_rows * C;
   const int c4n = C / 4, npiece = (DAC_FIN_T + 6) * c4n;
   f32x4 r[DAC_FIN_MAXP];
 #pragma unroll
@@ -118,7 +119,40 @@ __global__ __launch_bounds__(256) void dac_final_kernel(const float* in, const f
     for (int c = 0; c < C; c += 2) acc = fmaf(xr[c], wr[c], acc);
   }
   acc += dpp_mov<ZN_DPP_XOR1>(acc);
-  if (hf == 0 && t < T) out[(size_t)b * T + t] = tanhf(acc + bias[0]);
+  if (hf == 0 && t < T) out[(size_t)b * out_stride + t] = tanhf(acc + bias[0]);
+}
+__global__ __launch_bounds__(256) void dac_final_kernel(const float* in, const float* alpha, const float* w, const float* bias, float* out, int T,
+                                                        int C, int Tin, int ioff) {
+  dac_final_body(in, alpha, w, bias, out, T, C, Tin, ioff, Tin, T);
+}
+
+// ---- rows with their own windows (zn_dac_decode_spans).  The per-row integers travel by value in the kernel arguments and are indexed
+// with the workgroup-uniform row; a workgroup past its row's extent leaves before any load or barrier.
+#define DAC_MAX_ROWS C3_MAX_ROWS
+struct DacCodeRows { int n[DAC_MAX_ROWS]; };
+// codes [rows][nq][n_max], row r's frames in its first n[r] columns -> z[r][t][c], rows n_max apart
+__global__ __launch_bounds__(256) void dac_codes_rows_kernel(const int* codes, const float* table, float* z, int nq, int n_max, int hidden, int cbsize,
+                                                             DacCodeRows g) {
+  const int t = blockIdx.x, b = blockIdx.y;
+  if (t >= g.n[b]) return;
+  for (int c = threadIdx.x; c < hidden; c += 256) {
+    float acc = 0.f;
+    for (int i = 0; i < nq; ++i) {
+      int code = codes[((size_t)b * nq + i) * n_max + t];
+      code = code < 0 ? 0 : (code >= cbsize ? cbsize - 1 : code);
+      acc = acc + table[((size_t)i * cbsize + code) * hidden + c];
+    }
+    z[((size_t)b * n_max + t) * hidden + c] = acc;
+  }
+}
+struct DacFinalRow { int T, Tin, ioff; };
+struct DacFinalRows { DacFinalRow r[DAC_MAX_ROWS]; };
+// in: rows in_rows apart; out: row r's T_r samples at out + r * t_max
+__global__ __launch_bounds__(256) void dac_final_rows_kernel(const float* in, const float* alpha, const float* w, const float* bias, float* out, int C,
+                                                             int in_rows, int64_t t_max, DacFinalRows g) {
+  const DacFinalRow r = g.r[blockIdx.y];
+  if ((int)blockIdx.x * DAC_FIN_T >= r.T) return;
+  dac_final_body(in, alpha, w, bias, out, r.T, C, r.Tin, r.ioff, in_rows, t_max);
 }
 
 // ------------------------------------------------------------------------------------------------ encoder pieces
@@ -433,6 +467,7 @@ extern "C" int zn_dac_create(const zn_dac_config* cfg, const zn_dac_tensor* tens
   { hipError_t e = zn_conv3_set_attrs(); if (e != hipSuccess) { d->err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(e); return fail(ZN_ERR_HIP); } }
   { hipError_t e = zn_conv_set_attrs(); if (e != hipSuccess) { d->err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(e); return fail(ZN_ERR_HIP); } }
   (void)hipFuncSetAttribute((const void*)dac_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)hipFuncSetAttribute((const void*)dac_final_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   *out = d;
   return ZN_OK;
 }
@@ -662,6 +697,115 @@ extern "C" int zn_dac_decode_span(zn_dac d, const int32_t* codes, int32_t B, int
   const int T = (int)(s1 - s0);
   hipLaunchKernelGGL(dac_final_kernel, dim3((T + DAC_FIN_T - 1) / DAC_FIN_T, B), dim3(256), lds, s, x, d->fin_alpha, d->fin_w, d->fin_b, wav, T, d->fin_C,
                      LI, (int)(s0 - I0));
+  DHIP(d, hipGetLastError());
+  return ZN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ ragged span decode (serve_stream)
+// One layer for rows with their own windows: row r's five integers as launch_conv3_win derives them, from that row's
+// (I0, LI, O0, LO, u0, u1); the buffers are strided by the maxima of LI / LO over rows (in_rows > 0: the input's stride, given).
+struct RowWin { int64_t I0; int LI; int64_t O0; int LO; int64_t u0, u1; };
+static void launch_conv3_rows(const ConvLayer& L, const float* in, const float* skip, float* out32, float* out_act, const float* alpha_next,
+                              const RowWin* w, int rows, bool transpose, hipStream_t s, int in_rows = 0) {
+  Conv3Args a{};
+  a.in = in; a.Cin = L.Cin; a.w = L.w3; a.bias = L.bias; a.alpha = alpha_next; a.skip = skip; a.out32 = out32; a.out_act = out_act;
+  a.Cout = L.Cout; a.CoutPad = zn_conv3_pad(L.Cout);
+  Conv3Rows g{};
+  for (int r = 0; r < rows; ++r) {
+    Conv3Row& R = g.r[r];
+    R.Tin = w[r].LI; R.Tout = w[r].LO;
+    g.in_rows = std::max(g.in_rows, w[r].LI); g.out_rows = std::max(g.out_rows, w[r].LO);
+    if (!transpose) {
+      R.M = (int)(w[r].u1 - w[r].u0); R.off0 = -((L.K - 1) * L.dil) / 2 + (int)(w[r].u0 - w[r].I0); R.ooff = (int)(w[r].u0 - w[r].O0);
+    } else {
+      const int64_t st = L.stride, padT = (st + 1) / 2, g0 = floordiv(w[r].u0 + padT, st), g1 = floordiv(w[r].u1 - 1 + padT, st);
+      R.M = (int)(g1 - g0 + 1); R.off0 = (int)(g0 - w[r].I0); R.ooff = (int)(g0 * st - padT - w[r].O0);
+    }
+  }
+  if (in_rows > 0) g.in_rows = in_rows;
+  if (!transpose) { a.taps = L.K; a.offstep = L.dil; a.ostride = 1; a.phases = 1; }
+  else { a.taps = 2; a.offstep = -1; a.ostride = L.stride; a.phases = L.stride; }
+  zn_conv3_rows_launch(a, g, rows, s);
+}
+
+extern "C" int zn_dac_decode_spans(zn_dac d, const int32_t* codes, int32_t n_max, const zn_dac_span_row* rh, int32_t rows, float* wav, int64_t t_max,
+                                   zn_stream stream) {
+  if (!d) return ZN_ERR_ARG;
+  if (!d->split3)
+    DFAIL(d, ZN_ERR_UNSUPPORTED, "zn_dac_decode_spans: the handle was created with ZONOS_DAC_CONV=fp32; span decode runs on the three-term kernels only");
+  if (!codes || !wav || !rh || n_max < 1 || t_max < 1) DFAIL(d, ZN_ERR_ARG, "zn_dac_decode_spans: bad argument");
+  if (rows < 1 || rows > DAC_MAX_ROWS) DFAIL(d, ZN_ERR_ARG, "zn_dac_decode_spans: %d rows, one call holds 1..%d", rows, DAC_MAX_ROWS);
+  const zn_dac_config& c = d->cfg;
+  auto len = [](const int64_t* r) { return r[1] - r[0]; };
+  // every row's plan first: nothing is launched unless all rows pass
+  std::vector<DacSpan> P(rows);
+  std::vector<int64_t> S0(rows), S1(rows);
+  int64_t c1max = 0, xtmax[8] = {0};
+  for (int r = 0; r < rows; ++r) {
+    const int32_t c0 = rh[r].c0, n = rh[r].n;
+    if (c0 < 0 || n < 1) DFAIL(d, ZN_ERR_ARG, "zn_dac_decode_spans: row %d: bad window (c0 = %d, n = %d)", r, c0, n);
+    if (n > n_max) DFAIL(d, ZN_ERR_ARG, "zn_dac_decode_spans: row %d: %d frames, the codes hold n_max = %d per row", r, n, n_max);
+    if (zn_dac_span(&c, c0, n, rh[r].at_end, &S0[r], &S1[r]) != ZN_OK) DFAIL(d, ZN_ERR_ARG, "row %d: %s", r, g_dac_err.c_str());
+    if (S1[r] <= S0[r]) DFAIL(d, ZN_ERR_ARG, "zn_dac_decode_spans: row %d: frames [%d, %d) complete no sample (zn_dac_span)", r, c0, c0 + n);
+    if (S1[r] - S0[r] > t_max)
+      DFAIL(d, ZN_ERR_ARG, "zn_dac_decode_spans: row %d: %lld samples, wav holds t_max = %lld per row", r, (long long)(S1[r] - S0[r]), (long long)t_max);
+    dac_span_back(c, S0[r], S1[r], (int64_t)c0 + n, P[r]);
+    if (P[r].lat[0] < c0 || P[r].lat[1] > (int64_t)c0 + n) DFAIL(d, ZN_ERR_ARG, "zn_dac_decode_spans: row %d: inconsistent plan", r);
+    size_t need = std::max((size_t)n * c.hidden_size, (size_t)len(P[r].c1) * c.decoder_hidden_size);
+    int ch = c.decoder_hidden_size;
+    for (int i = 0; i < c.n_ratios; ++i) { ch /= 2; need = std::max(need, (size_t)len(P[r].xt[i]) * ch); xtmax[i] = std::max(xtmax[i], len(P[r].xt[i])); }
+    c1max = std::max(c1max, len(P[r].c1));
+    if (need * 4 >= 0x7fffffffull)                      // 32-bit buffer offsets inside a row (zn_dac_decode_span's limit)
+      DFAIL(d, ZN_ERR_UNSUPPORTED, "zn_dac_decode_spans: row %d: a window of %d frames is too long for the three-term kernels", r, n);
+  }
+  // a row of a buffer holds the longest window of any row of the layer that lives there
+  size_t need = std::max((size_t)n_max * c.hidden_size, (size_t)c1max * c.decoder_hidden_size);
+  { int ch = c.decoder_hidden_size;
+    for (int i = 0; i < c.n_ratios; ++i) { ch /= 2; need = std::max(need, (size_t)xtmax[i] * ch); } }
+  need *= rows;
+  hipStream_t s = (hipStream_t)stream;
+  if (need > d->buf_elems) {
+    DHIP(d, hipStreamSynchronize(s));
+    for (auto& p : d->buf) { if (p) (void)hipFree(p); p = nullptr; }
+    for (auto& p : d->buf) DHIP(d, hipMalloc(&p, need * sizeof(float)));
+    d->buf_elems = need;
+  }
+  float *x = d->buf[0], *p = d->buf[1], *q = d->buf[2];
+  { DacCodeRows g{};
+    for (int r = 0; r < rows; ++r) g.n[r] = rh[r].n;
+    hipLaunchKernelGGL(dac_codes_rows_kernel, dim3(n_max, rows), dim3(256), 0, s, codes, d->table, x, c.n_codebooks, n_max, c.hidden_size,
+                       c.codebook_size, g); }
+  // zn_dac_decode_span's sequence of layers; w[r]: row r's windows of the layer at hand.  The latent's rows are n_max apart, which the
+  // longest window may not reach: decoder.conv1 is told its input stride.
+  std::vector<RowWin> w(rows);
+  std::vector<int64_t> I0(rows); std::vector<int> LI(rows);
+  for (int r = 0; r < rows; ++r) w[r] = RowWin{rh[r].c0, rh[r].n, P[r].c1[0], (int)len(P[r].c1), P[r].c1[0], P[r].c1[1]};
+  launch_conv3_rows(d->conv1, x, nullptr, nullptr, q, d->blocks[0].convt.alpha, w.data(), rows, false, s, n_max);
+  std::swap(p, q);
+  for (int r = 0; r < rows; ++r) { I0[r] = P[r].c1[0]; LI[r] = (int)len(P[r].c1); }
+  for (int bi = 0; bi < c.n_ratios; ++bi) {
+    auto& Bk = d->blocks[bi];
+    for (int r = 0; r < rows; ++r) w[r] = RowWin{I0[r], LI[r], P[r].xt[bi][0], (int)len(P[r].xt[bi]), P[r].xt[bi][0], P[r].xt[bi][1]};
+    launch_conv3_rows(Bk.convt, p, nullptr, x, q, Bk.c1[0].alpha, w.data(), rows, true, s);
+    std::swap(p, q);
+    for (int u = 0; u < 3; ++u) {
+      const bool last_unit = u == 2, last_block = bi + 1 == c.n_ratios;
+      const float* an = !last_unit ? Bk.c1[u + 1].alpha : (!last_block ? d->blocks[bi + 1].convt.alpha : nullptr);
+      for (int r = 0; r < rows; ++r) {
+        const int64_t X0 = P[r].xt[bi][0]; const int Lx = (int)len(P[r].xt[bi]);
+        w[r] = RowWin{X0, Lx, X0, Lx, P[r].un[bi][u][0], P[r].un[bi][u][1]};
+      }
+      launch_conv3_rows(Bk.c1[u], p, nullptr, nullptr, q, Bk.c2[u].alpha, w.data(), rows, false, s);
+      launch_conv3_rows(Bk.c2[u], q, x, x, (last_unit && last_block) ? nullptr : p, an, w.data(), rows, false, s);
+    }
+    for (int r = 0; r < rows; ++r) { I0[r] = P[r].xt[bi][0]; LI[r] = (int)len(P[r].xt[bi]); }
+  }
+  DacFinalRows f{};
+  int64_t tmaxrow = 0;
+  for (int r = 0; r < rows; ++r) { f.r[r] = DacFinalRow{(int)(S1[r] - S0[r]), LI[r], (int)(S0[r] - I0[r])}; tmaxrow = std::max(tmaxrow, S1[r] - S0[r]); }
+  const size_t lds = (size_t)((DAC_FIN_T + 6) * (d->fin_C + 1) + 9 * d->fin_C) * sizeof(float);
+  hipLaunchKernelGGL(dac_final_rows_kernel, dim3((unsigned)((tmaxrow + DAC_FIN_T - 1) / DAC_FIN_T), rows), dim3(256), lds, s, x, d->fin_alpha, d->fin_w,
+                     d->fin_b, wav, d->fin_C, (int)xtmax[c.n_ratios - 1], t_max, f);
   DHIP(d, hipGetLastError());
   return ZN_OK;
 }

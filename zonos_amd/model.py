@@ -25,7 +25,8 @@ from .backbone import BACKBONES, HipEngine
 from .codebook_pattern import apply_delay_pattern, revert_delay_pattern
 from .conditioning import ConditioningCache, PrefixConditioner, pad_conditionings, prepare_conditioning_with_cache
 from .config import InferenceParams, ZonosConfig
-from .serving import ServeResult, SlotScheduler, check_serve_request, row_end_offset, serve_slack, stop_check_at  # noqa: F401  (row_end_offset, stop_check_at: defined there, used and re-exported here)
+from .serving import (ServeChunk, ServeResult, SlotScheduler, StreamLedger, check_serve_request, release_limit, row_end_offset,  # noqa: F401
+                      serve_slack, stop_check_at)     # (release_limit, row_end_offset, stop_check_at: defined there, used and re-exported here)
 from .utils import DEFAULT_DEVICE, find_multiple
 
 DEFAULT_BACKBONE_CLS = next(iter(BACKBONES.values()))
@@ -68,15 +69,6 @@ def finalise_codes(out: torch.Tensor, offset: int, nq: int, eos_id: int) -> torc
             valid_length = pos
             break
     return map_codes(out[..., :valid_length])
-
-
-def release_limit(offset: int, nq: int, eos_frame: int | None) -> int:
-    """Frames [0, limit) that are final while the generation runs, once the steps up to column `offset` have run: a frame is complete
-    when its codebook nq-1 (column f + nq) is written, and every frame before the first one whose codebook 0 is EOS (`eos_frame`, None
-    while there is none) survives `finalise_codes` (codebooks 1.. cannot sample EOS before the stop; the EOS diagonal after it lands on
-    the stop frame itself).  What the end keeps beyond that, `finalise_codes` decides."""
-    limit = max(0, offset - nq + 1)
-    return limit if eos_frame is None else min(limit, eos_frame)
 
 
 @dataclass
@@ -427,8 +419,9 @@ class Zonos(nn.Module):
         collection releases them.  A session runs no persistent kernel, so no hand-off timeout can occur; any library error raises.
         `_trace`: one step per enqueue; "logits" receives [slots, 9, 1025] per admission and per step, "slots" a (kind, session step,
         request index per slot) record for each of them (an admission's record names the admitted slots only).  `_stats` (tools/servebench.py)
-        receives the session's decode steps and admissions, and with _stats["time_admissions"] set the seconds spent in admissions, each
-        bracketed by a synchronisation."""
+        receives the session's decode steps and admissions, per request index the time.perf_counter() at which its admission was enqueued
+        (_stats["admitted_at"]), and with _stats["time_admissions"] set the seconds spent in admissions, each bracketed by a
+        synchronisation."""
         slots, sched_every, max_prompt, max_new_tokens = int(slots), int(sched_every), int(max_prompt), int(max_new_tokens)
         if not 1 <= slots <= MAX_BATCH_REQUESTS:
             raise ValueError(f"serve: slots must lie in 1..{MAX_BATCH_REQUESTS}, got {slots}")
@@ -439,13 +432,40 @@ class Zonos(nn.Module):
         dev = self.device
         return self._serve_gen(dev, torch.cuda.current_stream(dev), iter(requests), slots, max_prompt, max_new_tokens, bool(guided), sched_every, _trace, _stats)
 
-    def _serve_gen(self, dev, ts, source, slots, max_prompt, max_new_tokens, guided, sched_every, _trace, _stats=None):
+    def serve_stream(self, requests, slots: int = 8, max_prompt: int = 64, max_new_tokens: int = 86 * 30, guided: bool = True,
+                     sched_every: int = 8, chunk_frames: int = 16, _stats: dict | None = None) -> Iterator[ServeChunk]:
+        """`serve()` with audio as it happens: a generator of `ServeChunk(index, codes, wav, done, error)`.  The session is `serve()`'s -
+        the same admissions, steps and retirements.  At a scheduling point every busy slot whose final frames (`release_limit` of its
+        own column) have grown by at least `chunk_frames` since its last chunk yields them with the samples the DAC can decode from
+        them, and every request retired there yields its last chunk (done=True): what `_finalise_row` keeps beyond the frames released.
+        The windows of all slots are decoded in one ragged pass (`DACAutoencoder.stream_set`, zn_dac_decode_spans) on the session's
+        stream.  For every request the concatenated codes equal the `ServeResult.codes` of `serve()` for the same source and settings,
+        and the concatenated wav `autoencoder.decode()` of them, bit for bit.  A refused request yields
+        ServeChunk(index, None, None, True, ValueError).  The engine is held as by `serve()`; `_stats` as there."""
+        if int(chunk_frames) < 1:
+            raise ValueError(f"serve_stream: chunk_frames must be >= 1, got {chunk_frames}")
+        slots, sched_every, max_prompt, max_new_tokens = int(slots), int(sched_every), int(max_prompt), int(max_new_tokens)
+        if not 1 <= slots <= MAX_BATCH_REQUESTS:
+            raise ValueError(f"serve_stream: slots must lie in 1..{MAX_BATCH_REQUESTS}, got {slots}")
+        if sched_every < 1 or max_prompt < 1 or max_new_tokens < 1:
+            raise ValueError(f"serve_stream: sched_every={sched_every}, max_prompt={max_prompt}, max_new_tokens={max_new_tokens} must all be >= 1")
+        if self.device.type != "cuda":
+            raise _lib.ZonosHipError("zonos_amd runs on MI355X only: move the model to a cuda device (no CPU fallback)")
+        dev = self.device
+        return self._serve_gen(dev, torch.cuda.current_stream(dev), iter(requests), slots, max_prompt, max_new_tokens, bool(guided), sched_every, None,
+                               _stats, int(chunk_frames))
+
+    def _serve_gen(self, dev, ts, source, slots, max_prompt, max_new_tokens, guided, sched_every, _trace, _stats=None, chunk_frames=None):
+        """The session of serve() (chunk_frames None: yields ServeResult) and of serve_stream() (yields ServeChunk)."""
         nq, d, mask = self.config.codebook_dimension, self.config.backbone.d_model, self.masked_token_id
         halves = 2 if guided else 1
         R = slots * halves
         slack = serve_slack(sched_every)
         width = max_prompt + max_new_tokens + nq + slack              # columns of a slot's row of the code buffer
         sched = SlotScheduler(slots, nq, sched_every)
+        streaming = chunk_frames is not None
+        ledger = StreamLedger(nq, chunk_frames, self.eos_token_id) if streaming else None
+        dacs = self.autoencoder.stream_set(ts) if streaming else None
         eng = self._acquire_engine((R + 1) // 2)
         begun = False
         st = ts.cuda_stream
@@ -512,13 +532,18 @@ class Zonos(nn.Module):
                 for slot, index, _ in admitted:
                     held[slot] = index
                 record("admit", held)
+                for j, (slot, index, r) in enumerate(admitted):
+                    if streaming:
+                        ledger.open(slot, Ps[j], int(r.max_new_tokens))
+                    if _stats is not None:
+                        _stats.setdefault("admitted_at", {})[index] = time.perf_counter()
 
             rem, own = (C.c_int32 * slots)(), (C.c_int32 * slots)()
             while True:
                 out = []
                 with torch.inference_mode(), torch.cuda.device(dev), torch.cuda.stream(ts):
                     admitted, refused = sched.pull(source, accept)
-                    out += [ServeResult(index, None, err) for index, err in refused]
+                    out += [ServeChunk(index, None, None, True, err) if streaming else ServeResult(index, None, err) for index, err in refused]
                     if admitted:
                         timed = _stats is not None and _stats.get("time_admissions")
                         if timed:
@@ -546,18 +571,37 @@ class Zonos(nn.Module):
                         eng.call("zn_gen_row_state", rem, own, st)
                         if [own[b] for b in range(slots)] != [sched.own_steps(b) for b in range(slots)]:
                             raise _lib.ZonosHipError(f"serve: the device counts {list(own)} steps per slot, the scheduler {[sched.own_steps(b) for b in range(slots)]}")
+                        if streaming:                      # codebook 0 of the columns that decide a slot's EOS frame: one gather, one read-back
+                            cells = ledger.cells(own)
+                            if cells:
+                                flat = [b * nq * width + c for b, lo, hi in cells for c in range(lo, hi)]
+                                toks = delayed.view(-1)[torch.tensor(flat, dtype=torch.int64).to(dev)].cpu().tolist()
+                                for b, lo, hi in cells:
+                                    ledger.scan(b, lo, toks[:hi - lo])
+                                    del toks[:hi - lo]
                         rows_host = {}
                         for b in sched.wants_eos(rem):
                             rows_host[b] = delayed[b:b + 1].cpu()
                             r = sched.rows[b]
                             sched.set_eos(b, self._finalise_row(rows_host[b], r.prefix_len, r.max_new_tokens, slots, nq)[1])
                         known = {b: sched.rows[b] for b in range(slots) if sched.rows[b] is not None}
+                        tails = {}
                         for b, index, end in sched.due():
                             row = rows_host[b] if b in rows_host else delayed[b:b + 1].cpu()
                             codes, _, end_b = self._finalise_row(row, known[b].prefix_len, known[b].max_new_tokens, slots, nq)
                             assert end_b == end, (end_b, end)
                             eng.call("zn_gen_retire", b)
-                            out.append(ServeResult(index, codes.to(dev), None))
+                            if streaming:
+                                tails[index] = codes[..., ledger.close(b, codes.shape[2]):].to(dev)
+                            else:
+                                out.append(ServeResult(index, codes.to(dev), None))
+                        if streaming:
+                            # the frames that became final in the rows that run on, built on the device; then every window in one DAC pass
+                            pieces = {known[b].index: map_codes(revert_delay_pattern(delayed[b:b + 1, :, lo:hi + nq].to(torch.int64)))
+                                      for b, lo, hi in ledger.take(own)}
+                            wavs = dacs.push({**pieces, **tails}, end=set(tails))
+                            out += [ServeChunk(index, c, wavs[index], False, None) for index, c in pieces.items()]
+                            out += [ServeChunk(index, c, wavs[index], True, None) for index, c in tails.items()]
                 for res in out:
                     yield res
                 if stop:

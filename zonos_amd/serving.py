@@ -1,4 +1,5 @@
-"""The host side of `Zonos.serve()`: which request holds which slot of a running batch, and when it leaves.
+"""The host side of `Zonos.serve()`: which request holds which slot of a running batch, and when it leaves - and of
+`Zonos.serve_stream()`: which frames of a slot's row are final while it still runs (`StreamLedger`).
 
 Pure Python: no torch device, no library.  A session has `slots` rows that step together; a request joins at a scheduling point (every
 `sched_every` decode steps), runs its own decode loop inside its slot - the device keeps the slot's length, stop state, parameters, column
@@ -38,6 +39,15 @@ def row_end_offset(offset0: int, t_total: int, batch_size: int, nq: int, eos_col
         if stop_check_at(step_idx, batch_size) and remaining <= 0:
             return offset
     return t_total
+
+
+def release_limit(offset: int, nq: int, eos_frame: int | None) -> int:
+    """Frames [0, limit) that are final while the generation runs, once the steps up to column `offset` have run: a frame is complete
+    when its codebook nq-1 (column f + nq) is written, and every frame before the first one whose codebook 0 is EOS (`eos_frame`, None
+    while there is none) survives `finalise_codes` (codebooks 1.. cannot sample EOS before the stop; the EOS diagonal after it lands on
+    the stop frame itself).  What the end keeps beyond that, `finalise_codes` decides."""
+    limit = max(0, offset - nq + 1)
+    return limit if eos_frame is None else min(limit, eos_frame)
 
 
 def serve_slack(sched_every: int) -> int:
@@ -183,3 +193,86 @@ class SlotScheduler:
 
     def finished(self) -> bool:
         return self.exhausted and self.all_idle()
+
+
+class ServeChunk(NamedTuple):
+    """One piece of one request of `Zonos.serve_stream()`: the frames that became final (int64 [1, 9, k], in the coordinates of
+    `ServeResult.codes`: an audio prefix comes first) and the samples they completed (float32 [1, 1, m] on the model's device); k or m
+    may be 0.  `done`: the request's last chunk.  A refused request yields one chunk with codes = wav = None, done and its ValueError."""
+    index: int
+    codes: object
+    wav: object
+    done: bool
+    error: Exception | None = None
+
+
+@dataclass
+class _Tap:
+    prefix_len: int
+    max_new_tokens: int
+    released: int = 0               # frames handed out
+    scanned: int = 0                # codebook-0 columns up to here have been looked at
+    eos_frame: int | None = None    # the first generated frame whose codebook 0 is EOS
+
+
+class StreamLedger:
+    """Per slot of a streaming session: the frames released, the codebook-0 columns scanned and the first EOS frame.  A slot's own column
+    after `own` steps is prefix + 1 + own (a step writes the column after the one it read), capped at the last column of its row,
+    prefix + max_new_tokens + nq - 1: an overrunning row writes beyond its own columns only.  The frames [0, release_limit(column)) are
+    final; a chunk goes out when they have grown by `chunk_frames`.  The caller drives it at every scheduling point: `cells` (which
+    codebook-0 cells to read, for all slots in one gather), `scan` (what they held), `close` (the rows retired at this point), `take`
+    (the chunks of the rows that run on)."""
+
+    def __init__(self, nq: int, chunk_frames: int, eos_id: int):
+        if int(chunk_frames) < 1:
+            raise ValueError(f"chunk_frames must be >= 1, got {chunk_frames}")
+        self.nq, self.chunk_frames, self.eos_id = int(nq), int(chunk_frames), int(eos_id)
+        self.taps: dict[int, _Tap] = {}
+
+    def open(self, slot: int, prefix_len: int, max_new_tokens: int) -> None:
+        if slot in self.taps:
+            raise ValueError(f"StreamLedger: slot {slot} is already open")
+        self.taps[slot] = _Tap(int(prefix_len), int(max_new_tokens), scanned=int(prefix_len))
+
+    def column(self, slot: int, own_steps: int) -> int:
+        t = self.taps[slot]
+        return min(t.prefix_len + 1 + int(own_steps), t.prefix_len + t.max_new_tokens + self.nq - 1)
+
+    def limit(self, slot: int, own_steps: int) -> int:
+        return release_limit(self.column(slot, own_steps), self.nq, self.taps[slot].eos_frame)
+
+    def cells(self, own: Sequence[int]) -> list[tuple[int, int, int]]:
+        """(slot, lo, hi): codebook 0 of columns [lo, hi) of the slot's row decides its EOS frame and has not been read."""
+        out = []
+        for b, t in sorted(self.taps.items()):
+            hi = self.column(b, own[b]) + 1
+            if t.eos_frame is None and hi > t.scanned + 1:
+                out.append((b, t.scanned + 1, hi))
+        return out
+
+    def scan(self, slot: int, lo: int, tokens: Sequence[int]) -> None:
+        """`tokens`: codebook 0 of columns lo, lo + 1, ... (`cells`).  Column c holds frame c - 1."""
+        t = self.taps[slot]
+        if lo != t.scanned + 1:
+            raise ValueError(f"StreamLedger: slot {slot} scanned to column {t.scanned}, got cells from {lo}")
+        for k, tok in enumerate(tokens):
+            if t.eos_frame is None and int(tok) == self.eos_id:
+                t.eos_frame = lo + k - 1
+        t.scanned = lo + len(tokens) - 1
+
+    def take(self, own: Sequence[int]) -> list[tuple[int, int, int]]:
+        """(slot, lo, hi): frames [lo, hi) of the slot's row go out now; they count as released."""
+        out = []
+        for b, t in sorted(self.taps.items()):
+            hi = self.limit(b, own[b])
+            if hi - t.released >= self.chunk_frames:
+                out.append((b, t.released, hi))
+                t.released = hi
+        return out
+
+    def close(self, slot: int, final_frames: int) -> int:
+        """The slot retires with `final_frames` frames: the first frame of its last chunk."""
+        t = self.taps.pop(slot)
+        if final_frames < t.released:
+            raise RuntimeError(f"StreamLedger: slot {slot} released {t.released} frames, its request kept {final_frames}")
+        return t.released
