@@ -112,10 +112,24 @@ typedef struct zn_sampling {
 typedef struct zn_row_params {
   zn_sampling sp;           /* this utterance's sampling parameters; sp.seed seeds its own Gumbel stream */
   float cfg_scale;          /* guidance strength of this utterance's [cond, uncond] pair; == 1 for every row or for none (the row layout
-                               is fixed by zn_gen_begin's cfg_scale) */
+                               is fixed by zn_gen_begin's cfg_scale) - or, in a generation begun with cfg_scale == 1, != 1 in the two
+                               entries of a row pair (below) */
   int32_t max_new_tokens;   /* this utterance's budget of frames, 1 .. zn_gen_begin's max_new_tokens */
-  int32_t reserved[2];      /* pads the entry to ZN_ROW_PARAMS_BYTES; set to 0 */
+  int32_t reserved[2];      /* the row pair of a guided request in a MIXED generation: reserved[0] = cond_row + 1, reserved[1] = uncond_row + 1;
+                               both 0 (what every caller wrote before pairs existed): no pair, exactly the behaviour of the layout
+                               zn_gen_begin fixed */
 } zn_row_params;
+/* Mixed generations: guided and unguided requests in one generation or session (additive to ABI 9: the two reserved words get a meaning, all-zero
+ * keeps every bit).  The generation is begun in the UNGUIDED layout - zn_gen_begin(batch = R, cfg_scale = 1): R rows, R utterance slots, row u is
+ * utterance u.  An unguided request takes one slot and leaves both words 0.  A guided request takes any two slots o and f: the caller prefills
+ * row o with its conditional and row f with its unconditional positions, gives both slots identical code-buffer rows, prefix length and row_len,
+ * and gives both slots the SAME entry: the request's sampling parameters, seed, cfg_scale != 1, max_new_tokens and the pair (o + 1, f + 1).
+ * The sampler workgroup (codebook, u) of a paired utterance reads its conditional logits from raw row reserved[0] - 1 and its unconditional ones
+ * from raw row reserved[1] - 1 and mixes them as a generation begun with guidance does (uncond + (cond - uncond) * cfg_scale, the same fp32
+ * operations in the same order).  Slots o and f have the same inputs, the same Gumbel key and the same history, so both sample the same token
+ * into their own buffer rows; bookkeeping, lengths, remaining_steps and the stop state stay per slot, as in any unguided generation.  The
+ * request's codes are row o's (row f holds the same cells).  f < o is legal; the two rows need not be adjacent.  A generation whose table names
+ * a pair, and every session begun without guidance, stays off the persistent kernels (zn_decode_path_detail reports 0). */
 
 /* Slotted sessions (additive to ABI 9: new entry points only, no existing layout or call changes) - one request admitted into a slot of a slotted session (zn_gen_admit). */
 typedef struct zn_admit {
@@ -169,8 +183,11 @@ int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_stream stream)
  * still receives beyond its own length are the caller's to cut.
  * Legal only between zn_gen_begin and the generation's first zn_prefill / zn_prefill_rows (ZN_ERR_STATE otherwise; no graph has been
  * captured yet).  ZN_ERR_ARG: n != batch, a repetition_penalty_window outside 0..64, max_new_tokens_b outside 1 .. zn_gen_begin's
- * max_new_tokens, or cfg_scale_b == 1 on a generation begun with guidance (and the reverse): guided and unguided utterances do not share
- * a call.  An error leaves the generation as it was.  Without this call every row uses zn_gen_begin's values (the same bits as ABI 8).
+ * max_new_tokens, or cfg_scale_b == 1 on a generation begun with guidance.  In a generation begun with cfg_scale == 1 an entry with
+ * cfg_scale_b != 1 is legal exactly when it names a row pair (zn_row_params, "Mixed generations") and: both rows lie in 0 .. batch - 1, they are
+ * distinct, one of them is b itself, and the other row's entry names the same pair with byte-equal parameters (the two entries are equal as 64
+ * bytes); anything else is ZN_ERR_ARG with a message naming the utterance.  ZN_ERR_ARG as well: a pair named in a generation begun with guidance,
+ * or by an entry with cfg_scale_b == 1.  An error leaves the generation as it was.  Without this call every row uses zn_gen_begin's values (the same bits as ABI 8).
  * Synchronises the generation's stream. */
 int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int32_t n);
 /* An audio prefix of its own length per utterance of the generation begun by zn_gen_begin (a column shift per row of the code buffer).  The
@@ -215,7 +232,13 @@ int zn_gen_open_slots(zn_handle h, int32_t slack);
  * code cell.
  * ZN_ERR_ARG: a slot out of range or named twice, a row_len outside 1..S or none equal to S, a prefix_len outside 0 .. row_len - 2, a request
  * that does not fit (row_len - 1 + max_new_tokens + n_codebooks + slack > max_len, or prefix_len + max_new_tokens + n_codebooks + slack > W),
- * cfg_scale == 1 in a guided session or the reverse, a repetition_penalty_window outside 0..64.  ZN_ERR_STATE: no session, a busy slot, steps
+ * cfg_scale == 1 in a guided session, a repetition_penalty_window outside 0..64.  In a session begun with cfg_scale == 1 (hidden [n, S, d], one
+ * entry per row) a request with cfg_scale != 1 is admitted as a row pair: two entries of this call, for slots o and f, with equal params that
+ * name the pair (o + 1, f + 1), equal row_len and equal prefix_len, hidden row of entry o holding the conditional positions and that of entry f
+ * the unconditional ones (zn_row_params, "Mixed generations").  ZN_ERR_ARG, naming the slot: no pair named, a row out of range, the same row
+ * twice, a pair that does not hold the entry's own slot, the other slot missing from this call, its params not byte-equal, its row_len or
+ * prefix_len different; a pair named in a guided session or at cfg_scale == 1.  The first frame is sampled per admitted slot, as for any other
+ * slot: each slot of a pair mixes the two rows' logits for itself.  ZN_ERR_STATE: no session, a busy slot, steps
  * still owed to zn_all_stopped_end.  ZN_ERR_UNSUPPORTED: the position-by-position prefill (zn_debug_prefill_mode 0).  An error leaves the
  * session as it was.  The call does not synchronise (it waits for the previous admission's staged arguments to have been consumed). */
 int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const void* hidden_dev, int32_t S, zn_stream stream);

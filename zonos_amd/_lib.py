@@ -63,7 +63,8 @@ class zn_sampling(C.Structure):
 
 
 class zn_row_params(C.Structure):
-    """One utterance's settings in a batched generation (zn_gen_set_rows, zn_op_sample_rows): ZN_ROW_PARAMS_BYTES = 64 bytes."""
+    """One utterance's settings in a batched generation (zn_gen_set_rows, zn_op_sample_rows): ZN_ROW_PARAMS_BYTES = 64 bytes.  `reserved`:
+    both words 0, or the row pair of a guided request in a mixed generation (cond_row + 1, uncond_row + 1; include/zonos_hip.h)."""
     _fields_ = [("sp", zn_sampling), ("cfg_scale", C.c_float), ("max_new_tokens", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 

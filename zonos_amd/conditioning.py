@@ -325,3 +325,26 @@ def pad_conditionings(conds: list[torch.Tensor], cfg_scale: float = 2.0) -> tupl
         for half in range(halves):
             out[half * B + i, :lengths[i]] = c[half]
     return out, lengths
+
+
+def pad_conditioning_rows(conds: list[torch.Tensor]) -> tuple[torch.Tensor, list[int], list[int]]:
+    """`pad_conditionings` for a call that mixes guided and unguided requests (`Zonos.generate_batch(mixed_guidance=True)`, DESIGN.md
+    4.1g): `conds[i]` is [2, L_i, d] = [cond ‖ uncond] for a guided request, [1, L_i, d] for one with cfg_scale == 1.  The rows are laid
+    out in request order, a guided request's two rows next to each other (conditional first), each RIGHT-padded with zeros.  Returns
+    (tensor [R, L_max, d], the R rows' valid lengths, the first row of each request)."""
+    if not conds:
+        raise ValueError("pad_conditioning_rows: no conditionings")
+    d = conds[0].shape[-1]
+    for i, c in enumerate(conds):
+        if c.dim() != 3 or c.shape[0] not in (1, 2) or c.shape[1] < 1 or c.shape[2] != d:
+            raise ValueError(f"pad_conditioning_rows: conditioning {i} has shape {tuple(c.shape)}, expected [1 or 2, L >= 1, {d}]")
+    lengths = [int(c.shape[1]) for c in conds for _ in range(c.shape[0])]
+    first, r = [], 0
+    for c in conds:
+        first.append(r)
+        r += int(c.shape[0])
+    out = torch.zeros(r, max(lengths), d, dtype=conds[0].dtype, device=conds[0].device)
+    for i, c in enumerate(conds):
+        for half in range(c.shape[0]):
+            out[first[i] + half, :c.shape[1]] = c[half]
+    return out, lengths, first

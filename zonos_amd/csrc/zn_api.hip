@@ -99,6 +99,7 @@ struct zn_handle_s {
   int *remaining = nullptr, *stopping = nullptr;
   zn_row_params* row_tab = nullptr;   // [max_rows] per-utterance settings of this generation (zn_gen_set_rows)
   bool rows_set = false;              // this generation's samplers read row_tab
+  bool pairs_set = false;             // some entry of row_tab names a row pair (a mixed generation): the samplers follow it
   int* prefix_shift = nullptr;        // [max_rows] column shift per utterance of this generation (zn_gen_set_prefix_rows: <= 0; zn_gen_admit: either sign)
   bool prefix_set = false;            // some shift is not 0: this generation's embedding, sampler and bookkeeping launches read prefix_shift
   bool gen_prefilled = false;         // zn_prefill / zn_prefill_rows has run since zn_gen_begin
@@ -776,7 +777,7 @@ static bool stack_shapes_ok(zn_handle h) {
 // Nor a column shift per utterance (zn_gen_set_prefix_rows): the fused tail's sampler and sample1_kernel do not read it, so two unguided rows whose audio prefixes differ run the launches
 // path even when their lengths advance in lockstep.
 // Nor a slotted session (zn_gen_open_slots): its samplers read the row table, the shifts and the slots' step origins.
-static bool persist_allowed(zn_handle h) { return h->tune[ZN_TUNE_PERSISTENT] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2 && !h->prefix_set && !h->slots_open; }
+static bool persist_allowed(zn_handle h) { return h->tune[ZN_TUNE_PERSISTENT] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2 && !h->prefix_set && !h->slots_open && !h->pairs_set; }
 // Row counts a persistent kernel can serve on this model: two (the per-block chain and step_kernel) or one (step_r1_kernel, the whole-step
 // kernel only: one row beyond its 6144-key bound, or with it switched off, runs the launches path).
 static bool persist_shape(zn_handle h, int rows) { return h->ch_variant != 0 && (rows == 2 || (rows == 1 && h->ch_variant == 1)); }
@@ -1068,6 +1069,7 @@ static SampleArgs gen_sample_args(zn_handle h) {
   SampleArgs a = make_sample_args(h, h->sp);
   a.cfg_scale = h->cfg_scale; a.ctx = h->max_new < 100 ? h->max_new : 100;
   a.rows = h->rows_set ? h->row_tab : nullptr;
+  a.pairs = h->pairs_set ? 1 : 0;
   a.shift = h->prefix_set ? h->prefix_shift : nullptr;
   a.step0 = h->slots_open ? h->step0 : nullptr;
   return a;
@@ -1184,6 +1186,7 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   for (int v : len0) if (v > h->len_hi) h->len_hi = v;
   h->gen_active = true;
   h->rows_set = false;
+  h->pairs_set = false;
   h->prefix_set = false;
   h->slots_open = false;
   h->gen_prefilled = false;
@@ -1450,6 +1453,28 @@ extern "C" int zn_prefill_rows(zn_handle h, const void* hidden_dev, int32_t S, c
   return prefill_impl(h, hidden_dev, S, h->row_len, s);                     // len_hi += S: the bound of the longest row
 }
 
+// A guided entry of a generation begun without guidance (a mixed generation): legal exactly when it names a row pair
+// (reserved[0] = cond_row + 1, reserved[1] = uncond_row + 1), both rows in range and distinct, one of them the entry's own, and the partner's
+// entry - present in the same call - names the same pair with byte-equal parameters.  `slot_of(j)`: the row of entry j of the call; `entry(j)`.
+// Returns the index of the partner's entry, or -1 with `why` set.
+template <typename SlotOf, typename Entry>
+static int pair_partner(int j, int n, int B, SlotOf slot_of, Entry entry, const char** why) {
+  const zn_row_params& r = entry(j);
+  const int own = slot_of(j), rc = r.reserved[0] - 1, ru = r.reserved[1] - 1;
+  if (r.reserved[0] <= 0 && r.reserved[1] <= 0) { *why = "has a cfg_scale != 1 in a generation begun without guidance and names no row pair"; return -1; }
+  if (rc < 0 || rc >= B || ru < 0 || ru >= B) { *why = "names a row pair out of range"; return -1; }
+  if (rc == ru) { *why = "names the same row twice as its pair"; return -1; }
+  if (rc != own && ru != own) { *why = "names a row pair that does not hold its own row"; return -1; }
+  const int other = rc == own ? ru : rc;
+  for (int k = 0; k < n; ++k) {
+    if (slot_of(k) != other) continue;
+    if (memcmp(&entry(k), &r, sizeof(zn_row_params)) != 0) { *why = "and its pair's other row differ in their entries (the same pair, byte-equal parameters)"; return -1; }
+    return k;
+  }
+  *why = "names a row pair whose other row is not part of this call";
+  return -1;
+}
+
 extern "C" int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int32_t n) {
   if (!h) return ZN_ERR_ARG;
   if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_rows before zn_gen_begin");
@@ -1459,13 +1484,23 @@ extern "C" int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int3
   if (n != h->batch) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: %d entries for a generation of %d utterances", n, h->batch);
   const int nq = h->cfg.n_codebooks, budget = h->t_total - h->offset0 - nq + 1;   // zn_gen_begin's max_new_tokens (t_total = prefix + max_new_tokens + n_q)
   std::vector<int> rem(n);
+  bool pairs = false;
   for (int b = 0; b < n; ++b) {
     const zn_row_params& r = rows_host[b];
     if (r.sp.repetition_penalty_window < 0 || r.sp.repetition_penalty_window > 64)
       ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d: repetition_penalty_window out of range", b);
     if (r.max_new_tokens < 1 || r.max_new_tokens > budget)
       ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d: max_new_tokens %d not in 1..%d (the generation's own)", b, r.max_new_tokens, budget);
-    if ((r.cfg_scale == 1.0f) == guided(h))
+    const bool named = r.reserved[0] != 0 || r.reserved[1] != 0;
+    if (named && (guided(h) || r.cfg_scale == 1.0f))
+      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d names a row pair %s (pairs belong to guided entries of a generation begun with cfg_scale == 1)", b,
+              guided(h) ? "in a generation begun with guidance" : "at cfg_scale == 1");
+    if (!guided(h) && r.cfg_scale != 1.0f) {
+      const char* why = nullptr;
+      if (pair_partner(b, n, n, [](int j) { return j; }, [&](int j) -> const zn_row_params& { return rows_host[j]; }, &why) < 0)
+        ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d %s", b, why);
+      pairs = true;
+    } else if ((r.cfg_scale == 1.0f) == guided(h))
       ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d has cfg_scale %g in a generation begun %s guidance (cfg_scale == 1 for every row or for none)", b,
               (double)r.cfg_scale, guided(h) ? "with" : "without");
     rem[b] = r.max_new_tokens + nq - 1;
@@ -1475,6 +1510,7 @@ extern "C" int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int3
   HIPCHK(h, hipMemcpyAsync(h->remaining, rem.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipStreamSynchronize(s));  // the host arrays are the caller's / go out of scope
   h->rows_set = true;
+  h->pairs_set = pairs;
   return ZN_OK;
 }
 
@@ -1541,6 +1577,7 @@ extern "C" int zn_gen_open_slots(zn_handle h, int32_t slack) {
   h->slot_slack = slack;
   h->adm_cap_S = 0;                        // the pointer table names this generation's caches: rebuilt by the first admission
   h->rows_set = h->prefix_set = h->slots_open = true;
+  h->pairs_set = !guided(h);               // a session begun without guidance may admit row pairs at any point: its samplers (captured graphs included) follow the entries' pair words from the start
   return ZN_OK;
 }
 
@@ -1596,7 +1633,17 @@ extern "C" int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const voi
     if ((long long)q.prefix_len + r.max_new_tokens + nq + h->slot_slack > h->t_total)
       ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: %d prefix frames + %d frames + %d + slack %d exceed the code buffer's width %d", q.slot, q.prefix_len, r.max_new_tokens, nq,
               h->slot_slack, h->t_total);
-    if ((r.cfg_scale == 1.0f) == guided(h))
+    const bool named = r.reserved[0] != 0 || r.reserved[1] != 0;
+    if (named && (guided(h) || r.cfg_scale == 1.0f))
+      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d names a row pair %s (pairs belong to guided entries of a session begun with cfg_scale == 1)", q.slot,
+              guided(h) ? "in a session begun with guidance" : "at cfg_scale == 1");
+    if (!guided(h) && r.cfg_scale != 1.0f) {
+      const char* why = nullptr;
+      const int k = pair_partner(j, n, B, [&](int i) { return (int)a[i].slot; }, [&](int i) -> const zn_row_params& { return a[i].params; }, &why);
+      if (k < 0) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d %s", q.slot, why);
+      if (a[k].row_len != q.row_len || a[k].prefix_len != q.prefix_len)
+        ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d and its pair's other slot %d differ in row_len or prefix_len", q.slot, a[k].slot);
+    } else if ((r.cfg_scale == 1.0f) == guided(h))
       ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d has cfg_scale %g in a session begun %s guidance", q.slot, (double)r.cfg_scale, guided(h) ? "with" : "without");
     longest = longest || q.row_len == S;
   }

@@ -1587,6 +1587,10 @@ struct SampleArgs {
   // applies where use_penalty is set AND rows[b]'s penalty != 1; and the Gumbel key's utterance index is 0 (a request's stream does not
   // depend on its slot).  sample1_kernel does not read it: zn_api.hip never gives a table to a step that kernel serves.
   const zn_row_params* rows;
+  // Row pairs (a mixed generation): with `pairs` set, an entry whose reserved[0] > 0 names the raw rows reserved[0] - 1
+  // (conditional) and reserved[1] - 1 (unconditional) of its utterance, and the workgroup mixes them with the entry's cfg_scale whatever
+  // `mix` says; an entry with both words 0 keeps the launch-wide layout.  Off: the words are not looked at (zn_op_sample_rows).
+  int pairs;
   // Column shift per utterance (zn_gen_set_prefix_rows), NULL = every row reads the penalty history ending at column st->offset.  With it,
   // utterance b's history ends at column st->offset + shift[b] and clamps at the row's own column 0.  sample1_kernel does not read it either.
   const int* shift;
@@ -1730,8 +1734,12 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   int top_k = a.top_k, pen_window = a.pen_window, ctx = a.ctx, use_penalty = a.use_penalty;
   unsigned long long seed = a.seed;
   size_t key_b = (size_t)b;
+  int mix = a.mix, row_c = b, row_u = b + (a.mix ? a.batch : 0);  // a named row pair replaces both (uniform over the workgroup)
   if (a.rows) {
     const zn_row_params rp = a.rows[b];
+    if (a.pairs && rp.reserved[0] > 0) {                             // (validated by zn_gen_set_rows / zn_gen_admit; clamped all the same)
+      mix = 1; row_c = min(rp.reserved[0] - 1, a.batch - 1); row_u = max(0, min(rp.reserved[1] - 1, a.batch - 1));
+    }
     temperature = rp.sp.temperature; top_p = rp.sp.top_p; top_k = rp.sp.top_k; min_p = rp.sp.min_p;
     linear = rp.sp.linear; conf = rp.sp.conf; quad = rp.sp.quad;
     penalty = rp.sp.repetition_penalty; pen_window = rp.sp.repetition_penalty_window;
@@ -1750,12 +1758,24 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     cc[it] = rc[i];
     uu[it] = ru[i];
   }
+  // a row pair (mixed generation): the utterance's conditional and unconditional logits are the raw rows its entry names.
+  // The loads above stay as they were - requested with the entry, not behind it - and only a paired utterance pays the second round trip.
+  if (row_c != b || mix != a.mix) {
+    rc = a.raw + ((size_t)row_c * a.n_q + cb) * V;
+    ru = a.raw + ((size_t)row_u * a.n_q + cb) * V;
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+      const int i = min(tid + it * 256, V - 1);
+      cc[it] = rc[i];
+      uu[it] = ru[i];
+    }
+  }
   // ---- logits: CFG mix (model.py:231-232), logit bias (model.py:433-437,476)
 #pragma unroll
   for (int it = 0; it < IT; ++it) {
     const int i = tid + it * 256;
     if (i < V) {
-      float l = a.mix ? __fadd_rn(uu[it], __fmul_rn(__fsub_rn(cc[it], uu[it]), cfg_scale)) : cc[it];
+      float l = mix ? __fadd_rn(uu[it], __fmul_rn(__fsub_rn(cc[it], uu[it]), cfg_scale)) : cc[it];
       if (a.apply_bias && i == a.eos_id) {
         if (cb == 0) {
           l = __fadd_rn(l, -0.6931471824645996f);  // -log(2) in fp32

@@ -23,7 +23,7 @@ from . import _lib
 from .autoencoder import DACAutoencoder
 from .backbone import BACKBONES, HipEngine
 from .codebook_pattern import apply_delay_pattern, revert_delay_pattern
-from .conditioning import ConditioningCache, PrefixConditioner, pad_conditionings, prepare_conditioning_with_cache
+from .conditioning import ConditioningCache, PrefixConditioner, pad_conditioning_rows, pad_conditionings, prepare_conditioning_with_cache
 from .config import InferenceParams, ZonosConfig
 from .serving import (ServeChunk, ServeResult, SlotScheduler, StreamLedger, check_serve_request, release_limit, row_end_offset,  # noqa: F401
                       serve_slack, stop_check_at)     # (release_limit, row_end_offset, stop_check_at: defined there, used and re-exported here)
@@ -86,16 +86,25 @@ class GenRequest:
 MAX_BATCH_REQUESTS = 64       # utterances of one generate_batch() call: the batch the sampler tail's tables are sized for (ZN_TAIL_MAXB)
 
 
-def check_requests(requests: Sequence[GenRequest], nq: int, d_model: int, ragged_prefix: bool = False) -> tuple[bool, int | list[int]]:
+def check_requests(requests: Sequence[GenRequest], nq: int, d_model: int, ragged_prefix: bool = False,
+                   mixed_guidance: bool = False) -> tuple[bool | None, int | list[int]]:
     """What `generate_batch` refuses before any launch (ValueError); returns (guided, audio prefix length) of the call.  With `ragged_prefix`
-    the requests may bring audio prefixes of different lengths, and the second value is the list of their lengths (0 for None)."""
+    the requests may bring audio prefixes of different lengths, and the second value is the list of their lengths (0 for None).  With
+    `mixed_guidance` guided and cfg_scale == 1 requests may share the call: `guided` is then None when both kinds are present, every
+    request's conditioning is checked against its own cfg_scale, and the call's rows (one per unguided request, two per guided one) must
+    not exceed MAX_BATCH_REQUESTS."""
     n = len(requests)
     if n == 0:
         raise ValueError("generate_batch: no requests")
     if n > MAX_BATCH_REQUESTS:
         raise ValueError(f"generate_batch: {n} requests, one call holds at most {MAX_BATCH_REQUESTS}")
     guided = {float(r.cfg_scale) != 1.0 for r in requests}
-    if len(guided) > 1:
+    mixed = len(guided) > 1
+    if mixed and mixed_guidance:
+        rows = sum(2 if float(r.cfg_scale) != 1.0 else 1 for r in requests)
+        if rows > MAX_BATCH_REQUESTS:
+            raise ValueError(f"generate_batch: {rows} rows (one per cfg_scale == 1 request, two per guided one), a mixed call holds at most {MAX_BATCH_REQUESTS}")
+    elif mixed:
         raise ValueError("generate_batch: requests with cfg_scale == 1 and with guidance cannot share a call (the batch's row layout "
                          f"differs): cfg_scale = {[float(r.cfg_scale) for r in requests]}")
     prefix_lens = [0 if r.audio_prefix_codes is None else int(r.audio_prefix_codes.shape[-1]) for r in requests]
@@ -103,9 +112,10 @@ def check_requests(requests: Sequence[GenRequest], nq: int, d_model: int, ragged
     if len(prefixes) > 1 and not ragged_prefix:
         raise ValueError(f"generate_batch: audio prefixes of different lengths {sorted(prefixes)} in one call are not supported "
                          "(the audio prefix length is shared by the batch)")
-    halves = 2 if guided.pop() else 1
+    call_halves = None if mixed else (2 if guided.pop() else 1)
     for i, r in enumerate(requests):
         c = r.conditioning
+        halves = call_halves if call_halves is not None else (2 if float(r.cfg_scale) != 1.0 else 1)
         if c.dim() != 3 or c.shape[0] != halves or c.shape[1] < 1 or c.shape[2] != d_model:
             raise ValueError(f"generate_batch: request {i}: conditioning of shape {tuple(c.shape)}, expected [{halves}, L >= 1, {d_model}] at "
                              f"cfg_scale={r.cfg_scale}")
@@ -115,7 +125,7 @@ def check_requests(requests: Sequence[GenRequest], nq: int, d_model: int, ragged
         if a is not None and (a.dim() != 3 or a.shape[0] != 1 or a.shape[1] != nq):
             raise ValueError(f"generate_batch: request {i}: audio_prefix_codes of shape {tuple(a.shape)}, expected [1, {nq}, P]")
         _sampling_struct(r.sampling_params, 0)             # unknown sampling keys: TypeError, as in generate()
-    return halves == 2, (prefix_lens if ragged_prefix else prefixes.pop())
+    return (None if mixed else call_halves == 2), (prefix_lens if ragged_prefix else prefixes.pop())
 
 
 def _drain(gen):
@@ -352,7 +362,8 @@ class Zonos(nn.Module):
         return n
 
     @torch.inference_mode()
-    def generate_batch(self, requests: Sequence[GenRequest], ragged_prefix: bool = False, _trace: dict | None = None) -> list[torch.Tensor]:
+    def generate_batch(self, requests: Sequence[GenRequest], ragged_prefix: bool = False, _trace: dict | None = None,
+                       mixed_guidance: bool = False) -> list[torch.Tensor]:
         """One generation for several requests, each with its own sampling parameters, seed, cfg_scale and max_new_tokens (and its own
         prompt length); returns, per request, int64 [1, 9, T_b] as `generate()` returns it, cut and finalised for that request alone.
 
@@ -366,13 +377,22 @@ class Zonos(nn.Module):
         `ragged_prefix=True` lifts the last refusal: request b continues its own `audio_prefix_codes` of P_b frames (None: 0) and gets the
         codes it would get in a call whose requests all bring P_b frames.  Row b of the code buffer is left-aligned: its
         prefix, its max_new_tokens_b unknown cells, then the mask token; the device shifts the row's column by P_b - max_b P_b
-        (zn_gen_set_prefix_rows), and the right-padded prefill rows are assembled by one kernel (zn_op_assemble_prefill)."""
+        (zn_gen_set_prefix_rows), and the right-padded prefill rows are assembled by one kernel (zn_op_assemble_prefill).
+
+        `mixed_guidance=True` lifts the refusal of guided and cfg_scale == 1 requests together: the call runs in the
+        unguided layout with one row per cfg_scale == 1 request and two adjacent rows per guided one, in request order, at most
+        MAX_BATCH_REQUESTS rows; the sampler of a guided request's rows mixes the two rows' logits (zn_row_params' row pair).  A guided
+        request's result is read from its first row, and every request is finalised with the cadence of a call of len(requests)
+        utterances.  `_trace` logits are then [rows, 9, 1025].  It composes with `ragged_prefix`; a call of one kind only is the call
+        without the keyword."""
         reqs = list(requests)
         nq = self.config.codebook_dimension
-        guided, P = check_requests(reqs, nq, self.config.backbone.d_model, ragged_prefix)
+        guided, P = check_requests(reqs, nq, self.config.backbone.d_model, ragged_prefix, mixed_guidance)
         prefix_lens = None
         if ragged_prefix:
             prefix_lens, P = P, max(P)
+        if guided is None:
+            return self._generate_mixed(reqs, P, prefix_lens, _trace)
         if len(reqs) == 1:
             r = reqs[0]
             return [self.generate(r.conditioning, r.audio_prefix_codes, int(r.max_new_tokens), r.cfg_scale, 1, r.sampling_params, seed=r.seed,
@@ -402,7 +422,38 @@ class Zonos(nn.Module):
             eng.generating = False
             eng.lock.release()
 
-    def serve(self, requests, slots: int = 8, max_prompt: int = 64, max_new_tokens: int = 86 * 30, guided: bool = True, sched_every: int = 8,
+    def _generate_mixed(self, reqs, P, prefix_lens, _trace) -> list[torch.Tensor]:
+        """generate_batch(mixed_guidance=True) with both kinds of request present: a call of R rows in the unguided layout."""
+        dev = self.device
+        cond, lengths, first = pad_conditioning_rows([r.conditioning.to(dev) for r in reqs])
+        R = cond.shape[0]
+        self._check_rows(cond, 1.0, R, lengths)
+        owner = [i for i, r in enumerate(reqs) for _ in range(r.conditioning.shape[0])]          # row -> request
+        if prefix_lens is not None:
+            prefix, prefix_lens = [reqs[i].audio_prefix_codes for i in owner], [prefix_lens[i] for i in owner]
+        else:
+            prefix = None if P == 0 else torch.cat([reqs[i].audio_prefix_codes.to(dev) for i in owner], 0)
+        table = (_lib.zn_row_params * R)()
+        for i, r in enumerate(reqs):
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if r.seed is None else r.seed
+            for u in range(first[i], first[i] + r.conditioning.shape[0]):
+                table[u].sp = _sampling_struct(r.sampling_params, seed)
+                table[u].cfg_scale, table[u].max_new_tokens = float(r.cfg_scale), int(r.max_new_tokens)
+                if r.conditioning.shape[0] == 2:
+                    table[u].reserved[0], table[u].reserved[1] = first[i] + 1, first[i] + 2       # (cond_row + 1, uncond_row + 1)
+        max_new = max(int(r.max_new_tokens) for r in reqs)
+        eng = self._acquire_engine((R + 1) // 2)
+        try:
+            with torch.cuda.device(dev):
+                run = lambda: _drain(self._generation(eng, cond, prefix, max_new, 1.0, R, reqs[0].sampling_params, None, 0, _trace,
+                                                      torch.cuda.current_stream(dev), None, lengths, table, prefix_lens, first))
+                outs = self._with_timeout_policy(run, caller_saw_frames=_trace is not None)
+            return [o.to(dev) for o in outs]
+        finally:
+            eng.generating = False
+            eng.lock.release()
+
+    def serve(self, requests, slots: int = 8, max_prompt: int = 64, max_new_tokens: int = 86 * 30, guided: bool | None = True, sched_every: int = 8,
               _trace: dict | None = None, _stats: dict | None = None) -> Iterator[ServeResult]:
         """Requests join a running batch as slots free up: a generator of `ServeResult(index, codes, error)` in order of completion.
 
@@ -414,6 +465,12 @@ class Zonos(nn.Module):
         codes of its row in such a call.  `max_prompt` (conditioning positions + audio prefix frames of the longest
         request) and `max_new_tokens` size the KV cache and the code buffer once; a request that does not fit them, whose guidance differs
         from the session's (`guided`: cfg_scale != 1) or that is malformed yields ServeResult(index, None, ValueError) and takes no slot.
+
+        `guided=None` opens a MIXED session: `slots` then counts rows, a cfg_scale == 1 request takes one and a guided
+        request the two lowest idle ones (its conditional and its unconditional row; its codes are read from the lower).  Admission stays
+        FIFO: a guided request at the head of the queue waits until two rows are idle and nothing overtakes it.  Every request's codes
+        are those of its row in a `generate_batch()` call of `slots` ROWS of its own kind.  "retired" of `_trace` receives
+        (index, its slots, their rows of the code buffer) per retirement of such a session.
 
         The engine and the stream current at the call are held while the generator is alive; `close()`, leaving the loop early or garbage
         collection releases them.  A session runs no persistent kernel, so no hand-off timeout can occur; any library error raises.
@@ -430,9 +487,9 @@ class Zonos(nn.Module):
         if self.device.type != "cuda":
             raise _lib.ZonosHipError("zonos_amd runs on MI355X only: move the model to a cuda device (no CPU fallback)")
         dev = self.device
-        return self._serve_gen(dev, torch.cuda.current_stream(dev), iter(requests), slots, max_prompt, max_new_tokens, bool(guided), sched_every, _trace, _stats)
+        return self._serve_gen(dev, torch.cuda.current_stream(dev), iter(requests), slots, max_prompt, max_new_tokens, None if guided is None else bool(guided), sched_every, _trace, _stats)
 
-    def serve_stream(self, requests, slots: int = 8, max_prompt: int = 64, max_new_tokens: int = 86 * 30, guided: bool = True,
+    def serve_stream(self, requests, slots: int = 8, max_prompt: int = 64, max_new_tokens: int = 86 * 30, guided: bool | None = True,
                      sched_every: int = 8, chunk_frames: int = 16, _stats: dict | None = None) -> Iterator[ServeChunk]:
         """`serve()` with audio as it happens: a generator of `ServeChunk(index, codes, wav, done, error)`.  The session is `serve()`'s -
         the same admissions, steps and retirements.  At a scheduling point every busy slot whose final frames (`release_limit` of its
@@ -452,12 +509,13 @@ class Zonos(nn.Module):
         if self.device.type != "cuda":
             raise _lib.ZonosHipError("zonos_amd runs on MI355X only: move the model to a cuda device (no CPU fallback)")
         dev = self.device
-        return self._serve_gen(dev, torch.cuda.current_stream(dev), iter(requests), slots, max_prompt, max_new_tokens, bool(guided), sched_every, None,
+        return self._serve_gen(dev, torch.cuda.current_stream(dev), iter(requests), slots, max_prompt, max_new_tokens, None if guided is None else bool(guided), sched_every, None,
                                _stats, int(chunk_frames))
 
     def _serve_gen(self, dev, ts, source, slots, max_prompt, max_new_tokens, guided, sched_every, _trace, _stats=None, chunk_frames=None):
         """The session of serve() (chunk_frames None: yields ServeResult) and of serve_stream() (yields ServeChunk)."""
         nq, d, mask = self.config.codebook_dimension, self.config.backbone.d_model, self.masked_token_id
+        mixed = guided is None                                         # rows in the unguided layout; a guided request holds two of them
         halves = 2 if guided else 1
         R = slots * halves
         slack = serve_slack(sched_every)
@@ -494,7 +552,7 @@ class Zonos(nn.Module):
                     _sampling_struct(r.sampling_params, 0)
                 except TypeError as e:
                     raise ValueError(f"serve: {e}") from None
-                return P, int(r.max_new_tokens)
+                return P, int(r.max_new_tokens), (2 if mixed and float(r.cfg_scale) != 1.0 else 1)
 
             def record(kind, holders):
                 if _trace is not None:
@@ -502,25 +560,37 @@ class Zonos(nn.Module):
                     _trace.setdefault("slots", []).append((kind, sched.step, list(holders)))
 
             def admit(admitted):
-                n = len(admitted)
-                reqs = [r for _, _, r in admitted]
-                Ls = [int(r.conditioning.shape[1]) for r in reqs]
-                Ps = [0 if r.audio_prefix_codes is None else int(r.audio_prefix_codes.shape[2]) for r in reqs]
-                cond, _ = pad_conditionings([r.conditioning.to(dev) for r in reqs], 2.0 if guided else 1.0)
+                # one entry per admitted row: (slot, request, conditioning rows of that slot).  A two-slot request of a mixed session gives
+                # two entries, its conditional row into its owner slot and its unconditional one into the partner, both naming the pair.
+                entries = []
+                for slot, _, r in admitted:
+                    c, f = r.conditioning.to(dev), sched.partner(slot)
+                    if f is None:
+                        entries.append((slot, r, c, None))
+                    else:
+                        entries += [(slot, r, c[0:1], (slot, f)), (f, r, c[1:2], (slot, f))]
+                n = len(entries)
+                Ls = [int(c.shape[1]) for _, _, c, _ in entries]
+                Ps = [0 if r.audio_prefix_codes is None else int(r.audio_prefix_codes.shape[2]) for _, r, _, _ in entries]
+                cond, _ = pad_conditionings([c for _, _, c, _ in entries], 2.0 if guided else 1.0)
                 cond = cond.to(device=dev, dtype=torch.bfloat16).contiguous()
                 codes = torch.full((n, nq, width - nq), mask, dtype=torch.int32, device=dev)
-                for j, r in enumerate(reqs):                          # a slot's row: its prefix, its unknown cells, the mask token up to the width
+                for j, (_, r, _, _) in enumerate(entries):            # a slot's row: its prefix, its unknown cells, the mask token up to the width
                     if Ps[j]:
                         codes[j, :, :Ps[j]] = r.audio_prefix_codes[0].to(device=dev, dtype=torch.int32)
                     codes[j, :, Ps[j]:Ps[j] + int(r.max_new_tokens)] = -1
                 rows = apply_delay_pattern(codes, mask).contiguous()  # [n, nq, width]
                 adm = (_lib.zn_admit * n)()
-                for j, (slot, _, r) in enumerate(admitted):
+                seeds = {}
+                for j, (slot, r, _, pair) in enumerate(entries):
                     delayed[slot].copy_(rows[j])
-                    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if r.seed is None else r.seed
+                    if id(r) not in seeds:
+                        seeds[id(r)] = int(torch.randint(0, 2 ** 62, (1,)).item()) if r.seed is None else r.seed
                     adm[j].slot, adm[j].row_len, adm[j].prefix_len = slot, Ls[j] + Ps[j] + 1, Ps[j]
-                    adm[j].params.sp = _sampling_struct(r.sampling_params, seed)
+                    adm[j].params.sp = _sampling_struct(r.sampling_params, seeds[id(r)])
                     adm[j].params.cfg_scale, adm[j].params.max_new_tokens = float(r.cfg_scale), int(r.max_new_tokens)
+                    if pair is not None:
+                        adm[j].params.reserved[0], adm[j].params.reserved[1] = pair[0] + 1, pair[1] + 1
                 S = max(L + P + 1 for L, P in zip(Ls, Ps))
                 meta = torch.tensor([Ls, Ps], dtype=torch.int32).to(dev)
                 hidden = torch.empty(halves * n, S, d, dtype=torch.bfloat16, device=dev)
@@ -531,10 +601,12 @@ class Zonos(nn.Module):
                 held = [None] * slots
                 for slot, index, _ in admitted:
                     held[slot] = index
+                    if sched.partner(slot) is not None:
+                        held[sched.partner(slot)] = index
                 record("admit", held)
-                for j, (slot, index, r) in enumerate(admitted):
+                for slot, index, r in admitted:
                     if streaming:
-                        ledger.open(slot, Ps[j], int(r.max_new_tokens))
+                        ledger.open(slot, 0 if r.audio_prefix_codes is None else int(r.audio_prefix_codes.shape[2]), int(r.max_new_tokens))
                     if _stats is not None:
                         _stats.setdefault("admitted_at", {})[index] = time.perf_counter()
 
@@ -590,7 +662,11 @@ class Zonos(nn.Module):
                             row = rows_host[b] if b in rows_host else delayed[b:b + 1].cpu()
                             codes, _, end_b = self._finalise_row(row, known[b].prefix_len, known[b].max_new_tokens, slots, nq)
                             assert end_b == end, (end_b, end)
-                            eng.call("zn_gen_retire", b)
+                            held = [b] if known[b].partner is None else [b, known[b].partner]
+                            if mixed and _trace is not None:
+                                _trace.setdefault("retired", []).append((index, held, delayed[held].cpu()))
+                            for slot in held:                          # a guided request of a mixed session leaves both of its rows at once
+                                eng.call("zn_gen_retire", slot)
                             if streaming:
                                 tails[index] = codes[..., ledger.close(b, codes.shape[2]):].to(dev)
                             else:
@@ -720,13 +796,17 @@ class Zonos(nn.Module):
                                        seed, _trace, torch.cuda.current_stream(self.device), None, cond_lengths)).to(self.device)
 
     def _generation(self, eng, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params, callback, seed,
-                    _trace, ts, chunk, cond_lengths=None, row_table=None, prefix_lens=None):
+                    _trace, ts, chunk, cond_lengths=None, row_table=None, prefix_lens=None, request_rows=None):
         """One generation on `eng` (its lock held by the caller), with every launch on torch stream `ts`.  A generator: with `chunk` it yields
         (delayed codes, last column written) every `chunk` decode steps (Zonos.stream), and it returns the final codes on the host.  With
         `row_table` (zn_row_params per utterance, generate_batch) it returns one tensor per utterance.  With `prefix_lens` (generate_batch's
-        ragged_prefix; needs `row_table` and `cond_lengths`) `audio_prefix_codes` is a list of per-utterance prefixes (None or [1, nq, P_b])."""
+        ragged_prefix; needs `row_table` and `cond_lengths`) `audio_prefix_codes` is a list of per-utterance prefixes (None or [1, nq, P_b]).
+        With `request_rows` (generate_batch's mixed_guidance; needs `row_table`) the utterances are the rows of a mixed call: the loop checks
+        its stop flag with the cadence of a call of len(request_rows) requests, and one tensor per request is returned, read from the row
+        `request_rows` names for it."""
         dev = self.device
         B, nq = batch_size, self.config.codebook_dimension
+        cadence = B if request_rows is None else len(request_rows)
         R = prefix_conditioning.shape[0]                          # 2B with guidance, B when cfg_scale == 1 (checked by generate)
         if prefix_lens is not None:
             P = max(prefix_lens)
@@ -765,11 +845,15 @@ class Zonos(nn.Module):
             if prefix_lens is not None:
                 eng.call("zn_gen_set_prefix_rows", (C.c_int32 * B)(*prefix_lens), B)
             offset = yield from self._decode_loop(eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk, cond_lengths,
-                                                  prefix_lens)
+                                                  prefix_lens, cadence)
         finally:
             # the device's persistent-kernel tenancy goes back once this generation's kernels have drained (include/zonos_hip.h)
             ts.synchronize()
             eng.call("zn_gen_end")
+        if request_rows is not None:
+            host = delayed.cpu()
+            return [self._finalise_row(host[u:u + 1], P if prefix_lens is None else int(prefix_lens[u]), int(row_table[u].max_new_tokens), cadence, nq)[0]
+                    for u in request_rows]
         if row_table is not None:
             return self._finalise_rows(delayed.cpu(), row_table, P if prefix_lens is None else prefix_lens, B, nq)       # the same one device->host copy
         out = revert_delay_pattern(delayed.to(torch.int64)).cpu()     # one device->host copy (model.py:511)
@@ -793,14 +877,14 @@ class Zonos(nn.Module):
         return finalise_codes(revert_delay_pattern(row), end, nq, self.eos_token_id), eos_column, end
 
     def _decode_loop(self, eng, ip, delayed, prefix_conditioning, offset, t_total, B, nq, callback, _trace, st, chunk=None, cond_lengths=None,
-                     prefix_lens=None):
+                     prefix_lens=None, cadence=None):
         """Prefill, first frame and the hot loop (model.py:421-509); a generator that returns the final column offset.  With `chunk`, the
         steps are enqueued at least every `chunk` steps and it yields (delayed, column offset written last) there."""
         if prefix_lens is not None:
             S = self._prefill_ragged(eng, delayed, prefix_conditioning, t_total, B, st, cond_lengths, prefix_lens)
         else:
             S = self._prefill_shared(eng, delayed, prefix_conditioning, offset, B, st, cond_lengths)
-        return (yield from self._loop_after_prefill(eng, ip, delayed, S, offset, t_total, B, nq, callback, _trace, st, chunk))
+        return (yield from self._loop_after_prefill(eng, ip, delayed, S, offset, t_total, B, nq, callback, _trace, st, chunk, cadence))
 
     def _prefill_ragged(self, eng, delayed, prefix_conditioning, t_total, B, st, cond_lengths, prefix_lens) -> int:
         """generate_batch(ragged_prefix=True): row r = [cond_r[:L_b] ‖ embed(delayed_b[:, :P_b + 1]) ‖ zeros], b = r mod B, built for all rows
@@ -845,8 +929,10 @@ class Zonos(nn.Module):
             eng.call("zn_prefill_rows", hidden.data_ptr(), S, row_len, st)
         return S
 
-    def _loop_after_prefill(self, eng, ip, delayed, S, offset, t_total, B, nq, callback, _trace, st, chunk):
-        """First frame and the hot loop (model.py:423-509), the prefill of S positions done."""
+    def _loop_after_prefill(self, eng, ip, delayed, S, offset, t_total, B, nq, callback, _trace, st, chunk, cadence=None):
+        """First frame and the hot loop (model.py:423-509), the prefill of S positions done.  `cadence`: the batch size whose stop-check
+        cadence the loop follows (None: B; a mixed call has more utterance rows than requests)."""
+        cadence = B if cadence is None else cadence
         eng.call("zn_sample_first", st)
         ip.seqlen_offset += S
         if _trace is not None:
@@ -870,7 +956,7 @@ class Zonos(nn.Module):
                 break
             pending += 1
             ip.seqlen_offset += 1
-            check = stop_check_at(step_idx, B)
+            check = stop_check_at(step_idx, cadence)
             hook = chunk is not None and step_idx % chunk == chunk - 1
             if check or hook or callback is not None or _trace is not None:
                 eng.call("zn_decode_steps", pending, st)

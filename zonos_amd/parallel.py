@@ -71,31 +71,54 @@ def generate_sharded(generate_fn, conditionings: list[torch.Tensor], gather: boo
     return gather_codes(mine, len(conditionings), group=group) if gather else mine
 
 
-def request_groups(requests, share: list[int], batch_size: int, ragged_prefix: bool = False) -> list[list[int]]:
+MIXED_CALL_ROWS = 64          # rows of one generate_batch(mixed_guidance=True) call (model.MAX_BATCH_REQUESTS)
+
+
+def request_groups(requests, share: list[int], batch_size: int, ragged_prefix: bool = False, mixed_guidance: bool = False) -> list[list[int]]:
     """This rank's requests (indices `share`) as the calls it makes: requests that may share a `Zonos.generate_batch` call - all guided or
-    all at cfg_scale == 1, one audio prefix length (any, with `ragged_prefix`) - in groups of up to `batch_size`, each in request order."""
+    all at cfg_scale == 1, one audio prefix length (any, with `ragged_prefix`) - in groups of up to `batch_size`, each in request order.
+    With `mixed_guidance` the groups no longer split by guidance; a group then also ends before its rows (one per cfg_scale == 1 request,
+    two per guided one) would exceed MIXED_CALL_ROWS."""
     buckets: dict[tuple[bool, int], list[int]] = {}
     for i in share:
         r = requests[i]
-        key = (float(r.cfg_scale) != 1.0, 0 if ragged_prefix or r.audio_prefix_codes is None else int(r.audio_prefix_codes.shape[-1]))
+        key = (False if mixed_guidance else float(r.cfg_scale) != 1.0,
+               0 if ragged_prefix or r.audio_prefix_codes is None else int(r.audio_prefix_codes.shape[-1]))
         buckets.setdefault(key, []).append(i)
     step = max(1, int(batch_size))
-    return [idx[j:j + step] for idx in buckets.values() for j in range(0, len(idx), step)]
+    if not mixed_guidance:
+        return [idx[j:j + step] for idx in buckets.values() for j in range(0, len(idx), step)]
+    groups = []
+    for idx in buckets.values():
+        cur, rows = [], 0
+        for i in idx:
+            need = 2 if float(requests[i].cfg_scale) != 1.0 else 1
+            if cur and (len(cur) == step or rows + need > MIXED_CALL_ROWS):
+                groups.append(cur)
+                cur, rows = [], 0
+            cur.append(i)
+            rows += need
+        if cur:
+            groups.append(cur)
+    return groups
 
 
-def generate_sharded_requests(generate_batch_fn, requests, gather: bool = True, group=None, batch_size: int = 8, ragged_prefix: bool = False):
+def generate_sharded_requests(generate_batch_fn, requests, gather: bool = True, group=None, batch_size: int = 8, ragged_prefix: bool = False,
+                              mixed_guidance: bool = False):
     """`generate_sharded` for `model.GenRequest`s, each with its own sampling parameters, seed, cfg_scale and length: request i runs on rank
     i mod world, and a rank's share goes out in `request_groups` as `generate_batch_fn(list of requests) -> list of int64 [1, n_q, T]`
     (`Zonos.generate_batch`).  Returns the code tensors [n_q, T_i] in request order: of every request on every rank with `gather`, of this
     rank's share (`shard_indices` order) without.  `ragged_prefix`: requests with audio prefixes of different lengths share a call, made as
-    `generate_batch_fn(list of requests, ragged_prefix=True)`."""
+    `generate_batch_fn(list of requests, ragged_prefix=True)`.  `mixed_guidance`: guided and cfg_scale == 1 requests share a call as well, made
+    with `mixed_guidance=True`."""
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0
     share = shard_indices(len(requests), rank, world)
     done: dict[int, torch.Tensor] = {}
-    for idx in request_groups(requests, share, batch_size, ragged_prefix):
+    for idx in request_groups(requests, share, batch_size, ragged_prefix, mixed_guidance):
         batch = [requests[i] for i in idx]
-        outs = generate_batch_fn(batch, ragged_prefix=True) if ragged_prefix else generate_batch_fn(batch)
+        kw = {**({"ragged_prefix": True} if ragged_prefix else {}), **({"mixed_guidance": True} if mixed_guidance else {})}
+        outs = generate_batch_fn(batch, **kw)
         if len(outs) != len(idx):
             raise ValueError(f"generate_batch_fn returned {len(outs)} results for {len(idx)} requests")
         for i, o in zip(idx, outs):

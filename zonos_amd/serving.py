@@ -57,13 +57,17 @@ def serve_slack(sched_every: int) -> int:
 
 
 def check_serve_request(cond_shape: Sequence[int], prefix_shape: Sequence[int] | None, max_new_tokens, cfg_scale: float, *, nq: int,
-                        d_model: int, guided: bool, max_len: int, width: int, slack: int) -> tuple[int, int]:
+                        d_model: int, guided: bool | None, max_len: int, width: int, slack: int) -> tuple[int, int]:
     """What a session refuses (ValueError) before the request takes a slot; returns (L, P), its conditioning positions and audio prefix
     frames.  `max_len`: KV positions per row of the session; `width`: columns of a row of its code buffer.  A request fits when its
     prompt, its own steps and the slack stay inside both: L + P + max_new_tokens + nq + slack <= max_len (the last append of an
-    overrunning row) and P + max_new_tokens + nq + slack <= width (its penalty history stays in its own buffer row)."""
-    halves = 2 if guided else 1
-    if (float(cfg_scale) != 1.0) != guided:
+    overrunning row) and P + max_new_tokens + nq + slack <= width (its penalty history stays in its own buffer row).  `guided=None`: a
+    mixed session takes both kinds; the conditioning's first dimension follows the request's own cfg_scale."""
+    if guided is None:
+        halves = 2 if float(cfg_scale) != 1.0 else 1
+    else:
+        halves = 2 if guided else 1
+    if guided is not None and (float(cfg_scale) != 1.0) != guided:
         raise ValueError(f"serve: cfg_scale={cfg_scale} in a session {'with' if guided else 'without'} guidance (guided and cfg_scale == 1 "
                          "requests cannot share a session: the row layout differs)")
     c = tuple(cond_shape)
@@ -102,12 +106,19 @@ class _Row:
     step0: int                  # the session step at which it was admitted
     eos_known: bool = False
     eos_column: int | None = None
+    partner: int | None = None  # a request that holds two slots (a guided request of a mixed session): the other one
+    owner: bool = True          # the slot whose row the request is read from; the second slot only runs along
 
 
 class SlotScheduler:
     """Admits requests FIFO into free slots, retires rows, and says when the session ends.  The caller drives it at every scheduling
     point: `pull` (admissions), `advance` (the steps it enqueued), `wants_eos` / `set_eos` (the codebook-0 cells of the rows whose
-    remaining_steps reached 0), `due` (the rows to retire)."""
+    remaining_steps reached 0), `due` (the rows to retire).
+
+    A request needs one slot, or two (a guided request of a mixed session: `accept` returns a third value).  Admission
+    stays FIFO without overtaking: a two-slot request at the head of the queue waits, held in `waiting`, until two slots are idle, and
+    nothing behind it is pulled meanwhile.  It takes the two lowest idle slots, the lower one as its owner (`partner`, `is_owner`); both
+    are admitted at one scheduling point and retired at one - the point at which the owner's row is due."""
 
     def __init__(self, slots: int, nq: int, sched_every: int):
         if int(slots) < 1 or int(sched_every) < 1 or int(nq) < 1:
@@ -118,6 +129,7 @@ class SlotScheduler:
         self.rows: list[_Row | None] = [None] * self.slots
         self.pulled = 0                                # items that were requests (an index each)
         self.exhausted = False
+        self.waiting: tuple | None = None              # (index, item, prefix_len, max_new_tokens, need): pulled, accepted, not yet placed
 
     # ---------------------------------------------------------------- admission
     def free_slots(self) -> list[int]:
@@ -125,30 +137,53 @@ class SlotScheduler:
 
     def pull(self, source: Iterator, accept: Callable) -> tuple[list, list]:
         """One scheduling point's admissions: while a slot is free, take the next item of `source` - lazily, one item per free slot.
-        None: nothing is waiting right now.  `accept(request)` returns (prefix_len, max_new_tokens) or raises ValueError: a refused
-        request takes no slot.  Returns ([(slot, index, request)], [(index, error)])."""
+        None: nothing is waiting right now.  `accept(request)` returns (prefix_len, max_new_tokens) - or (prefix_len, max_new_tokens,
+        slots needed: 1 or 2) - or raises ValueError: a refused request takes no slot.  A request that needs more slots than are free
+        stays at the head of the queue (`waiting`) and ends this point's admissions.  Returns ([(slot, index, request)], [(index, error)]);
+        a two-slot request is named once, by its owner slot (`partner(slot)` is its other one)."""
         admitted, refused = [], []
-        for slot in self.free_slots():
-            while not self.exhausted:
+        while True:
+            free = self.free_slots()
+            if not free:
+                break
+            if self.waiting is None:
+                if self.exhausted:
+                    break
                 try:
                     item = next(source)
                 except StopIteration:
                     self.exhausted = True
                     break
                 if item is None:
-                    return admitted, refused
+                    break
                 index, self.pulled = self.pulled, self.pulled + 1
                 try:
-                    prefix_len, max_new = accept(item)
+                    got = tuple(accept(item))
+                    need = int(got[2]) if len(got) > 2 else 1
+                    if need not in (1, 2) or need > self.slots:
+                        raise ValueError(f"serve: the request needs {need} slots, the session has {self.slots}")
                 except ValueError as e:
                     refused.append((index, e))
                     continue
-                self.rows[slot] = _Row(index, int(prefix_len), int(max_new), self.step)
-                admitted.append((slot, index, item))
-                break
-            if self.exhausted:
-                break
+                self.waiting = (index, item, int(got[0]), int(got[1]), need)
+            index, item, prefix_len, max_new, need = self.waiting
+            if need > len(free):
+                break                                   # the head of the queue waits for a second idle slot; nothing overtakes it
+            self.waiting = None
+            own = free[0]
+            self.rows[own] = _Row(index, prefix_len, max_new, self.step, partner=free[1] if need == 2 else None)
+            if need == 2:
+                self.rows[free[1]] = _Row(index, prefix_len, max_new, self.step, partner=own, owner=False)
+            admitted.append((own, index, item))
         return admitted, refused
+
+    def partner(self, slot: int) -> int | None:
+        r = self.rows[slot]
+        return None if r is None else r.partner
+
+    def is_owner(self, slot: int) -> bool:
+        r = self.rows[slot]
+        return r is not None and r.owner
 
     # ---------------------------------------------------------------- the steps
     def advance(self, steps: int | None = None) -> None:
@@ -165,7 +200,7 @@ class SlotScheduler:
     def wants_eos(self, remaining: Sequence[int]) -> list[int]:
         """The busy slots whose remaining_steps reached 0 (stopped, or budget spent) and whose first codebook-0 EOS column is not known
         yet: every column that decides it has been written."""
-        return [b for b, r in enumerate(self.rows) if r is not None and not r.eos_known and remaining[b] <= 0]
+        return [b for b, r in enumerate(self.rows) if r is not None and r.owner and not r.eos_known and remaining[b] <= 0]
 
     def set_eos(self, slot: int, eos_column: int | None) -> None:
         r = self.rows[slot]
@@ -177,22 +212,25 @@ class SlotScheduler:
         return row_end_offset(offset0, r.prefix_len + r.max_new_tokens + self.nq, self.slots, self.nq, r.eos_column)
 
     def due(self) -> list[tuple[int, int, int]]:
-        """(slot, index, end offset) of every row whose own loop has left by now; the slots become idle."""
+        """(slot, index, end offset) of every row whose own loop has left by now; the slots become idle.  A two-slot request is named by
+        its owner slot, and its second slot (`partner`, asked before this call) becomes idle with it."""
         out = []
         for b, r in enumerate(self.rows):
-            if r is None or not r.eos_known:
+            if r is None or not r.owner or not r.eos_known:
                 continue
             end = self.end_offset(b)
             if self.step - r.step0 >= end - (r.prefix_len + 1):
                 out.append((b, r.index, end))
                 self.rows[b] = None
+                if r.partner is not None:
+                    self.rows[r.partner] = None
         return out
 
     def all_idle(self) -> bool:
         return all(r is None for r in self.rows)
 
     def finished(self) -> bool:
-        return self.exhausted and self.all_idle()
+        return self.exhausted and self.waiting is None and self.all_idle()
 
 
 class ServeChunk(NamedTuple):
@@ -221,7 +259,8 @@ class StreamLedger:
     prefix + max_new_tokens + nq - 1: an overrunning row writes beyond its own columns only.  The frames [0, release_limit(column)) are
     final; a chunk goes out when they have grown by `chunk_frames`.  The caller drives it at every scheduling point: `cells` (which
     codebook-0 cells to read, for all slots in one gather), `scan` (what they held), `close` (the rows retired at this point), `take`
-    (the chunks of the rows that run on)."""
+    (the chunks of the rows that run on).  Of a request that holds two slots (a mixed session) only the owner slot is opened here: its
+    second slot holds the same cells."""
 
     def __init__(self, nq: int, chunk_frames: int, eos_id: int):
         if int(chunk_frames) < 1:
