@@ -397,6 +397,31 @@ int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t iters, flo
 /* nn.LayerNorm + nn.Linear(no bias): out[r,n] = bf16(sum_k LN(x)[r,k] W[n,k]); ln_w == NULL skips the norm. */
 int zn_op_linear(zn_handle h, const void* x_dev, const void* ln_w, const void* ln_b, const void* W_dev,
                  void* out_dev, int32_t rows, int32_t N, int32_t K, zn_stream stream);
+/* One fused linear through the production dispatch, for per-op tests: plan_linear over the handle's settings and workspace, then the launcher
+ * the decode step and the prefill use, for the (prologue, epilogue) pairs they instantiate - no prologue or LayerNorm x {store, residual,
+ * SiLU gate, fp32, split + RoPE + KV append}, gated norm x store; any other pair is ZN_ERR_UNSUPPORTED.  pro / epi: 0 none, 1 LayerNorm,
+ * 2 gated RMS norm (gv: fp32 [rows][K]) / 0 store (+ optional bias), 1 residual, 2 SiLU gate (out [rows][N / 2]), 3 RoPE + KV append (q_out
+ * [rows][Hq * hd], kv [rows][max_len][2][Hkv][hd], lengths int32 [rows]; head geometry and RoPE table are the handle's; prefill: activation
+ * row r * pf_S + s is position pf_base + s of cache row r, and out [rows][N] receives the plain projection when plan[ZN_LP_ROPE_DONE] is 0),
+ * 4 fp32 (out_f32).  want_ln_stats_out: leave LayerNorm statistics of the output rows in the handle when the plan can; ln_stats_in = 1:
+ * normalise from the statistics the previous call on this handle left there.  plan[] (ZN_LP_*) is filled even on error.  ZN_ERR_ARG, before
+ * any launch, when a launch would outrun a workspace of the handle (LayerNorm launch buffer, statistics buffer). */
+enum zn_linear_plan_field {
+  ZN_LP_KERNEL = 0,      /* 0 GEMV, 1 GEMM16, 2 GEMM16S, 3 GEMM16K, 4 GEMM64S, 5 tiled GEMM */
+  ZN_LP_EPI = 1, ZN_LP_KS = 2, ZN_LP_NCH = 3, ZN_LP_UPW = 4, ZN_LP_BLOCKS = 5, ZN_LP_FULL = 6, ZN_LP_NW = 7, ZN_LP_TILE8 = 8, ZN_LP_NWV = 9,
+  ZN_LP_GROUPS = 10, ZN_LP_KSPLIT = 11, ZN_LP_LNP = 12, ZN_LP_LN_PRO = 13, ZN_LP_LN_LAUNCH = 14, ZN_LP_WRITES_LN_STATS = 15,
+  ZN_LP_READS_LN_STATS = 16, ZN_LP_ERR = 17, ZN_LP_ROPE_DONE = 18, ZN_LP_ROWS_PER_LAUNCH = 19, ZN_LP_NFIELDS = 24
+};
+typedef struct zn_linear_op {
+  int32_t pro, epi, rows, N, K, prefill, target_blocks, want_ln_stats_out, ln_stats_in;
+  int32_t max_len, pf_S, pf_base;
+  const void *x, *W, *ln_w, *ln_b, *gv, *bias, *resid;
+  void *out, *out_f32;
+  const int32_t* lengths;
+  void *kv, *q_out;
+  int32_t plan[24];
+} zn_linear_op;
+int zn_op_linear_fused(zn_handle h, zn_linear_op* op, zn_stream stream);
 /* Prefix-conditioner pieces (zonos/conditioning.py): nn.Linear with bias (Conditioner.project, :52-60; bias added in fp32
  * before the one bf16 rounding), nn.Embedding row gather (:364-365,467), FourierConditioner.apply_cond (:436-441), nn.SiLU. */
 int zn_op_linear_bias(zn_handle h, const void* x_dev, const void* W_dev, const void* bias_dev, void* out_dev, int32_t rows,

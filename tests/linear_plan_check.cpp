@@ -59,6 +59,7 @@ static void check_plan(const LinearEnv& e, const LinearPlan& p, int pro, int epi
   }
   if (p.kernel == LinearPlan::GEMM16K) CHECK(K == ZN_G16K_NKW * ZN_G16K_KCH * p.nch && (!prefill || rows <= 64), "%s: K %d rows %d", describe(p).c_str(), K, rows);
   if (p.kernel == LinearPlan::GEMM16) CHECK(K % (p.nw * 32) == 0 && p.blocks == (p.tile8 ? N / 8 : (epi == EPI_SILU ? N / 2 / 16 : (N + 15) / 16)), "%s", describe(p).c_str());
+  if (p.kernel == LinearPlan::GEMM_TILED) CHECK(prefill && K % 32 == 0, "%s: K %d (the tiled kernel walks whole 32-wide fragments)", describe(p).c_str(), K);
   (void)target;
 }
 
@@ -67,7 +68,7 @@ struct Pinned { const char* what; int rows; const char* plan; };
 int main(int argc, char** argv) {
   const bool print = argc > 1 && !strcmp(argv[1], "--print");
   const int rows_v[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 24, 64};
-  const int shapes[][2] = {{2048, 2048}, {3072, 2048}, {8512, 2048}, {9225, 2048}, {16384, 2048}, {2048, 4096}, {2048, 8192}, {1000, 512}, {72, 256}};
+  const int shapes[][2] = {{2048, 2048}, {3072, 2048}, {8512, 2048}, {9225, 2048}, {16384, 2048}, {2048, 4096}, {2048, 8192}, {1000, 512}, {72, 256}, {200, 136}};
   const int tiles_v[] = {0, 64, 200};
   for (int tune = 0; tune < 16; ++tune)
     for (int mt : tiles_v)

@@ -75,6 +75,9 @@ def test_bad_arguments_return_status_not_crash(lib):
     assert lib.zn_create(C.byref(zc), C.byref(w), 2, C.byref(h)) < 0
     assert b"divide" in lib.zn_last_error(None)
     assert lib.zn_decode_steps(None, 1, None) < 0
+    op = _lib.zn_linear_op(pro=_lib.PRO_LN, epi=_lib.EPI_SILU, rows=5, N=96, K=256)
+    assert lib.zn_op_linear_fused(None, C.byref(op), None) == -1 and lib.zn_op_linear_fused(None, None, None) == -1
+    assert C.sizeof(_lib.zn_linear_op) == 12 * 4 + 12 * C.sizeof(C.c_void_p) + 24 * 4 and len(_lib.LP_FIELDS) <= 24
     assert lib.zn_destroy(None) == 0
 
 

@@ -5,7 +5,8 @@ ZN_TUNE_NO_SPLIT_SMALL_M, ZN_TUNE_FC1_LN_LAUNCH, ZN_TUNE_NO_PREFILL_GEMM16K; ZN_
 (N, K) of test_small_m_linear_shapes_vs_fp32_reference plus fc1's.  Every plan names a kernel launch_linear holds an instantiation of (the
 header's own table, which the launcher's `if constexpr` guards read too) or carries an error; fc1 reads LayerNorm statistics only when the
 out_proj plan made under the same settings writes them, and those are written only by gemm16k_kernel<EPI_RESID> at N = 16 * ZN_G16_LNT; split-K
-plans fit the partial-tile buffer and the ticket array; GEMV grids cover their units and are mask-free only when exact.
+plans fit the partial-tile buffer and the ticket array; GEMV grids cover their units and are mask-free only when exact; the tiled GEMM is planned
+only for K a multiple of its 32-wide fragments ((200, 136) is in the walk for that).
 
 The last check pins the plans at the production shapes (in_proj, out_proj, fc1, fc2, heads at 2, 4, 6, 16 rows and a 48-row prefill, default
 settings).  The table was written down after the ordered kernel launch list (name, grid, workgroup size) of generations at those row counts and

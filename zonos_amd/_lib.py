@@ -76,6 +76,27 @@ class zn_admit(C.Structure):
     _fields_ = [("slot", C.c_int32), ("row_len", C.c_int32), ("prefix_len", C.c_int32), ("reserved", C.c_int32), ("params", zn_row_params)]
 
 
+# prologues / epilogues of a fused linear (zonos_amd/csrc/zn_linear_plan.h) and the fields of zn_linear_op.plan (enum zn_linear_plan_field)
+PRO_NONE, PRO_LN, PRO_GATED = 0, 1, 2
+EPI_STORE, EPI_RESID, EPI_SILU, EPI_ROPE_KV, EPI_F32, EPI_MAMBA = 0, 1, 2, 3, 4, 5
+LP_KERNELS = ("GEMV", "GEMM16", "GEMM16S", "GEMM16K", "GEMM64S", "GEMM_TILED")
+LP_FIELDS = ("kernel", "epi", "ks", "nch", "upw", "blocks", "full", "nw", "tile8", "nwv", "groups", "ksplit", "lnp", "ln_pro", "ln_launch",
+             "writes_ln_stats", "reads_ln_stats", "err", "rope_done", "rows_per_launch")
+
+
+class zn_linear_op(C.Structure):
+    """One fused linear for zn_op_linear_fused (include/zonos_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("pro", "epi", "rows", "N", "K", "prefill", "target_blocks", "want_ln_stats_out", "ln_stats_in",
+                                          "max_len", "pf_S", "pf_base")] + \
+               [(n, C.c_void_p) for n in ("x", "W", "ln_w", "ln_b", "gv", "bias", "resid", "out", "out_f32", "lengths", "kv", "q_out")] + \
+               [("plan", C.c_int32 * 24)]
+
+    def plan_dict(self) -> dict:
+        d = {k: int(self.plan[i]) for i, k in enumerate(LP_FIELDS)}
+        d["kernel"] = LP_KERNELS[d["kernel"]]
+        return d
+
+
 class zn_dac_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_codebooks", "codebook_size", "codebook_dim", "hidden_size", "decoder_hidden_size", "n_ratios")] + \
                [("ratios", C.c_int32 * 8), ("encoder_hidden_size", C.c_int32)]
@@ -131,6 +152,7 @@ SIGNATURES = {
     "zn_debug_trace": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zn_bench_kernel": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_void_p]),
     "zn_op_linear": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p]),
+    "zn_op_linear_fused": (C.c_int, [C.c_void_p, C.POINTER(zn_linear_op), C.c_void_p]),
     "zn_op_linear_bias": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p]),
     "zn_op_gather_rows": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]),
     "zn_op_fourier": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_float, C.c_void_p]),

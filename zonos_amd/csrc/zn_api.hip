@@ -2050,6 +2050,90 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
 }
 
 // ------------------------------------------------------------------------------------------------ single ops
+// A plan's LayerNorm launch normalises the rows of one launch group into nbuf [max_rows][d_model]: a caller-chosen K may not outrun it.
+static int check_ln_launch_fits(zn_handle h, const LinearPlan& p, int rows, int K, const char* who) {
+  if (p.err || !p.ln_launch) return ZN_OK;
+  const int per = p.rows_per_launch && p.rows_per_launch < rows ? p.rows_per_launch : rows;
+  if ((size_t)per * K > (size_t)h->max_rows * h->cfg.d_model)
+    ZN_FAIL(h, ZN_ERR_ARG, "%s: the LayerNorm launch over %d rows of K = %d exceeds the handle's buffer of %d x %d", who, per, K, h->max_rows, h->cfg.d_model);
+  return ZN_OK;
+}
+
+template <int PRO, int EPI>
+static int linear_fused_go(zn_handle h, const LinearPlan& p, const GemvArgs& a, int rows, hipStream_t s) {
+  return launch_linear<PRO, EPI>(h, p, a, rows, s);
+}
+
+extern "C" int zn_op_linear_fused(zn_handle h, zn_linear_op* op, zn_stream stream) {
+  if (!h || !op) return ZN_ERR_ARG;
+  for (int i = 0; i < ZN_LP_NFIELDS; ++i) op->plan[i] = 0;
+  op->plan[ZN_LP_ERR] = ZN_ERR_ARG;
+  const zn_config& c = h->cfg;
+  const int pro = op->pro, epi = op->epi, rows = op->rows, N = op->N, K = op->K;
+  const bool prefill = op->prefill != 0;
+  if (pro < 0 || pro >= ZN_NPRO || epi < 0 || epi >= ZN_NEPI || (op->prefill != 0 && op->prefill != 1) || (op->ln_stats_in != 0 && op->ln_stats_in != 1))
+    ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: bad prologue / epilogue / flag");
+  if (epi == EPI_MAMBA || (pro == PRO_GATED && epi != EPI_STORE)) { op->plan[ZN_LP_ERR] = ZN_ERR_UNSUPPORTED; ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_op_linear_fused: prologue %d with epilogue %d is not a production pair", pro, epi); }
+  if (!op->W || rows < 1 || N < 1 || K < 8 || K % 8 || op->target_blocks < 0) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: bad shape or weights");
+  if ((pro == PRO_GATED ? !op->gv : !op->x) || (pro != PRO_NONE && !op->ln_w) || (pro == PRO_LN && !op->ln_b))
+    ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: an operand of the prologue is missing");
+  if (pro == PRO_LN && K > 4096) { op->plan[ZN_LP_ERR] = ZN_ERR_UNSUPPORTED; ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_op_linear_fused: fused LayerNorm needs K <= 4096"); }
+  if (((epi == EPI_STORE || epi == EPI_RESID || epi == EPI_SILU || (epi == EPI_ROPE_KV && prefill)) && !op->out) || (epi == EPI_RESID && !op->resid) ||
+      (epi == EPI_F32 && !op->out_f32) || (epi == EPI_SILU && N % 2) || (op->bias && (epi != EPI_STORE || prefill)))
+    ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: an operand of the epilogue is missing or not served");
+  if (epi == EPI_ROPE_KV) {
+    if (!op->kv || !op->q_out || op->max_len < 1 || N != (c.n_heads + 2 * c.n_heads_kv) * h->hd) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: RoPE + KV append needs kv, q_out, max_len and N = (Hq + 2 Hkv) hd");
+    if (prefill ? (op->pf_S < 1 || rows % op->pf_S || op->pf_base < 0 || op->pf_base + op->pf_S > op->max_len) : !op->lengths)
+      ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: RoPE + KV append needs lengths (decode) or pf_S dividing rows with pf_base + pf_S <= max_len (prefill)");
+  }
+  LinearPlan p = plan_linear(linear_env(h), pro, epi, rows, N, K, op->target_blocks > 0 ? op->target_blocks : 1, prefill, op->want_ln_stats_out != 0, op->ln_stats_in != 0);
+  int* o = op->plan;
+  o[ZN_LP_KERNEL] = (int)p.kernel; o[ZN_LP_EPI] = p.epi; o[ZN_LP_KS] = p.ks; o[ZN_LP_NCH] = p.nch; o[ZN_LP_UPW] = p.upw; o[ZN_LP_BLOCKS] = p.blocks; o[ZN_LP_FULL] = p.full;
+  o[ZN_LP_NW] = p.nw; o[ZN_LP_TILE8] = p.tile8; o[ZN_LP_NWV] = p.nwv; o[ZN_LP_GROUPS] = p.groups; o[ZN_LP_KSPLIT] = p.ksplit; o[ZN_LP_LNP] = p.lnp; o[ZN_LP_LN_PRO] = p.ln_pro;
+  o[ZN_LP_LN_LAUNCH] = p.ln_launch; o[ZN_LP_WRITES_LN_STATS] = p.writes_ln_stats; o[ZN_LP_READS_LN_STATS] = p.reads_ln_stats; o[ZN_LP_ERR] = p.err;
+  o[ZN_LP_ROPE_DONE] = epi == EPI_ROPE_KV && p.epi == EPI_ROPE_KV && !p.err; o[ZN_LP_ROWS_PER_LAUNCH] = p.rows_per_launch;
+  if (p.err) ZN_FAIL(h, p.err, "%s", p.msg);
+  int rc;
+#define ZN_LF_REFUSE(...) do { o[ZN_LP_ERR] = ZN_ERR_ARG; ZN_FAIL(h, ZN_ERR_ARG, __VA_ARGS__); } while (0)
+  if ((rc = check_ln_launch_fits(h, p, rows, K, "zn_op_linear_fused"))) { o[ZN_LP_ERR] = rc; return rc; }
+  if ((p.writes_ln_stats || p.reads_ln_stats) && rows > h->max_rows) ZN_LF_REFUSE("zn_op_linear_fused: LayerNorm statistics of %d rows exceed the handle's %d", rows, h->max_rows);
+  if (op->ln_stats_in && !h->ln_part) ZN_LF_REFUSE("zn_op_linear_fused: the handle has no statistics buffer");
+  if (p.kernel == LinearPlan::GEMM_TILED && p.epi == EPI_SILU) {   // the tiled SiLU gate goes through pf_u [pf_rows][2 d_ff]
+    if (N % 4) ZN_LF_REFUSE("zn_op_linear_fused: the row-wise SiLU gate takes column pairs (N = %d is no multiple of 4)", N);
+    const size_t per = (size_t)2 * c.d_ff, need = ((size_t)rows * N + per - 1) / per;
+    if ((rc = ensure_prefill_ws(h, need))) { o[ZN_LP_ERR] = rc; return rc; }
+  }
+#undef ZN_LF_REFUSE
+  GemvArgs a = linear_args(h, op->W, N, K, (const bf16_t*)op->x, (bf16_t*)op->out, (const bf16_t*)op->resid);
+  a.ln_w = (const bf16_t*)op->ln_w; a.ln_b = (const bf16_t*)op->ln_b; a.gv = (const float*)op->gv; a.bias = (const bf16_t*)op->bias; a.out_f32 = (float*)op->out_f32;
+  a.ln_part_out = op->want_ln_stats_out ? h->ln_part : nullptr;
+  a.ln_part_in = op->ln_stats_in ? h->ln_part : nullptr;
+  if (epi == EPI_ROPE_KV) {
+    a.lengths = op->lengths; a.hd = h->hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv; a.q_out = (bf16_t*)op->q_out; a.kv = (bf16_t*)op->kv;
+    a.rope = h->rope; a.max_len = op->max_len; a.rope_positions = c.rope_positions;
+    if (prefill) { a.pf_S = op->pf_S; a.pf_base = op->pf_base; }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  rc = ZN_ERR_UNSUPPORTED;
+  const int e = p.epi;       // (prefill: EPI_ROPE_KV not served in the epilogue arrives here as EPI_STORE, as in prefill_linear)
+  if (pro == PRO_NONE) {
+    if (e == EPI_STORE) rc = linear_fused_go<PRO_NONE, EPI_STORE>(h, p, a, rows, s);
+    else if (e == EPI_RESID) rc = linear_fused_go<PRO_NONE, EPI_RESID>(h, p, a, rows, s);
+    else if (e == EPI_SILU) rc = linear_fused_go<PRO_NONE, EPI_SILU>(h, p, a, rows, s);
+    else if (e == EPI_F32) rc = linear_fused_go<PRO_NONE, EPI_F32>(h, p, a, rows, s);
+    else if (e == EPI_ROPE_KV) rc = linear_fused_go<PRO_NONE, EPI_ROPE_KV>(h, p, a, rows, s);
+  } else if (pro == PRO_LN) {
+    if (e == EPI_STORE) rc = linear_fused_go<PRO_LN, EPI_STORE>(h, p, a, rows, s);
+    else if (e == EPI_RESID) rc = linear_fused_go<PRO_LN, EPI_RESID>(h, p, a, rows, s);
+    else if (e == EPI_SILU) rc = linear_fused_go<PRO_LN, EPI_SILU>(h, p, a, rows, s);
+    else if (e == EPI_F32) rc = linear_fused_go<PRO_LN, EPI_F32>(h, p, a, rows, s);
+    else if (e == EPI_ROPE_KV) rc = linear_fused_go<PRO_LN, EPI_ROPE_KV>(h, p, a, rows, s);
+  } else if (e == EPI_STORE) rc = linear_fused_go<PRO_GATED, EPI_STORE>(h, p, a, rows, s);
+  if (rc) { o[ZN_LP_ERR] = rc; return rc; }
+  HIPCHK(h, hipGetLastError());
+  return ZN_OK;
+}
+
 extern "C" int zn_op_linear(zn_handle h, const void* x, const void* ln_w, const void* ln_b, const void* W, void* out, int32_t rows,
                             int32_t N, int32_t K, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
@@ -2058,6 +2142,7 @@ extern "C" int zn_op_linear(zn_handle h, const void* x, const void* ln_w, const 
   int rc;
   if (ln_w) {
     if (K > 4096) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_op_linear: fused LayerNorm needs K <= 4096");
+    if ((rc = check_ln_launch_fits(h, plan_linear(linear_env(h), PRO_LN, EPI_STORE, rows, N, K, 1024, false, false, false), rows, K, "zn_op_linear"))) return rc;
     a.ln_w = (const bf16_t*)ln_w; a.ln_b = (const bf16_t*)ln_b;
     rc = run_gemv<PRO_LN, EPI_STORE>(h, a, rows, 1024, (hipStream_t)stream);
   } else rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, 1024, (hipStream_t)stream);

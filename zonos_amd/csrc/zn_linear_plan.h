@@ -122,7 +122,11 @@ inline LinearPlan plan_linear(const LinearEnv& e, int pro, int epi, int rows, in
     const bool k16 = rows <= 64 && gemm16k_fits(e, epi, N, K) && e.no_prefill_gemm16k != 2;
     if (epi == EPI_ROPE_KV && !(k16 && K / (ZN_G16K_NKW * ZN_G16K_KCH) == 2)) p.epi = epi = EPI_STORE;
     if (k16) { p.kernel = LinearPlan::GEMM16K; p.nch = K / (ZN_G16K_NKW * ZN_G16K_KCH); return p; }
-    if (!plan_gemm64s(e, epi, rows, N, K, p)) p.kernel = LinearPlan::GEMM_TILED;
+    if (!plan_gemm64s(e, epi, rows, N, K, p)) {
+      // gemm_bf16_kernel walks K in whole 32-wide fragments: a shorter tail would read into the next row
+      if (K % 32) ZN_PLAN_FAIL("tiled gemm: K=%d not a multiple of 32", K);
+      p.kernel = LinearPlan::GEMM_TILED;
+    }
     return p;
   }
   if (rows <= 4) {
