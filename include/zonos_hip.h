@@ -448,6 +448,12 @@ int zn_op_attn_decode(zn_handle h, const void* q_dev, const void* kv_dev, int32_
  * [rows, positions, Hq*hd]; same CPU flash-attention rounding points as zn_op_attn_decode, incl. its query-block split. */
 int zn_op_attn_prefill(zn_handle h, const void* q_dev, const void* kv_dev, int32_t max_len, void* out_dev, int32_t positions,
                        int32_t rows, zn_stream stream);
+/* Test entry: the same attention with the two arguments the ragged prefill and the seam use.  `base` keys are already cached per row:
+ * position s sees keys 0..base+s, and base + positions <= max_len.  row_len_dev (int32[rows], may be NULL): row r holds
+ * row_len[r] <= positions valid positions and takes the query split of a sequence of that length; positions at or past it are neither
+ * read as keys nor written.  Refused before any launch: base < 0, base + positions > max_len, a null pointer, rows > max_rows. */
+int zn_op_attn_prefill_rows(zn_handle h, const void* q_dev, const void* kv_dev, int32_t max_len, void* out_dev, int32_t positions,
+                            int32_t rows, int32_t base, const int32_t* row_len_dev, zn_stream stream);
 /* mamba_ssm layer_norm_fn(prenorm=True) of the hybrid Block: s = h + res (fp32), res <- bf16(s) in place (res NULL:
  * s = h), out = bf16(LayerNorm(s)).  h/out bf16 [rows, d].  flags bit 0: RMSNorm instead of LayerNorm (rms_norm; b may be
  * NULL), bit 1: res is float [rows, d] and keeps the unrounded sum (residual_in_fp32). */

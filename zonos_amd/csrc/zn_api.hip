@@ -2312,6 +2312,20 @@ extern "C" int zn_op_attn_prefill(zn_handle h, const void* q, const void* kv, in
   return ZN_OK;
 }
 
+// Test entry: prefill_attention with the two arguments the ragged prefill and the seam pass (zn_op_attn_prefill fixes them at 0 / NULL).
+extern "C" int zn_op_attn_prefill_rows(zn_handle h, const void* q, const void* kv, int32_t max_len, void* out, int32_t positions, int32_t rows,
+                                       int32_t base, const int32_t* row_len, zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  if (!q || !kv || !out || rows < 1 || positions < 1 || base < 0 || max_len < 1 || (int64_t)base + positions > max_len)
+    ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_prefill_rows: bad argument (positions %d + %d of %d)", base, positions, max_len);
+  if (rows > h->max_rows) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_prefill_rows: rows %d > max_rows %d", rows, h->max_rows);
+  const int nq = h->cfg.n_heads * h->hd;
+  int rc = prefill_attention(h, (const bf16_t*)q, nq, (const bf16_t*)kv, max_len, (bf16_t*)out, nq, positions, rows, (hipStream_t)stream, base, row_len);
+  if (rc) return rc;
+  HIPCHK(h, hipGetLastError());
+  return ZN_OK;
+}
+
 extern "C" int zn_op_embed(zn_handle h, const int32_t* codes, void* out, int32_t batch, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
   if (!codes || !out || batch < 1) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_embed: bad argument");

@@ -485,3 +485,451 @@ def linear_case_reference(c: LinearCase, t: dict, eps: float, rope=None, rope_po
         kw = dict(rope=rope, positions=pos.clamp(max=rope_positions - 1), hd=c.hd, n_heads=2048 // c.hd, n_heads_kv=512 // c.hd)
     return linear_fused_reference(c.pro, c.epi, t["W"], x=t.get("x"), ln_w=t.get("ln_w"), ln_b=t.get("ln_b"), gv=t.get("gv"), bias=t.get("bias"),
                                   resid=t.get("resid"), eps=eps, **kw)
+
+
+# ------------------------------------------------------------------ attention: float64 interval reference, comparator, fp32 restatement, case tables
+# Decode and prefill attention against float64 arithmetic on the bf16 operands.  As for the fused linears the bar is an interval per output
+# element with bf16 ends (bf16_round64 is monotone: lo <= got <= hi is an exact test and no element is exempt).  With the true weights
+# w_t = softmax_t((q.k_t) scale) over the visible keys, exact_d = sum_t w_t v_td and A_d = sum_t w_t |v_td|, every kernel here computes
+#   out_d = fl(N_d * fl(1 / l)),   N_d = sum_t c_t P_t v_td (fp32, some order),   l = sum_t c_t e_t (fp32, some order),
+# where e_t = exp~(fl(s~_t - m)) with m the running maximum through the key's 512-key block, P_t = bf16(e_t) and c_t the product of the later
+# blocks' rescales f_j = exp(m_{j-1} - m_j).  c_t multiplies numerator and denominator alike and exp(-m) is common to all keys, so neither the
+# error of f_j nor the choice of m reaches the quotient: out_d = sum_t w_t rho_t v_td with every rho_t inside [1 / (1 + Theta), 1 + Theta], hence
+# |out_d - exact_d| <= Theta A_d.  Theta is assembled from these terms and nothing else (u = 2^-24, the unit roundoff of fp32):
+#   eps       score error, absolute: bf16 x bf16 products are exact in fp32; their fp32 sum in any order (fma chain, matrix cores) costs LF_SUM_BOUND
+#             per term over hd terms of sum_i |q_i k_ti|, the scale multiply and fl32(1 / sqrt(hd)) one rounding each (2 u |s_t|).  It enters a
+#             weight as e^{+-2 eps}: once through the numerator, once through the denominator.
+#   AT_SUB    rounding of s - m: u |s - m| with |s - m| <= -ln(FLT_MIN) + 1 on the keys that count (below), again twice.
+#   eta       AT_FEXP_ETA, the relative error of the exponential: the one term IEEE does not give.  zn_fexp_u20 is restated in numpy below
+#             (fexp_u20_np) and measured against float64 exp on a dense grid (fexp_u20_max_rel_error); libm's expf (<= 1 ulp) is far inside it.
+#   AT_BF16   P = bf16(e): 2^-8, half an ulp of an 8-bit significand (at most; 2^-9 is the error at the top of a binade).  The dominant term.
+#             The row sum takes the unrounded e, so it appears once.
+#   gamma     fp32 sums of L terms (row sum: positive terms; P.V: against sum |P v|) at LF_SUM_BOUND per term, plus one multiply and one add per
+#             512-key block for the recurrence acc = acc f_j + pv_j (2 u per block), for numerator and denominator each.
+#   2 u + u   the reciprocal (<= 1 ulp) and the final multiply; the final bf16 rounding is applied to the interval's ends.
+#   Theta = e^{2 (eps + AT_SUB)} (1 + eta) (1 + AT_BF16) (1 + gamma) (1 + 2 u) (1 + u) / ((1 - eta) (1 - gamma)) - 1.
+# Absolute term: a key with s_t - max_t s_t < ln(FLT_MIN) + AT_DEAD_MARGIN may be flushed to zero (fexp_u20 returns 0 below ln(FLT_MIN); a product
+# with an underflowing f_j loses its precision), or be kept: its whole weight, (1 + Theta) sum_dead w_t |v_td|, is added, and FLT_MIN L max|v| for
+# arithmetic in the subnormal range.  The margin of 1 covers eps (the reference refuses eps >= 0.5).
+AT_U = 2.0 ** -24
+AT_BF16 = 2.0 ** -8
+AT_LN_FLT_MIN = float(np.log(np.float64(np.finfo(np.float32).tiny)))       # -87.3365...
+AT_DEAD_MARGIN = 1.0
+AT_SUB = AT_U * (AT_DEAD_MARGIN - AT_LN_FLT_MIN)
+# max |fexp_u20_np(x) / exp(x) - 1| over fexp_u20_grid() measures AT_FEXP_MEASURED (tests/test_attention_compare_cpu.py measures it again and prints it);
+# the constant is the next power of two above it.
+AT_FEXP_MEASURED = 1.1243e-4                                               # at x = -36.0435, over 4 207 519 fp32 arguments
+AT_FEXP_ETA = 2.0 ** -13                                                   # 1.2207e-4
+_FEXP_LOW = np.uint32(0xc2aeac50).view(np.float32)                         # ln(FLT_MIN) as zn_fexp_u20 spells it
+
+
+def fexp_u20_np(x) -> np.ndarray:
+    """zn_fexp_u20 (zonos_amd/csrc/zn_common.h) in numpy: float32 operations, a truncating cast.  An fma is the float64 product (exact: 24 x 24
+    bits) plus the addend, rounded to float64 and then to float32 - a double rounding that can differ from the fused one by an ulp of float32
+    on rare inputs, five orders below the error measured here."""
+    x = np.asarray(x, dtype=np.float32)
+    fma = lambda a, b, c: (a.astype(np.float64) * np.float64(b) + np.float64(c)).astype(np.float32)
+    log2e = np.uint32(0x3fb8aa3b).view(np.float32)
+    c0, c1 = np.float32(0.00010703434948458272), np.float32(0.30354260500649682)
+    c2, c3 = np.float32(-0.22433836478672356), np.float32(-0.079204240219773236)
+    ok = x >= _FEXP_LOW                                                     # false for NaN too
+    src = np.where(ok, x, np.float32(0.0)) * log2e
+    frac = src - np.floor(src)
+    r = fma(frac, c3, c2)
+    r = fma(frac, r.astype(np.float64), c1)
+    r = fma(frac, r.astype(np.float64), c0)
+    src = src - r
+    tmp = (np.float64(8388608.0) * src.astype(np.float64) + np.float64(1065353216.0)).astype(np.float32)
+    i = np.clip(np.trunc(tmp), -2147483648.0, 2147483520.0).astype(np.int32)   # (the conversion saturates; arguments in [ln(FLT_MIN), 0] never get there)
+    return np.where(ok, i, np.int32(0)).astype(np.int32).view(np.float32)
+
+
+def fexp_u20_grid() -> np.ndarray:
+    """Every fp32 value of a dense grid on [ln(FLT_MIN), 0]: 2^22 equally spaced points, and 64 consecutive fp32 values on either side of every
+    multiple of ln 2 (where the polynomial's argument wraps)."""
+    g = np.linspace(float(_FEXP_LOW), 0.0, 1 << 22).astype(np.float32)
+    k = (np.arange(0, 127, dtype=np.float64) * -np.log(2.0)).astype(np.float32)
+    k = k[k >= _FEXP_LOW]
+    near = (k.view(np.int32)[:, None] + np.arange(-64, 65, dtype=np.int32)[None, :]).reshape(-1).view(np.float32)
+    near = near[(near >= _FEXP_LOW) & (near <= 0)]
+    return np.unique(np.concatenate([g, near, np.array([_FEXP_LOW, 0.0], dtype=np.float32)]))
+
+
+def fexp_u20_max_rel_error() -> tuple:
+    """(max relative deviation of fexp_u20_np from float64 exp over fexp_u20_grid(), the argument where it occurs, grid size)."""
+    x = fexp_u20_grid()
+    d = np.abs(fexp_u20_np(x).astype(np.float64) / np.exp(x.astype(np.float64)) - 1.0)
+    i = int(d.argmax())
+    return float(d[i]), float(x[i]), int(x.size)
+
+
+class AttentionRef(NamedTuple):
+    lo: torch.Tensor           # float64 tensors [R][Hq][Sq][hd]; lo and hi hold bf16 values
+    hi: torch.Tensor
+    exact: torch.Tensor
+    weight_abs: torch.Tensor   # A_d = sum_t w_t |v_td|
+    theta: torch.Tensor        # [R][Hq][Sq]
+    valid: torch.Tensor        # bool [R][Sq]: the query sees at least one key (others are not compared)
+    wmax: torch.Tensor         # [R][Hq][Sq] largest weight and its key: what the spotlight cases assert
+    tmax: torch.Tensor
+
+
+def attention_reference(q, k, v, scale: float, visible) -> AttentionRef:
+    """q bf16 [R][Hq][Sq][hd], k and v bf16 [R][Hkv][T][hd], visible bool [R][Sq][T] (the same for every head).  Keys no query of the row sees
+    may hold anything (NaN patterns): they are never touched."""
+    R, Hq, Sq, hd = q.shape
+    Hkv, T = k.shape[1], k.shape[2]
+    G = Hq // Hkv
+    lo, hi, exact, wabs = (torch.zeros(R, Hq, Sq, hd, dtype=torch.float64) for _ in range(4))
+    theta, wmax = torch.zeros(R, Hq, Sq, dtype=torch.float64), torch.zeros(R, Hq, Sq, dtype=torch.float64)
+    tmax = torch.zeros(R, Hq, Sq, dtype=torch.long)
+    valid = visible.any(-1)
+    for r in range(R):
+        vis = visible[r]                                                    # [Sq][T]
+        seen = vis.any(0)
+        n = int(seen.nonzero().max()) + 1 if bool(seen.any()) else 1        # keys past the last visible one are left out altogether
+        vis, seen = vis[:, :n], seen[:n]
+        kk = torch.where(seen[None, :, None], k[r, :, :n].double(), torch.zeros((), dtype=torch.float64)).repeat_interleave(G, 0)
+        vv = torch.where(seen[None, :, None], v[r, :, :n].double(), torch.zeros((), dtype=torch.float64)).repeat_interleave(G, 0)
+        qq = q[r].double()
+        s = torch.einsum("hsd,htd->hst", qq, kk) * scale
+        sabs = torch.einsum("hsd,htd->hst", qq.abs(), kk.abs()) * scale
+        eps = torch.where(vis[None], hd * LF_SUM_BOUND * sabs + 2 * AT_U * s.abs(), torch.zeros((), dtype=torch.float64)).amax(-1)
+        if float(eps.max()) >= 0.5:
+            raise ValueError(f"score error bound {float(eps.max()):.3g} >= 0.5: the dead-key margin does not cover it")
+        sm = torch.where(vis[None], s, torch.full((), float("-inf"), dtype=torch.float64))
+        M = sm.amax(-1, keepdim=True)
+        M = torch.where(torch.isfinite(M), M, torch.zeros_like(M))          # a query without keys: weights 0, not compared
+        e = torch.exp(sm - M)
+        w = e / e.sum(-1, keepdim=True).clamp(min=1e-300)
+        dead = vis[None] & (sm - M < AT_LN_FLT_MIN + AT_DEAD_MARGIN)
+        ex = torch.einsum("hst,htd->hsd", w, vv)
+        A = torch.einsum("hst,htd->hsd", w, vv.abs())
+        Ad = torch.einsum("hst,htd->hsd", w * dead, vv.abs())
+        L = vis.sum(-1).double()[None]                                      # [1][Sq]
+        gamma = LF_SUM_BOUND * L + 2 * AT_U * ((n + 511) // 512)
+        th = torch.exp(2 * (eps + AT_SUB)) * (1 + AT_FEXP_ETA) * (1 + AT_BF16) * (1 + gamma) * (1 + 2 * AT_U) * (1 + AT_U) / ((1 - AT_FEXP_ETA) * (1 - gamma)) - 1
+        tol = th[..., None] * A + (1 + th[..., None]) * Ad + float(np.finfo(np.float32).tiny) * L[..., None] * vv.abs().amax(1)[:, None, :]
+        if not bool(torch.isfinite(ex).all() and torch.isfinite(tol).all()):
+            raise ValueError("the float64 reference is not finite")
+        lo[r], hi[r], exact[r], wabs[r], theta[r] = bf16_round64(ex - tol), bf16_round64(ex + tol), ex, A, th
+        wmax[r], tmax[r] = w.max(-1)
+    return AttentionRef(lo, hi, exact, wabs, theta, valid, wmax, tmax)
+
+
+class AttentionCheck(NamedTuple):
+    outside: int               # compared elements outside [lo, hi] (a NaN is outside)
+    nonfinite: int             # compared elements that are NaN or Inf
+    total: int
+    headroom: float            # worst |got - exact| / (Theta A_d): reported, not asserted (the bf16 rounding of the output alone can exceed 1)
+    worst: tuple               # (row, head, position, dim) of the element farthest outside, or of the worst headroom
+    ok: bool
+
+    def line(self, label: str) -> str:
+        r, h, s, d = self.worst
+        return (f"[attention {label}] outside [lo, hi]: {self.outside} of {self.total}; non-finite {self.nonfinite}; worst |got - exact| / (Theta A) "
+                f"{self.headroom:.3f} at row {r} head {h} position {s} dim {d}")
+
+
+def attention_compare(got, ref: AttentionRef, label: str = "", quiet: bool = False) -> AttentionCheck:
+    """lo <= got <= hi on every element of every query that sees a key; got [R][Hq][Sq][hd].  Prints one line."""
+    g = torch.as_tensor(got).detach().cpu().double()
+    if g.shape != ref.lo.shape:
+        raise ValueError(f"shapes differ: {tuple(g.shape)} vs {tuple(ref.lo.shape)}")
+    cmp = ref.valid[:, None, :, None].expand_as(g)
+    fin = torch.isfinite(g)
+    inside = (g >= ref.lo) & (g <= ref.hi)
+    bad = cmp & ~inside
+    over = torch.where(fin, torch.maximum(ref.lo - g, g - ref.hi).clamp(min=0.0), torch.full_like(g, float("inf")))
+    ratio = (g - ref.exact).abs() / (ref.theta[..., None] * ref.weight_abs).clamp(min=1e-300)
+    ratio = torch.where(cmp & fin & (ref.weight_abs > 0), ratio, torch.zeros_like(ratio))
+    score = torch.where(cmp, over, torch.zeros_like(over)) if bool(bad.any()) else ratio
+    idx = int(score.argmax())
+    worst = tuple(int(i) for i in np.unravel_index(idx, tuple(g.shape)))
+    res = AttentionCheck(int(bad.sum()), int((cmp & ~fin).sum()), int(cmp.sum()), float(ratio.max()), worst, not bool(bad.any()) and bool((fin | ~cmp).all()))
+    if not quiet:
+        print("\n" + res.line(label))
+    return res
+
+
+def attention_restatement(q, k, v, scale: float, visible, span=None, mut: str = "") -> torch.Tensor:
+    """The kernels' arithmetic in plain fp32 (torch CPU matmuls for the two contractions, in whatever order they sum): 512-key blocks, the running
+    maximum, e = fexp_u20 on the first 16 floor(n / 16) keys of the block's span and libm exp on the rest, the row sum of the unrounded e,
+    P = bf16(e), the recurrence acc = acc f_j + pv_j, out = bf16(acc (1 / l)).  Keys no query of the row sees are zeroed first, as the kernels do.
+    span int [R][Sq]: keys the reference's query block spans (default: the query's own keys).  Shapes as attention_reference; returns bf16.
+    mut: "no_rescale" (f_j = 1), "no_max" (nothing subtracted), "tail_unmasked" (every key of the buffer counts) - tests/test_attention_compare_cpu.py."""
+    R, Hq, Sq, hd = q.shape
+    Hkv, T = k.shape[1], k.shape[2]
+    G = Hq // Hkv
+    out = torch.full((R, Hq, Sq, hd), float("nan"), dtype=torch.bfloat16)
+    sc32 = torch.tensor(np.float32(scale))
+    ninf = torch.full((), float("-inf"))
+    for r in range(R):
+        vis = visible[r] if mut != "tail_unmasked" else torch.ones_like(visible[r])
+        seen = vis.any(0)
+        n = int(seen.nonzero().max()) + 1 if bool(seen.any()) else 1
+        vis, seen = vis[:, :n], seen[:n]
+        kk = torch.where(seen[None, :, None], k[r, :, :n].float(), torch.zeros(())).repeat_interleave(G, 0)
+        vv = torch.where(seen[None, :, None], v[r, :, :n].float(), torch.zeros(())).repeat_interleave(G, 0)
+        s = torch.matmul(q[r].float(), kk.transpose(1, 2)) * sc32           # [Hq][Sq][n]
+        Lq = vis.sum(-1)
+        E = torch.maximum(span[r], Lq) if span is not None else Lq
+        m = torch.full((Hq, Sq), float("-inf"))
+        acc, l = torch.zeros(Hq, Sq, hd), torch.zeros(Hq, Sq)
+        for t0 in range(0, n, 512):
+            t1 = min(n, t0 + 512)
+            vb, sb = vis[None, :, t0:t1], s[:, :, t0:t1]
+            mj = torch.maximum(m, torch.where(vb, sb, ninf).amax(-1))
+            if mut == "no_max":
+                mj = torch.zeros_like(mj)
+            f = torch.exp(m - mj) if t0 > 0 else torch.zeros_like(mj)
+            f = torch.where(torch.isfinite(mj) & torch.isfinite(m), f, torch.zeros_like(f)) if t0 > 0 else f
+            if mut == "no_rescale" and t0 > 0:
+                f = torch.ones_like(f)
+            x = torch.where(vb, sb - torch.where(torch.isfinite(mj), mj, torch.zeros_like(mj))[..., None], torch.zeros(()))
+            nvec = (E - t0).clamp(min=0, max=512) & ~15                     # [Sq]
+            fast = torch.arange(t1 - t0)[None, :] < nvec[:, None]
+            e = torch.where(fast[None], torch.from_numpy(fexp_u20_np(x.numpy())), torch.exp(x))
+            e = torch.where(vb, e, torch.zeros(()))
+            acc = acc * f[..., None] + torch.matmul(e.to(torch.bfloat16).float(), vv[:, t0:t1])
+            l = l * f + e.sum(-1)
+            m = mj
+        out[r] = (acc * (1.0 / l)[..., None]).to(torch.bfloat16)
+    return out
+
+
+# ---- inputs.  Three families: "diffuse" (N(0, 1) q, K, V: every weight about 1 / L), "spot" (one key per (row, head) - per (row, position) in
+# prefill - is c q / |q| with its scaled score at AT_SPOT_SCORE, so it holds more than half of the weight; its V row is a positive ramp, distinct
+# by position, against V rows of the other sign; the first key PAST the context is a stronger spotlight still, had it been visible), and the
+# range cases "rise" / "fall" / "tie" (q and K along one direction per kv head: scaled scores run from -100 to 100 over the cache, so that every
+# block rescale f_j is below 1e-20 and the earlier blocks vanish, or from 100 to -100, f_j = 1 and the later blocks flush to zero, or hold their
+# maximum of 60 twice, on keys 511 and 512 with the same K row).
+AT_TAILS = ("zeros", "random", "0x7FC0", "0xFFFF", "0x7F80", "0xFF80")      # what the keys at or past a row's context hold, in turn
+AT_SEED = 40
+AT_SEEDS: dict = {}            # tag -> seed, for an operand whose default draw left a spotlight below half of the weight (none needed so far)
+AT_SPOT_SCORE, AT_NEXT_SCORE = 20.0, 30.0
+AT_EDGES = (0, 15, 16, 63, 64, 127, 128, 511, 512, 513, 1023, 1024)
+# (head size, group) -> (query heads, kv heads) of the single-layer model that serves it (d_model = query heads x head size)
+AT_GEOM = {(128, 1): (2, 2), (128, 2): (4, 2), (128, 4): (8, 2), (128, 8): (8, 1), (64, 4): (8, 2), (64, 2): (4, 2), (32, 4): (8, 2), (32, 8): (8, 1)}
+AT_LENS_512 = (1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 511, 512, 300, 2, 449, 512)
+AT_LENS_1032 = (1, 16, 17, 64, 65, 128, 129, 511, 512, 513, 1023, 1024, 1025, 1032, 700, 3)      # 1032: a multiple of 8, not of 64
+
+
+class AttnCase(NamedTuple):
+    name: str
+    kind: str                  # "decode" (zn_op_attn_decode) | "prefill" (zn_op_attn_prefill_rows)
+    family: str                # diffuse | spot | spot_next | rise | fall | tie
+    hd: int
+    G: int
+    cap: int                   # cache capacity (max_len)
+    lens: tuple = ()           # decode: keys per row; prefill with `ragged`: row_len per row
+    rows: int = 0              # prefill
+    S: int = 0
+    base: int = 0
+    ragged: bool = False
+    tune: tuple = ()           # ((zn_debug_tune key name, value), ...) in force during the call
+    ext: str = "null"          # decode: ext = NULL | "L" | "split" (L rounded up to the query split) | "short" (below L: the bits of NULL)
+    kernel: str = ""           # the kernel template (and branch) the case is there for
+
+    @property
+    def R(self) -> int:
+        return len(self.lens) if self.kind == "decode" else self.rows
+
+    @property
+    def heads(self) -> tuple:
+        return AT_GEOM[(self.hd, self.G)]
+
+
+def at_qsplit(S: int) -> int:
+    """Query split of the reference's CPU flash kernel for a sequence of S positions."""
+    return 256 if S >= 768 else 64 if S >= 192 else 32
+
+
+def _at_pick(lens: tuple, rows: int) -> tuple:
+    """`rows` of the 16 contexts; between them the row counts of a capacity walk all 16."""
+    return {16: lens, 6: lens[10:16], 5: lens[5:10], 4: lens[0:4], 2: (lens[11], lens[4]), 1: (lens[12],)}[rows]
+
+
+def attention_cases_decode() -> list:
+    out = []
+    fam = {16: "spot", 6: "diffuse", 5: "spot", 4: "diffuse", 2: "spot", 1: "diffuse"}
+
+    def shape(hd, G, rows, cap, tune=()):
+        t = dict(tune)
+        fused = cap <= min(512, t.get("ZN_TUNE_ATTN_FUSED_MAX_KEYS", 512))
+        sc = hd == 128 and (t.get("ZN_TUNE_ATTN_SPLIT_COLS") == 2 or (t.get("ZN_TUNE_ATTN_SPLIT_COLS") != 1 and rows > 4))
+        ds = (4 if fused else 2) if sc else 1
+        k = f"attn_block_kernel<{hd},{G},{'fused' if fused else 'split'},DS{ds}>" + ("" if fused else f" + attn_scores_kernel<{hd},{G}>")
+        if fused and ds > 1:
+            k += " remap" if rows * AT_GEOM[(hd, G)][1] % 8 == 0 else " no-remap"
+        return k
+    for cap, lens in ((512, AT_LENS_512), (520, AT_LENS_512), (1032, AT_LENS_1032)):
+        for rows in (1, 2, 4, 5, 6, 16):
+            out.append(AttnCase(f"d128g4 r{rows} cap{cap}", "decode", fam[rows], 128, 4, cap, _at_pick(lens, rows), kernel=shape(128, 4, rows, cap)))
+        for rows, mode in ((4, 2), (2, 2), (16, 1)):
+            tune = (("ZN_TUNE_ATTN_SPLIT_COLS", mode),)
+            out.append(AttnCase(f"d128g4 r{rows} cap{cap} split_cols={mode}", "decode", "spot", 128, 4, cap, _at_pick(lens, rows), tune=tune,
+                                kernel=shape(128, 4, rows, cap, tune)))
+    for rows in (2, 5):
+        tune = (("ZN_TUNE_ATTN_FUSED_MAX_KEYS", 1),)
+        out.append(AttnCase(f"d128g4 r{rows} cap512 fused_max=1", "decode", "spot", 128, 4, 512, _at_pick(AT_LENS_512, rows), tune=tune,
+                            kernel=shape(128, 4, rows, 512, tune)))
+    for hd, G in ((128, 1), (128, 2), (128, 8), (64, 4), (64, 2), (32, 4), (32, 8)):
+        for rows in (2, 5):
+            for cap, lens in ((512, AT_LENS_512), (1032, AT_LENS_1032)):
+                out.append(AttnCase(f"d{hd}g{G} r{rows} cap{cap}", "decode", "spot" if rows == 2 else "diffuse", hd, G, cap, _at_pick(lens, rows),
+                                    kernel=shape(hd, G, rows, cap)))
+    for family in ("rise", "fall", "tie"):
+        out.append(AttnCase(f"d128g4 {family} cap1536", "decode", family, 128, 4, 1536, (1536, 1300), kernel=shape(128, 4, 2, 1536)))
+    out.append(AttnCase("d128g4 fall cap512", "decode", "fall", 128, 4, 512, (512, 400), kernel=shape(128, 4, 2, 512)))
+    out.append(AttnCase("d64g4 rise cap1536", "decode", "rise", 64, 4, 1536, (1536, 1300), kernel=shape(64, 4, 2, 1536)))
+    for cap in (4096, 4608, 8192, 8704, 16384):          # the ticketed combine at nb = 8, 9, 16, 17, 32
+        out.append(AttnCase(f"d128g4 r2 cap{cap} nb{(cap + 511) // 512}", "decode", "spot", 128, 4, cap, (cap, cap - 700), kernel=shape(128, 4, 2, cap)))
+    for cap, lens in ((512, (300, 77)), (1032, (1000, 700))):
+        for ext in ("L", "split", "short"):
+            out.append(AttnCase(f"d128g4 r2 cap{cap} ext={ext}", "decode", "spot", 128, 4, cap, lens, ext=ext, kernel=shape(128, 4, 2, cap)))
+    return out
+
+
+def attention_cases_prefill() -> list:
+    out = []
+    configs = [("mfma", 128, G) for G in (1, 2, 4, 8)] + [("valu", 128, G) for G in (1, 2, 4, 8)] + [("valu", 64, 4), ("valu", 64, 2), ("valu", 32, 4), ("valu", 32, 8)]
+    for kern, hd, G in configs:
+        tune = (("ZN_TUNE_PREFILL_ATTN_VALU", 2 if kern == "valu" else 1),)
+        kname = f"attn_prefill_mfma_kernel<{G}>" if kern == "mfma" else f"attn_prefill_kernel<{hd},{G}>"
+        mk = lambda family, S, rows=2, base=0, lens=(), ragged=False: AttnCase(
+            f"p{hd}g{G} {kern} {family} S{S}" + (f"+{base}" if base else "") + (" ragged" if ragged else ""), "prefill", family, hd, G, base + S + 3, lens, rows, S, base,
+            ragged, tune, kernel=kname)
+        TQ = 64 // G
+        for i, S in enumerate(sorted({1, TQ - 1, TQ, TQ + 1} - {0})):
+            out.append(mk(("spot", "diffuse", "spot_next", "spot")[i % 4], S))
+        out.append(mk("spot", TQ + 5, rows=4, lens=(1, TQ, TQ + 1, TQ + 5), ragged=True))
+        out.append(mk("spot_next", 513, rows=1))
+        if (hd, G) in ((128, 4), (64, 4)):
+            for S, family in ((191, "spot"), (192, "diffuse"), (512, "spot"), (767, "spot_next"), (768, "spot")):
+                out.append(mk(family, S, rows=1))
+            for base in (5, 500, 511):
+                out.append(mk("spot", 20, base=base))
+            for family in ("rise", "fall", "tie"):
+                out.append(mk(family, 600, rows=1))
+    mf = (("ZN_TUNE_PREFILL_ATTN_VALU", 1),)
+    out.append(AttnCase("p128g4 mfma spot S1025", "prefill", "spot", 128, 4, 1028, (), 1, 1025, 0, False, mf, kernel="attn_prefill_mfma_kernel<4>"))
+    return out
+
+
+def at_seed(tag: str) -> int:
+    return AT_SEEDS.get(tag, AT_SEED)
+
+
+def _at_normal(tag: str, shape) -> torch.Tensor:
+    return torch.from_numpy(synth.normal(at_seed(tag), "at." + tag, shape))
+
+
+def attention_case_tensors(c: AttnCase) -> dict:
+    """CPU operands of a case.  q bf16 [R][Hq][Sq][hd]; k, v bf16 [R][Hkv][cap][hd] with finite data everywhere (the "random" tail); visible bool
+    [R][Sq][cap]; span int [R][Sq]: keys the reference's query block spans; ext (decode): int [R] or None; start int [R]: first cache position of
+    the tail; spots: (row, head, position, key) of every query whose largest weight must be >= 0.5 and sit on that key."""
+    hq, hkv = c.heads
+    G, hd, R, cap = c.G, c.hd, c.R, c.cap
+    Sq = 1 if c.kind == "decode" else c.S
+    scale = 1.0 / float(np.sqrt(hd))
+    tag = f"{c.kind}.{c.family}.{hd}.{hq}.{hkv}.{R}.{Sq}.{cap}"
+    q, k, v = _at_normal("q." + tag, (R, hq, Sq, hd)), _at_normal("k." + tag, (R, hkv, cap, hd)), _at_normal("v." + tag, (R, hkv, cap, hd))
+    tt = torch.arange(cap)
+    if c.kind == "decode":
+        L = torch.tensor(c.lens)
+        visible = (tt[None, None, :] < L[:, None, None])
+        start, pos0 = L.clone(), L - 1                                     # pos0: cache position of query 0
+    else:
+        Sv = torch.tensor(c.lens) if c.ragged else torch.full((R,), c.S)
+        ss = torch.arange(Sq)
+        visible = (tt[None, None, :] <= c.base + ss[None, :, None]) & (ss[None, :, None] < Sv[:, None, None])
+        start, pos0 = c.base + Sv, torch.full((R,), c.base)
+    spots = []
+    ramp = lambda t: (1.0 + torch.arange(hd) / hd) * (1.0 + (t % 7) / 8.0)
+    if c.family in ("rise", "fall", "tie"):
+        d = _at_normal("dir." + tag, (R, hkv, 1, hd))
+        d = d / d.norm(dim=-1, keepdim=True)
+        if c.family == "tie":
+            a = 2.0 * _at_normal("a." + tag, (R, hkv, cap, 1))
+            a[:, :, 511:513] = 60.0
+        else:
+            a = (-100.0 + 200.0 * tt / max(cap - 1, 1)).view(1, 1, cap, 1).expand(R, hkv, cap, 1)
+            a = -a if c.family == "fall" else a
+        k = d * a + 0.05 * k
+        if c.family == "tie":
+            k[:, :, 512] = k[:, :, 511]
+        gain = (1.0 + 0.1 * (torch.arange(hq) % G)).view(1, hq, 1, 1)
+        q = d.repeat_interleave(G, 1) * float(np.sqrt(hd)) * gain + 0.0 * q     # |q| scale = 1: the scaled score of key t is (1 + 0.1 g) a_t
+    elif c.family != "diffuse":
+        q = q.to(torch.bfloat16).float()
+        qn = q / q.norm(dim=-1, keepdim=True)
+        cq = lambda r, h, s, score: qn[r, h, s] * (score / (scale * float(q[r, h, s].norm())))
+        if c.kind == "decode":
+            v = -v.abs()
+            for r in range(R):
+                Lr = int(c.lens[r])
+                edges = sorted({e for e in AT_EDGES if e < Lr} | {Lr - 1})
+                for kvh in range(hkv):
+                    for g in range(min(G, len(edges))):
+                        h = kvh * G + g
+                        t = edges[(r * hq + h) % len(edges)] if len(edges) >= G else edges[g]
+                        k[r, kvh, t], v[r, kvh, t] = cq(r, h, 0, AT_SPOT_SCORE), ramp(t)
+                        spots.append((r, h, 0, t))
+                    if Lr < cap:                                           # had it been visible
+                        k[r, kvh, Lr], v[r, kvh, Lr] = cq(r, kvh * G, 0, AT_NEXT_SCORE), 4.0 * ramp(Lr)
+        else:
+            sign = torch.where(tt % 2 == 0, 1.0, -1.0)
+            v = torch.stack([ramp(t) for t in range(7)])[tt % 7][None, None] * sign.view(1, 1, cap, 1) + 0.0 * v
+            shift = 1 if c.family == "spot_next" else 0                    # spot_next: the key one past a query's own is its spotlight
+            for r in range(R):
+                for s in range(Sq):
+                    t = c.base + s + shift
+                    if t >= cap:
+                        continue
+                    for kvh in range(hkv):
+                        h = kvh * G + s % G
+                        k[r, kvh, t] = cq(r, h, s, AT_NEXT_SCORE if shift else AT_SPOT_SCORE)
+                        if not shift and bool(visible[r, s, t]):
+                            spots.append((r, h, s, t))
+    q, k, v = q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16)
+    ext = None
+    if c.kind == "decode":
+        L = torch.tensor(c.lens)
+        qs = torch.tensor([at_qsplit(int(l)) for l in c.lens])
+        ext = {"null": None, "L": L, "split": (L + qs - 1) // qs * qs, "short": (L - 5).clamp(min=1)}[c.ext]
+        span = (torch.maximum(ext, L) if ext is not None else L)[:, None]
+    else:
+        qs = torch.tensor([at_qsplit(int(s)) for s in Sv])[:, None]
+        ss = torch.arange(Sq)[None, :]
+        span = c.base + torch.minimum((ss // qs) * qs + qs, Sv[:, None])
+    return dict(q=q, k=k, v=v, visible=visible, span=span, ext=ext, start=start, scale=scale, spots=spots)
+
+
+def attention_device_layout(c: AttnCase, t: dict) -> tuple:
+    """(q, kv) as the ops take them: q [R][Hq hd] (decode) or [R][S][Hq hd], kv [R][cap][2][Hkv][hd]."""
+    hq, hkv = c.heads
+    q = t["q"][:, :, 0].reshape(c.R, hq * c.hd) if c.kind == "decode" else t["q"].transpose(1, 2).reshape(c.R, c.S, hq * c.hd)
+    kv = torch.stack([t["k"], t["v"]], 1).permute(0, 3, 1, 2, 4)
+    return q.contiguous(), kv.contiguous()
+
+
+def attention_apply_tail(c: AttnCase, q, kv, start, tail: str):
+    """Fills, in place (on whatever device the tensors live), the cache positions at or past start[r] - and for a ragged prefill the q rows at or
+    past row_len[r] - with one of AT_TAILS ("random": what is there)."""
+    if tail == "random":
+        return
+    bits = 0 if tail == "zeros" else int(tail, 16)
+    bits = bits - 65536 if bits >= 32768 else bits
+    kvi, qi = kv.view(torch.int16), q.view(torch.int16)
+    for r in range(c.R):
+        kvi[r, int(start[r]):] = bits
+        if c.kind == "prefill" and c.ragged:
+            qi[r, int(c.lens[r]):] = bits
+
+
+def attention_from_device_layout(c: AttnCase, out) -> torch.Tensor:
+    """out [R][Hq hd] or [R][S][Hq hd] -> [R][Hq][Sq][hd] on the CPU."""
+    hq, _ = c.heads
+    o = out.detach().cpu()
+    return o.view(c.R, hq, 1, c.hd) if c.kind == "decode" else o.view(c.R, c.S, hq, c.hd).transpose(1, 2).contiguous()
