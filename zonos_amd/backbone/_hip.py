@@ -208,6 +208,23 @@ class HipEngine:
         with torch.cuda.device(dev):
             _lib.check(self.lib.zn_create(C.byref(zc), C.byref(w), max_rows, C.byref(handle)), None, "zn_create")
         self.h = handle
+        # FP8 streams of the MLP projections (Zonos.quantize_mlp_fp8 left them as buffers next to the dequantised bf16 weights)
+        for i, blk in enumerate(backbone.layers):
+            mlp = getattr(blk, "mlp", None)
+            if mlp is None or getattr(mlp, "fc1_q", None) is None:
+                continue
+            if cfg.ssm_cfg:
+                raise _lib.ZonosHipError("FP8 MLP weights on a hybrid checkpoint: the hybrid stack has no FP8 path")
+            ts = [mlp.fc1_q, mlp.fc1_exp, mlp.fc2_q, mlp.fc2_exp]
+            self._keep += ts
+            with torch.cuda.device(dev):
+                _lib.check(self.lib.zn_set_mlp_fp8(self.h, i, *[t.data_ptr() for t in ts]), self.h, "zn_set_mlp_fp8")
+
+    def mlp_fp8_plan(self, rows: int) -> list:
+        """zn_mlp_fp8_plan: whether fc1 and fc2 of a decode step over `rows` rows would read the FP8 stream now."""
+        out = (C.c_int32 * 2)()
+        self.call("zn_mlp_fp8_plan", rows, out)
+        return [int(out[0]), int(out[1])]
 
     def __del__(self):
         try:

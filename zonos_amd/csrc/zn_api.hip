@@ -35,6 +35,10 @@ struct zn_handle_s {
   zn_config cfg;
   int max_rows = 0, hd = 0, G = 0;
   std::vector<zn_layer_weights> layers;
+  // optional FP8 stream of a layer's fc1 / fc2 (zn_set_mlp_fp8): E4M3 codes [N][K] and a scale exponent per weight row; the layer's bf16 fc1 / fc2
+  // hold the dequantised values, and every kernel but gemm16s_kernel<., NWV | ZN_G16S_W8> reads those
+  struct MlpFp8 { const uint8_t *fc1_q = nullptr, *fc2_q = nullptr; const int8_t *fc1_exp = nullptr, *fc2_exp = nullptr; };
+  std::vector<MlpFp8> mlp_fp8;
   const void* heads = nullptr;
   const void *norm_f_w = nullptr, *norm_f_b = nullptr;
   const float* rope = nullptr;
@@ -293,6 +297,7 @@ extern "C" int zn_create(const zn_config* cfg, const zn_weights* w, int32_t max_
   }
   if (const char* e = getenv("ZN_PREFILL_MODE")) h->prefill_mode = atoi(e);
   h->layers.assign(w->layers, w->layers + c.n_layer);
+  h->mlp_fp8.assign(c.n_layer, zn_handle_s::MlpFp8{});
   h->heads = w->heads; h->norm_f_w = w->norm_f_w; h->norm_f_b = w->norm_f_b; h->rope = w->rope_table;
 #define ZC(call) do { hipError_t _e = ZN_NOT_IN_CAPTURE(call); if (_e != hipSuccess) { g_create_err = std::string(#call) + ": " + hipGetErrorString(_e); zn_destroy(h); return ZN_ERR_HIP; } } while (0)
   ZC(hipMalloc(&h->emb_tables_dev, sizeof(void*) * c.n_codebooks));
@@ -415,6 +420,12 @@ static void launch_gemm16s_t(const GemvArgs& g, const LinearPlan& p, hipStream_t
   if (p.nwv == 4) hipLaunchKernelGGL((gemm16s_kernel<EPI, 4, LNP>), dim3(p.groups, p.ksplit), dim3(256), 0, s, g);
   else hipLaunchKernelGGL((gemm16s_kernel<EPI, 2, LNP>), dim3(p.groups, p.ksplit), dim3(128), 0, s, g);
 }
+// the same launch reading the FP8 stream (p.w8): fc1 <EPI_SILU, ., {false, true}> and fc2 <EPI_RESID, ., false> only (lin_has_w8)
+template <int EPI, bool LNP>
+static void launch_gemm16s_w8_t(const GemvArgs& g, const LinearPlan& p, hipStream_t s) {
+  if (p.nwv == 4) hipLaunchKernelGGL((gemm16s_kernel<EPI, 4 | ZN_G16S_W8, LNP>), dim3(p.groups, p.ksplit), dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((gemm16s_kernel<EPI, 2 | ZN_G16S_W8, LNP>), dim3(p.groups, p.ksplit), dim3(128), 0, s, g);
+}
 
 // Every decision about a linear of 1 .. 64 rows is plan_linear's (zn_linear_plan.h); what it may depend on:
 static LinearEnv linear_env(zn_handle h) {
@@ -445,6 +456,7 @@ static int launch_linear(zn_handle h, const LinearPlan& p, GemvArgs a, int rows,
   if (p.err) ZN_FAIL(h, p.err, "%s", p.msg);
   if (!linear_plan_launchable(p, PRO, EPI)) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "linear: no kernel %d for prologue %d / epilogue %d (ks=%d nch=%d)", (int)p.kernel, PRO, EPI, p.ks, p.nch);
   if ((p.reads_ln_stats && !a.ln_part_in) || (p.writes_ln_stats && !a.ln_part_out)) ZN_FAIL(h, ZN_ERR_STATE, "linear: the plan hands over LayerNorm statistics, the call has no buffer for them");
+  if (p.w8 && (!a.W8q || !a.W8exp)) ZN_FAIL(h, ZN_ERR_STATE, "linear: the plan reads an FP8 weight stream, the call has none");
   if (!p.writes_ln_stats) a.ln_part_out = nullptr;
   a.units = p.units; a.upw = p.upw;
   if (p.ksplit) { a.part = h->g16_part; a.tickets = h->g16_tickets; a.ksplit = p.ksplit; }
@@ -469,6 +481,11 @@ static int launch_linear(zn_handle h, const LinearPlan& p, GemvArgs a, int rows,
         }
         break;
       case LinearPlan::GEMM16S:
+        if constexpr (lin_has_w8(PRO, EPI)) if (p.w8) {
+          if constexpr (lin_has_lnp(PRO, EPI)) if (p.lnp) { launch_gemm16s_w8_t<EPI, true>(g, p, s); break; }
+          launch_gemm16s_w8_t<EPI, false>(g, p, s);
+          break;
+        }
         if constexpr (lin_has_lnp(PRO, EPI)) if (p.lnp) { launch_gemm16s_t<EPI, true>(g, p, s); break; }
         if constexpr (lin_has_gemm16(PRO)) launch_gemm16s_t<EPI, false>(g, p, s);
         break;
@@ -621,13 +638,18 @@ static GemvArgs heads_args(zn_handle h, const bf16_t* x) {
 }
 // The projection that completes the residual stream (the second out_proj call under double_out_proj, else the single one) and fc1, planned
 // together: fc1 normalises from handed-over LayerNorm statistics exactly when that projection's plan writes them (rows 5..16).
-struct PostAttnPlans { LinearPlan out, fc1; };
-static PostAttnPlans plan_post_attention(zn_handle h, int rows) {
+// mlp_w8: the layer's fc1 / fc2 are offered as an FP8 stream too (mlp_fp8_offered); fc2's plan rides along because the offer is made in one place.
+struct PostAttnPlans { LinearPlan out, fc1, fc2; };
+static bool mlp_fp8_offered(zn_handle h, int li) { return li >= 0 && h->mlp_fp8[li].fc1_q != nullptr && h->tune[ZN_TUNE_MLP_FP8] != 2; }
+static PostAttnPlans plan_post_attention(zn_handle h, int rows, bool mlp_w8 = false) {
   const zn_config& c = h->cfg;
   const LinearEnv e = linear_env(h);
+  LinearEnv em = e;
+  em.w8_offered = mlp_w8;
   PostAttnPlans pp;
   pp.out = plan_linear(e, PRO_NONE, EPI_RESID, rows, c.d_model, c.n_heads * h->hd, h->tune[ZN_TUNE_WG_OUT_PROJ], false, true, false);
-  pp.fc1 = plan_linear(e, PRO_LN, EPI_SILU, rows, 2 * c.d_ff, c.d_model, h->tune[ZN_TUNE_WG_FC1], false, false, pp.out.writes_ln_stats);
+  pp.fc1 = plan_linear(em, PRO_LN, EPI_SILU, rows, 2 * c.d_ff, c.d_model, h->tune[ZN_TUNE_WG_FC1], false, false, pp.out.writes_ln_stats);
+  pp.fc2 = plan_linear(em, PRO_NONE, EPI_RESID, rows, c.d_model, c.d_ff, h->tune[ZN_TUNE_WG_FC2], false, false, false);
   return pp;
 }
 
@@ -639,7 +661,8 @@ static int layer_in_proj(zn_handle h, int li, bf16_t* x, bf16_t* kv, int max_len
 // out_proj (-> out_proj again, _torch.py:419-420) -> residual -> LayerNorm -> fc1 -> y * silu(gate) -> fc2 -> residual
 static int layer_post_attention(zn_handle h, int li, bf16_t* x, int rows, hipStream_t s, bf16_t* x1_copy = nullptr) {
   const zn_layer_weights& lw = h->layers[li];
-  const PostAttnPlans pp = plan_post_attention(h, rows);
+  const PostAttnPlans pp = plan_post_attention(h, rows, mlp_fp8_offered(h, li));
+  const zn_handle_s::MlpFp8& f8 = h->mlp_fp8[li];
   int rc;
   GemvArgs o = out_proj_args(h, lw, h->o1, x, x);
   o.ln_part_out = h->ln_part;
@@ -649,8 +672,10 @@ static int layer_post_attention(zn_handle h, int li, bf16_t* x, int rows, hipStr
   }
   if ((rc = launch_linear<PRO_NONE, EPI_RESID>(h, pp.out, o, rows, s))) return rc;
   if (x1_copy) (void)hipMemcpyAsync(x1_copy, x, (size_t)rows * h->cfg.d_model * 2, hipMemcpyDeviceToDevice, s);      // diagnostic trace
-  if ((rc = launch_linear<PRO_LN, EPI_SILU>(h, pp.fc1, fc1_args(h, lw, x, pp.out.writes_ln_stats ? h->ln_part : nullptr), rows, s))) return rc;
-  return run_gemv<PRO_NONE, EPI_RESID>(h, fc2_args(h, lw, x), rows, h->tune[ZN_TUNE_WG_FC2], s);
+  GemvArgs f1 = fc1_args(h, lw, x, pp.out.writes_ln_stats ? h->ln_part : nullptr), f2 = fc2_args(h, lw, x);
+  f1.W8q = f8.fc1_q; f1.W8exp = f8.fc1_exp; f2.W8q = f8.fc2_q; f2.W8exp = f8.fc2_exp;
+  if ((rc = launch_linear<PRO_LN, EPI_SILU>(h, pp.fc1, f1, rows, s))) return rc;
+  return launch_linear<PRO_NONE, EPI_RESID>(h, pp.fc2, f2, rows, s);
 }
 
 // One decode step of block `li` on x [rows][d] in place (_torch.py:307-328), as launches.
@@ -2064,7 +2089,8 @@ static int linear_fused_go(zn_handle h, const LinearPlan& p, const GemvArgs& a, 
   return launch_linear<PRO, EPI>(h, p, a, rows, s);
 }
 
-extern "C" int zn_op_linear_fused(zn_handle h, zn_linear_op* op, zn_stream stream) {
+// zn_op_linear_fused, and (W_q != null) zn_op_linear_fp8: the same op with the weights offered as an FP8 stream as well
+static int linear_fused_impl(zn_handle h, zn_linear_op* op, const void* W_q, const void* W_exp, bool fp8, zn_stream stream) {
   if (!h || !op) return ZN_ERR_ARG;
   for (int i = 0; i < ZN_LP_NFIELDS; ++i) op->plan[i] = 0;
   op->plan[ZN_LP_ERR] = ZN_ERR_ARG;
@@ -2086,13 +2112,25 @@ extern "C" int zn_op_linear_fused(zn_handle h, zn_linear_op* op, zn_stream strea
     if (prefill ? (op->pf_S < 1 || rows % op->pf_S || op->pf_base < 0 || op->pf_base + op->pf_S > op->max_len) : !op->lengths)
       ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: RoPE + KV append needs lengths (decode) or pf_S dividing rows with pf_base + pf_S <= max_len (prefill)");
   }
-  LinearPlan p = plan_linear(linear_env(h), pro, epi, rows, N, K, op->target_blocks > 0 ? op->target_blocks : 1, prefill, op->want_ln_stats_out != 0, op->ln_stats_in != 0);
+  LinearEnv env = linear_env(h);
+  if (fp8) {
+#define ZN_F8_REFUSE(code, ...) do { op->plan[ZN_LP_ERR] = code; ZN_FAIL(h, code, __VA_ARGS__); } while (0)
+    if (!W_q || !W_exp) ZN_F8_REFUSE(ZN_ERR_ARG, "zn_op_linear_fp8: codes or exponents missing");
+    if (!lin_has_w8(pro, epi)) ZN_F8_REFUSE(ZN_ERR_UNSUPPORTED, "zn_op_linear_fp8: prologue %d with epilogue %d has no FP8 kernel (fc1: none or LayerNorm x SiLU gate; fc2: none x residual)", pro, epi);
+    if (prefill) ZN_F8_REFUSE(ZN_ERR_UNSUPPORTED, "zn_op_linear_fp8: the prefill kernels read bf16 weights");
+    if (K % ZN_G16_KC) ZN_F8_REFUSE(ZN_ERR_UNSUPPORTED, "zn_op_linear_fp8: K=%d is no multiple of %d", K, ZN_G16_KC);
+    env.w8_offered = h->tune[ZN_TUNE_MLP_FP8] != 2;
+  }
+  LinearPlan p = plan_linear(env, pro, epi, rows, N, K, op->target_blocks > 0 ? op->target_blocks : 1, prefill, op->want_ln_stats_out != 0, op->ln_stats_in != 0);
   int* o = op->plan;
+  o[ZN_LP_W8] = p.w8;
   o[ZN_LP_KERNEL] = (int)p.kernel; o[ZN_LP_EPI] = p.epi; o[ZN_LP_KS] = p.ks; o[ZN_LP_NCH] = p.nch; o[ZN_LP_UPW] = p.upw; o[ZN_LP_BLOCKS] = p.blocks; o[ZN_LP_FULL] = p.full;
   o[ZN_LP_NW] = p.nw; o[ZN_LP_TILE8] = p.tile8; o[ZN_LP_NWV] = p.nwv; o[ZN_LP_GROUPS] = p.groups; o[ZN_LP_KSPLIT] = p.ksplit; o[ZN_LP_LNP] = p.lnp; o[ZN_LP_LN_PRO] = p.ln_pro;
   o[ZN_LP_LN_LAUNCH] = p.ln_launch; o[ZN_LP_WRITES_LN_STATS] = p.writes_ln_stats; o[ZN_LP_READS_LN_STATS] = p.reads_ln_stats; o[ZN_LP_ERR] = p.err;
   o[ZN_LP_ROPE_DONE] = epi == EPI_ROPE_KV && p.epi == EPI_ROPE_KV && !p.err; o[ZN_LP_ROWS_PER_LAUNCH] = p.rows_per_launch;
   if (p.err) ZN_FAIL(h, p.err, "%s", p.msg);
+  if (fp8 && !p.w8) ZN_F8_REFUSE(ZN_ERR_UNSUPPORTED, "zn_op_linear_fp8: this op's plan (kernel %d) would not read the FP8 stream", (int)p.kernel);
+#undef ZN_F8_REFUSE
   int rc;
 #define ZN_LF_REFUSE(...) do { o[ZN_LP_ERR] = ZN_ERR_ARG; ZN_FAIL(h, ZN_ERR_ARG, __VA_ARGS__); } while (0)
   if ((rc = check_ln_launch_fits(h, p, rows, K, "zn_op_linear_fused"))) { o[ZN_LP_ERR] = rc; return rc; }
@@ -2108,6 +2146,7 @@ extern "C" int zn_op_linear_fused(zn_handle h, zn_linear_op* op, zn_stream strea
   a.ln_w = (const bf16_t*)op->ln_w; a.ln_b = (const bf16_t*)op->ln_b; a.gv = (const float*)op->gv; a.bias = (const bf16_t*)op->bias; a.out_f32 = (float*)op->out_f32;
   a.ln_part_out = op->want_ln_stats_out ? h->ln_part : nullptr;
   a.ln_part_in = op->ln_stats_in ? h->ln_part : nullptr;
+  a.W8q = (const uint8_t*)W_q; a.W8exp = (const int8_t*)W_exp;
   if (epi == EPI_ROPE_KV) {
     a.lengths = op->lengths; a.hd = h->hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv; a.q_out = (bf16_t*)op->q_out; a.kv = (bf16_t*)op->kv;
     a.rope = h->rope; a.max_len = op->max_len; a.rope_positions = c.rope_positions;
@@ -2131,6 +2170,70 @@ extern "C" int zn_op_linear_fused(zn_handle h, zn_linear_op* op, zn_stream strea
   } else if (e == EPI_STORE) rc = linear_fused_go<PRO_GATED, EPI_STORE>(h, p, a, rows, s);
   if (rc) { o[ZN_LP_ERR] = rc; return rc; }
   HIPCHK(h, hipGetLastError());
+  return ZN_OK;
+}
+extern "C" int zn_op_linear_fused(zn_handle h, zn_linear_op* op, zn_stream stream) { return linear_fused_impl(h, op, nullptr, nullptr, false, stream); }
+extern "C" int zn_op_linear_fp8(zn_handle h, zn_linear_op* op, const void* W_q, const void* W_exp, zn_stream stream) {
+  return linear_fused_impl(h, op, W_q, W_exp, true, stream);
+}
+
+extern "C" int zn_op_fp8_quantize_rows(zn_handle h, const void* W_dev, int32_t N, int32_t K, void* q_dev, void* exp_dev, zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  if (!W_dev || !q_dev || !exp_dev || N < 1 || K < 8 || K % 8) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_fp8_quantize_rows: bad argument (K a multiple of 8)");
+  hipLaunchKernelGGL(fp8_quantize_rows_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)W_dev, K, (uint8_t*)q_dev, (int8_t*)exp_dev);
+  HIPCHK(h, hipGetLastError());
+  return ZN_OK;
+}
+extern "C" int zn_op_fp8_dequant_rows(zn_handle h, const void* q_dev, const void* exp_dev, int32_t N, int32_t K, void* W_out_dev, zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  if (!q_dev || !exp_dev || !W_out_dev || N < 1 || K < 8 || K % 8) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_fp8_dequant_rows: bad argument (K a multiple of 8)");
+  hipLaunchKernelGGL(fp8_dequant_rows_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)q_dev, (const int8_t*)exp_dev, K, (bf16_t*)W_out_dev);
+  HIPCHK(h, hipGetLastError());
+  return ZN_OK;
+}
+// ZN_FP8_VERIFY: 8-element pieces of W [N][K] that differ from the dequantised stream (< 0: a HIP error)
+static long long fp8_mismatches(const void* q, const void* e, const void* W, int N, int K) {
+  unsigned* cnt = nullptr;
+  unsigned host = 0;
+  if (ZN_NOT_IN_CAPTURE(hipMalloc(&cnt, sizeof(unsigned))) != hipSuccess) return -1;
+  bool ok = ZN_NOT_IN_CAPTURE(hipMemset(cnt, 0, sizeof(unsigned))) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(fp8_compare_rows_kernel, dim3(N), dim3(256), 0, (hipStream_t)0, (const uint8_t*)q, (const int8_t*)e, K, (const bf16_t*)W, cnt);
+    ok = hipGetLastError() == hipSuccess && ZN_NOT_IN_CAPTURE(hipMemcpy(&host, cnt, sizeof(unsigned), hipMemcpyDeviceToHost)) == hipSuccess;
+  }
+  (void)hipFree(cnt);
+  return ok ? (long long)host : -1;
+}
+extern "C" int zn_set_mlp_fp8(zn_handle h, int32_t layer, const void* fc1_q, const void* fc1_exp, const void* fc2_q, const void* fc2_exp) {
+  if (!h) return ZN_ERR_ARG;
+  const zn_config& c = h->cfg;
+  if (c.arch == 1) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mlp_fp8: the hybrid stack has no FP8 path");
+  if (layer < 0 || layer >= c.n_layer) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mlp_fp8: layer %d out of range", layer);
+  if (h->layers[layer].kind != 0) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mlp_fp8: layer %d is a Mamba2 layer", layer);
+  if (c.d_model % ZN_G16_KC || c.d_ff % ZN_G16_KC) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mlp_fp8: d_model %d / d_ff %d must be multiples of %d", c.d_model, c.d_ff, ZN_G16_KC);
+  if (h->gen_active && !h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_set_mlp_fp8 inside a generation (between zn_gen_begin and zn_gen_end)");
+  const int n_set = (fc1_q != nullptr) + (fc1_exp != nullptr) + (fc2_q != nullptr) + (fc2_exp != nullptr);
+  if (n_set != 0 && n_set != 4) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mlp_fp8: all four pointers, or none");
+  if (n_set == 4) {
+    const char* v = getenv("ZN_FP8_VERIFY");
+    if (v && atoi(v) == 1) {
+      const long long b1 = fp8_mismatches(fc1_q, fc1_exp, h->layers[layer].fc1, 2 * c.d_ff, c.d_model);
+      const long long b2 = b1 < 0 ? -1 : fp8_mismatches(fc2_q, fc2_exp, h->layers[layer].fc2, c.d_model, c.d_ff);
+      if (b1 < 0 || b2 < 0) ZN_FAIL(h, ZN_ERR_HIP, "zn_set_mlp_fp8: the verification could not run");
+      if (b1 || b2) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mlp_fp8: layer %d's bf16 weights are not the dequantised stream (fc1: %lld, fc2: %lld pieces of 8 differ)", layer, b1, b2);
+    }
+  }
+  zn_handle_s::MlpFp8& f = h->mlp_fp8[layer];
+  f.fc1_q = (const uint8_t*)fc1_q; f.fc1_exp = (const int8_t*)fc1_exp; f.fc2_q = (const uint8_t*)fc2_q; f.fc2_exp = (const int8_t*)fc2_exp;
+  free_graph(h); h->emb_valid = false;
+  return ZN_OK;
+}
+extern "C" int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
+  if (!h || !out || rows < 1) return ZN_ERR_ARG;
+  bool all = h->cfg.arch == 0;                   // 1 only when every block has a stream: a handle with some blocks attached reports 0
+  for (int li = 0; all && li < h->cfg.n_layer; ++li) all = mlp_fp8_offered(h, li);
+  const PostAttnPlans pp = plan_post_attention(h, rows, all);
+  out[0] = pp.fc1.w8; out[1] = pp.fc2.w8;
   return ZN_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "zn_common.h"
 #include "../../include/zonos_hip.h"   // zn_row_params (the per-utterance table of sample_kernel)
 #include "zn_linear_plan.h"   // PRO_* / EPI_*, ZN_G16_KC, ZN_G16_LNT, ZN_G16K_NKW, ZN_G16K_KCH
+#include "zn_fp8_kernels.h"   // fp8x8_to_bf16: the FP8 weight stream of gemm16s_kernel<., NWV | ZN_G16S_W8>
 
 // ------------------------------------------------------------------------------------------------ GEMV
 
@@ -54,6 +55,9 @@ struct GemvArgs {
   // its activation chunks while staging them, in place of a layernorm_kernel launch in between.
   float* ln_part_out;
   const float* ln_part_in;
+  // gemm16s_kernel<., NWV | ZN_G16S_W8>: the weights as an FP8 stream (zn_fp8_kernels.h) - E4M3 codes [N][K] and one scale exponent per weight row [N]; W is unused
+  const uint8_t* W8q;
+  const int8_t* W8exp;
 };
 
 // EPI_MAMBA operands of activation row r and the weight-row pair starting at rowA (both rows lie in the same segment:
@@ -559,8 +563,27 @@ ZN_DEVINL float ld_wt(const float* p) { return __hip_atomic_load(p, __ATOMIC_REL
 // (GemvArgs::ln_part_in, ZN_G16_LNT tiles of 16 columns per row).  The workgroup adds them in a fixed order while its first weight chunk
 // is on the way and normalises every activation chunk as it stages it (the arithmetic of layernorm_kernel on each value; the statistics
 // are summed tile-wise instead of lane-wise) - no LayerNorm launch, no normalised copy of the rows in memory.
-template <int EPI, int NWV, bool LNP = false>
-__global__ __launch_bounds__(NWV * 64) void gemm16s_kernel(GemvArgs a) {
+// W8: the weight chunk arrives as FP8 codes (GemvArgs::W8q / W8exp, half the bytes) and is dequantised with its row's power-of-two scale on the
+// way into Ws - exactly (zn_fp8_kernels.h), so from Ws on the kernel is the bf16 one, bit for bit, when W holds the dequantised values.  A row
+// chunk is 256 bytes: 16 pieces of 16 codes, so each 16-lane phase still reads 256 contiguous bytes of one row; a thread has 4 loads in flight
+// where the bf16 stream has 8 (the same KC and LDS footprint, half the bytes in flight).
+// Measured at 16 rows, Zonos-v0.1 shapes, weights cycled through 26 layers (tools/fp8bench.py, profiles/fp8bench.txt), FP8 against the bf16
+// stream of the same weights: fc1 (K = 2048, one slice, LNP) 16.9 against 18.0 us, fc2 (K = 8192, 8 slices) 12.6 against 14.4 us, a batch-8 step
+// 1.367 against 1.436 ms.  The conversion decides it: with v_cvt_pk_f32_fp8 + multiplies + packs (8 VALU instructions per 4 codes, ~150 per thread and
+// chunk in front of the LDS writes; ZN_FP8_CVT_SCALEF32 = 0) fc1 took 20.2 us and the step 1.474 ms - slower than bf16 at half the bytes; with
+// v_cvt_scalef32_pk_bf16_fp8 (2 per 4 codes) the halved stream shows.  The kernel stays bound by its chunk round trips rather than by bytes
+// (fc1: 2.0 TB/s of codes).  Not built or measured: KC = 512 for W8 (8 loads in flight, half the hand-overs; needs slices that are multiples
+// of 512 and 83 KB of LDS at NWV = 4), two chunks in flight (the bf16 kernel's note at the loop measured more in flight per thread slower).
+// W8 travels as a flag in the second template argument (SHAPE = NWV, or NWV | ZN_G16S_W8), not as a fourth parameter: the symbols of the
+// bf16 instantiations are pinned (tests/test_abi.py finds the ticketed kernels by their mangled names, and these new ones match too), and a
+// device function shared by two kernel names compiles the bf16 kernels to different code than before (the compiler schedules the inlined
+// body's loads differently), whereas this form leaves each of them instruction for instruction what it was.
+#define ZN_G16S_W8 64
+template <int EPI, int SHAPE, bool LNP = false>
+__global__ __launch_bounds__((SHAPE & 7) * 64) void gemm16s_kernel(GemvArgs a) {
+  constexpr int NWV = SHAPE & 7;
+  constexpr bool W8 = (SHAPE & ZN_G16S_W8) != 0;
+  static_assert((NWV == 2 || NWV == 4) && (SHAPE & ~(7 | ZN_G16S_W8)) == 0, "gemm16s: 2 or 4 waves, optionally | ZN_G16S_W8");
   constexpr int KC = ZN_G16_KC, LDW = KC + 8, NT = NWV * 64, TN = NWV * 16, HALF = TN / 2;
   constexpr int XP = 512 / NT;                        // activation pieces per thread (16 rows x 32 pieces)
   __shared__ __attribute__((aligned(16))) bf16_t Ws[TN * LDW];
@@ -590,11 +613,26 @@ __global__ __launch_bounds__(NWV * 64) void gemm16s_kernel(GemvArgs a) {
   u32x4 wr[8], xr[XP];
   const bf16_t* wp[8];
   int wl[8];
+  constexpr int NQ = W8 ? 4 : 1;                        // W8: 16 x 16 B (16 codes) per row chunk, 4 pieces per thread
+  u32x4 wq[NQ];
+  const uint8_t* wqp[NQ];
+  int wql[NQ];
+  float wqs[NQ];
+  if constexpr (W8) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int idx = j * NT + tid, row = idx >> 5, c16 = idx & 31;      // 32 x 16 B per row chunk
-    wp[j] = a.W + (size_t)wrow(row) * K + kbeg + c16 * 8;
-    wl[j] = row * LDW + c16 * 8;
+    for (int j = 0; j < NQ; ++j) {
+      const int idx = j * NT + tid, row = idx >> 4, c16 = idx & 15, gr = wrow(row);
+      wqp[j] = a.W8q + (size_t)gr * K + kbeg + c16 * 16;
+      wql[j] = row * LDW + c16 * 16;
+      wqs[j] = fp8_row_scale(a.W8exp[gr]);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int idx = j * NT + tid, row = idx >> 5, c16 = idx & 31;      // 32 x 16 B per row chunk
+      wp[j] = a.W + (size_t)wrow(row) * K + kbeg + c16 * 8;
+      wl[j] = row * LDW + c16 * 8;
+    }
   }
   const bf16_t* xp[XP];
   int xl[XP];
@@ -618,8 +656,13 @@ __global__ __launch_bounds__(NWV * 64) void gemm16s_kernel(GemvArgs a) {
 #pragma unroll
   for (int j = 0; j < XP; ++j) xr[j] = ld16(xp[j]);
   if constexpr (LNP) { lnw = ld16(a.ln_w + lnk); lnb = ld16(a.ln_b + lnk); __builtin_amdgcn_sched_barrier(0); }
+  if constexpr (W8) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) wr[j] = ld_nt16(wp[j]);
+    for (int j = 0; j < NQ; ++j) wq[j] = ld_nt16(wqp[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wr[j] = ld_nt16(wp[j]);
+  }
   // (LNP: the statistics end later than the first weight chunk arrives - their inputs are as far away as the weights.  Requesting the second
   // weight chunk here as well, for the loop's first iteration to take over: 1.765 vs 1.688 ms per batch-8 step - more in flight per thread is
   // slower, as the note at the loop says.)
@@ -678,8 +721,16 @@ __global__ __launch_bounds__(NWV * 64) void gemm16s_kernel(GemvArgs a) {
     __syncthreads();                                   // the previous chunk's fragment reads are done
 #pragma unroll
     for (int j = 0; j < XP; ++j) *(u32x4*)&Xs[xl[j]] = xr[j];       // (LNP: normalised one iteration earlier, below)
+    if constexpr (W8) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) *(u32x4*)&Ws[wl[j]] = wr[j];
+      for (int j = 0; j < NQ; ++j) {
+        *(u32x4*)&Ws[wql[j]] = fp8x8_to_bf16(u32x2{wq[j].x, wq[j].y}, wqs[j]);
+        *(u32x4*)&Ws[wql[j] + 8] = fp8x8_to_bf16(u32x2{wq[j].z, wq[j].w}, wqs[j]);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) *(u32x4*)&Ws[wl[j]] = wr[j];
+    }
     __syncthreads();
     if (c + 1 < nchunks) {
 #pragma unroll
@@ -688,8 +739,13 @@ __global__ __launch_bounds__(NWV * 64) void gemm16s_kernel(GemvArgs a) {
         lnw = ld16(a.ln_w + lnk + (c + 1) * KC); lnb = ld16(a.ln_b + lnk + (c + 1) * KC);
         __builtin_amdgcn_sched_barrier(0);             // requests return in order: the activations must not queue behind the weights (the scheduler interleaved them)
       }
+      if constexpr (W8) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) wr[j] = ld_nt16(wp[j] + (size_t)(c + 1) * KC);
+        for (int j = 0; j < NQ; ++j) wq[j] = ld_nt16(wqp[j] + (size_t)(c + 1) * KC);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wr[j] = ld_nt16(wp[j] + (size_t)(c + 1) * KC);
+      }
       if constexpr (LNP) __builtin_amdgcn_sched_barrier(0);
     }
     const bf16_t* wf = &Ws[(wave * 16 + n) * LDW + 8 * g];

@@ -18,6 +18,7 @@ struct LinearEnv {
   int small_m_lds = 2, no_split_small_m = 0, gemm16k_max_tiles = 0, fc1_ln_launch = 0, no_prefill_gemm16k = 0;
   size_t g16_part_bytes = 0;      // split-K partial tiles
   bool has_g16_part = false, has_ln_part = false;
+  bool w8_offered = false;        // the caller holds the weights as an FP8 stream as well (zn_fp8_kernels.h) and has not switched it off
 };
 
 struct LinearPlan {
@@ -32,6 +33,7 @@ struct LinearPlan {
   int nw = 0; bool tile8 = false;                  // GEMM16 (direct fragments): waves per workgroup, 8-row instead of 16-row weight tiles
   int nwv = 0, groups = 0, ksplit = 0; bool lnp = false;   // GEMM16S / GEMM64S: 16-row tiles per workgroup, grid x, grid y; LayerNorm from handed-over statistics
   bool ln_pro = false;        // GEMM16K (nch = 128-wide chunks per wave): LayerNorm as its prologue
+  bool w8 = false;            // GEMM16S, decode: the launch reads the FP8 stream (gemm16s_kernel<., NWV | ZN_G16S_W8>) instead of the bf16 weights
   int err = 0;                // shapes nobody serves: a ZN_ERR_* code (-4 = ZN_ERR_UNSUPPORTED) and its message
   char msg[96] = {};
 };
@@ -44,14 +46,17 @@ constexpr bool lin_has_tile8(int epi) { return epi != EPI_SILU; }
 constexpr bool lin_has_lnp(int pro, int epi) { return pro == PRO_LN && epi == EPI_SILU; }
 constexpr bool lin_has_gemm16k(int pro, int epi) { return lin_has_gemm16(pro) && epi != EPI_SILU; }   // row-pair epilogues only
 constexpr bool lin_has_gemm16k_ln(int pro, int nch) { return pro == PRO_LN && nch == 2; }  // (the LayerNorm prologue at K = 4096 would not fit the register file)
+// gemm16s_kernel<., NWV | ZN_G16S_W8>: fc1 (SiLU gate; its LayerNorm is a launch in front or comes from handed-over statistics, so the kernel's prologue is none
+// either way) and fc2 (no prologue, residual)
+constexpr bool lin_has_w8(int pro, int epi) { return (epi == EPI_SILU && (pro == PRO_NONE || pro == PRO_LN)) || (epi == EPI_RESID && pro == PRO_NONE); }
 constexpr bool lin_has_prefill(int pro, int epi) { return pro == PRO_NONE && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_SILU); }   // GEMM64S, GEMM_TILED
 inline bool linear_plan_launchable(const LinearPlan& p, int pro, int epi) {
   switch (p.kernel) {
     case LinearPlan::GEMV: return (p.ks == 1 || (p.ks == 4 && lin_has_gemv_ks4(pro))) && (p.nch == 1 || p.nch == 2 || p.nch == 4 || p.nch == 8);
     case LinearPlan::GEMM16: return lin_has_gemm16(pro) && (p.nw == 4 || p.nw == 8 || p.nw == 16) && (!p.tile8 || lin_has_tile8(epi));
-    case LinearPlan::GEMM16S: return lin_has_gemm16(pro) && (p.nwv == 2 || p.nwv == 4) && (!p.lnp || lin_has_lnp(pro, epi));
+    case LinearPlan::GEMM16S: return lin_has_gemm16(pro) && (p.nwv == 2 || p.nwv == 4) && (!p.lnp || lin_has_lnp(pro, epi)) && (!p.w8 || lin_has_w8(pro, epi));
     case LinearPlan::GEMM16K: return lin_has_gemm16k(pro, epi) && (p.nch == 2 || p.nch == 4) && (!p.ln_pro || lin_has_gemm16k_ln(pro, p.nch));
-    case LinearPlan::GEMM64S: case LinearPlan::GEMM_TILED: return lin_has_prefill(pro, epi);
+    case LinearPlan::GEMM64S: case LinearPlan::GEMM_TILED: return !p.w8 && lin_has_prefill(pro, epi);
   }
   return false;
 }
@@ -109,8 +114,8 @@ inline bool plan_gemm64s(const LinearEnv& e, int epi, int rows, int N, int K, Li
 // rows in (4, 16] per group one weight pass on the matrix cores.  prefill = true: the rows of a prompt in one launch, normalised by the caller.
 // want_ln_stats_out: the caller would hand LayerNorm statistics of this projection's output to its consumer; have_ln_stats_in: the producer of
 // x left them (writes_ln_stats of its plan).  target_blocks: the GEMV's grid (ZN_TUNE_WG_*).
-inline LinearPlan plan_linear(const LinearEnv& e, int pro, int epi, int rows, int N, int K, int target_blocks, bool prefill, bool want_ln_stats_out,
-                              bool have_ln_stats_in) {
+inline LinearPlan plan_linear_bf16(const LinearEnv& e, int pro, int epi, int rows, int N, int K, int target_blocks, bool prefill, bool want_ln_stats_out,
+                                   bool have_ln_stats_in) {
   LinearPlan p;
   p.epi = epi;
 #define ZN_PLAN_FAIL(...) do { p.err = -4; snprintf(p.msg, sizeof p.msg, __VA_ARGS__); return p; } while (0)
@@ -173,4 +178,13 @@ inline LinearPlan plan_linear(const LinearEnv& e, int pro, int epi, int rows, in
   p.blocks = p.tile8 ? N / 8 : tiles;
   return p;
 #undef ZN_PLAN_FAIL
+}
+
+// The plan, and on top of it the one thing an offered FP8 stream changes: a decode launch of gemm16s_kernel for fc1 or fc2 reads the stream.
+// Kernel, grid, split, statistics hand-over - everything else is decided without looking at the offer.
+inline LinearPlan plan_linear(const LinearEnv& e, int pro, int epi, int rows, int N, int K, int target_blocks, bool prefill, bool want_ln_stats_out,
+                              bool have_ln_stats_in) {
+  LinearPlan p = plan_linear_bf16(e, pro, epi, rows, N, K, target_blocks, prefill, want_ln_stats_out, have_ln_stats_in);
+  p.w8 = e.w8_offered && !prefill && !p.err && p.kernel == LinearPlan::GEMM16S && lin_has_w8(pro, epi);
+  return p;
 }

@@ -156,6 +156,7 @@ class Zonos(nn.Module):
         self._spare: HipEngine | None = None          # second handle over the same weights (a concurrent generate() call)
         self._spare_guard = threading.RLock()
         self._repeats = 0                             # generations repeated on the launches path after a reported hand-off timeout
+        self.mlp_weights = "bf16"                     # "fp8" after quantize_mlp_fp8()
 
     # ------------------------------------------------------------------ loading
     @property
@@ -172,9 +173,13 @@ class Zonos(nn.Module):
         return cls.from_local(config_path, model_path, device, **kwargs)
 
     @classmethod
-    def from_local(cls, config_path: str, model_path: str, device: str = DEFAULT_DEVICE, backbone: str | None = None) -> "Zonos":
-        """model.py:128-176: bf16 model, embeddings zero-padded to the 1032-row tables, heads.{i} fused."""
+    def from_local(cls, config_path: str, model_path: str, device: str = DEFAULT_DEVICE, backbone: str | None = None,
+                   mlp_weights: str = "bf16") -> "Zonos":
+        """model.py:128-176: bf16 model, embeddings zero-padded to the 1032-row tables, heads.{i} fused.  mlp_weights="fp8":
+        quantize_mlp_fp8() after loading (lossy with respect to the checkpoint; see there); the default changes nothing."""
         import safetensors
+        if mlp_weights not in ("bf16", "fp8"):
+            raise _lib.ZonosHipError(f"mlp_weights must be 'bf16' or 'fp8', not {mlp_weights!r}")
         config = ZonosConfig.from_dict(json.load(open(config_path)))
         backbone_cls = BACKBONES[backbone] if backbone else DEFAULT_BACKBONE_CLS
         model = cls(config, backbone_cls).to(device, torch.bfloat16)
@@ -198,7 +203,38 @@ class Zonos(nn.Module):
                                      f"unexpected tensors {unexpected[:8]}{'...' if len(unexpected) > 8 else ''}, "
                                      f"missing tensors {missing[:8]}{'...' if len(missing) > 8 else ''}")
         model.load_state_dict(sd, strict=True)
+        if mlp_weights == "fp8":
+            model.quantize_mlp_fp8()
         return model
+
+    @torch.inference_mode()
+    def quantize_mlp_fp8(self) -> "Zonos":
+        """Weight-only FP8 for fc1 / fc2 of every transformer block (zonos_amd/quant.py: E4M3 codes, one power-of-two scale per weight
+        row).  Quantises on the device, OVERWRITES the bf16 parameters in place with the dequantised values and keeps the codes and
+        exponents as buffers of the block's mlp (fc1_q, fc1_exp, fc2_q, fc2_exp; not part of the state dict).  Decode steps of 5 or
+        more rows then stream the codes - half the bytes - and compute exactly what the bf16 kernels compute on the dequantised
+        weights, which every other path keeps reading.  Lossy with respect to the checkpoint (|Wdq - w| <= 2^-4 |w|), exact with
+        respect to the model's own weights afterwards; the effect on audio quality is unmeasured.  Cached engines are dropped."""
+        if self.config.backbone.ssm_cfg:
+            raise _lib.ZonosHipError("quantize_mlp_fp8: the hybrid stack has no FP8 path")
+        if self.device.type != "cuda":
+            raise _lib.ZonosHipError("quantize_mlp_fp8 runs on the device: move the model to a cuda device first")
+        eng = self.engine(1)
+        for blk in self.backbone.layers:
+            for name in ("fc1", "fc2"):
+                W = getattr(blk.mlp, name).weight.data
+                N, K = W.shape
+                q = torch.empty((N, K), dtype=torch.uint8, device=W.device)
+                e = torch.empty((N,), dtype=torch.int8, device=W.device)
+                eng.call("zn_op_fp8_quantize_rows", W.data_ptr(), N, K, q.data_ptr(), e.data_ptr(), eng.stream())
+                eng.call("zn_op_fp8_dequant_rows", q.data_ptr(), e.data_ptr(), N, K, W.data_ptr(), eng.stream())
+                blk.mlp.register_buffer(name + "_q", q, persistent=False)
+                blk.mlp.register_buffer(name + "_exp", e, persistent=False)
+        torch.cuda.synchronize(self.device)
+        self._engine = self._spare = None
+        self.backbone._engine = None
+        self.mlp_weights = "fp8"
+        return self
 
     def _load_from_state_dict(self, state_dict, prefix, *args):
         """model.py:208-223: per-codebook heads.{i}.weight [1025,d] -> fused_heads.weight [9*1025,d]."""

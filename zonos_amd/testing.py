@@ -933,3 +933,59 @@ def attention_from_device_layout(c: AttnCase, out) -> torch.Tensor:
     hq, _ = c.heads
     o = out.detach().cpu()
     return o.view(c.R, hq, 1, c.hd) if c.kind == "decode" else o.view(c.R, c.S, hq, c.hd).transpose(1, 2).contiguous()
+
+
+# ------------------------------------------------------------------ weight-only FP8 (zonos_amd/quant.py): the inputs the CPU specification and the device kernels are both tested on
+
+FP8_SEED = 41
+FP8_MATRIX_SHAPES = ((96, 256), (64, 8192))
+
+
+def fp8_seeded_matrix(N: int, K: int) -> torch.Tensor:
+    """bf16 [N, K]: normal values with a row scale that spans 2^-12 .. 2^12, so that the rows' scale exponents differ and small values of a row
+    fall into the codes' subnormal range."""
+    w = torch.from_numpy(synth.normal(FP8_SEED, f"fp8.w.{N}.{K}", (N, K)))
+    return (w * torch.exp2(torch.linspace(-12.0, 12.0, N))[:, None]).to(torch.bfloat16)
+
+
+def fp8_adversarial_rows(K: int = 256) -> tuple:
+    """(bf16 [rows, K], names): all zero; one non-zero element; amax exactly 448 * 2^j and one bf16 ulp either side of it; values on the
+    midpoints of the code grid (ties to even both ways); values in the codes' subnormal range; amax beyond the clamp on both sides."""
+    rows, names = [], []
+
+    def add(name, vals):
+        r = torch.zeros(K, dtype=torch.float64)
+        v = torch.as_tensor(vals, dtype=torch.float64)
+        r[: v.numel()] = v
+        b = r.to(torch.float32).to(torch.bfloat16)
+        assert torch.equal(b.double(), r), f"{name}: a value of the row is not a bf16"
+        rows.append(b)
+        names.append(name)
+    add("zero", [])
+    add("one element", [0.0, 0.0, -0.3984375])
+    add("negative zero", [-0.0, 0.0, 1.0])
+    for j in (-20, 0, 9):
+        s = 2.0 ** j
+        # 448 = 1.75 * 2^8: the bf16 neighbours are 446 and 450
+        add(f"amax 448*2^{j}", [448.0 * s, -224.0 * s, 17.0 * s])
+        add(f"amax 446*2^{j}", [-446.0 * s, 224.0 * s, 17.0 * s])
+        add(f"amax 450*2^{j}", [450.0 * s, -225.0 * s, 17.0 * s])
+    # midpoints of the grid at scale 2^0 (amax 448): in [16, 32) the step is 2 - 17 lies between 16 (even mantissa) and 18 (odd), 19 between
+    # 18 and 20, ...; in [1, 2) the step is 1/8; 2^-6 .. : the lowest normal binade; below: subnormal steps of 2^-9, midpoints at odd
+    # multiples of 2^-10 (2^-10 itself ties to zero, 3 * 2^-10 up to 2 * 2^-9)
+    add("midpoints", [448.0, 17.0, -19.0, 21.0, 23.0, 1.0625, -1.1875, 1.9375, 240.0 + 8.0, -(224.0 + 8.0), 2.0 ** -6 + 2.0 ** -10, 2.0 ** -6 + 3 * 2.0 ** -10,
+                      31.0, -31.5, 255.0])
+    add("subnormal codes", [448.0, 2.0 ** -10, -(2.0 ** -10), 3 * 2.0 ** -10, 5 * 2.0 ** -10, -7 * 2.0 ** -10, 2.0 ** -9, 2.0 ** -11, 15 * 2.0 ** -10, 2.0 ** -6 - 2.0 ** -10,
+                            2.0 ** -7, 1.5 * 2.0 ** -10, 0.75 * 2.0 ** -9, 2.0 ** -30])
+    big, tiny = 2.0 ** 120, 2.0 ** -120
+    add("beyond the clamp, large", [big, -big * 1.5, 448.0 * 2.0 ** 100, 450.0 * 2.0 ** 100, 2.0 ** 90, 2.0 ** -9 * 2.0 ** 100, 1.0, 1.9921875 * 2.0 ** 127])
+    add("beyond the clamp, small", [tiny, -tiny, 2.0 ** -110, 3 * 2.0 ** -110, 2.0 ** -109, -(2.0 ** -108), 2.0 ** -126, 2.0 ** -133])
+    return torch.stack(rows), names
+
+
+def fp8_row_shifts(N: int) -> torch.Tensor:
+    """int32 [N] in -3 .. 3: powers of two to scale the rows of a weight matrix by, so that the rows' FP8 scale exponents differ from row to row
+    inside a 32-row workgroup, between value row u and gate row N / 2 + u (at the N of linear_cases_gemm16s / LF_PAIR_FC1 / d_ff = 8192), and
+    between the last two rows - a kernel that looked a scale up under the wrong row index could not reproduce the bf16 launch."""
+    r = torch.arange(N)
+    return ((r * 5 + (r >> 4) + (r >> 10)) % 7 - 3).to(torch.int32)
