@@ -22,6 +22,7 @@ from zonos_amd import _lib, synth
 from zonos_amd.autoencoder import DACAutoencoder
 from zonos_amd.codebook_pattern import apply_delay_pattern
 from zonos_amd.model import GenRequest, ServeResult, _drain, _sampling_struct
+from zonos_amd.rows import GenCall, Hooks
 from zonos_amd.serving import ServeChunk, row_end_offset
 from zonos_amd.testing import build_model
 
@@ -402,14 +403,12 @@ def test_a_pair_with_its_unconditional_row_below(models):
     owners = [17] + [b for b, (role, _) in enumerate(layout) if role == "u"]
     assert _gemm_class(18 * 3) == 0
     with _hooks(model, 9, arch):
-        eng = model._acquire_engine(9)
-        try:
+        call = GenCall(cond, [2] * 18, [None] * 18, [0] * 18, [int(r.max_new_tokens) for _, r in layout], 10, 1.0, _sampling_struct({}, 0),
+                       table=table, request_rows=owners)
+        with model._engine_held(9) as eng:
             tr = {"logits": []}
-            outs = _drain(model._generation(eng, cond, None, 10, 1.0, 18, {}, None, 0, tr, torch.cuda.current_stream(), None, [2] * 18, table, None, owners))
+            outs = _drain(model._generation(eng, call, torch.cuda.current_stream(), Hooks(trace=tr)))
             assert eng.lib.zn_decode_path_detail(eng.h) == 0
-        finally:
-            eng.generating = False
-            eng.lock.release()
         logits = torch.stack([lg.cpu() for lg in tr["logits"]])
         assert _same_bits(logits[:, 3], logits[:, 17])
         for out, b, r in [(outs[0], 17, g), (outs[1], 0, u[0]), (outs[16], 16, u[15])]:

@@ -3,7 +3,7 @@ zn_op_assemble_prefill) - the parts that need no GPU.
 
 * What `check_requests(..., ragged_prefix=True)` accepts and still refuses.
 * The call, transcribed: the left-aligned code buffer, the device's bookkeeping with a column shift per row (frame_update_body) under
-  `_decode_loop`'s stop-check cadence, and `_finalise_rows`' per-row cut - every row equals the row generated alone with its own prefix
+  `_decode_loop`'s stop-check cadence, and `GenCall.finalise`'s per-row cut - every row equals the row generated alone with its own prefix
   and budget.
 * The new entry points: declared, bound, and refusing bad arguments with a status."""
 import os
@@ -165,7 +165,7 @@ def run_call(tokens: np.ndarray, budgets, prefixes, cadence_B: int, deferred: bo
 
 
 def finalise_row(delayed, b, P_b, budget, B):
-    """`Zonos._finalise_rows` for row b: its own P_b + budget + 9 columns, cut at row_end_offset(P_b + 1, ...)."""
+    """`GenCall.finalise` (`rows.finalise_row`) for row b: its own P_b + budget + 9 columns, cut at row_end_offset(P_b + 1, ...)."""
     offset0, t_b = P_b + 1, P_b + budget + NQ
     row = delayed[b:b + 1, :, :t_b]
     hit = (row[0, 0, offset0 + 1:] == EOS).nonzero()

@@ -4,41 +4,16 @@
 Pure Python: no torch device, no library.  A session has `slots` rows that step together; a request joins at a scheduling point (every
 `sched_every` decode steps), runs its own decode loop inside its slot - the device keeps the slot's length, stop state, parameters, column
 and step origin per row - and is retired at the first scheduling point at which a `generate_batch()` call of `slots` requests would have
-stopped watching it (`row_end_offset`).  Its codes are then cut and finalised exactly as `_finalise_rows` does for that call.
+stopped watching it (`row_end_offset`).  Its codes are then cut and finalised exactly as `rows.finalise_row` does for that call.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
 from typing import Callable, Iterator, NamedTuple, Sequence
 
+from .rows import check_request_shapes, row_end_offset, stop_check_at     # noqa: F401  (the last two: defined there, re-exported here)
+
 STOP_CHECK_SPAN = 16          # a row whose remaining_steps reached 0 leaves at the next check of its own cadence: at most 16 steps on
-
-
-def stop_check_at(step_idx: int, batch_size: int) -> bool:
-    """The reference's stop-check cadence (tensor_ops.py:90-103) as `_decode_loop` runs it: is the stop flag read after loop step
-    `step_idx` (0-based) of a call of `batch_size` utterances?"""
-    return step_idx % 16 == 15 or (step_idx % 8 == 7 and max(0, batch_size * 10 - (step_idx + 1)) < 5)
-
-
-def row_end_offset(offset0: int, t_total: int, batch_size: int, nq: int, eos_column: int | None) -> int:
-    """The column at which the decode loop of a call of `batch_size` utterances would have ended had it watched one row alone
-    (`generate_batch`: every request is cut and finalised for itself, while the call runs on to its last row).  The row starts at column
-    `offset0` (audio prefix + 1) with its own `t_total` = prefix + max_new_tokens + nq columns and remaining_steps = t_total - offset0;
-    `eos_column` is the first column beyond offset0 whose codebook 0 holds EOS (None: there is none below t_total).  Loop step i writes
-    column offset0 + i + 1; a step that samples EOS in codebook 0 caps remaining_steps at nq; every step takes one off (tensor_ops.py:87,
-    155-211).  The loop leaves at the first check of the call's cadence (`stop_check_at`) at which remaining_steps <= 0 - the deferred
-    read-back of `_decode_loop` rolls back to that same check - or at t_total when the row's budget ends before any such check."""
-    remaining, offset = t_total - offset0, offset0
-    for step_idx in range(t_total - offset0):
-        offset += 1
-        if offset >= t_total:
-            break
-        if eos_column is not None and offset == eos_column:
-            remaining = min(remaining, nq)
-        remaining -= 1
-        if stop_check_at(step_idx, batch_size) and remaining <= 0:
-            return offset
-    return t_total
 
 
 def release_limit(offset: int, nq: int, eos_frame: int | None) -> int:
@@ -70,18 +45,8 @@ def check_serve_request(cond_shape: Sequence[int], prefix_shape: Sequence[int] |
     if guided is not None and (float(cfg_scale) != 1.0) != guided:
         raise ValueError(f"serve: cfg_scale={cfg_scale} in a session {'with' if guided else 'without'} guidance (guided and cfg_scale == 1 "
                          "requests cannot share a session: the row layout differs)")
-    c = tuple(cond_shape)
-    if len(c) != 3 or c[0] != halves or c[1] < 1 or c[2] != d_model:
-        raise ValueError(f"serve: conditioning of shape {c}, expected [{halves}, L >= 1, {d_model}] at cfg_scale={cfg_scale}")
-    if int(max_new_tokens) != max_new_tokens or int(max_new_tokens) < 1:
-        raise ValueError(f"serve: max_new_tokens must be a positive integer, got {max_new_tokens}")
-    P = 0
-    if prefix_shape is not None:
-        a = tuple(prefix_shape)
-        if len(a) != 3 or a[0] != 1 or a[1] != nq:
-            raise ValueError(f"serve: audio_prefix_codes of shape {a}, expected [1, {nq}, P]")
-        P = int(a[2])
-    L, n = int(c[1]), int(max_new_tokens)
+    L, P = check_request_shapes("serve: ", cond_shape, halves, d_model, cfg_scale, max_new_tokens, prefix_shape, nq)
+    n = int(max_new_tokens)
     if L + P + n + nq + slack > max_len:
         raise ValueError(f"serve: {L} conditioning positions + {P} prefix frames + {n} frames + {nq} + slack {slack} exceed the session's "
                          f"{max_len} KV positions per row (max_prompt / max_new_tokens of serve())")
