@@ -345,7 +345,10 @@ enum zn_tune_key {
   ZN_TUNE_STACK_PRE = 18,           /* 2 = block 0's in_proj as a launch before the whole-step kernel; default: inside it */
   ZN_TUNE_ATTN_SPLIT_COLS = 19,     /* value-column parts of the decode attention: 1 = never split, 2 = always; default: from 5 rows on */
   ZN_TUNE_MLP_FP8 = 20,             /* 2 = ignore the FP8 streams attached by zn_set_mlp_fp8: every launch reads the bf16 fc1 / fc2 */
-  ZN_TUNE_NKEYS = 21
+  ZN_TUNE_WIDE_ROWS = 21,           /* decode steps of 17..64 rows: 1 = every projection in groups of 16 rows (each weight streamed once per group);
+                                       2 = up to 64 rows per weight pass also in zn_op_linear_fused / zn_op_linear_fp8; default: generation steps and
+                                       zn_bench_kernel take up to 64 rows per weight pass, the per-op entry points groups of 16.  Same bits either way */
+  ZN_TUNE_NKEYS = 22
 };
 /* Values of ZN_TUNE_HOOK.  The first three arm the next zn_gen_begin, which consumes them. */
 enum zn_tune_hook {
@@ -413,6 +416,7 @@ enum zn_linear_plan_field {
   ZN_LP_GROUPS = 10, ZN_LP_KSPLIT = 11, ZN_LP_LNP = 12, ZN_LP_LN_PRO = 13, ZN_LP_LN_LAUNCH = 14, ZN_LP_WRITES_LN_STATS = 15,
   ZN_LP_READS_LN_STATS = 16, ZN_LP_ERR = 17, ZN_LP_ROPE_DONE = 18, ZN_LP_ROWS_PER_LAUNCH = 19,
   ZN_LP_W8 = 20,         /* 1 = the launch read the weights as an FP8 stream (zn_op_linear_fp8) */
+  ZN_LP_ROW_TILES = 21,  /* 16-row activation blocks per weight pass: 1, or 2 .. 4 under the wide plan (ZN_TUNE_WIDE_ROWS; then ZN_LP_ROWS_PER_LAUNCH = 64) */
   ZN_LP_NFIELDS = 24
 };
 typedef struct zn_linear_op {
@@ -438,15 +442,15 @@ int zn_op_fp8_quantize_rows(zn_handle h, const void* W_dev, int32_t N, int32_t K
 /* q, exp -> W_out bf16 [N][K] = value(q) * 2^exp, exact.  K a multiple of 8, every exp in [-100, 100] (the caller's to ensure). */
 int zn_op_fp8_dequant_rows(zn_handle h, const void* q_dev, const void* exp_dev, int32_t N, int32_t K, void* W_out_dev, zn_stream stream);
 /* Attaches the FP8 stream of fc1 [2 d_ff][d_model] and fc2 [d_model][d_ff] of transformer block `layer`; all four pointers NULL detaches it.
- * CONTRACT: the layer's bf16 fc1 and fc2 (zn_layer_weights) hold exactly the dequantised stream.  Decode launches of 5..16 rows per group then
- * read the codes (half the bytes) and compute the same bits; every other path keeps reading the bf16 copy, so one model computes one function
+ * CONTRACT: the layer's bf16 fc1 and fc2 (zn_layer_weights) hold exactly the dequantised stream.  Decode launches of 5..64 rows per weight pass (groups of 16 rows, or
+ * up to 64 under the wide plan of 17 rows and more: ZN_TUNE_WIDE_ROWS) then read the codes (half the bytes) and compute the same bits; every other path keeps reading the bf16 copy, so one model computes one function
  * on every path.  The library does not check the contract unless ZN_FP8_VERIFY=1 is in the environment of this call: then both matrices are
  * compared on the device and a mismatch is ZN_ERR_ARG (nothing is attached).  The caller keeps the memory alive while it is attached.  Drops the
  * captured graphs.  ZN_ERR_UNSUPPORTED: a hybrid handle (arch 1), a Mamba2 layer, d_model or d_ff no multiple of 256.  ZN_ERR_STATE: between
  * zn_gen_begin and zn_gen_end.  ZN_ERR_ARG: a layer out of range, or some but not all pointers NULL. */
 int zn_set_mlp_fp8(zn_handle h, int32_t layer, const void* fc1_q, const void* fc1_exp, const void* fc2_q, const void* fc2_exp);
 /* zn_op_linear_fused with the weights offered as an FP8 stream as well (op->W: the dequantised bf16 copy, still required): the production
- * plan, and where it launches gemm16s_kernel in decode for no prologue or LayerNorm x SiLU gate (fc1) or no prologue x residual (fc2), that
+ * plan, and where it launches gemm16s_kernel (or, 17..64 rows under the wide plan, gemm16w_kernel) in decode for no prologue or LayerNorm x SiLU gate (fc1) or no prologue x residual (fc2), that
  * launch reads W_q / W_exp - plan[ZN_LP_W8] = 1, every other plan field as zn_op_linear_fused reports it.  Refused before any launch, as
  * ZN_ERR_UNSUPPORTED: any other (prologue, epilogue) pair, a prefill op, K no multiple of 256, a plan that would not read the stream
  * (zn_debug_tune(ZN_TUNE_MLP_FP8, 2) included). */
@@ -454,6 +458,11 @@ int zn_op_linear_fp8(zn_handle h, zn_linear_op* op, const void* W_q, const void*
 /* out[0], out[1]: whether fc1 and fc2 of a decode step over `rows` rows would read FP8 in EVERY block of this handle now (the tune keys; a
  * handle with streams attached to some blocks only reports 0, 0 although those blocks do read them). */
 int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
+/* ---------------------------------------------------------------- decode steps of 17..64 rows (additive to ABI 9, like the FP8 calls above: look the symbol up)
+ * out[0..4]: activation rows per weight pass of in_proj, out_proj, fc1, fc2 and the heads in a decode step of `rows` rows as this handle would
+ * run it now (4 up to 4 rows, 16 up to 16 rows and under zn_debug_tune(ZN_TUNE_WIDE_ROWS, 1), 64 where the wide plan applies): a step of R rows
+ * reads the projection's weights ceil(R / out[k]) times. */
+int zn_decode_rows_plan(zn_handle h, int32_t rows, int32_t out[5]);
 /* Prefix-conditioner pieces (zonos/conditioning.py): nn.Linear with bias (Conditioner.project, :52-60; bias added in fp32
  * before the one bf16 rounding), nn.Embedding row gather (:364-365,467), FourierConditioner.apply_cond (:436-441), nn.SiLU. */
 int zn_op_linear_bias(zn_handle h, const void* x_dev, const void* W_dev, const void* bias_dev, void* out_dev, int32_t rows,

@@ -32,7 +32,8 @@ ZN_TUNE_RESERVED_17 = 17
 ZN_TUNE_STACK_PRE = 18
 ZN_TUNE_ATTN_SPLIT_COLS = 19
 ZN_TUNE_MLP_FP8 = 20
-ZN_TUNE_NKEYS = 21
+ZN_TUNE_WIDE_ROWS = 21
+ZN_TUNE_NKEYS = 22
 # values of ZN_TUNE_HOOK (enum zn_tune_hook)
 ZN_HOOK_TAG_WRAP, ZN_HOOK_TIMEOUT_WORD, ZN_HOOK_PAUSE, ZN_HOOK_RESET_WAIT_STATS = 7, 9, 11, 13
 
@@ -82,7 +83,7 @@ PRO_NONE, PRO_LN, PRO_GATED = 0, 1, 2
 EPI_STORE, EPI_RESID, EPI_SILU, EPI_ROPE_KV, EPI_F32, EPI_MAMBA = 0, 1, 2, 3, 4, 5
 LP_KERNELS = ("GEMV", "GEMM16", "GEMM16S", "GEMM16K", "GEMM64S", "GEMM_TILED")
 LP_FIELDS = ("kernel", "epi", "ks", "nch", "upw", "blocks", "full", "nw", "tile8", "nwv", "groups", "ksplit", "lnp", "ln_pro", "ln_launch",
-             "writes_ln_stats", "reads_ln_stats", "err", "rope_done", "rows_per_launch", "w8")
+             "writes_ln_stats", "reads_ln_stats", "err", "rope_done", "rows_per_launch", "w8", "row_tiles")
 
 
 class zn_linear_op(C.Structure):
@@ -159,6 +160,7 @@ SIGNATURES = {
     "zn_op_fp8_dequant_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "zn_set_mlp_fp8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zn_mlp_fp8_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zn_decode_rows_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zn_op_linear_bias": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p]),
     "zn_op_gather_rows": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]),
     "zn_op_fourier": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_float, C.c_void_p]),

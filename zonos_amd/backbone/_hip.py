@@ -226,6 +226,13 @@ class HipEngine:
         self.call("zn_mlp_fp8_plan", rows, out)
         return [int(out[0]), int(out[1])]
 
+    def decode_rows_plan(self, rows: int) -> dict:
+        """zn_decode_rows_plan: activation rows per weight pass of in_proj, out_proj, fc1, fc2 and the heads in a decode step of `rows` rows
+        as the handle would run it now (16: the projection's weights are streamed once per 16 rows; 64: once per 64)."""
+        out = (C.c_int32 * 5)()
+        self.call("zn_decode_rows_plan", rows, out)
+        return dict(zip(("in_proj", "out_proj", "fc1", "fc2", "heads"), (int(v) for v in out)))
+
     def __del__(self):
         try:
             if getattr(self, "h", None):

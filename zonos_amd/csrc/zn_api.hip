@@ -2,6 +2,7 @@
 // workspace, launch geometry, hipGraph capture of one decode step.
 #include "../../include/zonos_hip.h"
 #include "zn_decode_kernels.h"
+#include "zn_wide_kernels.h"
 #include "zn_chain_kernel.h"
 #include "zn_step_kernel.h"
 #include "zn_prefill_kernels.h"
@@ -427,9 +428,21 @@ static void launch_gemm16s_w8_t(const GemvArgs& g, const LinearPlan& p, hipStrea
   else hipLaunchKernelGGL((gemm16s_kernel<EPI, 2 | ZN_G16S_W8, LNP>), dim3(p.groups, p.ksplit), dim3(128), 0, s, g);
 }
 
+// gemm16w_kernel over nr = 17..64 rows of a plan with row_tiles > 1: RB = ceil(nr / 16) activation blocks per staged weight chunk
+template <int EPI, bool W8>
+static void launch_gemm16w_t(const GemvArgs& g, const LinearPlan& p, int nr, hipStream_t s) {
+  const dim3 grid(p.groups_wide, p.ksplit), block(256);
+  const int rb = (nr + 15) / 16;
+  if (rb == 2) hipLaunchKernelGGL((gemm16w_kernel<EPI, W8, 2>), grid, block, 0, s, g);
+  else if (rb == 3) hipLaunchKernelGGL((gemm16w_kernel<EPI, W8, 3>), grid, block, 0, s, g);
+  else hipLaunchKernelGGL((gemm16w_kernel<EPI, W8, 4>), grid, block, 0, s, g);
+}
+
 // Every decision about a linear of 1 .. 64 rows is plan_linear's (zn_linear_plan.h); what it may depend on:
-static LinearEnv linear_env(zn_handle h) {
+// step: the plan of a generation step (wide from 17 rows on unless ZN_TUNE_WIDE_ROWS = 1); else of a per-op entry point (wide only under = 2).
+static LinearEnv linear_env(zn_handle h, bool step = true) {
   LinearEnv e;
+  e.wide_rows = h->tune[ZN_TUNE_WIDE_ROWS] == 2 || (step && h->tune[ZN_TUNE_WIDE_ROWS] != 1);
   e.small_m_lds = h->tune[ZN_TUNE_SMALL_M_LDS]; e.no_split_small_m = h->tune[ZN_TUNE_NO_SPLIT_SMALL_M]; e.gemm16k_max_tiles = h->tune[ZN_TUNE_GEMM16K_MAX_TILES];
   e.fc1_ln_launch = h->tune[ZN_TUNE_FC1_LN_LAUNCH]; e.no_prefill_gemm16k = h->tune[ZN_TUNE_NO_PREFILL_GEMM16K];
   e.g16_part_bytes = h->g16_part_bytes; e.has_g16_part = h->g16_part != nullptr; e.has_ln_part = h->ln_part != nullptr;
@@ -450,7 +463,8 @@ static void advance_rows(GemvArgs& g, int r0, int nr, int out_cols) {
   if (g.ln_part_out) g.ln_part_out += (size_t)r0 * ZN_G16_LNT * 2;
   if (g.ln_part_in) g.ln_part_in += (size_t)r0 * ZN_G16_LNT * 2;
 }
-// Launches what the plan says over `rows` activation rows, group by group (weights are re-streamed per group): the template switches, and nothing that decides.
+// Launches what the plan says over `rows` activation rows, group by group of rows_per_launch (weights are re-streamed per group: 16 rows, or 64 under the wide
+// plan, whose last group follows its own size: 16 rows or fewer are the 16-row plan's launch): the template switches, and nothing that decides.
 template <int PRO, int EPI>
 static int launch_linear(zn_handle h, const LinearPlan& p, GemvArgs a, int rows, hipStream_t s) {
   if (p.err) ZN_FAIL(h, p.err, "%s", p.msg);
@@ -481,6 +495,16 @@ static int launch_linear(zn_handle h, const LinearPlan& p, GemvArgs a, int rows,
         }
         break;
       case LinearPlan::GEMM16S:
+        if constexpr (lin_has_wide16s(PRO, EPI)) if (p.row_tiles > 1 && nr > 16) {
+          if constexpr (lin_has_lnp(PRO, EPI)) if (p.lnp) {      // LayerNorm from the handed-over statistics, in the 16-row plan's order, as one launch
+            if (p.nwv == 4) hipLaunchKernelGGL((ln_from_stats_kernel<16>), dim3(nr), dim3(64), 0, s, g.x, g.ln_part_in, a.ln_w, a.ln_b, h->nbuf, a.eps);
+            else hipLaunchKernelGGL((ln_from_stats_kernel<8>), dim3(nr), dim3(64), 0, s, g.x, g.ln_part_in, a.ln_w, a.ln_b, h->nbuf, a.eps);
+            g.x = h->nbuf;
+          }
+          if (p.w8) launch_gemm16w_t<EPI, true>(g, p, nr, s);
+          else launch_gemm16w_t<EPI, false>(g, p, nr, s);
+          break;
+        }
         if constexpr (lin_has_w8(PRO, EPI)) if (p.w8) {
           if constexpr (lin_has_lnp(PRO, EPI)) if (p.lnp) { launch_gemm16s_w8_t<EPI, true>(g, p, s); break; }
           launch_gemm16s_w8_t<EPI, false>(g, p, s);
@@ -489,7 +513,7 @@ static int launch_linear(zn_handle h, const LinearPlan& p, GemvArgs a, int rows,
         if constexpr (lin_has_lnp(PRO, EPI)) if (p.lnp) { launch_gemm16s_t<EPI, true>(g, p, s); break; }
         if constexpr (lin_has_gemm16(PRO)) launch_gemm16s_t<EPI, false>(g, p, s);
         break;
-      case LinearPlan::GEMM16K:   // decode: one 16-row group per launch; prefill: ceil(rows / 16) of them
+      case LinearPlan::GEMM16K:   // decode: one 16-row group per launch (the wide plan: up to four); prefill: ceil(rows / 16) of them
         if constexpr (lin_has_gemm16k(PRO, EPI)) {
           const dim3 grid((a.N + 15) / 16, (nr + 15) / 16), block(ZN_G16K_NKW * 64);
           if constexpr (lin_has_gemm16k_ln(PRO, 2)) if (p.ln_pro) { hipLaunchKernelGGL((gemm16k_kernel<EPI, 2, PRO_LN>), grid, block, 0, s, g); break; }
@@ -511,8 +535,8 @@ static int launch_linear(zn_handle h, const LinearPlan& p, GemvArgs a, int rows,
   return ZN_OK;
 }
 template <int PRO, int EPI>
-static int run_gemv(zn_handle h, const GemvArgs& a, int rows, int target_blocks, hipStream_t s) {
-  return launch_linear<PRO, EPI>(h, plan_linear(linear_env(h), PRO, EPI, rows, a.N, a.K, target_blocks, false, false, false), a, rows, s);
+static int run_gemv(zn_handle h, const GemvArgs& a, int rows, int target_blocks, hipStream_t s, bool step = true) {
+  return launch_linear<PRO, EPI>(h, plan_linear(linear_env(h, step), PRO, EPI, rows, a.N, a.K, target_blocks, false, false, false), a, rows, s);
 }
 // A projection over the M rows of a batched prefill (x normalised by the caller): the small-M kernels up to 64 rows, else the tiled GEMM.
 // with_gemm16k = false: fc1 / fc2, which were measured on the 64-row kernel only.  EPI_ROPE_KV (in_proj): *rope_done tells whether split, RoPE and
@@ -2077,7 +2101,7 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
 // ------------------------------------------------------------------------------------------------ single ops
 // A plan's LayerNorm launch normalises the rows of one launch group into nbuf [max_rows][d_model]: a caller-chosen K may not outrun it.
 static int check_ln_launch_fits(zn_handle h, const LinearPlan& p, int rows, int K, const char* who) {
-  if (p.err || !p.ln_launch) return ZN_OK;
+  if (p.err || !(p.ln_launch || (p.lnp && p.row_tiles > 1))) return ZN_OK;      // (the wide plan normalises from handed-over statistics into nbuf too)
   const int per = p.rows_per_launch && p.rows_per_launch < rows ? p.rows_per_launch : rows;
   if ((size_t)per * K > (size_t)h->max_rows * h->cfg.d_model)
     ZN_FAIL(h, ZN_ERR_ARG, "%s: the LayerNorm launch over %d rows of K = %d exceeds the handle's buffer of %d x %d", who, per, K, h->max_rows, h->cfg.d_model);
@@ -2112,7 +2136,7 @@ static int linear_fused_impl(zn_handle h, zn_linear_op* op, const void* W_q, con
     if (prefill ? (op->pf_S < 1 || rows % op->pf_S || op->pf_base < 0 || op->pf_base + op->pf_S > op->max_len) : !op->lengths)
       ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: RoPE + KV append needs lengths (decode) or pf_S dividing rows with pf_base + pf_S <= max_len (prefill)");
   }
-  LinearEnv env = linear_env(h);
+  LinearEnv env = linear_env(h, false);
   if (fp8) {
 #define ZN_F8_REFUSE(code, ...) do { op->plan[ZN_LP_ERR] = code; ZN_FAIL(h, code, __VA_ARGS__); } while (0)
     if (!W_q || !W_exp) ZN_F8_REFUSE(ZN_ERR_ARG, "zn_op_linear_fp8: codes or exponents missing");
@@ -2128,6 +2152,7 @@ static int linear_fused_impl(zn_handle h, zn_linear_op* op, const void* W_q, con
   o[ZN_LP_NW] = p.nw; o[ZN_LP_TILE8] = p.tile8; o[ZN_LP_NWV] = p.nwv; o[ZN_LP_GROUPS] = p.groups; o[ZN_LP_KSPLIT] = p.ksplit; o[ZN_LP_LNP] = p.lnp; o[ZN_LP_LN_PRO] = p.ln_pro;
   o[ZN_LP_LN_LAUNCH] = p.ln_launch; o[ZN_LP_WRITES_LN_STATS] = p.writes_ln_stats; o[ZN_LP_READS_LN_STATS] = p.reads_ln_stats; o[ZN_LP_ERR] = p.err;
   o[ZN_LP_ROPE_DONE] = epi == EPI_ROPE_KV && p.epi == EPI_ROPE_KV && !p.err; o[ZN_LP_ROWS_PER_LAUNCH] = p.rows_per_launch;
+  o[ZN_LP_ROW_TILES] = p.row_tiles;
   if (p.err) ZN_FAIL(h, p.err, "%s", p.msg);
   if (fp8 && !p.w8) ZN_F8_REFUSE(ZN_ERR_UNSUPPORTED, "zn_op_linear_fp8: this op's plan (kernel %d) would not read the FP8 stream", (int)p.kernel);
 #undef ZN_F8_REFUSE
@@ -2237,6 +2262,25 @@ extern "C" int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
   return ZN_OK;
 }
 
+// Activation rows per weight pass of a decode step of `rows` rows as this handle would run it now: in_proj, out_proj, fc1, fc2, heads (the plans of
+// layer_in_proj, plan_post_attention and heads_logits for a transformer block; with FP8 streams attached to every block, the plans that read them).
+extern "C" int zn_decode_rows_plan(zn_handle h, int32_t rows, int32_t out[5]) {
+  if (!h || !out || rows < 1) return ZN_ERR_ARG;
+  const zn_config& c = h->cfg;
+  bool all = c.arch == 0;
+  for (int li = 0; all && li < c.n_layer; ++li) all = mlp_fp8_offered(h, li);
+  const PostAttnPlans pp = plan_post_attention(h, rows, all);
+  const LinearEnv e = linear_env(h);
+  const LinearPlan in = plan_linear(e, PRO_LN, EPI_ROPE_KV, rows, (c.n_heads + 2 * c.n_heads_kv) * h->hd, c.d_model, h->tune[ZN_TUNE_WG_IN_PROJ], false, false, false);
+  const LinearPlan hd = plan_linear(e, PRO_LN, EPI_F32, rows, c.n_codebooks * c.vocab_head, c.d_model, h->tune[ZN_TUNE_WG_HEADS], false, false, false);
+  const LinearPlan* ps[5] = {&in, &pp.out, &pp.fc1, &pp.fc2, &hd};
+  for (int k = 0; k < 5; ++k) {
+    if (ps[k]->err) ZN_FAIL(h, ps[k]->err, "%s", ps[k]->msg);
+    out[k] = ps[k]->rows_per_launch;
+  }
+  return ZN_OK;
+}
+
 extern "C" int zn_op_linear(zn_handle h, const void* x, const void* ln_w, const void* ln_b, const void* W, void* out, int32_t rows,
                             int32_t N, int32_t K, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
@@ -2245,10 +2289,10 @@ extern "C" int zn_op_linear(zn_handle h, const void* x, const void* ln_w, const 
   int rc;
   if (ln_w) {
     if (K > 4096) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_op_linear: fused LayerNorm needs K <= 4096");
-    if ((rc = check_ln_launch_fits(h, plan_linear(linear_env(h), PRO_LN, EPI_STORE, rows, N, K, 1024, false, false, false), rows, K, "zn_op_linear"))) return rc;
+    if ((rc = check_ln_launch_fits(h, plan_linear(linear_env(h, false), PRO_LN, EPI_STORE, rows, N, K, 1024, false, false, false), rows, K, "zn_op_linear"))) return rc;
     a.ln_w = (const bf16_t*)ln_w; a.ln_b = (const bf16_t*)ln_b;
-    rc = run_gemv<PRO_LN, EPI_STORE>(h, a, rows, 1024, (hipStream_t)stream);
-  } else rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, 1024, (hipStream_t)stream);
+    rc = run_gemv<PRO_LN, EPI_STORE>(h, a, rows, 1024, (hipStream_t)stream, false);
+  } else rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, 1024, (hipStream_t)stream, false);
   if (rc) return rc;
   HIPCHK(h, hipGetLastError());
   return ZN_OK;

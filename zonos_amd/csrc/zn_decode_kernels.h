@@ -872,6 +872,15 @@ __global__ __launch_bounds__(ZN_G16K_NKW * 64) void gemm16k_kernel(GemvArgs a) {
     a.x += r0 * K; a.nrows -= (int)r0;
     if (a.out) a.out += r0 * a.N;
     if (a.resid) a.resid += r0 * a.N;
+    // a decode step of 17..64 rows (the wide plan): row group y of the per-row operands the prefill form does not use
+    if constexpr (EPI == EPI_F32) a.out_f32 += r0 * a.N;
+    if constexpr (EPI == EPI_ROPE_KV) {
+      if (a.pf_S == 0) {
+        a.lengths += r0;
+        a.q_out += r0 * a.n_heads * a.hd;
+        a.kv += r0 * a.max_len * 2 * a.n_heads_kv * a.hd;
+      }
+    }
   }
   if (a.nrows > 16) a.nrows = 16;
   int pf_r = 0;                                            // prefill rows: cache row of this thread's activation row

@@ -19,12 +19,17 @@ struct LinearEnv {
   size_t g16_part_bytes = 0;      // split-K partial tiles
   bool has_g16_part = false, has_ln_part = false;
   bool w8_offered = false;        // the caller holds the weights as an FP8 stream as well (zn_fp8_kernels.h) and has not switched it off
+  bool wide_rows = false;         // decode steps of more than 16 rows: up to 64 rows per weight pass (plan_linear) instead of groups of 16
 };
 
 struct LinearPlan {
   enum Kernel { GEMV, GEMM16, GEMM16S, GEMM16K, GEMM64S, GEMM_TILED } kernel = GEMV;
   int epi = 0;                // the epilogue the kernel carries: the one asked for, or (prefill, EPI_ROPE_KV not served) EPI_STORE: rope_kv_rows_kernel follows
-  int rows_per_launch = 0;    // 4 (GEMV), 16 (decode MFMA kernels), 0 = all rows in one launch (prefill)
+  int rows_per_launch = 0;    // 4 (GEMV), 16 (decode MFMA kernels), 64 (the wide plan), 0 = all rows in one launch (prefill)
+  int row_tiles = 1;          // 16-row activation blocks per weight pass: 1, or (the wide plan of 17..64 decode rows) 2 .. 4.  GEMM16K: grid y;
+                              // GEMM16S: gemm16w_kernel<., ., RB = row_tiles>, whose 64-row workgroups (groups_wide of them) keep ksplit and the
+                              // statistics order of nwv
+  int groups_wide = 0;
   bool ln_launch = false;     // a layernorm_kernel launch over the rows of each group runs first (into nbuf)
   bool writes_ln_stats = false, reads_ln_stats = false;   // LayerNorm statistics per 16-column tile: left by this launch / normalised from
   // GEMV: K slices per row pair, 512-wide chunks per slice, units (weight-row pairs) and units per wave (ks 1) or block (ks 4), grid, mask-free
@@ -49,13 +54,16 @@ constexpr bool lin_has_gemm16k_ln(int pro, int nch) { return pro == PRO_LN && nc
 // gemm16s_kernel<., NWV | ZN_G16S_W8>: fc1 (SiLU gate; its LayerNorm is a launch in front or comes from handed-over statistics, so the kernel's prologue is none
 // either way) and fc2 (no prologue, residual)
 constexpr bool lin_has_w8(int pro, int epi) { return (epi == EPI_SILU && (pro == PRO_NONE || pro == PRO_LN)) || (epi == EPI_RESID && pro == PRO_NONE); }
+// gemm16w_kernel (zn_wide_kernels.h), decode steps of 17..64 rows: fc1 (SiLU gate; LayerNorm none, from a launch, or from handed-over statistics) and fc2 (residual)
+constexpr bool lin_has_wide16s(int pro, int epi) { return (epi == EPI_SILU && (pro == PRO_NONE || pro == PRO_LN)) || (epi == EPI_RESID && pro == PRO_NONE); }
 constexpr bool lin_has_prefill(int pro, int epi) { return pro == PRO_NONE && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_SILU); }   // GEMM64S, GEMM_TILED
 inline bool linear_plan_launchable(const LinearPlan& p, int pro, int epi) {
   switch (p.kernel) {
     case LinearPlan::GEMV: return (p.ks == 1 || (p.ks == 4 && lin_has_gemv_ks4(pro))) && (p.nch == 1 || p.nch == 2 || p.nch == 4 || p.nch == 8);
     case LinearPlan::GEMM16: return lin_has_gemm16(pro) && (p.nw == 4 || p.nw == 8 || p.nw == 16) && (!p.tile8 || lin_has_tile8(epi));
-    case LinearPlan::GEMM16S: return lin_has_gemm16(pro) && (p.nwv == 2 || p.nwv == 4) && (!p.lnp || lin_has_lnp(pro, epi)) && (!p.w8 || lin_has_w8(pro, epi));
-    case LinearPlan::GEMM16K: return lin_has_gemm16k(pro, epi) && (p.nch == 2 || p.nch == 4) && (!p.ln_pro || lin_has_gemm16k_ln(pro, p.nch));
+    case LinearPlan::GEMM16S: return lin_has_gemm16(pro) && (p.nwv == 2 || p.nwv == 4) && (!p.lnp || lin_has_lnp(pro, epi)) && (!p.w8 || lin_has_w8(pro, epi)) &&
+                                     (p.row_tiles == 1 || (p.row_tiles >= 2 && p.row_tiles <= 4 && lin_has_wide16s(pro, epi)));
+    case LinearPlan::GEMM16K: return (p.row_tiles >= 1 && p.row_tiles <= 4) && lin_has_gemm16k(pro, epi) && (p.nch == 2 || p.nch == 4) && (!p.ln_pro || lin_has_gemm16k_ln(pro, p.nch));
     case LinearPlan::GEMM64S: case LinearPlan::GEMM_TILED: return !p.w8 && lin_has_prefill(pro, epi);
   }
   return false;
@@ -180,11 +188,39 @@ inline LinearPlan plan_linear_bf16(const LinearEnv& e, int pro, int epi, int row
 #undef ZN_PLAN_FAIL
 }
 
+#define ZN_WIDE_ROWS 64       // activation rows per weight pass of the wide plan
+// The wide form of a 16-row decode plan p16 for a group of `rows` rows (17..64; more rows run in groups of 64, the last group planned by its own
+// size): what fixes an output bit - the kernel family, ksplit (slice boundaries, in-order addition), the order of the tile statistics (nwv), every
+// LayerNorm decision - stays p16's; the activation rows of one weight pass grow to 16 * row_tiles.  Returns p16 itself where no wide form exists.
+inline LinearPlan plan_wide(const LinearEnv& e, const LinearPlan& p16, int pro, int epi, int rows, int N) {
+  if (p16.err || rows <= 16) return p16;
+  LinearPlan p = p16;
+  const int tiles = ((rows < ZN_WIDE_ROWS ? rows : ZN_WIDE_ROWS) + 15) / 16;
+  if (p16.kernel == LinearPlan::GEMM16K) {
+    // one launch, grid y = row tiles: the tile's weights come from HBM once and from the XCD's L2 for the other row groups, as in a short prefill
+    // (us per projection at 32 / 64 rows, groups of 16 -> one launch: in_proj 16.4 -> 14.9 / 32.4 -> 22.0, out_proj 10.4 -> 5.4 / 20.4 -> 7.9, heads 25.8 -> 20.0 / 51.1 -> 35.8).
+    // The Mamba2 in_proj (EPI_MAMBA) stays per 16: its conv-window epilogue was never run over row groups.
+    if (epi == EPI_MAMBA) return p16;
+    p.rows_per_launch = ZN_WIDE_ROWS; p.row_tiles = tiles;
+    return p;
+  }
+  if (p16.kernel != LinearPlan::GEMM16S || !lin_has_wide16s(pro, epi)) return p16;   // GEMM16 direct fragments, the Mamba2 projections, STORE, F32
+  const int nrows_w = (epi == EPI_SILU) ? N / 2 : N, per = (epi == EPI_SILU) ? 32 : 64;
+  const int groups = (nrows_w + per - 1) / per;      // (fc1 at 32 / 64 rows: 31.6 -> 19.6 / 62.9 -> 22.5 us, fc2 23.9 -> 13.0 / 47.3 -> 18.3; other workgroup sizes not measured)
+  if ((size_t)p16.ksplit * 16 * tiles * groups * 64 * sizeof(float) > e.g16_part_bytes) return p16;   // partial tiles [ksplit][16 row_tiles][64 groups] fp32
+  p.rows_per_launch = ZN_WIDE_ROWS; p.row_tiles = tiles; p.groups_wide = groups;
+  return p;
+}
+
 // The plan, and on top of it the one thing an offered FP8 stream changes: a decode launch of gemm16s_kernel for fc1 or fc2 reads the stream.
 // Kernel, grid, split, statistics hand-over - everything else is decided without looking at the offer.
 inline LinearPlan plan_linear(const LinearEnv& e, int pro, int epi, int rows, int N, int K, int target_blocks, bool prefill, bool want_ln_stats_out,
                               bool have_ln_stats_in) {
   LinearPlan p = plan_linear_bf16(e, pro, epi, rows, N, K, target_blocks, prefill, want_ln_stats_out, have_ln_stats_in);
   p.w8 = e.w8_offered && !prefill && !p.err && p.kernel == LinearPlan::GEMM16S && lin_has_w8(pro, epi);
+  // LinearEnv::wide_rows, decode, more than 16 rows: the same plan over up to 64 rows per weight pass (plan_wide).  Wide at EVERY row count from 17 on:
+  // measured (tools/widebench.py, profiles/widebench.txt; Zonos-v0.1 shapes, medians of 20, ms per decode step, groups of 16 -> wide) 18 rows 2.630 -> 1.771,
+  // 32 rows 2.723 -> 1.822, 48 rows 4.178 -> 2.400, 64 rows 5.495 -> 2.585 (FP8 stream: 2.490 -> 1.633 ... 5.186 -> 2.445); the repetitions spread by <= 0.04 ms
+  if (e.wide_rows && !prefill && rows > 16) return plan_wide(e, p, pro, epi, rows, N);
   return p;
 }

@@ -221,6 +221,12 @@ class Zonos(nn.Module):
                 self._spare = None
             return e
 
+    def decode_rows_plan(self, rows: int) -> dict:
+        """Activation rows per weight pass of in_proj, out_proj, fc1, fc2 and the heads in a decode step of `rows` rows (two per guided
+        utterance) as this model's engine runs it now: 4 up to 4 rows, 16 up to 16 rows, 64 from 17 rows on - a step of 32 rows then reads
+        every weight once, not once per 16 rows (`zn_debug_tune(ZN_TUNE_WIDE_ROWS, 1)` on the engine restores the groups of 16)."""
+        return self.engine((int(rows) + 1) // 2).decode_rows_plan(int(rows))
+
     def handoff_counters(self) -> dict:
         """Hand-off timeouts are never silent: per engine, what the library counted (include/zonos_hip.h zn_get_counters) plus the
         generations this model repeated after a reported timeout."""
