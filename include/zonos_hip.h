@@ -348,7 +348,11 @@ enum zn_tune_key {
   ZN_TUNE_WIDE_ROWS = 21,           /* decode steps of 17..64 rows: 1 = every projection in groups of 16 rows (each weight streamed once per group);
                                        2 = up to 64 rows per weight pass also in zn_op_linear_fused / zn_op_linear_fp8; default: generation steps and
                                        zn_bench_kernel take up to 64 rows per weight pass, the per-op entry points groups of 16.  Same bits either way */
-  ZN_TUNE_NKEYS = 22
+  ZN_TUNE_WIDE_HYBRID = 22,         /* the Mamba2 in_proj of a hybrid decode step of 17..64 rows (under the wide plan; ZN_TUNE_WIDE_ROWS = 1 still groups everything by 16):
+                                       1 = groups of 16 rows, 2 = row groups on the grid of gemm16k_kernel (the weight tile re-read through L2 per 16 rows), 3 = the
+                                       row-tile loop (gemm16k_rows_kernel: the weight tile requested once per up to 64 rows); default: the form the plan picks for the
+                                       row count (wide_hybrid_form, zn_linear_plan.h).  Same bits in every form */
+  ZN_TUNE_NKEYS = 23
 };
 /* Values of ZN_TUNE_HOOK.  The first three arm the next zn_gen_begin, which consumes them. */
 enum zn_tune_hook {
@@ -391,7 +395,8 @@ int zn_op_backbone_forward(zn_handle h, const void* hidden_dev, void* out_dev, c
  * bytes = those four weight matrices, out_proj counted once), 6 = the whole-step kernel (every block of a decode step and the heads in
  * ONE launch, one or two rows) on scratch KV caches of its own holding `ctx` keys per row; bytes = every weight the step reads once
  * (in_proj of block 0 included: the launch's pre-block; excluded under zn_debug_tune(ZN_TUNE_STACK_PRE, 2), where it is a launch of its own) + K/V of
- * ctx keys read and one row written per layer.
+ * ctx keys read and one row written per layer, 7 = the Mamba2 in_proj with its conv-window epilogue (hybrid handles; a scratch window; cycles through
+ * the Mamba2 layers; every launch of the plan's launch set counts as one: ms_per_launch prices the projection over all its rows).
  * rows: bits 0-7 = activation rows; bit 8 = keep streaming layer 0's weights (cache-hot variant); bits 16-30 = ctx for which == 6
  * (0 = 450, the mean context of a 10 s utterance). */
 int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t iters, float* ms_per_launch,
@@ -463,6 +468,9 @@ int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
  * run it now (4 up to 4 rows, 16 up to 16 rows and under zn_debug_tune(ZN_TUNE_WIDE_ROWS, 1), 64 where the wide plan applies): a step of R rows
  * reads the projection's weights ceil(R / out[k]) times. */
 int zn_decode_rows_plan(zn_handle h, int32_t rows, int32_t out[5]);
+/* The same report for a hybrid handle (arch 1), as its decode step plans them: out[0..6] = Mamba2 in_proj, Mamba2 out_proj, attention in_proj, out_proj,
+ * fc1, fc2, heads (the first layer of each kind; 0 for a kind the stack does not have).  ZN_ERR_STATE on a transformer handle. */
+int zn_hybrid_rows_plan(zn_handle h, int32_t rows, int32_t out[7]);
 /* Prefix-conditioner pieces (zonos/conditioning.py): nn.Linear with bias (Conditioner.project, :52-60; bias added in fp32
  * before the one bf16 rounding), nn.Embedding row gather (:364-365,467), FourierConditioner.apply_cond (:436-441), nn.SiLU. */
 int zn_op_linear_bias(zn_handle h, const void* x_dev, const void* W_dev, const void* bias_dev, void* out_dev, int32_t rows,

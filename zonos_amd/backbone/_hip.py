@@ -233,6 +233,13 @@ class HipEngine:
         self.call("zn_decode_rows_plan", rows, out)
         return dict(zip(("in_proj", "out_proj", "fc1", "fc2", "heads"), (int(v) for v in out)))
 
+    def hybrid_rows_plan(self, rows: int) -> dict:
+        """zn_hybrid_rows_plan: the same report for a hybrid stack - the Mamba2 in_proj and out_proj, then the attention layers' in_proj, out_proj, fc1, fc2,
+        and the heads (0 for a kind of layer the stack does not have).  Raises on a transformer engine."""
+        out = (C.c_int32 * 7)()
+        self.call("zn_hybrid_rows_plan", rows, out)
+        return dict(zip(("mamba_in_proj", "mamba_out_proj", "in_proj", "out_proj", "fc1", "fc2", "heads"), (int(v) for v in out)))
+
     def __del__(self):
         try:
             if getattr(self, "h", None):

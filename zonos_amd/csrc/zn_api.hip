@@ -443,6 +443,8 @@ static void launch_gemm16w_t(const GemvArgs& g, const LinearPlan& p, int nr, hip
 static LinearEnv linear_env(zn_handle h, bool step = true) {
   LinearEnv e;
   e.wide_rows = h->tune[ZN_TUNE_WIDE_ROWS] == 2 || (step && h->tune[ZN_TUNE_WIDE_ROWS] != 1);
+  // the Mamba2 in_proj of a generation step (mamba_mixer, zn_op_mamba_step included): ZN_TUNE_WIDE_HYBRID, unset = the form plan_wide picks for the row count
+  e.wide_hybrid = !step ? 0 : h->tune[ZN_TUNE_WIDE_HYBRID] ? h->tune[ZN_TUNE_WIDE_HYBRID] : 4;
   e.small_m_lds = h->tune[ZN_TUNE_SMALL_M_LDS]; e.no_split_small_m = h->tune[ZN_TUNE_NO_SPLIT_SMALL_M]; e.gemm16k_max_tiles = h->tune[ZN_TUNE_GEMM16K_MAX_TILES];
   e.fc1_ln_launch = h->tune[ZN_TUNE_FC1_LN_LAUNCH]; e.no_prefill_gemm16k = h->tune[ZN_TUNE_NO_PREFILL_GEMM16K];
   e.g16_part_bytes = h->g16_part_bytes; e.has_g16_part = h->g16_part != nullptr; e.has_ln_part = h->ln_part != nullptr;
@@ -516,6 +518,10 @@ static int launch_linear(zn_handle h, const LinearPlan& p, GemvArgs a, int rows,
       case LinearPlan::GEMM16K:   // decode: one 16-row group per launch (the wide plan: up to four); prefill: ceil(rows / 16) of them
         if constexpr (lin_has_gemm16k(PRO, EPI)) {
           const dim3 grid((a.N + 15) / 16, (nr + 15) / 16), block(ZN_G16K_NKW * 64);
+          if constexpr (lin_has_gemm16k_rows(PRO, EPI, 2)) if (p.row_loop && nr > 16) {    // the row-tile loop: one workgroup per weight tile walks the row tiles
+            hipLaunchKernelGGL((gemm16k_rows_kernel<2>), dim3(grid.x), block, 0, s, g);
+            break;
+          }
           if constexpr (lin_has_gemm16k_ln(PRO, 2)) if (p.ln_pro) { hipLaunchKernelGGL((gemm16k_kernel<EPI, 2, PRO_LN>), grid, block, 0, s, g); break; }
           if (p.nch == 2) hipLaunchKernelGGL((gemm16k_kernel<EPI, 2, PRO_NONE>), grid, block, 0, s, g);
           else hipLaunchKernelGGL((gemm16k_kernel<EPI, 4, PRO_NONE>), grid, block, 0, s, g);
@@ -983,19 +989,22 @@ static void launch_add_ln(zn_handle h, const bf16_t* hid, bf16_t* res, int has_r
   hipLaunchKernelGGL(add_ln_kernel, dim3(rows), dim3(256), 0, s, a);
 }
 
+// The Mamba2 in_proj with the conv window update + SiLU of its xBC rows in the epilogue (causal_conv1d_update; one launch less): n [rows][d] -> m_zx, m_xbc
+static int mamba_in_proj(zn_handle h, const zn_layer_weights& lw, const bf16_t* n, void* conv_state, int rows, hipStream_t s) {
+  const zn_config& c = h->cfg;
+  GemvArgs a{};
+  a.W = (const bf16_t*)lw.m_in_proj; a.N = h->m_d_in_proj; a.K = c.d_model; a.x = n; a.out = h->m_zx;
+  a.conv_state = (bf16_t*)conv_state; a.conv_w = (const bf16_t*)lw.m_conv_w; a.conv_b = (const bf16_t*)lw.m_conv_b; a.xbc = h->m_xbc;
+  a.d_inner = c.m_d_inner; a.conv_dim = h->m_conv_dim;
+  return run_gemv<PRO_NONE, EPI_MAMBA>(h, a, rows, (h->m_d_in_proj / 2 + 3) / 4, s);
+}
+
 // One token through the Mamba2 mixer of layer li (mamba_ssm Mamba2.step): n [rows][d] normalised -> out [rows][d]
 static int mamba_mixer(zn_handle h, int li, const bf16_t* n, void* state, bf16_t* out, int rows, hipStream_t s) {
   const zn_config& c = h->cfg;
   const zn_layer_weights& lw = h->layers[li];
   int rc;
-  {
-    GemvArgs a{};
-    // in_proj with the conv window update + SiLU of its xBC rows in the epilogue (causal_conv1d_update; one launch less)
-    a.W = (const bf16_t*)lw.m_in_proj; a.N = h->m_d_in_proj; a.K = c.d_model; a.x = n; a.out = h->m_zx;
-    a.conv_state = (bf16_t*)state; a.conv_w = (const bf16_t*)lw.m_conv_w; a.conv_b = (const bf16_t*)lw.m_conv_b; a.xbc = h->m_xbc;
-    a.d_inner = c.m_d_inner; a.conv_dim = h->m_conv_dim;
-    if ((rc = run_gemv<PRO_NONE, EPI_MAMBA>(h, a, rows, (h->m_d_in_proj / 2 + 3) / 4, s))) return rc;
-  }
+  if ((rc = mamba_in_proj(h, lw, n, state, rows, s))) return rc;
   size_t conv_bytes = 0;   // the state buffer is laid out for exactly `rows` rows (zn_mamba_state_bytes_per_layer)
   (void)zn_mamba_state_bytes_per_layer(&c, rows, &conv_bytes);
   MambaArgs m{};
@@ -1991,7 +2000,7 @@ extern "C" int zn_debug_eos_bias(zn_handle h, float bias) { if (!h) return ZN_ER
 extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t iters, float* ms_per_launch, double* bytes_per_launch,
                                zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
-  if (!ms_per_launch || !bytes_per_launch || iters < 1 || (rows & 0xff) < 1 || (rows & 0xff) > h->max_rows || which < 0 || which > 6)
+  if (!ms_per_launch || !bytes_per_launch || iters < 1 || (rows & 0xff) < 1 || (rows & 0xff) > h->max_rows || which < 0 || which > 7)
     ZN_FAIL(h, ZN_ERR_ARG, "zn_bench_kernel: bad argument");
   h->gen_stream = (hipStream_t)stream;
   const bool same_layer = (rows & 0x100) != 0;   // measurement variant: keep hitting layer 0 (weights stay in the Infinity Cache)
@@ -2038,6 +2047,15 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
     int rcb = build_stack_table(h);
     if (rcb) return rcb;
   }
+  // which == 7: the Mamba2 in_proj (conv-window epilogue included) on a scratch window, cycling through the Mamba2 layers
+  std::vector<int> mamba_layers;
+  bf16_t* tconv = nullptr;
+  if (which == 7) {
+    for (int li = 0; li < c.n_layer; ++li) if (c.arch == 1 && h->layers[li].kind == 1) mamba_layers.push_back(li);
+    if (mamba_layers.empty()) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the handle has no Mamba2 layer");
+    HIPCHK(h, hipMalloc(&tconv, (size_t)rows * h->m_conv_dim * 4 * 2));
+    HIPCHK(h, hipMemsetAsync(tconv, 0, (size_t)rows * h->m_conv_dim * 4 * 2, s));
+  }
   hipEvent_t e0, e1;
   HIPCHK(h, hipEventCreate(&e0));
   HIPCHK(h, hipEventCreate(&e1));
@@ -2058,6 +2076,7 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
       else if (which == 1) rc = run_gemv<PRO_NONE, EPI_RESID>(h, fc2_args(h, lw, h->x), rows, h->tune[ZN_TUNE_WG_FC2], s);
       else if (which == 2) rc = run_gemv<PRO_NONE, EPI_RESID>(h, out_proj_args(h, lw, h->o1, h->x, h->x), rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s);
       else if (which == 6) rc = launch_stack(h, s, rows, stack_nbk);
+      else if (which == 7) rc = mamba_in_proj(h, h->layers[mamba_layers[same_layer ? 0 : i % mamba_layers.size()]], h->x, tconv, rows, s);
       else if (which == 5) {
         if (i % c.n_layer == c.n_layer - 1) continue;       // the last block's launch has no in_proj: not the launch being priced
         rc = launch_chain(h, i % c.n_layer, std::vector<const void*>(c.n_layer, tkv), 8, tlen, s);
@@ -2073,6 +2092,7 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   if (tkv) (void)hipFree(tkv);
   if (tlen) (void)hipFree(tlen);
+  if (tconv) (void)hipFree(tconv);
   if (which == 6) {
     for (void* p : skv) if (p) (void)hipFree(p);
     h->kv_layers = saved_kv; h->max_len = saved_max_len; h->lengths = saved_lengths;
@@ -2088,7 +2108,7 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   // chain launch: out_proj (read once, applied twice), fc1, fc2 of the block and in_proj of the next one
   const double wbytes = which == 5 ? ((double)d * nq + 3.0 * c.d_ff * d + (double)(nq + 2 * nkv) * d) * 2 : which == 0 ? 2.0 * c.d_ff * d * 2 : which == 1 ? (double)d * c.d_ff * 2 : which == 2 ? (double)d * c.n_heads * h->hd * 2
                         : which == 4 ? (double)(nq + 2 * nkv) * d * 2 : (double)c.n_codebooks * c.vocab_head * d * 2;
-  *bytes_per_launch = wbytes;   // algorithmic bytes = the weight matrix, read once (activations are KBs)
+  *bytes_per_launch = which == 7 ? (double)h->m_d_in_proj * d * 2 : wbytes;   // algorithmic bytes = the weight matrix, read once (activations are KBs)
   if (which == 6) {             // every block's out_proj (once), fc1, fc2, in_proj; the heads; K and V of `ctx` keys read, one row written
     const double per_block = ((double)d * nq + 3.0 * c.d_ff * d) * 2, inp = (double)(nq + 2 * nkv) * d * 2, kvpos = 2.0 * nkv * 2;
     const int nin = stack_pre(h) ? c.n_layer : c.n_layer - 1;      // in_proj of block 0 inside the launch (the pre-block) or before it
@@ -2277,6 +2297,43 @@ extern "C" int zn_decode_rows_plan(zn_handle h, int32_t rows, int32_t out[5]) {
   for (int k = 0; k < 5; ++k) {
     if (ps[k]->err) ZN_FAIL(h, ps[k]->err, "%s", ps[k]->msg);
     out[k] = ps[k]->rows_per_launch;
+  }
+  return ZN_OK;
+}
+
+// Activation rows per weight pass of a hybrid decode step of `rows` rows: the plans mamba_mixer, hybrid_layer and hybrid_heads make (the same calls of
+// plan_linear: prologue, epilogue, shape and target of each run_gemv there), for the first Mamba2 and the first attention layer; 0 where the stack has no such layer.
+extern "C" int zn_hybrid_rows_plan(zn_handle h, int32_t rows, int32_t out[7]) {
+  if (!h || !out || rows < 1) return ZN_ERR_ARG;
+  const zn_config& c = h->cfg;
+  if (c.arch != 1) ZN_FAIL(h, ZN_ERR_STATE, "zn_hybrid_rows_plan: not a hybrid handle");
+  const LinearEnv e = linear_env(h);
+  const int d = c.d_model, nq = c.n_heads * h->hd, nkv = c.n_heads_kv * h->hd;
+  int mamba = -1, attn = -1;
+  for (int li = c.n_layer - 1; li >= 0; --li) (h->layers[li].kind == 1 ? mamba : attn) = li;
+  for (int k = 0; k < 7; ++k) out[k] = 0;
+  LinearPlan ps[7];
+  bool on[7] = {};
+  if (mamba >= 0) {
+    const bool gated_pro = c.m_ngroups == 1 && c.m_d_inner % 8 == 0 && rows <= 4 && c.m_d_inner <= 4096;
+    ps[0] = plan_linear(e, PRO_NONE, EPI_MAMBA, rows, h->m_d_in_proj, d, (h->m_d_in_proj / 2 + 3) / 4, false, false, false);
+    ps[1] = plan_linear(e, gated_pro ? PRO_GATED : PRO_NONE, EPI_STORE, rows, d, c.m_d_inner, h->tune[ZN_TUNE_WG_FC2], false, false, false);
+    on[0] = on[1] = true;
+  }
+  if (attn >= 0) {
+    const bool rope_epi = c.rope_mode == 0 && !h->layers[attn].in_proj_bias;
+    ps[2] = plan_linear(e, PRO_NONE, rope_epi ? EPI_ROPE_KV : EPI_STORE, rows, nq + 2 * nkv, d, h->tune[ZN_TUNE_WG_IN_PROJ], false, false, false);
+    ps[3] = plan_linear(e, PRO_NONE, EPI_STORE, rows, d, nq, h->tune[ZN_TUNE_WG_OUT_PROJ], false, false, false);
+    ps[4] = plan_linear(e, PRO_NONE, EPI_SILU, rows, 2 * c.d_ff, d, h->tune[ZN_TUNE_WG_FC1], false, false, false);
+    ps[5] = plan_linear(e, PRO_NONE, EPI_STORE, rows, d, c.d_ff, h->tune[ZN_TUNE_WG_FC2], false, false, false);
+    on[2] = on[3] = on[4] = on[5] = true;
+  }
+  ps[6] = plan_linear(e, PRO_NONE, EPI_F32, rows, c.n_codebooks * c.vocab_head, d, h->tune[ZN_TUNE_WG_HEADS], false, false, false);
+  on[6] = true;
+  for (int k = 0; k < 7; ++k) {
+    if (!on[k]) continue;
+    if (ps[k].err) ZN_FAIL(h, ps[k].err, "%s", ps[k].msg);
+    out[k] = ps[k].rows_per_launch;
   }
   return ZN_OK;
 }

@@ -881,6 +881,8 @@ __global__ __launch_bounds__(ZN_G16K_NKW * 64) void gemm16k_kernel(GemvArgs a) {
         a.kv += r0 * a.max_len * 2 * a.n_heads_kv * a.hd;
       }
     }
+    // the Mamba2 in_proj over row groups (LinearEnv::wide_hybrid = 2): mamba_epi_operands and the epilogue index window and xBC by the local row
+    if constexpr (EPI == EPI_MAMBA) { a.conv_state += r0 * a.conv_dim * 4; a.xbc += r0 * a.conv_dim; }
   }
   if (a.nrows > 16) a.nrows = 16;
   int pf_r = 0;                                            // prefill rows: cache row of this thread's activation row

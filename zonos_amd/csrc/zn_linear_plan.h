@@ -20,6 +20,8 @@ struct LinearEnv {
   bool has_g16_part = false, has_ln_part = false;
   bool w8_offered = false;        // the caller holds the weights as an FP8 stream as well (zn_fp8_kernels.h) and has not switched it off
   bool wide_rows = false;         // decode steps of more than 16 rows: up to 64 rows per weight pass (plan_linear) instead of groups of 16
+  int wide_hybrid = 0;            // under wide_rows, the Mamba2 in_proj (GEMM16K x EPI_MAMBA): 0 / 1 groups of 16, 2 row groups on grid y, 3 the row-tile loop
+                                  // (gemm16k_rows_kernel), 4 = the form wide_hybrid_form picks for the row count (ZN_TUNE_WIDE_HYBRID unset)
 };
 
 struct LinearPlan {
@@ -30,6 +32,8 @@ struct LinearPlan {
                               // GEMM16S: gemm16w_kernel<., ., RB = row_tiles>, whose 64-row workgroups (groups_wide of them) keep ksplit and the
                               // statistics order of nwv
   int groups_wide = 0;
+  bool row_loop = false;      // GEMM16K x EPI_MAMBA with row_tiles > 1: gemm16k_rows_kernel (grid y = 1: the workgroup keeps its weight tile as B fragments and walks
+                              // the row tiles) instead of gemm16k_kernel's row groups on grid y
   bool ln_launch = false;     // a layernorm_kernel launch over the rows of each group runs first (into nbuf)
   bool writes_ln_stats = false, reads_ln_stats = false;   // LayerNorm statistics per 16-column tile: left by this launch / normalised from
   // GEMV: K slices per row pair, 512-wide chunks per slice, units (weight-row pairs) and units per wave (ks 1) or block (ks 4), grid, mask-free
@@ -51,6 +55,7 @@ constexpr bool lin_has_tile8(int epi) { return epi != EPI_SILU; }
 constexpr bool lin_has_lnp(int pro, int epi) { return pro == PRO_LN && epi == EPI_SILU; }
 constexpr bool lin_has_gemm16k(int pro, int epi) { return lin_has_gemm16(pro) && epi != EPI_SILU; }   // row-pair epilogues only
 constexpr bool lin_has_gemm16k_ln(int pro, int nch) { return pro == PRO_LN && nch == 2; }  // (the LayerNorm prologue at K = 4096 would not fit the register file)
+constexpr bool lin_has_gemm16k_rows(int pro, int epi, int nch) { return pro == PRO_NONE && epi == EPI_MAMBA && nch == 2; }   // gemm16k_rows_kernel: the Mamba2 in_proj at K = 2048, what production launches
 // gemm16s_kernel<., NWV | ZN_G16S_W8>: fc1 (SiLU gate; its LayerNorm is a launch in front or comes from handed-over statistics, so the kernel's prologue is none
 // either way) and fc2 (no prologue, residual)
 constexpr bool lin_has_w8(int pro, int epi) { return (epi == EPI_SILU && (pro == PRO_NONE || pro == PRO_LN)) || (epi == EPI_RESID && pro == PRO_NONE); }
@@ -63,7 +68,8 @@ inline bool linear_plan_launchable(const LinearPlan& p, int pro, int epi) {
     case LinearPlan::GEMM16: return lin_has_gemm16(pro) && (p.nw == 4 || p.nw == 8 || p.nw == 16) && (!p.tile8 || lin_has_tile8(epi));
     case LinearPlan::GEMM16S: return lin_has_gemm16(pro) && (p.nwv == 2 || p.nwv == 4) && (!p.lnp || lin_has_lnp(pro, epi)) && (!p.w8 || lin_has_w8(pro, epi)) &&
                                      (p.row_tiles == 1 || (p.row_tiles >= 2 && p.row_tiles <= 4 && lin_has_wide16s(pro, epi)));
-    case LinearPlan::GEMM16K: return (p.row_tiles >= 1 && p.row_tiles <= 4) && lin_has_gemm16k(pro, epi) && (p.nch == 2 || p.nch == 4) && (!p.ln_pro || lin_has_gemm16k_ln(pro, p.nch));
+    case LinearPlan::GEMM16K: return (p.row_tiles >= 1 && p.row_tiles <= 4) && lin_has_gemm16k(pro, epi) && (p.nch == 2 || p.nch == 4) && (!p.ln_pro || lin_has_gemm16k_ln(pro, p.nch)) &&
+                                     (!p.row_loop || (p.row_tiles >= 2 && !p.ln_pro && lin_has_gemm16k_rows(pro, epi, p.nch)));
     case LinearPlan::GEMM64S: case LinearPlan::GEMM_TILED: return !p.w8 && lin_has_prefill(pro, epi);
   }
   return false;
@@ -189,6 +195,12 @@ inline LinearPlan plan_linear_bf16(const LinearEnv& e, int pro, int epi, int row
 }
 
 #define ZN_WIDE_ROWS 64       // activation rows per weight pass of the wide plan
+// The form of the Mamba2 in_proj (GEMM16K x EPI_MAMBA) over a group of `rows` rows (17..64) when ZN_TUNE_WIDE_HYBRID is unset: 1 groups of 16, 2 row groups on
+// grid y, 3 the row-tile loop.  The loop at EVERY row count: measured (tools/hybridwidebench.py, profiles/hybridwidebench.txt; Zonos-v0.1-hybrid shapes, in_proj
+// 8512 x 2048, medians of 20 alternated repetitions, us per in_proj, groups of 16 / grid y / loop) 18 rows 21.58 / 17.23 / 15.25, 32 rows 23.77 / 19.64 / 18.70,
+// 48 rows 34.93 / 26.33 / 24.08, 64 rows 46.10 / 33.22 / 29.76 (the repetitions spread by <= 0.27 us); ms per decode step of the 46-layer stack 18 rows 2.581 /
+// 2.379 / 2.300, 32 rows 2.886 / 2.691 / 2.654, 48 rows 4.009 / 3.632 / 3.514, 64 rows 4.878 / 4.316 / 4.136 (spread <= 0.074 ms)
+inline int wide_hybrid_form(int rows) { (void)rows; return 3; }
 // The wide form of a 16-row decode plan p16 for a group of `rows` rows (17..64; more rows run in groups of 64, the last group planned by its own
 // size): what fixes an output bit - the kernel family, ksplit (slice boundaries, in-order addition), the order of the tile statistics (nwv), every
 // LayerNorm decision - stays p16's; the activation rows of one weight pass grow to 16 * row_tiles.  Returns p16 itself where no wide form exists.
@@ -199,8 +211,15 @@ inline LinearPlan plan_wide(const LinearEnv& e, const LinearPlan& p16, int pro, 
   if (p16.kernel == LinearPlan::GEMM16K) {
     // one launch, grid y = row tiles: the tile's weights come from HBM once and from the XCD's L2 for the other row groups, as in a short prefill
     // (us per projection at 32 / 64 rows, groups of 16 -> one launch: in_proj 16.4 -> 14.9 / 32.4 -> 22.0, out_proj 10.4 -> 5.4 / 20.4 -> 7.9, heads 25.8 -> 20.0 / 51.1 -> 35.8).
-    // The Mamba2 in_proj (EPI_MAMBA) stays per 16: its conv-window epilogue was never run over row groups.
-    if (epi == EPI_MAMBA) return p16;
+    if (epi == EPI_MAMBA) {
+      // The Mamba2 in_proj (8512 x 2048 at the hybrid checkpoint's sizes): LinearEnv::wide_hybrid picks groups of 16, the row groups on grid y above (conv
+      // window and xBC of row group y: the kernel's blockIdx.y block), or the row-tile loop, which requests the weight tile once and keeps it as B fragments
+      // while it walks the row tiles - no re-read through L2 per 16 rows.  The loop exists for what production launches (lin_has_gemm16k_rows); elsewhere
+      // form 3 is form 2.
+      const int form = e.wide_hybrid == 4 ? wide_hybrid_form(rows < ZN_WIDE_ROWS ? rows : ZN_WIDE_ROWS) : e.wide_hybrid;
+      if (form != 2 && form != 3) return p16;
+      p.row_loop = form == 3 && !p16.ln_pro && lin_has_gemm16k_rows(pro, epi, p16.nch);
+    }
     p.rows_per_launch = ZN_WIDE_ROWS; p.row_tiles = tiles;
     return p;
   }

@@ -238,3 +238,95 @@ __global__ __launch_bounds__(256) void gemm16w_kernel(GemvArgs a) {
     }
   }
 }
+
+// ------------------------------------------------------------------------------------------------ the Mamba2 in_proj over up to four row tiles per weight pass
+// gemm16k_kernel<EPI_MAMBA, NCH, PRO_NONE> (zn_decode_kernels.h) over 17..64 rows without the re-read per 16 rows: grid (ceil(N / 16), 1).  The workgroup
+// requests its 16-row weight tile ONCE - each wave its K / 8 slice, through its Ws into B fragments, exactly as gemm16k_kernel does - keeps the B
+// fragments in registers (NCH * 16 VGPRs) and walks the ceil(min(rows, 64) / 16) activation tiles.  Per tile: the A fragments of rows 16 rt .., the tile's
+// epilogue operands (window state, taps, bias), the same chained v_mfma_f32_16x16x32_bf16 sequence per wave (chunks and steps ascending from 0.f), Ct,
+// barrier, the eight partial tiles added in wave order from 0.f, gemv_epilogue<EPI_MAMBA>, and a barrier before Ct is reused.  An output element
+// therefore sees the instruction sequence the 16-row launch gives it.  The NEXT tile's activations and epilogue operands are requested before the
+// current tile's partials meet, so their round trip hides behind the barrier and the epilogue (the tiles' window rows are disjoint: no hazard).
+template <int NCH>      // NCH = 128-wide chunks per wave: K = 8 * 128 * NCH
+__global__ __launch_bounds__(ZN_G16K_NKW * 64) void gemm16k_rows_kernel(GemvArgs a) {
+  constexpr int NKW = ZN_G16K_NKW, KCH = ZN_G16K_KCH, LDW = KCH + 8, KS = KCH * NCH, MAXT = ZN_WIDE_ROWS / 16;
+  __shared__ __attribute__((aligned(16))) bf16_t Ws[NKW][16 * LDW];
+  __shared__ float Ct[NKW][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, g = lane >> 4;
+  const int tile = blockIdx.x, K = a.K, kbeg = wave * KS;
+  const int rows = a.nrows < ZN_WIDE_ROWS ? a.nrows : ZN_WIDE_ROWS, ntiles = (rows + 15) / 16;
+  // epilogue item (tid < 128): activation row 16 rt + em, weight-row pair epj of the tile
+  const int em = tid & 15, epj = (tid >> 4) & 7;
+  const int erowA = tile * 16 + 2 * epj, erowB = erowA + 1;
+  const bool e_col = tid < 128 && erowA < a.N, eb_ok = erowB < a.N;
+  // tile 0: epilogue operands first, then the activations - both ahead of the weight stream, as in gemm16k_kernel
+  unsigned resid = 0;
+  u32x4 cst = u32x4{0, 0, 0, 0}, cw = u32x4{0, 0, 0, 0};
+  bool e_on = e_col && em < rows;
+  if (e_on) mamba_epi_operands(a, em, erowA, resid, cst, cw);
+  u32x4 wr[NCH][4], xr[NCH][KCH / 32], bw[NCH][KCH / 32];
+  {
+    const bf16_t* xp = a.x + (size_t)min(n, rows - 1) * K + kbeg + 8 * g;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int st = 0; st < KCH / 32; ++st) xr[c][st] = ld16(xp + c * KCH + 32 * st);
+  }
+  // weights: load i of chunk c = rows 4i .. 4i+3 of the tile, 16 lanes x 16 B = 256 contiguous bytes of one row each
+  const int wsub = lane & 15, wq = lane >> 4;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = min(tile * 16 + 4 * i + wq, a.N - 1);        // clamped: never out of bounds; masked in the epilogue
+      wr[c][i] = ld_nt16(a.W + (size_t)row * K + kbeg + c * KCH + 8 * wsub);
+    }
+  bf16_t* ws = &Ws[wave][0];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *(u32x4*)(ws + (4 * i + wq) * LDW + 8 * wsub) = wr[c][i];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");           // the region is private to the wave: its LDS ops complete in order
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int st = 0; st < KCH / 32; ++st) bw[c][st] = *(const u32x4*)(ws + n * LDW + 32 * st + 8 * g);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int rt = 0; rt < MAXT; ++rt) {
+    if (rt >= ntiles) break;                                         // uniform
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int st = 0; st < KCH / 32; ++st)
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(zn_bf16x8, xr[c][st]), __builtin_bit_cast(zn_bf16x8, bw[c][st]), acc, 0, 0, 0);
+    // the next tile's activations and epilogue operands
+    const int r1 = 16 * (rt + 1);
+    unsigned resid_n = 0;
+    u32x4 cst_n = u32x4{0, 0, 0, 0}, cw_n = u32x4{0, 0, 0, 0};
+    const bool e_on_n = e_col && r1 + em < rows;
+    if (r1 < rows) {                                                 // uniform
+      const bf16_t* xp = a.x + (size_t)min(r1 + n, rows - 1) * K + kbeg + 8 * g;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int st = 0; st < KCH / 32; ++st) xr[c][st] = ld16(xp + c * KCH + 32 * st);
+      if (e_on_n) mamba_epi_operands(a, r1 + em, erowA, resid_n, cst_n, cw_n);
+    }
+    // D layout: col (weight row of the tile) = lane & 15, row (activation row) = 4*(lane>>4) + reg
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) Ct[wave][n][4 * g + reg] = acc[reg];
+    __syncthreads();
+    if (e_on) {
+      float vA = 0.f, vB = 0.f;
+#pragma unroll
+      for (int w = 0; w < NKW; ++w) { vA += Ct[w][2 * epj][em]; vB += Ct[w][2 * epj + 1][em]; }
+      gemv_epilogue<EPI_MAMBA>(a, 16 * rt + em, erowA, erowB, eb_ok, erowA >> 1, vA, eb_ok ? vB : 0.f, resid, 1.f, 0.f, 0, cst, cw);
+    }
+    __syncthreads();                                                 // Ct is rewritten by the next tile
+    e_on = e_on_n; resid = resid_n; cst = cst_n; cw = cw_n;
+  }
+}

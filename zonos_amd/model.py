@@ -227,6 +227,12 @@ class Zonos(nn.Module):
         every weight once, not once per 16 rows (`zn_debug_tune(ZN_TUNE_WIDE_ROWS, 1)` on the engine restores the groups of 16)."""
         return self.engine((int(rows) + 1) // 2).decode_rows_plan(int(rows))
 
+    def hybrid_rows_plan(self, rows: int) -> dict:
+        """The same report for a hybrid checkpoint: activation rows per weight pass of the Mamba2 in_proj and out_proj, the attention layers' in_proj,
+        out_proj, fc1 and fc2, and the heads (`zn_debug_tune(ZN_TUNE_WIDE_HYBRID, 1)` on the engine puts the Mamba2 in_proj back to groups of 16).  Raises
+        on a transformer checkpoint."""
+        return self.engine((int(rows) + 1) // 2).hybrid_rows_plan(int(rows))
+
     def handoff_counters(self) -> dict:
         """Hand-off timeouts are never silent: per engine, what the library counted (include/zonos_hip.h zn_get_counters) plus the
         generations this model repeated after a reported timeout."""
