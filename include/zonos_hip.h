@@ -352,7 +352,8 @@ enum zn_tune_key {
                                        1 = groups of 16 rows, 2 = row groups on the grid of gemm16k_kernel (the weight tile re-read through L2 per 16 rows), 3 = the
                                        row-tile loop (gemm16k_rows_kernel: the weight tile requested once per up to 64 rows); default: the form the plan picks for the
                                        row count (wide_hybrid_form, zn_linear_plan.h).  Same bits in every form */
-  ZN_TUNE_NKEYS = 23
+  ZN_TUNE_MAMBA_FP8 = 23,           /* 2 = ignore the FP8 streams attached by zn_set_mamba_fp8: every launch reads the bf16 in_proj / out_proj of the Mamba2 layers */
+  ZN_TUNE_NKEYS = 24
 };
 /* Values of ZN_TUNE_HOOK.  The first three arm the next zn_gen_begin, which consumes them. */
 enum zn_tune_hook {
@@ -396,7 +397,9 @@ int zn_op_backbone_forward(zn_handle h, const void* hidden_dev, void* out_dev, c
  * ONE launch, one or two rows) on scratch KV caches of its own holding `ctx` keys per row; bytes = every weight the step reads once
  * (in_proj of block 0 included: the launch's pre-block; excluded under zn_debug_tune(ZN_TUNE_STACK_PRE, 2), where it is a launch of its own) + K/V of
  * ctx keys read and one row written per layer, 7 = the Mamba2 in_proj with its conv-window epilogue (hybrid handles; a scratch window; cycles through
- * the Mamba2 layers; every launch of the plan's launch set counts as one: ms_per_launch prices the projection over all its rows).
+ * the Mamba2 layers; every launch of the plan's launch set counts as one: ms_per_launch prices the projection over all its rows), 8 = the Mamba2 out_proj of 5 rows and more
+ * (hybrid handles; no prologue, store; cycles through the Mamba2 layers).  7 and 8 read what a decode step would read: the FP8 stream where zn_set_mamba_fp8 attached one;
+ * bytes stay those of the bf16 matrix.
  * rows: bits 0-7 = activation rows; bit 8 = keep streaming layer 0's weights (cache-hot variant); bits 16-30 = ctx for which == 6
  * (0 = 450, the mean context of a 10 s utterance). */
 int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t iters, float* ms_per_launch,
@@ -463,6 +466,19 @@ int zn_op_linear_fp8(zn_handle h, zn_linear_op* op, const void* W_q, const void*
 /* out[0], out[1]: whether fc1 and fc2 of a decode step over `rows` rows would read FP8 in EVERY block of this handle now (the tune keys; a
  * handle with streams attached to some blocks only reports 0, 0 although those blocks do read them). */
 int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
+/* ---------------------------------------------------------------- weight-only FP8 for the Mamba2 projections of a hybrid handle (additive to ABI 9 in the same way:
+ * two entry points and one tune key; look the symbols up).  Same format, same quantiser (zn_op_fp8_quantize_rows).
+ * Attaches the FP8 stream of in_proj [d_in_proj][d_model] and out_proj [d_model][d_inner] of Mamba2 layer `layer`; all four pointers NULL detaches it.
+ * CONTRACT, as for zn_set_mlp_fp8: the layer's bf16 m_in_proj and m_out_proj (zn_layer_weights) hold exactly the dequantised stream.  Decode launches of
+ * 5..64 rows per weight pass (zn_op_mamba_step, decode steps, serving sessions, captured graphs) then read the codes and compute the same bits; rows <= 4 (the
+ * GEMV with the gated-norm prologue) and the prefill keep reading the bf16 copy.  ZN_FP8_VERIFY=1 in the environment of this call: both matrices are compared on
+ * the device, a mismatch is ZN_ERR_ARG and attaches nothing.  The caller keeps the memory alive while it is attached.  Drops the captured graphs.
+ * ZN_ERR_UNSUPPORTED: a transformer handle, an attention layer of a hybrid handle, widths the FP8 kernels do not serve (d_model != 2048 or d_inner != 4096).
+ * ZN_ERR_STATE: between zn_gen_begin and zn_gen_end.  ZN_ERR_ARG: a layer out of range, or some but not all pointers NULL. */
+int zn_set_mamba_fp8(zn_handle h, int32_t layer, const void* in_q, const void* in_exp, const void* out_q, const void* out_exp);
+/* out[0], out[1]: whether in_proj and out_proj of a decode step over `rows` rows would read FP8 in EVERY Mamba2 layer of this handle now (the tune keys; a
+ * handle with streams attached to some Mamba2 layers only, or with no Mamba2 layer, reports 0, 0). */
+int zn_mamba_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
 /* ---------------------------------------------------------------- decode steps of 17..64 rows (additive to ABI 9, like the FP8 calls above: look the symbol up)
  * out[0..4]: activation rows per weight pass of in_proj, out_proj, fc1, fc2 and the heads in a decode step of `rows` rows as this handle would
  * run it now (4 up to 4 rows, 16 up to 16 rows and under zn_debug_tune(ZN_TUNE_WIDE_ROWS, 1), 64 where the wide plan applies): a step of R rows

@@ -34,7 +34,8 @@ ZN_TUNE_ATTN_SPLIT_COLS = 19
 ZN_TUNE_MLP_FP8 = 20
 ZN_TUNE_WIDE_ROWS = 21
 ZN_TUNE_WIDE_HYBRID = 22
-ZN_TUNE_NKEYS = 23
+ZN_TUNE_MAMBA_FP8 = 23
+ZN_TUNE_NKEYS = 24
 # values of ZN_TUNE_HOOK (enum zn_tune_hook)
 ZN_HOOK_TAG_WRAP, ZN_HOOK_TIMEOUT_WORD, ZN_HOOK_PAUSE, ZN_HOOK_RESET_WAIT_STATS = 7, 9, 11, 13
 
@@ -161,6 +162,8 @@ SIGNATURES = {
     "zn_op_fp8_dequant_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "zn_set_mlp_fp8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zn_mlp_fp8_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zn_set_mamba_fp8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zn_mamba_fp8_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zn_decode_rows_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zn_hybrid_rows_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zn_op_linear_bias": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p]),

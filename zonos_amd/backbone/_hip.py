@@ -219,6 +219,21 @@ class HipEngine:
             self._keep += ts
             with torch.cuda.device(dev):
                 _lib.check(self.lib.zn_set_mlp_fp8(self.h, i, *[t.data_ptr() for t in ts]), self.h, "zn_set_mlp_fp8")
+        # ... and of the Mamba2 projections (Zonos.quantize_mamba_fp8: buffers of the mixer)
+        for i, blk in enumerate(backbone.layers):
+            mx = blk.mixer if getattr(blk, "is_mamba", False) else None
+            if mx is None or getattr(mx, "in_proj_q", None) is None:
+                continue
+            ts = [mx.in_proj_q, mx.in_proj_exp, mx.out_proj_q, mx.out_proj_exp]
+            self._keep += ts
+            with torch.cuda.device(dev):
+                _lib.check(self.lib.zn_set_mamba_fp8(self.h, i, *[t.data_ptr() for t in ts]), self.h, "zn_set_mamba_fp8")
+
+    def mamba_fp8_plan(self, rows: int) -> list:
+        """zn_mamba_fp8_plan: whether in_proj and out_proj of every Mamba2 layer would read the FP8 stream in a decode step over `rows` rows now."""
+        out = (C.c_int32 * 2)()
+        self.call("zn_mamba_fp8_plan", rows, out)
+        return [int(out[0]), int(out[1])]
 
     def mlp_fp8_plan(self, rows: int) -> list:
         """zn_mlp_fp8_plan: whether fc1 and fc2 of a decode step over `rows` rows would read the FP8 stream now."""

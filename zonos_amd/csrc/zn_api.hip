@@ -3,6 +3,7 @@
 #include "../../include/zonos_hip.h"
 #include "zn_decode_kernels.h"
 #include "zn_wide_kernels.h"
+#include "zn_mamba_fp8_kernels.h"
 #include "zn_chain_kernel.h"
 #include "zn_step_kernel.h"
 #include "zn_prefill_kernels.h"
@@ -40,6 +41,9 @@ struct zn_handle_s {
   // hold the dequantised values, and every kernel but gemm16s_kernel<., NWV | ZN_G16S_W8> reads those
   struct MlpFp8 { const uint8_t *fc1_q = nullptr, *fc2_q = nullptr; const int8_t *fc1_exp = nullptr, *fc2_exp = nullptr; };
   std::vector<MlpFp8> mlp_fp8;
+  // the same for a Mamba2 layer's in_proj / out_proj (zn_set_mamba_fp8); read by gemm16k8_kernel / gemm16k8_rows_kernel only
+  struct MambaFp8 { const uint8_t *in_q = nullptr, *out_q = nullptr; const int8_t *in_exp = nullptr, *out_exp = nullptr; };
+  std::vector<MambaFp8> mamba_fp8;
   const void* heads = nullptr;
   const void *norm_f_w = nullptr, *norm_f_b = nullptr;
   const float* rope = nullptr;
@@ -299,6 +303,7 @@ extern "C" int zn_create(const zn_config* cfg, const zn_weights* w, int32_t max_
   if (const char* e = getenv("ZN_PREFILL_MODE")) h->prefill_mode = atoi(e);
   h->layers.assign(w->layers, w->layers + c.n_layer);
   h->mlp_fp8.assign(c.n_layer, zn_handle_s::MlpFp8{});
+  h->mamba_fp8.assign(c.n_layer, zn_handle_s::MambaFp8{});
   h->heads = w->heads; h->norm_f_w = w->norm_f_w; h->norm_f_b = w->norm_f_b; h->rope = w->rope_table;
 #define ZC(call) do { hipError_t _e = ZN_NOT_IN_CAPTURE(call); if (_e != hipSuccess) { g_create_err = std::string(#call) + ": " + hipGetErrorString(_e); zn_destroy(h); return ZN_ERR_HIP; } } while (0)
   ZC(hipMalloc(&h->emb_tables_dev, sizeof(void*) * c.n_codebooks));
@@ -518,6 +523,14 @@ static int launch_linear(zn_handle h, const LinearPlan& p, GemvArgs a, int rows,
       case LinearPlan::GEMM16K:   // decode: one 16-row group per launch (the wide plan: up to four); prefill: ceil(rows / 16) of them
         if constexpr (lin_has_gemm16k(PRO, EPI)) {
           const dim3 grid((a.N + 15) / 16, (nr + 15) / 16), block(ZN_G16K_NKW * 64);
+          // the same launches reading the FP8 stream (p.w8: the Mamba2 in_proj at nch 2, out_proj at nch 4; lin_has_w8k)
+          if constexpr (lin_has_w8k(PRO, EPI, EPI == EPI_MAMBA ? 2 : 4)) if (p.w8) {
+            if constexpr (EPI == EPI_MAMBA) {
+              if (p.row_loop && nr > 16) hipLaunchKernelGGL((gemm16k8_rows_kernel<2>), dim3(grid.x), block, 0, s, g);
+              else hipLaunchKernelGGL((gemm16k8_kernel<EPI_MAMBA, 2>), grid, block, 0, s, g);
+            } else hipLaunchKernelGGL((gemm16k8_kernel<EPI_STORE, 4>), grid, block, 0, s, g);
+            break;
+          }
           if constexpr (lin_has_gemm16k_rows(PRO, EPI, 2)) if (p.row_loop && nr > 16) {    // the row-tile loop: one workgroup per weight tile walks the row tiles
             hipLaunchKernelGGL((gemm16k_rows_kernel<2>), dim3(grid.x), block, 0, s, g);
             break;
@@ -990,13 +1003,31 @@ static void launch_add_ln(zn_handle h, const bf16_t* hid, bf16_t* res, int has_r
 }
 
 // The Mamba2 in_proj with the conv window update + SiLU of its xBC rows in the epilogue (causal_conv1d_update; one launch less): n [rows][d] -> m_zx, m_xbc
-static int mamba_in_proj(zn_handle h, const zn_layer_weights& lw, const bf16_t* n, void* conv_state, int rows, hipStream_t s) {
+static bool mamba_fp8_offered(zn_handle h, int li) { return li >= 0 && h->mamba_fp8[li].in_q != nullptr && h->tune[ZN_TUNE_MAMBA_FP8] != 2; }
+// linear_env of a generation step with layer li's FP8 streams offered (LinearEnv::w8k_offered): the ONE env mamba_mixer and zn_mamba_fp8_plan plan from
+static LinearEnv mamba_env(zn_handle h, bool w8k) {
+  LinearEnv e = linear_env(h);
+  e.w8k_offered = w8k;
+  return e;
+}
+static int mamba_in_proj(zn_handle h, int li, const bf16_t* n, void* conv_state, int rows, hipStream_t s) {
   const zn_config& c = h->cfg;
+  const zn_layer_weights& lw = h->layers[li];
   GemvArgs a{};
   a.W = (const bf16_t*)lw.m_in_proj; a.N = h->m_d_in_proj; a.K = c.d_model; a.x = n; a.out = h->m_zx;
   a.conv_state = (bf16_t*)conv_state; a.conv_w = (const bf16_t*)lw.m_conv_w; a.conv_b = (const bf16_t*)lw.m_conv_b; a.xbc = h->m_xbc;
   a.d_inner = c.m_d_inner; a.conv_dim = h->m_conv_dim;
-  return run_gemv<PRO_NONE, EPI_MAMBA>(h, a, rows, (h->m_d_in_proj / 2 + 3) / 4, s);
+  a.W8q = h->mamba_fp8[li].in_q; a.W8exp = h->mamba_fp8[li].in_exp;
+  return launch_linear<PRO_NONE, EPI_MAMBA>(h, plan_linear(mamba_env(h, mamba_fp8_offered(h, li)), PRO_NONE, EPI_MAMBA, rows, a.N, a.K, (h->m_d_in_proj / 2 + 3) / 4, false, false, false), a, rows, s);
+}
+
+// The Mamba2 out_proj without a prologue (more than 4 rows, or several norm groups: g [rows][d_inner] is the gated norm's output) -> out [rows][d]
+static int mamba_out_proj(zn_handle h, int li, const bf16_t* g, bf16_t* out, int rows, hipStream_t s) {
+  const zn_config& c = h->cfg;
+  GemvArgs o{};
+  o.W = (const bf16_t*)h->layers[li].m_out_proj; o.N = c.d_model; o.K = c.m_d_inner; o.out = out; o.x = g;
+  o.W8q = h->mamba_fp8[li].out_q; o.W8exp = h->mamba_fp8[li].out_exp;
+  return launch_linear<PRO_NONE, EPI_STORE>(h, plan_linear(mamba_env(h, mamba_fp8_offered(h, li)), PRO_NONE, EPI_STORE, rows, o.N, o.K, h->tune[ZN_TUNE_WG_FC2], false, false, false), o, rows, s);
 }
 
 // One token through the Mamba2 mixer of layer li (mamba_ssm Mamba2.step): n [rows][d] normalised -> out [rows][d]
@@ -1004,7 +1035,7 @@ static int mamba_mixer(zn_handle h, int li, const bf16_t* n, void* state, bf16_t
   const zn_config& c = h->cfg;
   const zn_layer_weights& lw = h->layers[li];
   int rc;
-  if ((rc = mamba_in_proj(h, lw, n, state, rows, s))) return rc;
+  if ((rc = mamba_in_proj(h, li, n, state, rows, s))) return rc;
   size_t conv_bytes = 0;   // the state buffer is laid out for exactly `rows` rows (zn_mamba_state_bytes_per_layer)
   (void)zn_mamba_state_bytes_per_layer(&c, rows, &conv_bytes);
   MambaArgs m{};
@@ -1023,15 +1054,14 @@ static int mamba_mixer(zn_handle h, int li, const bf16_t* n, void* state, bf16_t
   m.vg = gated_pro ? h->m_vg : nullptr;
   if (c.m_d_state == 128) hipLaunchKernelGGL((mamba_ssm_kernel<128, 2>), dim3(h->m_nheads, (rows + 1) / 2), dim3(256), 0, s, m);
   else hipLaunchKernelGGL((mamba_ssm_kernel<64, 2>), dim3(h->m_nheads, (rows + 1) / 2), dim3(256), 0, s, m);
-  GemvArgs o{};
-  o.W = (const bf16_t*)lw.m_out_proj; o.N = c.d_model; o.K = c.m_d_inner; o.out = out;
   if (gated_pro) {
+    GemvArgs o{};
+    o.W = (const bf16_t*)lw.m_out_proj; o.N = c.d_model; o.K = c.m_d_inner; o.out = out;
     o.gv = h->m_vg; o.ln_w = (const bf16_t*)lw.m_norm_w; o.eps = c.norm_eps;
     return run_gemv<PRO_GATED, EPI_STORE>(h, o, rows, h->tune[ZN_TUNE_WG_FC2], s);
   }
   hipLaunchKernelGGL(mamba_gated_norm_kernel, dim3(c.m_ngroups, rows), dim3(256), 0, s, m);
-  o.x = h->m_g;
-  return run_gemv<PRO_NONE, EPI_STORE>(h, o, rows, h->tune[ZN_TUNE_WG_FC2], s);
+  return mamba_out_proj(h, li, h->m_g, out, rows, s);
 }
 
 // One token through hybrid layer li (mamba_ssm Block, fused_add_norm): hidden h->x / residual h->res in, same out.
@@ -2000,7 +2030,7 @@ extern "C" int zn_debug_eos_bias(zn_handle h, float bias) { if (!h) return ZN_ER
 extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t iters, float* ms_per_launch, double* bytes_per_launch,
                                zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
-  if (!ms_per_launch || !bytes_per_launch || iters < 1 || (rows & 0xff) < 1 || (rows & 0xff) > h->max_rows || which < 0 || which > 7)
+  if (!ms_per_launch || !bytes_per_launch || iters < 1 || (rows & 0xff) < 1 || (rows & 0xff) > h->max_rows || which < 0 || which > 8)
     ZN_FAIL(h, ZN_ERR_ARG, "zn_bench_kernel: bad argument");
   h->gen_stream = (hipStream_t)stream;
   const bool same_layer = (rows & 0x100) != 0;   // measurement variant: keep hitting layer 0 (weights stay in the Infinity Cache)
@@ -2050,11 +2080,16 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   // which == 7: the Mamba2 in_proj (conv-window epilogue included) on a scratch window, cycling through the Mamba2 layers
   std::vector<int> mamba_layers;
   bf16_t* tconv = nullptr;
-  if (which == 7) {
+  if (which == 8 && rows <= 4) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the Mamba2 out_proj is measured from 5 rows on (up to 4 rows it carries the gated norm as its prologue)");
+  if (which == 7 || which == 8) {
     for (int li = 0; li < c.n_layer; ++li) if (c.arch == 1 && h->layers[li].kind == 1) mamba_layers.push_back(li);
     if (mamba_layers.empty()) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the handle has no Mamba2 layer");
-    HIPCHK(h, hipMalloc(&tconv, (size_t)rows * h->m_conv_dim * 4 * 2));
-    HIPCHK(h, hipMemsetAsync(tconv, 0, (size_t)rows * h->m_conv_dim * 4 * 2, s));
+    if (which == 8) {
+      HIPCHK(h, hipMemsetAsync(h->m_g, 0, (size_t)rows * c.m_d_inner * 2, s));
+    } else {
+      HIPCHK(h, hipMalloc(&tconv, (size_t)rows * h->m_conv_dim * 4 * 2));
+      HIPCHK(h, hipMemsetAsync(tconv, 0, (size_t)rows * h->m_conv_dim * 4 * 2, s));
+    }
   }
   hipEvent_t e0, e1;
   HIPCHK(h, hipEventCreate(&e0));
@@ -2076,7 +2111,8 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
       else if (which == 1) rc = run_gemv<PRO_NONE, EPI_RESID>(h, fc2_args(h, lw, h->x), rows, h->tune[ZN_TUNE_WG_FC2], s);
       else if (which == 2) rc = run_gemv<PRO_NONE, EPI_RESID>(h, out_proj_args(h, lw, h->o1, h->x, h->x), rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s);
       else if (which == 6) rc = launch_stack(h, s, rows, stack_nbk);
-      else if (which == 7) rc = mamba_in_proj(h, h->layers[mamba_layers[same_layer ? 0 : i % mamba_layers.size()]], h->x, tconv, rows, s);
+      else if (which == 7) rc = mamba_in_proj(h, mamba_layers[same_layer ? 0 : i % mamba_layers.size()], h->x, tconv, rows, s);
+      else if (which == 8) rc = mamba_out_proj(h, mamba_layers[same_layer ? 0 : i % mamba_layers.size()], h->m_g, h->x, rows, s);
       else if (which == 5) {
         if (i % c.n_layer == c.n_layer - 1) continue;       // the last block's launch has no in_proj: not the launch being priced
         rc = launch_chain(h, i % c.n_layer, std::vector<const void*>(c.n_layer, tkv), 8, tlen, s);
@@ -2108,7 +2144,7 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   // chain launch: out_proj (read once, applied twice), fc1, fc2 of the block and in_proj of the next one
   const double wbytes = which == 5 ? ((double)d * nq + 3.0 * c.d_ff * d + (double)(nq + 2 * nkv) * d) * 2 : which == 0 ? 2.0 * c.d_ff * d * 2 : which == 1 ? (double)d * c.d_ff * 2 : which == 2 ? (double)d * c.n_heads * h->hd * 2
                         : which == 4 ? (double)(nq + 2 * nkv) * d * 2 : (double)c.n_codebooks * c.vocab_head * d * 2;
-  *bytes_per_launch = which == 7 ? (double)h->m_d_in_proj * d * 2 : wbytes;   // algorithmic bytes = the weight matrix, read once (activations are KBs)
+  *bytes_per_launch = which == 7 ? (double)h->m_d_in_proj * d * 2 : which == 8 ? (double)d * c.m_d_inner * 2 : wbytes;   // algorithmic bytes = the weight matrix, read once (activations are KBs)
   if (which == 6) {             // every block's out_proj (once), fc1, fc2, in_proj; the heads; K and V of `ctx` keys read, one row written
     const double per_block = ((double)d * nq + 3.0 * c.d_ff * d) * 2, inp = (double)(nq + 2 * nkv) * d * 2, kvpos = 2.0 * nkv * 2;
     const int nin = stack_pre(h) ? c.n_layer : c.n_layer - 1;      // in_proj of block 0 inside the launch (the pre-block) or before it
@@ -2279,6 +2315,49 @@ extern "C" int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
   for (int li = 0; all && li < h->cfg.n_layer; ++li) all = mlp_fp8_offered(h, li);
   const PostAttnPlans pp = plan_post_attention(h, rows, all);
   out[0] = pp.fc1.w8; out[1] = pp.fc2.w8;
+  return ZN_OK;
+}
+
+extern "C" int zn_set_mamba_fp8(zn_handle h, int32_t layer, const void* in_q, const void* in_exp, const void* out_q, const void* out_exp) {
+  if (!h) return ZN_ERR_ARG;
+  const zn_config& c = h->cfg;
+  if (c.arch != 1) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mamba_fp8: a transformer handle has no Mamba2 layer (zn_set_mlp_fp8 serves its fc1 / fc2)");
+  if (layer < 0 || layer >= c.n_layer) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mamba_fp8: layer %d out of range", layer);
+  if (h->layers[layer].kind != 1) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mamba_fp8: layer %d is an attention layer", layer);
+  if (c.d_model != 2 * ZN_G16K_NKW * ZN_G16K_KCH || c.m_d_inner != 4 * ZN_G16K_NKW * ZN_G16K_KCH)
+    ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mamba_fp8: the FP8 kernels serve d_model 2048 and d_inner 4096 (got d_model %d, d_inner %d)", c.d_model, c.m_d_inner);
+  if (h->gen_active && !h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_set_mamba_fp8 inside a generation (between zn_gen_begin and zn_gen_end)");
+  const int n_set = (in_q != nullptr) + (in_exp != nullptr) + (out_q != nullptr) + (out_exp != nullptr);
+  if (n_set != 0 && n_set != 4) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mamba_fp8: all four pointers, or none");
+  if (n_set == 4) {
+    const char* v = getenv("ZN_FP8_VERIFY");
+    if (v && atoi(v) == 1) {
+      const long long b1 = fp8_mismatches(in_q, in_exp, h->layers[layer].m_in_proj, h->m_d_in_proj, c.d_model);
+      const long long b2 = b1 < 0 ? -1 : fp8_mismatches(out_q, out_exp, h->layers[layer].m_out_proj, c.d_model, c.m_d_inner);
+      if (b1 < 0 || b2 < 0) ZN_FAIL(h, ZN_ERR_HIP, "zn_set_mamba_fp8: the verification could not run");
+      if (b1 || b2) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mamba_fp8: layer %d's bf16 weights are not the dequantised stream (in_proj: %lld, out_proj: %lld pieces of 8 differ)", layer, b1, b2);
+    }
+  }
+  zn_handle_s::MambaFp8& f = h->mamba_fp8[layer];
+  f.in_q = (const uint8_t*)in_q; f.in_exp = (const int8_t*)in_exp; f.out_q = (const uint8_t*)out_q; f.out_exp = (const int8_t*)out_exp;
+  free_graph(h); h->emb_valid = false;
+  return ZN_OK;
+}
+// the two plans mamba_mixer makes for a layer whose streams are offered (the same calls of plan_linear)
+extern "C" int zn_mamba_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
+  if (!h || !out || rows < 1) return ZN_ERR_ARG;
+  const zn_config& c = h->cfg;
+  out[0] = out[1] = 0;
+  if (c.arch != 1) return ZN_OK;
+  int n_mamba = 0;
+  bool all = true;                               // 1 only when every Mamba2 layer has a stream
+  for (int li = 0; li < c.n_layer; ++li)
+    if (h->layers[li].kind == 1) { ++n_mamba; all = all && mamba_fp8_offered(h, li); }
+  if (!n_mamba || !all) return ZN_OK;
+  const LinearEnv e = mamba_env(h, true);
+  const bool gated_pro = c.m_ngroups == 1 && c.m_d_inner % 8 == 0 && rows <= 4 && c.m_d_inner <= 4096;
+  out[0] = plan_linear(e, PRO_NONE, EPI_MAMBA, rows, h->m_d_in_proj, c.d_model, (h->m_d_in_proj / 2 + 3) / 4, false, false, false).w8;
+  out[1] = plan_linear(e, gated_pro ? PRO_GATED : PRO_NONE, EPI_STORE, rows, c.d_model, c.m_d_inner, h->tune[ZN_TUNE_WG_FC2], false, false, false).w8;
   return ZN_OK;
 }
 

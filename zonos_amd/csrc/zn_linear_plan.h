@@ -19,6 +19,7 @@ struct LinearEnv {
   size_t g16_part_bytes = 0;      // split-K partial tiles
   bool has_g16_part = false, has_ln_part = false;
   bool w8_offered = false;        // the caller holds the weights as an FP8 stream as well (zn_fp8_kernels.h) and has not switched it off
+  bool w8k_offered = false;       // the same for a GEMM16K projection (the Mamba2 in_proj / out_proj: zn_mamba_fp8_kernels.h); an offer of its own: w8_offered never marks a GEMM16K plan
   bool wide_rows = false;         // decode steps of more than 16 rows: up to 64 rows per weight pass (plan_linear) instead of groups of 16
   int wide_hybrid = 0;            // under wide_rows, the Mamba2 in_proj (GEMM16K x EPI_MAMBA): 0 / 1 groups of 16, 2 row groups on grid y, 3 the row-tile loop
                                   // (gemm16k_rows_kernel), 4 = the form wide_hybrid_form picks for the row count (ZN_TUNE_WIDE_HYBRID unset)
@@ -42,7 +43,8 @@ struct LinearPlan {
   int nw = 0; bool tile8 = false;                  // GEMM16 (direct fragments): waves per workgroup, 8-row instead of 16-row weight tiles
   int nwv = 0, groups = 0, ksplit = 0; bool lnp = false;   // GEMM16S / GEMM64S: 16-row tiles per workgroup, grid x, grid y; LayerNorm from handed-over statistics
   bool ln_pro = false;        // GEMM16K (nch = 128-wide chunks per wave): LayerNorm as its prologue
-  bool w8 = false;            // GEMM16S, decode: the launch reads the FP8 stream (gemm16s_kernel<., NWV | ZN_G16S_W8>) instead of the bf16 weights
+  bool w8 = false;            // GEMM16S, decode: the launch reads the FP8 stream (gemm16s_kernel<., NWV | ZN_G16S_W8>) instead of the bf16 weights;
+                              // GEMM16K, decode (LinearEnv::w8k_offered): gemm16k8_kernel / gemm16k8_rows_kernel in place of gemm16k_kernel / gemm16k_rows_kernel
   int err = 0;                // shapes nobody serves: a ZN_ERR_* code (-4 = ZN_ERR_UNSUPPORTED) and its message
   char msg[96] = {};
 };
@@ -59,6 +61,8 @@ constexpr bool lin_has_gemm16k_rows(int pro, int epi, int nch) { return pro == P
 // gemm16s_kernel<., NWV | ZN_G16S_W8>: fc1 (SiLU gate; its LayerNorm is a launch in front or comes from handed-over statistics, so the kernel's prologue is none
 // either way) and fc2 (no prologue, residual)
 constexpr bool lin_has_w8(int pro, int epi) { return (epi == EPI_SILU && (pro == PRO_NONE || pro == PRO_LN)) || (epi == EPI_RESID && pro == PRO_NONE); }
+// gemm16k8_kernel<EPI, NCH> / gemm16k8_rows_kernel<2> (zn_mamba_fp8_kernels.h): the Mamba2 in_proj (no prologue, K = 2048) and out_proj (no prologue, store, K = 4096)
+constexpr bool lin_has_w8k(int pro, int epi, int nch) { return pro == PRO_NONE && ((epi == EPI_MAMBA && nch == 2) || (epi == EPI_STORE && nch == 4)); }
 // gemm16w_kernel (zn_wide_kernels.h), decode steps of 17..64 rows: fc1 (SiLU gate; LayerNorm none, from a launch, or from handed-over statistics) and fc2 (residual)
 constexpr bool lin_has_wide16s(int pro, int epi) { return (epi == EPI_SILU && (pro == PRO_NONE || pro == PRO_LN)) || (epi == EPI_RESID && pro == PRO_NONE); }
 constexpr bool lin_has_prefill(int pro, int epi) { return pro == PRO_NONE && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_SILU); }   // GEMM64S, GEMM_TILED
@@ -69,7 +73,8 @@ inline bool linear_plan_launchable(const LinearPlan& p, int pro, int epi) {
     case LinearPlan::GEMM16S: return lin_has_gemm16(pro) && (p.nwv == 2 || p.nwv == 4) && (!p.lnp || lin_has_lnp(pro, epi)) && (!p.w8 || lin_has_w8(pro, epi)) &&
                                      (p.row_tiles == 1 || (p.row_tiles >= 2 && p.row_tiles <= 4 && lin_has_wide16s(pro, epi)));
     case LinearPlan::GEMM16K: return (p.row_tiles >= 1 && p.row_tiles <= 4) && lin_has_gemm16k(pro, epi) && (p.nch == 2 || p.nch == 4) && (!p.ln_pro || lin_has_gemm16k_ln(pro, p.nch)) &&
-                                     (!p.row_loop || (p.row_tiles >= 2 && !p.ln_pro && lin_has_gemm16k_rows(pro, epi, p.nch)));
+                                     (!p.row_loop || (p.row_tiles >= 2 && !p.ln_pro && lin_has_gemm16k_rows(pro, epi, p.nch))) &&
+                                     (!p.w8 || (!p.ln_pro && lin_has_w8k(pro, epi, p.nch)));
     case LinearPlan::GEMM64S: case LinearPlan::GEMM_TILED: return !p.w8 && lin_has_prefill(pro, epi);
   }
   return false;
@@ -237,6 +242,14 @@ inline LinearPlan plan_linear(const LinearEnv& e, int pro, int epi, int rows, in
                               bool have_ln_stats_in) {
   LinearPlan p = plan_linear_bf16(e, pro, epi, rows, N, K, target_blocks, prefill, want_ln_stats_out, have_ln_stats_in);
   p.w8 = e.w8_offered && !prefill && !p.err && p.kernel == LinearPlan::GEMM16S && lin_has_w8(pro, epi);
+  // ... and a decode launch of gemm16k_kernel / gemm16k_rows_kernel for the Mamba2 in_proj or out_proj reads its stream (w8k_offered), at EVERY row count from 5 on:
+  // measured (tools/hybridfp8bench.py, profiles/hybridfp8bench.txt; Zonos-v0.1-hybrid shapes, one quantised model, the stream against the bf16 copy under
+  // ZN_TUNE_MAMBA_FP8 = 2, medians of 20 alternated repetitions, FP8 / bf16) us per in_proj (8512 x 2048) 8 rows 7.57 / 10.67, 16 rows 9.76 / 12.35, 18 rows
+  // 12.43 / 15.25, 32 rows 15.59 / 18.73, 48 rows 21.34 / 24.17, 64 rows 27.13 / 29.91; us per out_proj (2048 x 4096) 5.87 / 6.56, 7.23 / 7.79, 7.31 / 7.92,
+  // 7.25 / 7.75, 11.45 / 12.93, 11.43 / 12.82 (the repetitions spread by <= 0.18 us); ms per decode step of the 46-layer stack 8 rows 1.519 / 1.664, 16 rows
+  // 1.864 / 1.988, 18 rows 2.176 / 2.323, 32 rows 2.522 / 2.691, 48 rows 3.348 / 3.545, 64 rows 3.973 / 4.175 (spread <= 0.08 ms, 0.20 at 64 rows): no band
+  // of row counts in which the stream is slower, so none is declined
+  if (e.w8k_offered && !prefill && !p.err && p.kernel == LinearPlan::GEMM16K && !p.ln_pro && lin_has_w8k(pro, epi, p.nch)) p.w8 = true;
   // LinearEnv::wide_rows, decode, more than 16 rows: the same plan over up to 64 rows per weight pass (plan_wide).  Wide at EVERY row count from 17 on:
   // measured (tools/widebench.py, profiles/widebench.txt; Zonos-v0.1 shapes, medians of 20, ms per decode step, groups of 16 -> wide) 18 rows 2.630 -> 1.771,
   // 32 rows 2.723 -> 1.822, 48 rows 4.178 -> 2.400, 64 rows 5.495 -> 2.585 (FP8 stream: 2.490 -> 1.633 ... 5.186 -> 2.445); the repetitions spread by <= 0.04 ms

@@ -109,6 +109,7 @@ class Zonos(nn.Module):
         self._spare_guard = threading.RLock()
         self._repeats = 0                             # generations repeated on the launches path after a reported hand-off timeout
         self.mlp_weights = "bf16"                     # "fp8" after quantize_mlp_fp8()
+        self.mamba_weights = "bf16"                   # "fp8" after quantize_mamba_fp8()
 
     # ------------------------------------------------------------------ loading
     @property
@@ -126,12 +127,15 @@ class Zonos(nn.Module):
 
     @classmethod
     def from_local(cls, config_path: str, model_path: str, device: str = DEFAULT_DEVICE, backbone: str | None = None,
-                   mlp_weights: str = "bf16") -> "Zonos":
+                   mlp_weights: str = "bf16", mamba_weights: str = "bf16") -> "Zonos":
         """model.py:128-176: bf16 model, embeddings zero-padded to the 1032-row tables, heads.{i} fused.  mlp_weights="fp8":
-        quantize_mlp_fp8() after loading (lossy with respect to the checkpoint; see there); the default changes nothing."""
+        quantize_mlp_fp8() after loading (lossy with respect to the checkpoint; see there); mamba_weights="fp8": quantize_mamba_fp8() (the
+        hybrid checkpoint; likewise); the defaults change nothing."""
         import safetensors
         if mlp_weights not in ("bf16", "fp8"):
             raise _lib.ZonosHipError(f"mlp_weights must be 'bf16' or 'fp8', not {mlp_weights!r}")
+        if mamba_weights not in ("bf16", "fp8"):
+            raise _lib.ZonosHipError(f"mamba_weights must be 'bf16' or 'fp8', not {mamba_weights!r}")
         config = ZonosConfig.from_dict(json.load(open(config_path)))
         backbone_cls = BACKBONES[backbone] if backbone else DEFAULT_BACKBONE_CLS
         model = cls(config, backbone_cls).to(device, torch.bfloat16)
@@ -157,6 +161,8 @@ class Zonos(nn.Module):
         model.load_state_dict(sd, strict=True)
         if mlp_weights == "fp8":
             model.quantize_mlp_fp8()
+        if mamba_weights == "fp8":
+            model.quantize_mamba_fp8()
         return model
 
     @torch.inference_mode()
@@ -187,6 +193,51 @@ class Zonos(nn.Module):
         self.backbone._engine = None
         self.mlp_weights = "fp8"
         return self
+
+    @torch.inference_mode()
+    def quantize_mamba_fp8(self) -> "Zonos":
+        """Weight-only FP8 for in_proj / out_proj of every Mamba2 layer of a hybrid model (zonos_amd/quant.py: E4M3 codes, one power-of-two
+        scale per weight row) - about four fifths of the weight bytes a hybrid decode step reads.  Like quantize_mlp_fp8: quantises on the
+        device, OVERWRITES the bf16 parameters in place with the dequantised values and keeps the codes and exponents as buffers of the
+        mixer (in_proj_q, in_proj_exp, out_proj_q, out_proj_exp; not part of the state dict).  Decode steps of 5 or more rows then stream
+        the codes - half the bytes - and compute exactly what the bf16 kernels compute on the dequantised weights; steps of up to 4 rows
+        and the prefill keep reading the bf16 copy.  Lossy with respect to the checkpoint (|Wdq - w| <= 2^-4 |w|), exact with respect to
+        the model's own weights afterwards; the effect on audio quality is unmeasured.  Cached engines are dropped.
+        Raises ZonosHipError - and changes nothing - on a transformer model, and on a hybrid model of other widths than the FP8 kernels
+        serve (d_model 2048, d_inner 4096: Zonos-v0.1-hybrid): a stream that no decode step would read is refused, not carried along."""
+        bb = self.config.backbone
+        if not bb.ssm_cfg:
+            raise _lib.ZonosHipError("quantize_mamba_fp8: a transformer model has no Mamba2 layers (quantize_mlp_fp8 serves its fc1 / fc2)")
+        if self.device.type != "cuda":
+            raise _lib.ZonosHipError("quantize_mamba_fp8 runs on the device: move the model to a cuda device first")
+        mixers = [blk.mixer for blk in self.backbone.layers if blk.is_mamba]
+        for mx in mixers:
+            d_in, d_model = mx.out_proj.weight.shape[1], mx.in_proj.weight.shape[1]
+            if d_model != 2048 or d_in != 4096:
+                raise _lib.ZonosHipError(f"quantize_mamba_fp8: the FP8 kernels serve d_model 2048 and d_inner 4096 (got d_model {d_model}, d_inner {d_in})")
+        eng = self.engine(1)
+        for mx in mixers:
+            for name in ("in_proj", "out_proj"):
+                W = getattr(mx, name).weight.data
+                N, K = W.shape
+                q = torch.empty((N, K), dtype=torch.uint8, device=W.device)
+                e = torch.empty((N,), dtype=torch.int8, device=W.device)
+                eng.call("zn_op_fp8_quantize_rows", W.data_ptr(), N, K, q.data_ptr(), e.data_ptr(), eng.stream())
+                eng.call("zn_op_fp8_dequant_rows", q.data_ptr(), e.data_ptr(), N, K, W.data_ptr(), eng.stream())
+                mx.register_buffer(name + "_q", q, persistent=False)
+                mx.register_buffer(name + "_exp", e, persistent=False)
+        torch.cuda.synchronize(self.device)
+        self._engine = self._spare = None
+        self.backbone._engine = None
+        self.mamba_weights = "fp8"
+        return self
+
+    def mamba_fp8_plan(self, rows: int) -> dict:
+        """Whether in_proj and out_proj of the Mamba2 layers would read the FP8 stream in a decode step of `rows` rows (two per guided
+        utterance) as this model's engine runs it now: {"in_proj": bool, "out_proj": bool}; both False before quantize_mamba_fp8(), up to
+        4 rows, and under zn_debug_tune(ZN_TUNE_MAMBA_FP8, 2) on the engine."""
+        a, b = self.engine((int(rows) + 1) // 2).mamba_fp8_plan(int(rows))
+        return {"in_proj": bool(a), "out_proj": bool(b)}
 
     def _load_from_state_dict(self, state_dict, prefix, *args):
         """model.py:208-223: per-codebook heads.{i}.weight [1025,d] -> fused_heads.weight [9*1025,d]."""
