@@ -353,7 +353,12 @@ enum zn_tune_key {
                                        row-tile loop (gemm16k_rows_kernel: the weight tile requested once per up to 64 rows); default: the form the plan picks for the
                                        row count (wide_hybrid_form, zn_linear_plan.h).  Same bits in every form */
   ZN_TUNE_MAMBA_FP8 = 23,           /* 2 = ignore the FP8 streams attached by zn_set_mamba_fp8: every launch reads the bf16 in_proj / out_proj of the Mamba2 layers */
-  ZN_TUNE_NKEYS = 24
+  ZN_TUNE_FP8_SMALL_ROWS = 24,      /* decode launches of 1..4 rows (the GEMV) of a projection with an FP8 stream attached (zn_set_mlp_fp8: fc1 / fc2; zn_set_mamba_fp8:
+                                       in_proj / out_proj): 2 = they read the stream (gemv8_kernel, the next unit requested ahead), 3 = the same with a ring of two units
+                                       requested ahead (measurement only: never faster, profiles/smallrowsbench.txt); unset or 1 = they read the bf16 copy.  ZN_TUNE_MLP_FP8 / ZN_TUNE_MAMBA_FP8 = 2 switch the stream off
+                                       here too.  Same bits either way; the persistent kernels always read the bf16 copy, and the key never changes the path a
+                                       generation takes */
+  ZN_TUNE_NKEYS = 25
 };
 /* Values of ZN_TUNE_HOOK.  The first three arm the next zn_gen_begin, which consumes them. */
 enum zn_tune_hook {
@@ -397,9 +402,11 @@ int zn_op_backbone_forward(zn_handle h, const void* hidden_dev, void* out_dev, c
  * ONE launch, one or two rows) on scratch KV caches of its own holding `ctx` keys per row; bytes = every weight the step reads once
  * (in_proj of block 0 included: the launch's pre-block; excluded under zn_debug_tune(ZN_TUNE_STACK_PRE, 2), where it is a launch of its own) + K/V of
  * ctx keys read and one row written per layer, 7 = the Mamba2 in_proj with its conv-window epilogue (hybrid handles; a scratch window; cycles through
- * the Mamba2 layers; every launch of the plan's launch set counts as one: ms_per_launch prices the projection over all its rows), 8 = the Mamba2 out_proj of 5 rows and more
- * (hybrid handles; no prologue, store; cycles through the Mamba2 layers).  7 and 8 read what a decode step would read: the FP8 stream where zn_set_mamba_fp8 attached one;
- * bytes stay those of the bf16 matrix.
+ * the Mamba2 layers; every launch of the plan's launch set counts as one: ms_per_launch prices the projection over all its rows), 8 = the Mamba2 out_proj
+ * (hybrid handles; store; cycles through the Mamba2 layers; no prologue from 5 rows on or with several norm groups, else - up to 4 rows - the gated norm as its prologue
+ * on zeroed gated values, as a step launches it).  7 and 8 read what a decode step would read: the FP8 stream where zn_set_mamba_fp8 attached one (up to 4 rows: under
+ * ZN_TUNE_FP8_SMALL_ROWS = 2 only); bytes stay those of the bf16 matrix.  0 and 1 at up to 4 rows likewise read the stream of zn_set_mlp_fp8 under that key, when every
+ * block has one; from 5 rows on they price the bf16 launches.
  * rows: bits 0-7 = activation rows; bit 8 = keep streaming layer 0's weights (cache-hot variant); bits 16-30 = ctx for which == 6
  * (0 = 450, the mean context of a 10 s utterance). */
 int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t iters, float* ms_per_launch,
@@ -451,7 +458,7 @@ int zn_op_fp8_quantize_rows(zn_handle h, const void* W_dev, int32_t N, int32_t K
 int zn_op_fp8_dequant_rows(zn_handle h, const void* q_dev, const void* exp_dev, int32_t N, int32_t K, void* W_out_dev, zn_stream stream);
 /* Attaches the FP8 stream of fc1 [2 d_ff][d_model] and fc2 [d_model][d_ff] of transformer block `layer`; all four pointers NULL detaches it.
  * CONTRACT: the layer's bf16 fc1 and fc2 (zn_layer_weights) hold exactly the dequantised stream.  Decode launches of 5..64 rows per weight pass (groups of 16 rows, or
- * up to 64 under the wide plan of 17 rows and more: ZN_TUNE_WIDE_ROWS) then read the codes (half the bytes) and compute the same bits; every other path keeps reading the bf16 copy, so one model computes one function
+ * up to 64 under the wide plan of 17 rows and more: ZN_TUNE_WIDE_ROWS) then read the codes (half the bytes) and compute the same bits, and under ZN_TUNE_FP8_SMALL_ROWS = 2 so do the GEMV launches of 1..4 rows; every other path keeps reading the bf16 copy, so one model computes one function
  * on every path.  The library does not check the contract unless ZN_FP8_VERIFY=1 is in the environment of this call: then both matrices are
  * compared on the device and a mismatch is ZN_ERR_ARG (nothing is attached).  The caller keeps the memory alive while it is attached.  Drops the
  * captured graphs.  ZN_ERR_UNSUPPORTED: a hybrid handle (arch 1), a Mamba2 layer, d_model or d_ff no multiple of 256.  ZN_ERR_STATE: between
@@ -464,20 +471,22 @@ int zn_set_mlp_fp8(zn_handle h, int32_t layer, const void* fc1_q, const void* fc
  * (zn_debug_tune(ZN_TUNE_MLP_FP8, 2) included). */
 int zn_op_linear_fp8(zn_handle h, zn_linear_op* op, const void* W_q, const void* W_exp, zn_stream stream);
 /* out[0], out[1]: whether fc1 and fc2 of a decode step over `rows` rows would read FP8 in EVERY block of this handle now (the tune keys; a
- * handle with streams attached to some blocks only reports 0, 0 although those blocks do read them). */
+ * handle with streams attached to some blocks only reports 0, 0 although those blocks do read them).  rows <= 4 says what the launches path (the GEMV)
+ * reads: 1, 1 only under zn_debug_tune(ZN_TUNE_FP8_SMALL_ROWS, 2); a generation that runs on a persistent kernel reads the bf16 copy whatever this reports. */
 int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
 /* ---------------------------------------------------------------- weight-only FP8 for the Mamba2 projections of a hybrid handle (additive to ABI 9 in the same way:
  * two entry points and one tune key; look the symbols up).  Same format, same quantiser (zn_op_fp8_quantize_rows).
  * Attaches the FP8 stream of in_proj [d_in_proj][d_model] and out_proj [d_model][d_inner] of Mamba2 layer `layer`; all four pointers NULL detaches it.
  * CONTRACT, as for zn_set_mlp_fp8: the layer's bf16 m_in_proj and m_out_proj (zn_layer_weights) hold exactly the dequantised stream.  Decode launches of
  * 5..64 rows per weight pass (zn_op_mamba_step, decode steps, serving sessions, captured graphs) then read the codes and compute the same bits; rows <= 4 (the
- * GEMV with the gated-norm prologue) and the prefill keep reading the bf16 copy.  ZN_FP8_VERIFY=1 in the environment of this call: both matrices are compared on
+ * GEMV with the gated-norm prologue; unless ZN_TUNE_FP8_SMALL_ROWS = 2) and the prefill keep reading the bf16 copy.  ZN_FP8_VERIFY=1 in the environment of this call: both matrices are compared on
  * the device, a mismatch is ZN_ERR_ARG and attaches nothing.  The caller keeps the memory alive while it is attached.  Drops the captured graphs.
  * ZN_ERR_UNSUPPORTED: a transformer handle, an attention layer of a hybrid handle, widths the FP8 kernels do not serve (d_model != 2048 or d_inner != 4096).
  * ZN_ERR_STATE: between zn_gen_begin and zn_gen_end.  ZN_ERR_ARG: a layer out of range, or some but not all pointers NULL. */
 int zn_set_mamba_fp8(zn_handle h, int32_t layer, const void* in_q, const void* in_exp, const void* out_q, const void* out_exp);
 /* out[0], out[1]: whether in_proj and out_proj of a decode step over `rows` rows would read FP8 in EVERY Mamba2 layer of this handle now (the tune keys; a
- * handle with streams attached to some Mamba2 layers only, or with no Mamba2 layer, reports 0, 0). */
+ * handle with streams attached to some Mamba2 layers only, or with no Mamba2 layer, reports 0, 0).  rows <= 4: 1, 1 only under
+ * zn_debug_tune(ZN_TUNE_FP8_SMALL_ROWS, 2), where the GEMV launches read the stream too. */
 int zn_mamba_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
 /* ---------------------------------------------------------------- decode steps of 17..64 rows (additive to ABI 9, like the FP8 calls above: look the symbol up)
  * out[0..4]: activation rows per weight pass of in_proj, out_proj, fc1, fc2 and the heads in a decode step of `rows` rows as this handle would

@@ -35,7 +35,8 @@ ZN_TUNE_MLP_FP8 = 20
 ZN_TUNE_WIDE_ROWS = 21
 ZN_TUNE_WIDE_HYBRID = 22
 ZN_TUNE_MAMBA_FP8 = 23
-ZN_TUNE_NKEYS = 24
+ZN_TUNE_FP8_SMALL_ROWS = 24
+ZN_TUNE_NKEYS = 25
 # values of ZN_TUNE_HOOK (enum zn_tune_hook)
 ZN_HOOK_TAG_WRAP, ZN_HOOK_TIMEOUT_WORD, ZN_HOOK_PAUSE, ZN_HOOK_RESET_WAIT_STATS = 7, 9, 11, 13
 

@@ -230,13 +230,15 @@ class HipEngine:
                 _lib.check(self.lib.zn_set_mamba_fp8(self.h, i, *[t.data_ptr() for t in ts]), self.h, "zn_set_mamba_fp8")
 
     def mamba_fp8_plan(self, rows: int) -> list:
-        """zn_mamba_fp8_plan: whether in_proj and out_proj of every Mamba2 layer would read the FP8 stream in a decode step over `rows` rows now."""
+        """zn_mamba_fp8_plan: whether in_proj and out_proj of every Mamba2 layer would read the FP8 stream in a decode step over `rows` rows now
+        (rows <= 4: only under ZN_TUNE_FP8_SMALL_ROWS = 2)."""
         out = (C.c_int32 * 2)()
         self.call("zn_mamba_fp8_plan", rows, out)
         return [int(out[0]), int(out[1])]
 
     def mlp_fp8_plan(self, rows: int) -> list:
-        """zn_mlp_fp8_plan: whether fc1 and fc2 of a decode step over `rows` rows would read the FP8 stream now."""
+        """zn_mlp_fp8_plan: whether fc1 and fc2 of a decode step over `rows` rows would read the FP8 stream now (rows <= 4: what the launches
+        path reads - the stream only under ZN_TUNE_FP8_SMALL_ROWS = 2; the persistent kernels read the bf16 copy)."""
         out = (C.c_int32 * 2)()
         self.call("zn_mlp_fp8_plan", rows, out)
         return [int(out[0]), int(out[1])]

@@ -4,6 +4,7 @@
 #include "zn_decode_kernels.h"
 #include "zn_wide_kernels.h"
 #include "zn_mamba_fp8_kernels.h"
+#include "zn_gemv_fp8_kernels.h"
 #include "zn_chain_kernel.h"
 #include "zn_step_kernel.h"
 #include "zn_prefill_kernels.h"
@@ -403,6 +404,29 @@ static int launch_gemv_rows(const GemvArgs& a, int rgroup, int ks, int nch, int 
   }
   return -1;
 }
+// the same launch reading the FP8 stream (p.w8 on a GEMV plan; gemv8_kernel): the instantiations of lin_has_w8v - one (KS, NCH) per (PRO, EPI) - each for
+// R = 2 and 4, FULL, and one or two units requested ahead (depth: ZN_TUNE_FP8_SMALL_ROWS = 2 / 3)
+template <int R, int NCH, int KS, int PRO, int EPI>
+static void launch_gemv8_t(const GemvArgs& a, int blocks, bool full, int depth, hipStream_t s) {
+  if (depth == 1) {
+    if (full) hipLaunchKernelGGL((gemv8_kernel<R, NCH, KS, PRO, EPI, true, 1>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gemv8_kernel<R, NCH, KS, PRO, EPI, false, 1>), dim3(blocks), dim3(256), 0, s, a);
+  } else {
+    if (full) hipLaunchKernelGGL((gemv8_kernel<R, NCH, KS, PRO, EPI, true, 2>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gemv8_kernel<R, NCH, KS, PRO, EPI, false, 2>), dim3(blocks), dim3(256), 0, s, a);
+  }
+}
+template <int PRO, int EPI>
+static int launch_gemv8_rows(const GemvArgs& a, int rgroup, int ks, int nch, int blocks, bool full, int depth, hipStream_t s) {
+  constexpr int KS = (EPI == EPI_SILU || EPI == EPI_MAMBA) ? 1 : 4, NCH = EPI == EPI_STORE ? 2 : 4;
+  if constexpr (lin_has_w8v(PRO, EPI, KS, NCH)) {
+    if (ks != KS || nch != NCH) return -1;
+    if (rgroup <= 2) launch_gemv8_t<2, NCH, KS, PRO, EPI>(a, blocks, full && rgroup == 2, depth, s);
+    else launch_gemv8_t<4, NCH, KS, PRO, EPI>(a, blocks, full && rgroup == 4, depth, s);
+    return 0;
+  }
+  return -1;
+}
 
 static void launch_gemm(const bf16_t* A, int lda, const bf16_t* W, bf16_t* out, int ldo, const bf16_t* resid, int M, int N, int K, hipStream_t s,
                         const bf16_t* bias = nullptr) {
@@ -455,6 +479,8 @@ static LinearEnv linear_env(zn_handle h, bool step = true) {
   e.g16_part_bytes = h->g16_part_bytes; e.has_g16_part = h->g16_part != nullptr; e.has_ln_part = h->ln_part != nullptr;
   return e;
 }
+// ZN_TUNE_FP8_SMALL_ROWS: the GEMV launches (1..4 rows) of a projection whose FP8 stream is offered read it (LinearEnv::w8v_offered); 3 = with a ring of two units ahead
+static bool fp8_small_rows(zn_handle h) { return h->tune[ZN_TUNE_FP8_SMALL_ROWS] == 2 || h->tune[ZN_TUNE_FP8_SMALL_ROWS] == 3; }
 // g serves the row group [r0, r0 + nr) of the rows it described: every per-row pointer moves there.
 static void advance_rows(GemvArgs& g, int r0, int nr, int out_cols) {
   g.nrows = nr;
@@ -492,6 +518,10 @@ static int launch_linear(zn_handle h, const LinearPlan& p, GemvArgs a, int rows,
     }
     switch (p.kernel) {
       case LinearPlan::GEMV:
+        if (p.w8) {      // (launchable: lin_has_w8v holds this (PRO, EPI, ks, nch))
+          (void)launch_gemv8_rows<PRO, EPI>(g, nr, p.ks, p.nch, p.blocks, p.full, h->tune[ZN_TUNE_FP8_SMALL_ROWS] == 3 ? 2 : 1, s);
+          break;
+        }
         (void)launch_gemv_rows<PRO, EPI>(g, nr, p.ks, p.nch, p.blocks, p.full, s);      // (its instantiations: linear_plan_launchable)
         break;
       case LinearPlan::GEMM16:
@@ -689,6 +719,7 @@ static PostAttnPlans plan_post_attention(zn_handle h, int rows, bool mlp_w8 = fa
   const LinearEnv e = linear_env(h);
   LinearEnv em = e;
   em.w8_offered = mlp_w8;
+  em.w8v_offered = mlp_w8 && fp8_small_rows(h);
   PostAttnPlans pp;
   pp.out = plan_linear(e, PRO_NONE, EPI_RESID, rows, c.d_model, c.n_heads * h->hd, h->tune[ZN_TUNE_WG_OUT_PROJ], false, true, false);
   pp.fc1 = plan_linear(em, PRO_LN, EPI_SILU, rows, 2 * c.d_ff, c.d_model, h->tune[ZN_TUNE_WG_FC1], false, false, pp.out.writes_ln_stats);
@@ -1008,6 +1039,7 @@ static bool mamba_fp8_offered(zn_handle h, int li) { return li >= 0 && h->mamba_
 static LinearEnv mamba_env(zn_handle h, bool w8k) {
   LinearEnv e = linear_env(h);
   e.w8k_offered = w8k;
+  e.w8v_offered = w8k && fp8_small_rows(h);      // the GEMV launches of 1..4 rows: an offer of its own
   return e;
 }
 static int mamba_in_proj(zn_handle h, int li, const bf16_t* n, void* conv_state, int rows, hipStream_t s) {
@@ -1030,6 +1062,19 @@ static int mamba_out_proj(zn_handle h, int li, const bf16_t* g, bf16_t* out, int
   return launch_linear<PRO_NONE, EPI_STORE>(h, plan_linear(mamba_env(h, mamba_fp8_offered(h, li)), PRO_NONE, EPI_STORE, rows, o.N, o.K, h->tune[ZN_TUNE_WG_FC2], false, false, false), o, rows, s);
 }
 
+// The Mamba2 out_proj of up to 4 rows with RMSNormGated (one group) as its prologue: m_vg [rows][d_inner] fp32 gated values -> out [rows][d].  Planned from
+// mamba_env like the other two projections of the mixer: with the default env this is the plan of a plain GEMV, under ZN_TUNE_FP8_SMALL_ROWS it reads the stream.
+static int mamba_out_proj_gated(zn_handle h, int li, bf16_t* out, int rows, hipStream_t s) {
+  const zn_config& c = h->cfg;
+  const zn_layer_weights& lw = h->layers[li];
+  GemvArgs o{};
+  o.W = (const bf16_t*)lw.m_out_proj; o.N = c.d_model; o.K = c.m_d_inner; o.out = out;
+  o.gv = h->m_vg; o.ln_w = (const bf16_t*)lw.m_norm_w; o.eps = c.norm_eps;
+  o.W8q = h->mamba_fp8[li].out_q; o.W8exp = h->mamba_fp8[li].out_exp;
+  return launch_linear<PRO_GATED, EPI_STORE>(h, plan_linear(mamba_env(h, mamba_fp8_offered(h, li)), PRO_GATED, EPI_STORE, rows, o.N, o.K, h->tune[ZN_TUNE_WG_FC2], false, false, false), o, rows, s);
+}
+static bool mamba_gated_pro(const zn_config& c, int rows) { return c.m_ngroups == 1 && c.m_d_inner % 8 == 0 && rows <= 4 && c.m_d_inner <= 4096; }
+
 // One token through the Mamba2 mixer of layer li (mamba_ssm Mamba2.step): n [rows][d] normalised -> out [rows][d]
 static int mamba_mixer(zn_handle h, int li, const bf16_t* n, void* state, bf16_t* out, int rows, hipStream_t s) {
   const zn_config& c = h->cfg;
@@ -1050,16 +1095,11 @@ static int mamba_mixer(zn_handle h, int li, const bf16_t* n, void* state, bf16_t
   // in fp32 and the row statistic + weight run as the prologue of out_proj (one launch less; batch-1 step 1.28 -> 1.17 ms);
   // more rows, or several norm groups: a launch of its own (at 16 rows the prologue's fp32 fragment loads in each of the
   // 128 workgroups cost more than the launch: 1.92 -> 2.14 ms, measured)
-  const bool gated_pro = c.m_ngroups == 1 && c.m_d_inner % 8 == 0 && rows <= 4 && c.m_d_inner <= 4096;
+  const bool gated_pro = mamba_gated_pro(c, rows);
   m.vg = gated_pro ? h->m_vg : nullptr;
   if (c.m_d_state == 128) hipLaunchKernelGGL((mamba_ssm_kernel<128, 2>), dim3(h->m_nheads, (rows + 1) / 2), dim3(256), 0, s, m);
   else hipLaunchKernelGGL((mamba_ssm_kernel<64, 2>), dim3(h->m_nheads, (rows + 1) / 2), dim3(256), 0, s, m);
-  if (gated_pro) {
-    GemvArgs o{};
-    o.W = (const bf16_t*)lw.m_out_proj; o.N = c.d_model; o.K = c.m_d_inner; o.out = out;
-    o.gv = h->m_vg; o.ln_w = (const bf16_t*)lw.m_norm_w; o.eps = c.norm_eps;
-    return run_gemv<PRO_GATED, EPI_STORE>(h, o, rows, h->tune[ZN_TUNE_WG_FC2], s);
-  }
+  if (gated_pro) return mamba_out_proj_gated(h, li, out, rows, s);
   hipLaunchKernelGGL(mamba_gated_norm_kernel, dim3(c.m_ngroups, rows), dim3(256), 0, s, m);
   return mamba_out_proj(h, li, h->m_g, out, rows, s);
 }
@@ -2080,12 +2120,14 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   // which == 7: the Mamba2 in_proj (conv-window epilogue included) on a scratch window, cycling through the Mamba2 layers
   std::vector<int> mamba_layers;
   bf16_t* tconv = nullptr;
-  if (which == 8 && rows <= 4) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the Mamba2 out_proj is measured from 5 rows on (up to 4 rows it carries the gated norm as its prologue)");
+  // which == 8: the Mamba2 out_proj; up to 4 rows with one norm group it carries the gated norm as its prologue, as in a step (on zeroed gated values)
+  const bool out_gated = which == 8 && c.arch == 1 && mamba_gated_pro(c, rows);
   if (which == 7 || which == 8) {
     for (int li = 0; li < c.n_layer; ++li) if (c.arch == 1 && h->layers[li].kind == 1) mamba_layers.push_back(li);
     if (mamba_layers.empty()) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the handle has no Mamba2 layer");
     if (which == 8) {
       HIPCHK(h, hipMemsetAsync(h->m_g, 0, (size_t)rows * c.m_d_inner * 2, s));
+      if (out_gated) HIPCHK(h, hipMemsetAsync(h->m_vg, 0, (size_t)rows * c.m_d_inner * sizeof(float), s));
     } else {
       HIPCHK(h, hipMalloc(&tconv, (size_t)rows * h->m_conv_dim * 4 * 2));
       HIPCHK(h, hipMemsetAsync(tconv, 0, (size_t)rows * h->m_conv_dim * 4 * 2, s));
@@ -2097,7 +2139,11 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   int rc = ZN_OK;
   // which == 0 at 5..16 rows: the launch a decode step makes there - fc1 normalising from the statistics its producer left (plan_post_attention);
   // the producer runs once, outside the timed loop, on the zeroed rows
-  const PostAttnPlans pp = plan_post_attention(h, rows);
+  // up to 4 rows: fc1 / fc2 as layer_post_attention plans them for a block whose FP8 stream is offered (the GEMV reads it under ZN_TUNE_FP8_SMALL_ROWS = 2);
+  // without a stream on every block, and from 5 rows on, the plans of the bf16 weights as before
+  bool mlp_w8 = rows <= 4 && c.arch == 0;
+  for (int li = 0; mlp_w8 && li < c.n_layer; ++li) mlp_w8 = mlp_fp8_offered(h, li);
+  const PostAttnPlans pp = plan_post_attention(h, rows, mlp_w8);
   if (which == 0 && pp.out.writes_ln_stats) {
     GemvArgs b = out_proj_args(h, h->layers[0], h->o1, h->x, h->x);
     b.ln_part_out = h->ln_part;
@@ -2107,11 +2153,20 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
     if (pass == 1) HIPCHK(h, hipEventRecord(e0, s));
     for (int i = 0; i < (pass ? iters : (iters < 8 ? iters : 8)) && rc == ZN_OK; ++i) {
       const zn_layer_weights& lw = h->layers[same_layer ? 0 : i % c.n_layer];
-      if (which == 0) rc = launch_linear<PRO_LN, EPI_SILU>(h, pp.fc1, fc1_args(h, lw, h->x, pp.out.writes_ln_stats ? h->ln_part : nullptr), rows, s);
-      else if (which == 1) rc = run_gemv<PRO_NONE, EPI_RESID>(h, fc2_args(h, lw, h->x), rows, h->tune[ZN_TUNE_WG_FC2], s);
+      const zn_handle_s::MlpFp8& f8 = h->mlp_fp8[same_layer ? 0 : i % c.n_layer];
+      if (which == 0) {
+        GemvArgs f1 = fc1_args(h, lw, h->x, pp.out.writes_ln_stats ? h->ln_part : nullptr);
+        f1.W8q = f8.fc1_q; f1.W8exp = f8.fc1_exp;
+        rc = launch_linear<PRO_LN, EPI_SILU>(h, pp.fc1, f1, rows, s);
+      } else if (which == 1 && pp.fc2.w8) {      // (the plan of run_gemv below in every other field)
+        GemvArgs f2 = fc2_args(h, lw, h->x);
+        f2.W8q = f8.fc2_q; f2.W8exp = f8.fc2_exp;
+        rc = launch_linear<PRO_NONE, EPI_RESID>(h, pp.fc2, f2, rows, s);
+      } else if (which == 1) rc = run_gemv<PRO_NONE, EPI_RESID>(h, fc2_args(h, lw, h->x), rows, h->tune[ZN_TUNE_WG_FC2], s);
       else if (which == 2) rc = run_gemv<PRO_NONE, EPI_RESID>(h, out_proj_args(h, lw, h->o1, h->x, h->x), rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s);
       else if (which == 6) rc = launch_stack(h, s, rows, stack_nbk);
       else if (which == 7) rc = mamba_in_proj(h, mamba_layers[same_layer ? 0 : i % mamba_layers.size()], h->x, tconv, rows, s);
+      else if (which == 8 && out_gated) rc = mamba_out_proj_gated(h, mamba_layers[same_layer ? 0 : i % mamba_layers.size()], h->x, rows, s);
       else if (which == 8) rc = mamba_out_proj(h, mamba_layers[same_layer ? 0 : i % mamba_layers.size()], h->m_g, h->x, rows, s);
       else if (which == 5) {
         if (i % c.n_layer == c.n_layer - 1) continue;       // the last block's launch has no in_proj: not the launch being priced
@@ -2200,6 +2255,7 @@ static int linear_fused_impl(zn_handle h, zn_linear_op* op, const void* W_q, con
     if (prefill) ZN_F8_REFUSE(ZN_ERR_UNSUPPORTED, "zn_op_linear_fp8: the prefill kernels read bf16 weights");
     if (K % ZN_G16_KC) ZN_F8_REFUSE(ZN_ERR_UNSUPPORTED, "zn_op_linear_fp8: K=%d is no multiple of %d", K, ZN_G16_KC);
     env.w8_offered = h->tune[ZN_TUNE_MLP_FP8] != 2;
+    env.w8v_offered = env.w8_offered && fp8_small_rows(h);
   }
   LinearPlan p = plan_linear(env, pro, epi, rows, N, K, op->target_blocks > 0 ? op->target_blocks : 1, prefill, op->want_ln_stats_out != 0, op->ln_stats_in != 0);
   int* o = op->plan;

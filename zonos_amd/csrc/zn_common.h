@@ -30,6 +30,8 @@ __device__ __forceinline__ float dot8(const u32x4& w, const u32x4& x, float c) {
 // streamed-once weights: non-temporal 16-B load (MI355X_MICROARCH.md "nt-weights")
 __device__ __forceinline__ u32x4 ld_nt16(const void* p) { return __builtin_nontemporal_load((const u32x4*)p); }
 __device__ __forceinline__ u32x4 ld16(const void* p) { return *(const u32x4*)p; }
+// eight FP8 codes of a streamed-once weight row (zn_gemv_fp8_kernels.h): one 8-B non-temporal load
+__device__ __forceinline__ u32x2 ld_nt8(const void* p) { return __builtin_nontemporal_load((const u32x2*)p); }
 // The same through a GLOBAL-address-space pointer, for weights whose address was read from a device table: loaded through a
 // generic pointer they become flat_load instructions, which count on lgkmcnt as well as vmcnt - every wait for an LDS read then
 // also waits for every weight tile still in flight (found in the whole-step kernels' ISA: 201 flat loads).

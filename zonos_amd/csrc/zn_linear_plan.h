@@ -20,6 +20,7 @@ struct LinearEnv {
   bool has_g16_part = false, has_ln_part = false;
   bool w8_offered = false;        // the caller holds the weights as an FP8 stream as well (zn_fp8_kernels.h) and has not switched it off
   bool w8k_offered = false;       // the same for a GEMM16K projection (the Mamba2 in_proj / out_proj: zn_mamba_fp8_kernels.h); an offer of its own: w8_offered never marks a GEMM16K plan
+  bool w8v_offered = false;       // the same for the GEMV of 1..4 decode rows (zn_gemv_fp8_kernels.h; ZN_TUNE_FP8_SMALL_ROWS = 2); an offer of its own: w8_offered and w8k_offered never mark a GEMV plan
   bool wide_rows = false;         // decode steps of more than 16 rows: up to 64 rows per weight pass (plan_linear) instead of groups of 16
   int wide_hybrid = 0;            // under wide_rows, the Mamba2 in_proj (GEMM16K x EPI_MAMBA): 0 / 1 groups of 16, 2 row groups on grid y, 3 the row-tile loop
                                   // (gemm16k_rows_kernel), 4 = the form wide_hybrid_form picks for the row count (ZN_TUNE_WIDE_HYBRID unset)
@@ -44,7 +45,8 @@ struct LinearPlan {
   int nwv = 0, groups = 0, ksplit = 0; bool lnp = false;   // GEMM16S / GEMM64S: 16-row tiles per workgroup, grid x, grid y; LayerNorm from handed-over statistics
   bool ln_pro = false;        // GEMM16K (nch = 128-wide chunks per wave): LayerNorm as its prologue
   bool w8 = false;            // GEMM16S, decode: the launch reads the FP8 stream (gemm16s_kernel<., NWV | ZN_G16S_W8>) instead of the bf16 weights;
-                              // GEMM16K, decode (LinearEnv::w8k_offered): gemm16k8_kernel / gemm16k8_rows_kernel in place of gemm16k_kernel / gemm16k_rows_kernel
+                              // GEMM16K, decode (LinearEnv::w8k_offered): gemm16k8_kernel / gemm16k8_rows_kernel in place of gemm16k_kernel / gemm16k_rows_kernel;
+                              // GEMV, decode (LinearEnv::w8v_offered): gemv8_kernel in place of gemv_kernel
   int err = 0;                // shapes nobody serves: a ZN_ERR_* code (-4 = ZN_ERR_UNSUPPORTED) and its message
   char msg[96] = {};
 };
@@ -63,12 +65,19 @@ constexpr bool lin_has_gemm16k_rows(int pro, int epi, int nch) { return pro == P
 constexpr bool lin_has_w8(int pro, int epi) { return (epi == EPI_SILU && (pro == PRO_NONE || pro == PRO_LN)) || (epi == EPI_RESID && pro == PRO_NONE); }
 // gemm16k8_kernel<EPI, NCH> / gemm16k8_rows_kernel<2> (zn_mamba_fp8_kernels.h): the Mamba2 in_proj (no prologue, K = 2048) and out_proj (no prologue, store, K = 4096)
 constexpr bool lin_has_w8k(int pro, int epi, int nch) { return pro == PRO_NONE && ((epi == EPI_MAMBA && nch == 2) || (epi == EPI_STORE && nch == 4)); }
+// gemv8_kernel<R, NCH, KS, PRO, EPI, ., .> (zn_gemv_fp8_kernels.h), R = 2 and 4: what production launches at 1..4 rows - the transformer's fc1 (LayerNorm, SiLU gate, K = 2048)
+// and fc2 (residual, K = 8192 in four quarters), the Mamba2 in_proj (K = 2048) and out_proj (K = 4096 in four quarters; gated-norm prologue with one norm group, else none)
+constexpr bool lin_has_w8v(int pro, int epi, int ks, int nch) {
+  return (pro == PRO_LN && epi == EPI_SILU && ks == 1 && nch == 4) || (pro == PRO_NONE && epi == EPI_RESID && ks == 4 && nch == 4) ||
+         (pro == PRO_NONE && epi == EPI_MAMBA && ks == 1 && nch == 4) || ((pro == PRO_GATED || pro == PRO_NONE) && epi == EPI_STORE && ks == 4 && nch == 2);
+}
 // gemm16w_kernel (zn_wide_kernels.h), decode steps of 17..64 rows: fc1 (SiLU gate; LayerNorm none, from a launch, or from handed-over statistics) and fc2 (residual)
 constexpr bool lin_has_wide16s(int pro, int epi) { return (epi == EPI_SILU && (pro == PRO_NONE || pro == PRO_LN)) || (epi == EPI_RESID && pro == PRO_NONE); }
 constexpr bool lin_has_prefill(int pro, int epi) { return pro == PRO_NONE && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_SILU); }   // GEMM64S, GEMM_TILED
 inline bool linear_plan_launchable(const LinearPlan& p, int pro, int epi) {
   switch (p.kernel) {
-    case LinearPlan::GEMV: return (p.ks == 1 || (p.ks == 4 && lin_has_gemv_ks4(pro))) && (p.nch == 1 || p.nch == 2 || p.nch == 4 || p.nch == 8);
+    case LinearPlan::GEMV: return (p.ks == 1 || (p.ks == 4 && lin_has_gemv_ks4(pro))) && (p.nch == 1 || p.nch == 2 || p.nch == 4 || p.nch == 8) &&
+                                  (!p.w8 || lin_has_w8v(pro, epi, p.ks, p.nch));
     case LinearPlan::GEMM16: return lin_has_gemm16(pro) && (p.nw == 4 || p.nw == 8 || p.nw == 16) && (!p.tile8 || lin_has_tile8(epi));
     case LinearPlan::GEMM16S: return lin_has_gemm16(pro) && (p.nwv == 2 || p.nwv == 4) && (!p.lnp || lin_has_lnp(pro, epi)) && (!p.w8 || lin_has_w8(pro, epi)) &&
                                      (p.row_tiles == 1 || (p.row_tiles >= 2 && p.row_tiles <= 4 && lin_has_wide16s(pro, epi)));
@@ -250,6 +259,16 @@ inline LinearPlan plan_linear(const LinearEnv& e, int pro, int epi, int rows, in
   // 1.864 / 1.988, 18 rows 2.176 / 2.323, 32 rows 2.522 / 2.691, 48 rows 3.348 / 3.545, 64 rows 3.973 / 4.175 (spread <= 0.08 ms, 0.20 at 64 rows): no band
   // of row counts in which the stream is slower, so none is declined
   if (e.w8k_offered && !prefill && !p.err && p.kernel == LinearPlan::GEMM16K && !p.ln_pro && lin_has_w8k(pro, epi, p.nch)) p.w8 = true;
+  // ... and a decode GEMV launch (1..4 rows) of fc1, fc2 or a Mamba2 projection reads its stream (w8v_offered) where gemv8_kernel has the instantiation.
+  // At EVERY (projection, row count): measured (tools/smallrowsbench.py, profiles/smallrowsbench.txt; Zonos-v0.1 and Zonos-v0.1-hybrid shapes, one quantised model, the
+  // stream against the bf16 GEMV with ZN_TUNE_FP8_SMALL_ROWS unset, medians of 20 alternated repetitions, us per launch at 1 / 2 / 3 / 4 rows, FP8 : bf16) fc1
+  // 11.57 : 14.78, 9.78 : 13.49, 20.20 : 22.59, 12.09 : 14.84; fc2 5.63 : 7.61, 6.34 : 8.15, 7.32 : 9.91, 7.95 : 9.32; in_proj (8512 x 2048) 7.38 : 9.57, 6.83 : 8.78,
+  // 9.06 : 10.62, 8.48 : 10.47; out_proj with the gated norm 5.66 : 6.30, 5.64 : 6.70, 8.13 : 8.56, 7.88 : 8.64; out_proj without it 4.27 : 5.01, 4.08 : 5.22,
+  // 4.84 : 5.64, 5.23 : 6.16 (the repetitions spread by <= 0.36 us, 0.70 for the gated out_proj at 2 rows: below every difference); ms per decode step of the
+  // 46-layer hybrid stack 1.078 : 1.202 (1 guided utterance), 1.271 : 1.389 (2), 1.053 : 1.170 (1 unguided), 1.305 : 1.396 (3), of the 26-layer transformer
+  // 1.148 : 1.245 (2 guided utterances), 0.978 : 1.120 (a one-slot session) (spread <= 0.05 ms): no (projection, row count) where the stream is slower, so none
+  // is declined
+  if (e.w8v_offered && !prefill && !p.err && p.kernel == LinearPlan::GEMV && rows <= 4 && lin_has_w8v(pro, epi, p.ks, p.nch)) p.w8 = true;
   // LinearEnv::wide_rows, decode, more than 16 rows: the same plan over up to 64 rows per weight pass (plan_wide).  Wide at EVERY row count from 17 on:
   // measured (tools/widebench.py, profiles/widebench.txt; Zonos-v0.1 shapes, medians of 20, ms per decode step, groups of 16 -> wide) 18 rows 2.630 -> 1.771,
   // 32 rows 2.723 -> 1.822, 48 rows 4.178 -> 2.400, 64 rows 5.495 -> 2.585 (FP8 stream: 2.490 -> 1.633 ... 5.186 -> 2.445); the repetitions spread by <= 0.04 ms

@@ -110,6 +110,7 @@ class Zonos(nn.Module):
         self._repeats = 0                             # generations repeated on the launches path after a reported hand-off timeout
         self.mlp_weights = "bf16"                     # "fp8" after quantize_mlp_fp8()
         self.mamba_weights = "bf16"                   # "fp8" after quantize_mamba_fp8()
+        self.fp8_small_rows = False                   # decode steps of 1..4 rows on the launches path read an attached FP8 stream too (set_fp8_small_rows)
 
     # ------------------------------------------------------------------ loading
     @property
@@ -127,10 +128,11 @@ class Zonos(nn.Module):
 
     @classmethod
     def from_local(cls, config_path: str, model_path: str, device: str = DEFAULT_DEVICE, backbone: str | None = None,
-                   mlp_weights: str = "bf16", mamba_weights: str = "bf16") -> "Zonos":
+                   mlp_weights: str = "bf16", mamba_weights: str = "bf16", fp8_small_rows: bool = False) -> "Zonos":
         """model.py:128-176: bf16 model, embeddings zero-padded to the 1032-row tables, heads.{i} fused.  mlp_weights="fp8":
         quantize_mlp_fp8() after loading (lossy with respect to the checkpoint; see there); mamba_weights="fp8": quantize_mamba_fp8() (the
-        hybrid checkpoint; likewise); the defaults change nothing."""
+        hybrid checkpoint; likewise); fp8_small_rows: set_fp8_small_rows() (decode steps of 1..4 rows read the stream too); the defaults
+        change nothing."""
         import safetensors
         if mlp_weights not in ("bf16", "fp8"):
             raise _lib.ZonosHipError(f"mlp_weights must be 'bf16' or 'fp8', not {mlp_weights!r}")
@@ -163,15 +165,18 @@ class Zonos(nn.Module):
             model.quantize_mlp_fp8()
         if mamba_weights == "fp8":
             model.quantize_mamba_fp8()
+        if fp8_small_rows:
+            model.set_fp8_small_rows(True)
         return model
 
     @torch.inference_mode()
-    def quantize_mlp_fp8(self) -> "Zonos":
+    def quantize_mlp_fp8(self, small_rows: bool = False) -> "Zonos":
         """Weight-only FP8 for fc1 / fc2 of every transformer block (zonos_amd/quant.py: E4M3 codes, one power-of-two scale per weight
         row).  Quantises on the device, OVERWRITES the bf16 parameters in place with the dequantised values and keeps the codes and
         exponents as buffers of the block's mlp (fc1_q, fc1_exp, fc2_q, fc2_exp; not part of the state dict).  Decode steps of 5 or
         more rows then stream the codes - half the bytes - and compute exactly what the bf16 kernels compute on the dequantised
-        weights, which every other path keeps reading.  Lossy with respect to the checkpoint (|Wdq - w| <= 2^-4 |w|), exact with
+        weights, which every other path keeps reading: steps of up to 4 rows keep reading the bf16 copy unless `small_rows`
+        (set_fp8_small_rows: then the GEMV launches of 1..4 rows stream the codes too; the persistent kernels never do).  Lossy with respect to the checkpoint (|Wdq - w| <= 2^-4 |w|), exact with
         respect to the model's own weights afterwards; the effect on audio quality is unmeasured.  Cached engines are dropped."""
         if self.config.backbone.ssm_cfg:
             raise _lib.ZonosHipError("quantize_mlp_fp8: the hybrid stack has no FP8 path")
@@ -192,16 +197,19 @@ class Zonos(nn.Module):
         self._engine = self._spare = None
         self.backbone._engine = None
         self.mlp_weights = "fp8"
+        if small_rows:
+            self.set_fp8_small_rows(True)
         return self
 
     @torch.inference_mode()
-    def quantize_mamba_fp8(self) -> "Zonos":
+    def quantize_mamba_fp8(self, small_rows: bool = False) -> "Zonos":
         """Weight-only FP8 for in_proj / out_proj of every Mamba2 layer of a hybrid model (zonos_amd/quant.py: E4M3 codes, one power-of-two
         scale per weight row) - about four fifths of the weight bytes a hybrid decode step reads.  Like quantize_mlp_fp8: quantises on the
         device, OVERWRITES the bf16 parameters in place with the dequantised values and keeps the codes and exponents as buffers of the
         mixer (in_proj_q, in_proj_exp, out_proj_q, out_proj_exp; not part of the state dict).  Decode steps of 5 or more rows then stream
-        the codes - half the bytes - and compute exactly what the bf16 kernels compute on the dequantised weights; steps of up to 4 rows
-        and the prefill keep reading the bf16 copy.  Lossy with respect to the checkpoint (|Wdq - w| <= 2^-4 |w|), exact with respect to
+        the codes - half the bytes - and compute exactly what the bf16 kernels compute on the dequantised weights; the prefill keeps
+        reading the bf16 copy, and steps of up to 4 rows keep reading the bf16 copy unless `small_rows` (set_fp8_small_rows: then in_proj and
+        out_proj of a step of 1..4 rows stream the codes too - batch 1 and 2, stream(), one-slot sessions).  Lossy with respect to the checkpoint (|Wdq - w| <= 2^-4 |w|), exact with respect to
         the model's own weights afterwards; the effect on audio quality is unmeasured.  Cached engines are dropped.
         Raises ZonosHipError - and changes nothing - on a transformer model, and on a hybrid model of other widths than the FP8 kernels
         serve (d_model 2048, d_inner 4096: Zonos-v0.1-hybrid): a stream that no decode step would read is refused, not carried along."""
@@ -230,12 +238,24 @@ class Zonos(nn.Module):
         self._engine = self._spare = None
         self.backbone._engine = None
         self.mamba_weights = "fp8"
+        if small_rows:
+            self.set_fp8_small_rows(True)
+        return self
+
+    def set_fp8_small_rows(self, on: bool) -> "Zonos":
+        """Whether decode steps of 1..4 rows on the launches path read the FP8 streams of a quantised model (quantize_mlp_fp8 / quantize_mamba_fp8)
+        instead of the dequantised bf16 copy: the same bits from half the weight bytes (zn_debug_tune(ZN_TUNE_FP8_SMALL_ROWS, 2) on every engine
+        of the model).  Off by default; without a stream it changes nothing.  Which path a generation takes does not change, and the persistent
+        kernels (the transformer at batch 1) keep reading the bf16 copy.  Cached engines are dropped."""
+        self.fp8_small_rows = bool(on)
+        self._engine = self._spare = None
+        self.backbone._engine = None
         return self
 
     def mamba_fp8_plan(self, rows: int) -> dict:
         """Whether in_proj and out_proj of the Mamba2 layers would read the FP8 stream in a decode step of `rows` rows (two per guided
         utterance) as this model's engine runs it now: {"in_proj": bool, "out_proj": bool}; both False before quantize_mamba_fp8(), up to
-        4 rows, and under zn_debug_tune(ZN_TUNE_MAMBA_FP8, 2) on the engine."""
+        4 rows unless fp8_small_rows, and under zn_debug_tune(ZN_TUNE_MAMBA_FP8, 2) on the engine."""
         a, b = self.engine((int(rows) + 1) // 2).mamba_fp8_plan(int(rows))
         return {"in_proj": bool(a), "out_proj": bool(b)}
 
@@ -257,10 +277,13 @@ class Zonos(nn.Module):
         return super()._apply(fn, *a, **k)
 
     def _new_engine(self, batch_size: int) -> HipEngine:
-        return HipEngine(self.backbone, [m.weight for m in self.embeddings], self.fused_heads.weight,
-                         max_rows=2 * batch_size, double_out_proj=getattr(self.backbone, "ref_double_out_proj", True),
-                         n_codebooks=self.autoencoder.num_codebooks, vocab_head=1025, vocab_embed=self.embeddings[0].weight.shape[0],
-                         eos_id=self.eos_token_id, mask_id=self.masked_token_id)
+        eng = HipEngine(self.backbone, [m.weight for m in self.embeddings], self.fused_heads.weight,
+                        max_rows=2 * batch_size, double_out_proj=getattr(self.backbone, "ref_double_out_proj", True),
+                        n_codebooks=self.autoencoder.num_codebooks, vocab_head=1025, vocab_embed=self.embeddings[0].weight.shape[0],
+                        eos_id=self.eos_token_id, mask_id=self.masked_token_id)
+        if self.fp8_small_rows:      # (every engine of the model: the cached one and the spare)
+            eng.call("zn_debug_tune", _lib.ZN_TUNE_FP8_SMALL_ROWS, 2)
+        return eng
 
     def engine(self, batch_size: int = 1) -> HipEngine:
         # (both handles are created and replaced under one lock: two threads arriving together must not each build an engine,
