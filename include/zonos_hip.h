@@ -358,7 +358,9 @@ enum zn_tune_key {
                                        requested ahead (measurement only: never faster, profiles/smallrowsbench.txt); unset or 1 = they read the bf16 copy.  ZN_TUNE_MLP_FP8 / ZN_TUNE_MAMBA_FP8 = 2 switch the stream off
                                        here too.  Same bits either way; the persistent kernels always read the bf16 copy, and the key never changes the path a
                                        generation takes */
-  ZN_TUNE_NKEYS = 25
+  ZN_TUNE_KV_FP8 = 25,              /* 2 = the decode attention ignores the code cache of zn_set_kv_fp8 and reads the bf16 cache; the appends still round and still write both
+                                       caches, so the result is the same bits.  The key never changes the path a generation takes */
+  ZN_TUNE_NKEYS = 26
 };
 /* Values of ZN_TUNE_HOOK.  The first three arm the next zn_gen_begin, which consumes them. */
 enum zn_tune_hook {
@@ -488,6 +490,36 @@ int zn_set_mamba_fp8(zn_handle h, int32_t layer, const void* in_q, const void* i
  * handle with streams attached to some Mamba2 layers only, or with no Mamba2 layer, reports 0, 0).  rows <= 4: 1, 1 only under
  * zn_debug_tune(ZN_TUNE_FP8_SMALL_ROWS, 2), where the GEMV launches read the stream too. */
 int zn_mamba_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
+/* ---------------------------------------------------------------- FP8 KV cache for the decode attention at 5 rows and more (additive to ABI 9 in the same way: look the
+ * symbols up).  Off by default; with it off nothing changes in any path, buffer or result.
+ * Format (specification: kv_round_e4m3 of zonos_amd/quant.py): OCP E4M3 codes at scale exponent 0 - no scale: the fused append holds two elements of a head vector per
+ * thread and cannot take an absmax.  Round to nearest even; finite values and the infinities saturate at +-448; NaN stays NaN.  Lossy with respect to the bf16 model
+ * (|dq - x| <= 2^-4 |x| in the codes' normal range, <= 2^-10 below 2^-6), exact with respect to its own rounded cache.
+ * While the mode is in effect - a generation or session (zn_gen_begin, zn_gen_open_slots) on a handle with the mode on whose decode step has 5 rows or more (the launches
+ * path; more than 64 rows run in groups, as without the mode) - every KV append of that generation (the decode steps' in_proj epilogue, the prefill's epilogue and
+ * rope_kv_rows_kernel, an admission's prefill) rounds K (after RoPE) and V to the E4M3 grid, writes the dequantised bf16 values into the cache of zn_gen_begin, so that every
+ * reader, the prefill attention included, sees the rounded values, and writes the one-byte codes into a second cache uint8 [rows][max_len][2][Hkv][hd] per layer, which
+ * the decode attention then reads instead (half the bytes, the same bits).  With fewer rows the mode is inert: nothing is rounded (the persistent kernels and the
+ * 1..4-row GEMV).  The bf16 cache stays allocated and current: the mode costs 1.5 x the KV bytes. */
+/* on != 0 switches the mode on for the generations begun afterwards.  ZN_ERR_UNSUPPORTED: a hybrid handle (arch 1: its attention layers stay bf16).  ZN_ERR_STATE: between
+ * zn_gen_begin and zn_gen_end.  Drops the captured graphs. */
+int zn_set_kv_fp8(zn_handle h, int32_t on);
+/* Bytes of one layer's code cache [rows, max_len, 2, Hkv, hd] uint8: half of zn_kv_bytes_per_layer, which keeps reporting the bf16 cache alone. */
+size_t zn_kv_fp8_bytes_per_layer(const zn_config* cfg, int32_t rows, int32_t max_len);
+/* The code caches of the generation begun by zn_gen_begin: a host array of n_layer device pointers, caller-owned like the bf16 caches and with their rows and max_len.
+ * Legal where zn_gen_set_rows is (before or after zn_gen_open_slots).  A generation in which the mode is in effect needs this call: its prefill, admissions and decode
+ * steps return ZN_ERR_STATE without it.  Where the mode is not in effect (mode off, fewer than 5 rows) the call is accepted and the caches are never touched. */
+int zn_gen_bind_kv_fp8(zn_handle h, const void* const* codes_layers_dev);
+/* out[0]: whether a generation of `rows` rows begun on this handle now rounds its K/V (the mode is on and in effect at that row count); out[1]: whether its decode
+ * attention reads the codes (out[0], ZN_TUNE_KV_FP8 != 2, and the row count is one the plan has not declined: see DESIGN.md 4.1k). */
+int zn_kv_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
+/* Per-op tests: while codes_dev != NULL, zn_op_linear_fused's RoPE + KV append (decode and prefill epilogue) and zn_op_rope_kv_rows round and write the codes of the cache
+ * they append to into codes_dev (same rows and max_len as that cache), and zn_op_attn_decode reads codes_dev where zn_kv_fp8_plan's out[1] would be 1 for its row count
+ * with the mode on.  NULL (the default) restores the bf16 behaviour.  Independent of zn_set_kv_fp8. */
+int zn_op_bind_kv_fp8(zn_handle h, void* codes_dev);
+/* The prefill's row-wise split + RoPE + KV append alone (rope_kv_rows_kernel, what follows a projection whose plan reports ZN_LP_ROPE_DONE = 0): qkv bf16
+ * [rows][S][(Hq + 2 Hkv) hd], q rotated in place, k and v to positions base .. base + S - 1 of kv [rows][max_len][2][Hkv][hd]; positions at or past max_len write nothing. */
+int zn_op_rope_kv_rows(zn_handle h, void* qkv_dev, void* kv_dev, int32_t max_len, int32_t S, int32_t base, int32_t rows, zn_stream stream);
 /* ---------------------------------------------------------------- decode steps of 17..64 rows (additive to ABI 9, like the FP8 calls above: look the symbol up)
  * out[0..4]: activation rows per weight pass of in_proj, out_proj, fc1, fc2 and the heads in a decode step of `rows` rows as this handle would
  * run it now (4 up to 4 rows, 16 up to 16 rows and under zn_debug_tune(ZN_TUNE_WIDE_ROWS, 1), 64 where the wide plan applies): a step of R rows

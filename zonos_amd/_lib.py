@@ -36,7 +36,8 @@ ZN_TUNE_WIDE_ROWS = 21
 ZN_TUNE_WIDE_HYBRID = 22
 ZN_TUNE_MAMBA_FP8 = 23
 ZN_TUNE_FP8_SMALL_ROWS = 24
-ZN_TUNE_NKEYS = 25
+ZN_TUNE_KV_FP8 = 25
+ZN_TUNE_NKEYS = 26
 # values of ZN_TUNE_HOOK (enum zn_tune_hook)
 ZN_HOOK_TAG_WRAP, ZN_HOOK_TIMEOUT_WORD, ZN_HOOK_PAUSE, ZN_HOOK_RESET_WAIT_STATS = 7, 9, 11, 13
 
@@ -165,6 +166,12 @@ SIGNATURES = {
     "zn_mlp_fp8_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zn_set_mamba_fp8": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zn_mamba_fp8_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zn_set_kv_fp8": (C.c_int, [C.c_void_p, C.c_int32]),
+    "zn_kv_fp8_bytes_per_layer": (C.c_size_t, [C.POINTER(zn_config), C.c_int32, C.c_int32]),
+    "zn_gen_bind_kv_fp8": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "zn_kv_fp8_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zn_op_bind_kv_fp8": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "zn_op_rope_kv_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "zn_decode_rows_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zn_hybrid_rows_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zn_op_linear_bias": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p]),

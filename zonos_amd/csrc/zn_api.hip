@@ -2,6 +2,7 @@
 // workspace, launch geometry, hipGraph capture of one decode step.
 #include "../../include/zonos_hip.h"
 #include "zn_decode_kernels.h"
+#include "zn_attn_fp8_kernels.h"
 #include "zn_wide_kernels.h"
 #include "zn_mamba_fp8_kernels.h"
 #include "zn_gemv_fp8_kernels.h"
@@ -45,6 +46,10 @@ struct zn_handle_s {
   // the same for a Mamba2 layer's in_proj / out_proj (zn_set_mamba_fp8); read by gemm16k8_kernel / gemm16k8_rows_kernel only
   struct MambaFp8 { const uint8_t *in_q = nullptr, *out_q = nullptr; const int8_t *in_exp = nullptr, *out_exp = nullptr; };
   std::vector<MambaFp8> mamba_fp8;
+  // FP8 KV cache (zn_set_kv_fp8): the mode, this generation's code caches (zn_gen_bind_kv_fp8; empty: none bound) and the code cache of the per-op entry points
+  bool kv_fp8 = false;
+  std::vector<const void*> kv8_layers;
+  uint8_t* op_kv8 = nullptr;
   const void* heads = nullptr;
   const void *norm_f_w = nullptr, *norm_f_b = nullptr;
   const float* rope = nullptr;
@@ -492,6 +497,7 @@ static void advance_rows(GemvArgs& g, int r0, int nr, int out_cols) {
   if (g.lengths) g.lengths += r0;
   if (g.q_out) g.q_out += (size_t)r0 * g.n_heads * g.hd;
   if (g.kv) g.kv += (size_t)r0 * g.max_len * 2 * g.n_heads_kv * g.hd;
+  if (g.kv8) g.kv8 += (size_t)r0 * g.max_len * 2 * g.n_heads_kv * g.hd;
   if (g.conv_state) { g.conv_state += (size_t)r0 * g.conv_dim * 4; g.xbc += (size_t)r0 * g.conv_dim; }
   if (g.ln_part_out) g.ln_part_out += (size_t)r0 * ZN_G16_LNT * 2;
   if (g.ln_part_in) g.ln_part_in += (size_t)r0 * ZN_G16_LNT * 2;
@@ -621,6 +627,8 @@ static int attn_fused_for(zn_handle h, int keys_upper_bound) {
 #ifndef ZN_ATTN_DSS
 #define ZN_ATTN_DSS 2
 #endif
+// FP8: the same launches reading the code cache a.kv8 (zn_attn_fp8_kernels.h) - the form the caller's plan chose by leaving a code cache in the arguments (run_attention).
+#define ZN_ATTN_LAUNCH(FP8, BF16, grid_, block_) do { if (a.kv8) hipLaunchKernelGGL(FP8, grid_, block_, 0, s, a); else hipLaunchKernelGGL(BF16, grid_, block_, 0, s, a); } while (0)
 template <int HD>
 static int launch_attn_g(const AttnArgs& a, int G, dim3 grid, int fused, bool split_cols, hipStream_t s) {
   constexpr int DS = HD == 128 ? ZN_ATTN_DSS : 1;       // value-column parts per (row, kv head[, block]) when split_cols (attn_block_kernel)
@@ -628,18 +636,33 @@ static int launch_attn_g(const AttnArgs& a, int G, dim3 grid, int fused, bool sp
   switch (G) {
 #define ZN_ATTN_CASE(GG) case GG: \
     if (fused) { \
-      if (split_cols && DSF > 1) hipLaunchKernelGGL((attn_block_kernel<HD, GG, true, DSF>), dim3(grid.y * grid.z * DSF), dim3(512), 0, s, a); \
-      else hipLaunchKernelGGL((attn_block_kernel<HD, GG, true>), dim3(grid.y * grid.z), dim3(512), 0, s, a); \
+      if (split_cols && DSF > 1) ZN_ATTN_LAUNCH((attn_block_fp8_kernel<HD, GG, true, DSF>), (attn_block_kernel<HD, GG, true, DSF>), dim3(grid.y * grid.z * DSF), dim3(512)); \
+      else ZN_ATTN_LAUNCH((attn_block_fp8_kernel<HD, GG, true>), (attn_block_kernel<HD, GG, true>), dim3(grid.y * grid.z), dim3(512)); \
       return 0; \
     } \
-    hipLaunchKernelGGL((attn_scores_kernel<HD, GG>), grid, dim3(256), 0, s, a); \
-    if (split_cols && DS > 1) hipLaunchKernelGGL((attn_block_kernel<HD, GG, false, DS>), dim3(grid.y * DS, grid.z * a.nbcap), dim3(512), 0, s, a); \
-    else hipLaunchKernelGGL((attn_block_kernel<HD, GG, false>), dim3(grid.y, grid.z * a.nbcap), dim3(512), 0, s, a); \
+    ZN_ATTN_LAUNCH((attn_scores_fp8_kernel<HD, GG>), (attn_scores_kernel<HD, GG>), grid, dim3(256)); \
+    if (split_cols && DS > 1) ZN_ATTN_LAUNCH((attn_block_fp8_kernel<HD, GG, false, DS>), (attn_block_kernel<HD, GG, false, DS>), dim3(grid.y * DS, grid.z * a.nbcap), dim3(512)); \
+    else ZN_ATTN_LAUNCH((attn_block_fp8_kernel<HD, GG, false>), (attn_block_kernel<HD, GG, false>), dim3(grid.y, grid.z * a.nbcap), dim3(512)); \
     return 0;
     ZN_ATTN_CASE(1) ZN_ATTN_CASE(2) ZN_ATTN_CASE(4) ZN_ATTN_CASE(8)
 #undef ZN_ATTN_CASE
   }
   return -1;
+}
+#undef ZN_ATTN_LAUNCH
+
+// ---- FP8 KV cache (zn_set_kv_fp8).  In effect: a generation of 5 rows or more on a transformer handle with the mode on - always the launches path
+// (the persistent kernels serve one or two rows).  Then every KV append rounds to the E4M3 grid and writes both caches.
+#define ZN_KV_FP8_MIN_ROWS 5
+static bool kv_fp8_rows(zn_handle h, int rows) { return h->cfg.arch == 0 && rows >= ZN_KV_FP8_MIN_ROWS; }
+static bool kv_fp8_gen(zn_handle h) { return h->kv_fp8 && kv_fp8_rows(h, h->rows); }
+static uint8_t* kv8_of(zn_handle h, int li) { return kv_fp8_gen(h) && !h->kv8_layers.empty() ? (uint8_t*)const_cast<void*>(h->kv8_layers[li]) : nullptr; }
+// The decode attention's side of the plan, in one place: does an attention launch over `rows` rows that has a code cache read it?  ZN_TUNE_KV_FP8 = 2: never (the bf16
+// cache holds the dequantised codes: the same bits).  No row count is declined: the FP8 reads have not been measured against the bf16 reads yet (tools/kvfp8bench.py).
+static bool kv_fp8_attn_reads(zn_handle h, int rows) { return h->tune[ZN_TUNE_KV_FP8] != 2 && kv_fp8_rows(h, rows); }
+static int kv_fp8_bound(zn_handle h, const char* who) {
+  if (kv_fp8_gen(h) && h->kv8_layers.empty()) ZN_FAIL(h, ZN_ERR_STATE, "%s: the FP8 KV cache is in effect (zn_set_kv_fp8, %d rows) and no code caches are bound (zn_gen_bind_kv_fp8)", who, h->rows);
+  return ZN_OK;
 }
 
 static int ensure_attn_ws(zn_handle h, int max_len) {
@@ -661,13 +684,14 @@ static int ensure_attn_ws(zn_handle h, int max_len) {
 }
 
 static int run_attention(zn_handle h, const bf16_t* q, const bf16_t* kv, int max_len, const int* lengths, const int* ext, int ext_scalar,
-                         bf16_t* out, int rows, int fused, hipStream_t s, unsigned long long* stamps = nullptr) {
+                         bf16_t* out, int rows, int fused, hipStream_t s, unsigned long long* stamps = nullptr, const uint8_t* kv8 = nullptr) {
   const zn_config& c = h->cfg;
   if (max_len > h->lcap || rows > h->max_rows) ZN_FAIL(h, ZN_ERR_STATE, "attention workspace too small (max_len %d rows %d)", max_len, rows);
   AttnArgs a{};
   a.q = q; a.kv = kv; a.lengths = lengths; a.ext = ext; a.ext_scalar = ext_scalar; a.max_len = max_len;
   a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv; a.lcap = h->lcap; a.scale = (float)(1.0 / std::sqrt((double)h->hd));
   a.scores = h->scores; a.cmax = h->cmax; a.out = out; a.rows = rows; a.stamps = stamps;
+  a.kv8 = kv8 && kv_fp8_attn_reads(h, rows) ? kv8 : nullptr;      // kv8: the code cache of `kv` (the FP8 KV cache in effect), or NULL
   const int hd = h->hd;
   dim3 grid((max_len + ZN_ACHUNK - 1) / ZN_ACHUNK, c.n_heads_kv, rows);
   // fused: one launch for contexts of one 512-key block (the caller bounds the context: attn_fused_for); else: scores, then the P.V pass
@@ -688,11 +712,12 @@ static GemvArgs linear_args(zn_handle h, const void* W, int N, int K, const bf16
   a.W = (const bf16_t*)W; a.N = N; a.K = K; a.x = x; a.out = out; a.resid = resid; a.eps = h->cfg.norm_eps;
   return a;
 }
-static GemvArgs in_proj_args(zn_handle h, const zn_layer_weights& lw, const bf16_t* x, bf16_t* kv, int max_len, const int* lengths) {
+static GemvArgs in_proj_args(zn_handle h, const zn_layer_weights& lw, const bf16_t* x, bf16_t* kv, int max_len, const int* lengths, uint8_t* kv8 = nullptr, bool kv_round = false) {
   const zn_config& c = h->cfg;
   GemvArgs a = linear_args(h, lw.in_proj, (c.n_heads + 2 * c.n_heads_kv) * h->hd, c.d_model, x, nullptr);
   a.ln_w = (const bf16_t*)lw.norm_w; a.ln_b = (const bf16_t*)lw.norm_b; a.lengths = lengths; a.hd = h->hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
   a.q_out = h->q; a.kv = kv; a.rope = h->rope; a.max_len = max_len; a.rope_positions = c.rope_positions;
+  a.kv8 = kv8; a.kv_round = kv_round ? 1 : 0;
   return a;
 }
 static GemvArgs out_proj_args(zn_handle h, const zn_layer_weights& lw, const bf16_t* in, bf16_t* out, const bf16_t* resid) {
@@ -728,8 +753,8 @@ static PostAttnPlans plan_post_attention(zn_handle h, int rows, bool mlp_w8 = fa
 }
 
 // LayerNorm -> in_proj -> split -> RoPE(q,k) -> KV append of block `li` (q in h->q, k/v in the cache row lengths[r])
-static int layer_in_proj(zn_handle h, int li, bf16_t* x, bf16_t* kv, int max_len, const int* lengths, int rows, hipStream_t s) {
-  return run_gemv<PRO_LN, EPI_ROPE_KV>(h, in_proj_args(h, h->layers[li], x, kv, max_len, lengths), rows, h->tune[ZN_TUNE_WG_IN_PROJ], s);
+static int layer_in_proj(zn_handle h, int li, bf16_t* x, bf16_t* kv, int max_len, const int* lengths, int rows, hipStream_t s, uint8_t* kv8 = nullptr, bool kv_round = false) {
+  return run_gemv<PRO_LN, EPI_ROPE_KV>(h, in_proj_args(h, h->layers[li], x, kv, max_len, lengths, kv8, kv_round), rows, h->tune[ZN_TUNE_WG_IN_PROJ], s);
 }
 
 // out_proj (-> out_proj again, _torch.py:419-420) -> residual -> LayerNorm -> fc1 -> y * silu(gate) -> fc2 -> residual
@@ -996,9 +1021,10 @@ static int decode_blocks(zn_handle h, const StepPlan& p, const int* ext, int ext
   };
   if (!chain) {
     for (int li = 0; li < c.n_layer; ++li) {
-      if ((rc = layer_in_proj(h, li, h->x, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, h->rows, s))) return rc;
+      // (the FP8 KV cache in effect - 5 rows or more, so never the chain below: the append rounds and writes both caches, the attention reads what its plan says)
+      if ((rc = layer_in_proj(h, li, h->x, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, h->rows, s, kv8_of(h, li), kv_fp8_gen(h)))) return rc;
       trace_q(li);
-      if ((rc = run_attention(h, h->q, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, ext, ext_scalar, h->o1, h->rows, p.attn_fused, s))) return rc;
+      if ((rc = run_attention(h, h->q, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, ext, ext_scalar, h->o1, h->rows, p.attn_fused, s, nullptr, kv8_of(h, li)))) return rc;
       if ((rc = layer_post_attention(h, li, h->x, h->rows, s, h->dbg_trace ? (bf16_t*)((char*)h->dbg_trace + (size_t)(8 * li + 7) * tb) : nullptr))) return rc;
       trace(li);
     }
@@ -1269,6 +1295,7 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   h->batch = batch; h->rows = rows; h->max_len = max_len; h->t_total = t_total; h->offset0 = offset0; h->max_new = max_new_tokens;
   h->cfg_scale = cfg_scale; h->sp = *sp;
   h->kv_layers.assign(kv_layers_dev, kv_layers_dev + h->cfg.n_layer);
+  h->kv8_layers.clear();
   h->lengths = lengths_dev; h->codes = delayed_codes_dev;
   // The hand-off tags are 32-bit and advance by n_layer per decode step (~41 hours of continuous batch-1 decoding): long before they
   // can wrap, between two generations, the epoch restarts at 1 over zeroed granule buffers (tag 0 is never a launch's epoch).
@@ -1396,8 +1423,9 @@ static int prefill_attention(zn_handle h, const bf16_t* q, int ldq, const bf16_t
 // projections run over all R * S positions (pad rows are computed and dropped: no op mixes positions except the attention, which bounds
 // every row by row_len[r]); RoPE and the KV append run over the pad positions too - cache slots at or past row_len[r], which the row's own
 // decode steps overwrite, one per step, before the attention's extent reaches them.
+// kv_round: the FP8 KV cache is in effect for these appends (rounded K/V into kv_layers); kv8_layers (may be NULL: an admission's scratch cache) receive the codes.
 static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, int R, const void* const* kv_layers, int max_len, int base, hipStream_t s,
-                                    const int* row_len = nullptr) {
+                                    const int* row_len = nullptr, const void* const* kv8_layers = nullptr, bool kv_round = false) {
   const zn_config& c = h->cfg;
   const int M = R * S, d = c.d_model, hd = h->hd, nq = c.n_heads * hd, nkv = c.n_heads_kv * hd, nqkv = nq + 2 * nkv, F = c.d_ff;
   int rc = ensure_prefill_ws(h, (size_t)M);
@@ -1412,9 +1440,10 @@ static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, in
     GemvArgs g = linear_args(h, lw.in_proj, nqkv, d, h->pf_n, h->pf_qkv, nullptr);
     g.hd = hd; g.n_heads = c.n_heads; g.n_heads_kv = c.n_heads_kv; g.q_out = h->pf_qkv; g.kv = kv; g.rope = h->rope; g.max_len = max_len;
     g.rope_positions = c.rope_positions; g.pf_S = S; g.pf_base = base;
+    g.kv8 = kv8_layers ? (uint8_t*)const_cast<void*>(kv8_layers[li]) : nullptr; g.kv_round = kv_round ? 1 : 0;
     bool rope_done = false;
     if ((rc = prefill_linear<EPI_ROPE_KV>(h, g, M, s, true, &rope_done))) return rc;
-    if (!rope_done) hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(S, R), dim3(256), 0, s, h->pf_qkv, kv, h->rope, S, base, max_len, c.n_heads, c.n_heads_kv, hd, c.rope_positions);
+    if (!rope_done) hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(S, R), dim3(256), 0, s, h->pf_qkv, kv, h->rope, S, base, max_len, c.n_heads, c.n_heads_kv, hd, c.rope_positions, g.kv8, g.kv_round);
     rc = prefill_attention(h, h->pf_qkv, rope_done ? nq : nqkv, kv, max_len, h->pf_a, nq, S, R, s, base, row_len);
     if (rc) return rc;
     if (c.double_out_proj && (rc = prefill_linear<EPI_STORE>(h, linear_args(h, lw.out_proj, d, nq, h->pf_a, h->pf_n, nullptr), M, s))) return rc;
@@ -1429,7 +1458,7 @@ static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, in
 static int prefill_batched(zn_handle h, const bf16_t* hidden, int S, hipStream_t s, const int* row_len) {
   const zn_config& c = h->cfg;
   const int R = h->rows, d = c.d_model;
-  int rc = transformer_prefill_core(h, hidden, S, R, h->kv_layers.data(), h->max_len, 0, s, row_len);
+  int rc = transformer_prefill_core(h, hidden, S, R, h->kv_layers.data(), h->max_len, 0, s, row_len, kv_fp8_gen(h) ? h->kv8_layers.data() : nullptr, kv_fp8_gen(h));
   if (rc) return rc;
   hipLaunchKernelGGL(gather_last_kernel, dim3(R), dim3(256), 0, s, h->pf_x, h->x, S, d, row_len);
   hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > R ? 64 : R), 0, s, h->lengths, R, S, row_len);
@@ -1547,6 +1576,7 @@ extern "C" int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_str
   if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill before zn_gen_begin");
   if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill in a slotted session: zn_gen_admit fills the slots");
   if (!hidden_dev || S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill: bad S=%d (max_len %d)", S, h->max_len);
+  if (int rc = kv_fp8_bound(h, "zn_prefill")) return rc;
   h->gen_prefilled = true;
   return prefill_impl(h, hidden_dev, S, nullptr, (hipStream_t)stream);
 }
@@ -1556,6 +1586,7 @@ extern "C" int zn_prefill_rows(zn_handle h, const void* hidden_dev, int32_t S, c
   if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill_rows before zn_gen_begin");
   if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill_rows in a slotted session: zn_gen_admit fills the slots");
   if (!hidden_dev || !row_len || S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: null argument or bad S=%d (max_len %d)", S, h->max_len);
+  if (int rc = kv_fp8_bound(h, "zn_prefill_rows")) return rc;
   const int R = h->rows, B = h->batch;
   int hi = 0;
   bool uniform = true;
@@ -1727,7 +1758,7 @@ static int ensure_admit_cache(zn_handle h, int S, hipStream_t s) {
   h->adm_caches.resize(c.n_layer);
   for (int li = 0; li < c.n_layer; ++li) {
     h->adm_caches[li] = (char*)h->adm_cache + (size_t)li * h->adm_layer_bytes;
-    tab[li] = AdmitLayer{h->adm_caches[li], const_cast<void*>(h->kv_layers[li]), (c.arch == 1 && h->layers[li].kind == 1) ? 1 : 0, 0};
+    tab[li] = AdmitLayer{h->adm_caches[li], const_cast<void*>(h->kv_layers[li]), (c.arch == 1 && h->layers[li].kind == 1) ? 1 : 0, 0, kv8_of(h, li)};
   }
   HIPCHK(h, hipMemcpyAsync(h->adm_layers, tab.data(), tab.size() * sizeof(AdmitLayer), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipStreamSynchronize(s));      // the host vector goes out of scope
@@ -1743,6 +1774,7 @@ extern "C" int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const voi
   if (!a || !hidden_dev || n < 1 || n > B) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: null argument or %d requests for a session of %d slots", n, B);
   if (S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: bad S=%d (max_len %d)", S, h->max_len);
   if (h->stop_pending) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_admit: steps are still owed to a deferred stop read-back (zn_all_stopped_end first)");
+  if (int rc = kv_fp8_bound(h, "zn_gen_admit")) return rc;
   bool longest = false;
   for (int j = 0; j < n; ++j) {
     const zn_admit& q = a[j];
@@ -1807,7 +1839,7 @@ extern "C" int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const voi
     for (int li = 0; li < c.n_layer; ++li)                               // a prefill continues the state it finds: the scratch rows begin at zero
       if (h->layers[li].kind == 1) HIPCHK(h, hipMemsetAsync(const_cast<void*>(h->adm_caches[li]), 0, zb, s));
     if ((rc = hybrid_prefill_core(h, (const bf16_t*)hidden_dev, S, Rs, h->adm_caches.data(), S, 0, h->prefill_mode == 2, s, row_len_dev))) return rc;
-  } else if ((rc = transformer_prefill_core(h, (const bf16_t*)hidden_dev, S, Rs, h->adm_caches.data(), S, 0, s, row_len_dev))) return rc;
+  } else if ((rc = transformer_prefill_core(h, (const bf16_t*)hidden_dev, S, Rs, h->adm_caches.data(), S, 0, s, row_len_dev, nullptr, kv_fp8_gen(h)))) return rc;   // (FP8 KV cache: the scratch rows are rounded, admit_rows_kernel writes their codes)
   AdmitArgs m{};
   m.layers = h->adm_layers; m.n_layer = c.n_layer; m.n = n; m.halves = halves; m.B = B; m.S = S; m.max_len = h->max_len;
   m.kv_row_bytes = 2 * c.n_heads_kv * h->hd * 2;
@@ -1902,6 +1934,7 @@ extern "C" int zn_decode_steps(zn_handle h, int32_t n, zn_stream stream) {
   if (n < 0) ZN_FAIL(h, ZN_ERR_ARG, "n < 0");
   hipStream_t s = (hipStream_t)stream;
   h->gen_stream = s;
+  if (int rc = kv_fp8_bound(h, "zn_decode_steps")) return rc;
   if (h->slots_open)
     for (int b = 0; b < h->batch; ++b)
       if (h->slot_busy[b] && h->slot_len[b] + n > h->max_len)
@@ -2287,6 +2320,7 @@ static int linear_fused_impl(zn_handle h, zn_linear_op* op, const void* W_q, con
   if (epi == EPI_ROPE_KV) {
     a.lengths = op->lengths; a.hd = h->hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv; a.q_out = (bf16_t*)op->q_out; a.kv = (bf16_t*)op->kv;
     a.rope = h->rope; a.max_len = op->max_len; a.rope_positions = c.rope_positions;
+    a.kv8 = h->op_kv8; a.kv_round = h->op_kv8 != nullptr;      // zn_op_bind_kv_fp8
     if (prefill) { a.pf_S = op->pf_S; a.pf_base = op->pf_base; }
   }
   hipStream_t s = (hipStream_t)stream;
@@ -2363,6 +2397,48 @@ extern "C" int zn_set_mlp_fp8(zn_handle h, int32_t layer, const void* fc1_q, con
   zn_handle_s::MlpFp8& f = h->mlp_fp8[layer];
   f.fc1_q = (const uint8_t*)fc1_q; f.fc1_exp = (const int8_t*)fc1_exp; f.fc2_q = (const uint8_t*)fc2_q; f.fc2_exp = (const int8_t*)fc2_exp;
   free_graph(h); h->emb_valid = false;
+  return ZN_OK;
+}
+extern "C" int zn_set_kv_fp8(zn_handle h, int32_t on) {
+  if (!h) return ZN_ERR_ARG;
+  if (h->cfg.arch == 1) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_kv_fp8: the hybrid stack's attention layers keep a bf16 KV cache");
+  if (h->gen_active && !h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_set_kv_fp8 inside a generation (between zn_gen_begin and zn_gen_end)");
+  h->kv_fp8 = on != 0;
+  free_graph(h); h->emb_valid = false;
+  return ZN_OK;
+}
+extern "C" size_t zn_kv_fp8_bytes_per_layer(const zn_config* c, int32_t rows, int32_t max_len) { return zn_kv_bytes_per_layer(c, rows, max_len) / 2; }
+extern "C" int zn_gen_bind_kv_fp8(zn_handle h, const void* const* codes_layers_dev) {
+  if (!h) return ZN_ERR_ARG;
+  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_bind_kv_fp8 before zn_gen_begin");
+  if (h->gen_prefilled) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_bind_kv_fp8 after the generation's prefill: the code caches are bound between zn_gen_begin and the first prefill or admission");
+  if (!codes_layers_dev) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_bind_kv_fp8: null argument");
+  for (int li = 0; li < h->cfg.n_layer; ++li)
+    if (!codes_layers_dev[li] && h->layers[li].kind == 0) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_bind_kv_fp8: layer %d has no code cache", li);
+  h->kv8_layers.assign(codes_layers_dev, codes_layers_dev + h->cfg.n_layer);
+  h->adm_cap_S = 0;          // a session's admission table names the code caches: rebuilt by the next admission
+  return ZN_OK;
+}
+extern "C" int zn_kv_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
+  if (!h || !out || rows < 1) return ZN_ERR_ARG;
+  out[0] = h->kv_fp8 && kv_fp8_rows(h, rows);
+  out[1] = out[0] && kv_fp8_attn_reads(h, rows);
+  return ZN_OK;
+}
+extern "C" int zn_op_bind_kv_fp8(zn_handle h, void* codes_dev) {
+  if (!h) return ZN_ERR_ARG;
+  if (h->cfg.arch == 1) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_op_bind_kv_fp8: the hybrid stack's attention layers keep a bf16 KV cache");
+  h->op_kv8 = (uint8_t*)codes_dev;
+  return ZN_OK;
+}
+extern "C" int zn_op_rope_kv_rows(zn_handle h, void* qkv_dev, void* kv_dev, int32_t max_len, int32_t S, int32_t base, int32_t rows, zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  const zn_config& c = h->cfg;
+  if (!qkv_dev || !kv_dev || max_len < 1 || S < 1 || base < 0 || rows < 1) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_rope_kv_rows: bad argument");
+  if (c.arch != 0) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_op_rope_kv_rows: the transformer prefill's kernel (interleaved pairs)");
+  hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(S, rows), dim3(256), 0, (hipStream_t)stream, (bf16_t*)qkv_dev, (bf16_t*)kv_dev, h->rope, S, base, max_len, c.n_heads, c.n_heads_kv,
+                     h->hd, c.rope_positions, h->op_kv8, h->op_kv8 != nullptr ? 1 : 0);
+  HIPCHK(h, hipGetLastError());
   return ZN_OK;
 }
 extern "C" int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
@@ -2634,7 +2710,7 @@ extern "C" int zn_op_attn_decode(zn_handle h, const void* q, const void* kv, int
   if (rows > h->max_rows) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_decode: rows > max_rows");
   int rc = ensure_attn_ws(h, max_len);
   if (rc) return rc;
-  rc = run_attention(h, (const bf16_t*)q, (const bf16_t*)kv, max_len, lengths, ext, 0, (bf16_t*)out, rows, attn_fused_for(h, max_len), (hipStream_t)stream);
+  rc = run_attention(h, (const bf16_t*)q, (const bf16_t*)kv, max_len, lengths, ext, 0, (bf16_t*)out, rows, attn_fused_for(h, max_len), (hipStream_t)stream, nullptr, h->op_kv8);
   if (rc) return rc;
   HIPCHK(h, hipGetLastError());
   return ZN_OK;

@@ -58,6 +58,10 @@ struct GemvArgs {
   // gemm16s_kernel<., NWV | ZN_G16S_W8>: the weights as an FP8 stream (zn_fp8_kernels.h) - E4M3 codes [N][K] and one scale exponent per weight row [N]; W is unused
   const uint8_t* W8q;
   const int8_t* W8exp;
+  // EPI_ROPE_KV with the FP8 KV cache in effect (zn_set_kv_fp8): kv_round != 0 rounds K (after RoPE) and V to the E4M3 grid before the append (kv receives the
+  // dequantised values), and kv8 (uint8 [rows][max_len][2][Hkv][hd], may be NULL: a scratch cache whose codes nobody reads) receives the codes
+  uint8_t* kv8;
+  int kv_round;
 };
 
 // EPI_MAMBA operands of activation row r and the weight-row pair starting at rowA (both rows lie in the same segment:
@@ -92,6 +96,16 @@ ZN_DEVINL void zn_rope_pair(float x0, float x1, float cs, float sn, float& re, f
   const float a = x0 * cs, b = x1 * sn, c = x1 * cs, d = x0 * sn;
   re = a - b;
   im = c + d;
+}
+
+// One packed pair of K or V into the cache at element offset o; with the FP8 KV cache in effect, rounded to the E4M3 grid first, its two codes beside it.
+ZN_DEVINL void kv_append_pair(const GemvArgs& a, size_t o, unsigned pr) {
+  if (a.kv_round) {
+    unsigned codes;
+    pr = kv_fp8_round_pair(pr, codes);
+    if (a.kv8) *(unsigned short*)(a.kv8 + o) = (unsigned short)codes;
+  }
+  *(unsigned*)(a.kv + o) = pr;
 }
 
 // Fused epilogues shared by the GEMV (rows <= 4) and the small-M MFMA kernel (rows <= 16): finishes activation row r
@@ -137,10 +151,9 @@ ZN_DEVINL void gemv_epilogue(const GemvArgs& a, int r, int rowA, int rowB, bool 
       float re, im;
       zn_rope_pair(x0, x1, cs, sn, re, im);
       if (rowA < nq) *(unsigned*)(a.q_out + (size_t)r * nq + rowA) = pack2(re, im);
-      else if (pos < a.max_len)
-        *(unsigned*)(a.kv + (((size_t)r * a.max_len + pos) * 2 + 0) * nk + (rowA - nq)) = pack2(re, im);
+      else if (pos < a.max_len) kv_append_pair(a, (((size_t)r * a.max_len + pos) * 2 + 0) * nk + (rowA - nq), pack2(re, im));
     } else if (pos < a.max_len) {
-      *(unsigned*)(a.kv + (((size_t)r * a.max_len + pos) * 2 + 1) * nk + (rowA - nq - nk)) = pack2(x0, x1);
+      kv_append_pair(a, (((size_t)r * a.max_len + pos) * 2 + 1) * nk + (rowA - nq - nk), pack2(x0, x1));
     }
   }
 }
@@ -879,6 +892,7 @@ __global__ __launch_bounds__(ZN_G16K_NKW * 64) void gemm16k_kernel(GemvArgs a) {
         a.lengths += r0;
         a.q_out += r0 * a.n_heads * a.hd;
         a.kv += r0 * a.max_len * 2 * a.n_heads_kv * a.hd;
+        if (a.kv8) a.kv8 += r0 * a.max_len * 2 * a.n_heads_kv * a.hd;
       }
     }
     // the Mamba2 in_proj over row groups (LinearEnv::wide_hybrid = 2): mamba_epi_operands and the epilogue index window and xBC by the local row
@@ -1050,6 +1064,7 @@ __global__ __launch_bounds__(ZN_G16K_NKW * 64) void gemm16k_kernel(GemvArgs a) {
 struct AttnArgs {
   const bf16_t* q;      // [rows][Hq*hd] (post-RoPE)
   const bf16_t* kv;     // [rows][max_len][2][Hkv][hd]
+  const uint8_t* kv8;   // the same cache as E4M3 codes, one byte per element (zn_attn_fp8_kernels.h: the source of the forms instantiated with AttnKvFp8); else unused
   const int* lengths;   // position of the newest key (already appended): L = lengths[r] + 1 keys
   const int* ext;       // optional int32 [rows]: keys the reference's block loop spans (prefill emulation)
   int ext_scalar;       // used when ext == NULL and > 0
@@ -1065,6 +1080,17 @@ struct AttnArgs {
   unsigned long long* stamps;   // optional [8] diagnostic timeline (s_memrealtime) of workgroup 0 of the fused launch
 };
 #define ZN_ACHUNK 64
+// Where the decode attention's K and V tiles come from: the element type of the cache it walks and the requests of 8 / 4 / 2 consecutive elements of a
+// row, each returning bf16 (4, 2, 1 packed words).  Everything else in the kernels below - addresses in elements, clamping, LDS layouts, MFMA
+// operands, summation orders, masking - does not depend on it: the kernels' bodies are templates over it (attn_scores_body, attn_block_body), and
+// AttnKvFp8 (zn_attn_fp8_kernels.h, with the FP8 forms of the two kernels) reads one-byte codes instead.
+struct AttnKvBf16 {
+  typedef bf16_t elem;
+  static ZN_DEVINL const elem* cache(const AttnArgs& a) { return a.kv; }
+  static ZN_DEVINL u32x4 ld8(const elem* p) { return ld16(p); }
+  static ZN_DEVINL u32x2 ld4(const elem* p) { return *(const u32x2*)p; }
+  static ZN_DEVINL unsigned ld2(const elem* p) { return *(const unsigned*)p; }
+};
 
 // A single CU sustains only a few tens of GB/s, so the KV read of a (row, kv-head) pair is spread over one workgroup
 // per 64-key chunk (grid = chunks x Hkv x rows, ~112 workgroups at 10 s of context).  Pass 1: scores + chunk maxima.
@@ -1073,8 +1099,8 @@ struct AttnArgs {
 // B = 16 keys, k = 32 consecutive head dims per step, steps in ascending order), fp32 accumulate, then the reference's fp32
 // scale - ONE summation order for q.k on every path, so that the paths stay bit-identical to one another at every context length.
 // Each wave owns one 16-key tile and requests its keys straight in the B-fragment layout (lane = (key l & 15, k-group l >> 4)).
-template <int HD, int G>
-__global__ __launch_bounds__(256) void attn_scores_kernel(AttnArgs a) {
+template <int HD, int G, class KV>
+ZN_DEVINL void attn_scores_body(const AttnArgs& a) {
   static_assert(HD % 32 == 0 && G <= 16, "score tile shape");
   constexpr int KST = HD / 32;     // MFMA steps over the head dimension
   typedef __attribute__((ext_vector_type(4))) float f32x4_t;
@@ -1086,10 +1112,10 @@ __global__ __launch_bounds__(256) void attn_scores_kernel(AttnArgs a) {
   const int kn = lane & 15, kg = lane >> 4;
   const size_t kvrow = (size_t)2 * a.n_heads_kv * HD;
   const int t = chunk * ZN_ACHUNK + wave * 16 + kn;
-  const bf16_t* kp = a.kv + ((size_t)r * a.max_len + (size_t)min(t, a.max_len - 1)) * kvrow + (size_t)kvh * HD + 8 * kg;
+  const typename KV::elem* kp = KV::cache(a) + ((size_t)r * a.max_len + (size_t)min(t, a.max_len - 1)) * kvrow + (size_t)kvh * HD + 8 * kg;
   u32x4 kk[KST];
 #pragma unroll
-  for (int st = 0; st < KST; ++st) kk[st] = ld16(kp + 32 * st);
+  for (int st = 0; st < KST; ++st) kk[st] = KV::ld8(kp + 32 * st);
   zn_bf16x8 qa[KST];
 #pragma unroll
   for (int st = 0; st < KST; ++st) {
@@ -1122,6 +1148,9 @@ __global__ __launch_bounds__(256) void attn_scores_kernel(AttnArgs a) {
     a.cmax[((size_t)r * a.n_heads + kvh * G + g) * (a.lcap / ZN_ACHUNK) + chunk] = fmaxf(fmaxf(sm[0][g], sm[1][g]), fmaxf(sm[2][g], sm[3][g]));
   }
 }
+
+template <int HD, int G>
+__global__ __launch_bounds__(256) void attn_scores_kernel(AttnArgs a) { attn_scores_body<HD, G, AttnKvBf16>(a); }
 
 // ---- Pass 2 of ONE 512-key block of a (row, kv head) pair: the library's definition of the decode attention, shared by the launches below and
 // by the whole-step kernel's attention role (zn_step_kernel.h), so that every path gives the same bits at every context length:
@@ -1210,18 +1239,18 @@ ZN_DEVINL void attn_block_pv(const bf16_t (*p)[512], const AttnV<HD>& V, float (
 }
 
 // The value rows of this wave's 64 keys in AttnV's layout, by plain loads (rows clamped to the cache: the caller masks keys past the context).
-template <int HD>
-ZN_DEVINL void attn_block_load_v(AttnV<HD>& V, const bf16_t* vcol0, size_t kvrow, int key0, int row_max, int lane) {
+template <int HD, class KV = AttnKvBf16>
+ZN_DEVINL void attn_block_load_v(AttnV<HD>& V, const typename KV::elem* vcol0, size_t kvrow, int key0, int row_max, int lane) {
   constexpr int DPL = HD / 16;
   const int kn = lane & 15, kg = lane >> 4;
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const bf16_t* src = vcol0 + (size_t)min(key0 + 32 * ks + 8 * kg + j, row_max) * kvrow + DPL * kn;
-      if constexpr (DPL == 8) { const u32x4 x = ld16(src); V.v[ks][j][0] = x.x; V.v[ks][j][1] = x.y; V.v[ks][j][2] = x.z; V.v[ks][j][3] = x.w; }
-      else if constexpr (DPL == 4) { const u32x2 x = *(const u32x2*)src; V.v[ks][j][0] = x.x; V.v[ks][j][1] = x.y; }
-      else V.v[ks][j][0] = *(const unsigned*)src;
+      const typename KV::elem* src = vcol0 + (size_t)min(key0 + 32 * ks + 8 * kg + j, row_max) * kvrow + DPL * kn;
+      if constexpr (DPL == 8) { const u32x4 x = KV::ld8(src); V.v[ks][j][0] = x.x; V.v[ks][j][1] = x.y; V.v[ks][j][2] = x.z; V.v[ks][j][3] = x.w; }
+      else if constexpr (DPL == 4) { const u32x2 x = KV::ld4(src); V.v[ks][j][0] = x.x; V.v[ks][j][1] = x.y; }
+      else V.v[ks][j][0] = KV::ld2(src);
     }
 }
 // Rows past the context may be uninitialised memory (NaN bit patterns; 0 x NaN = NaN on the matrix cores): zero them.
@@ -1250,14 +1279,14 @@ ZN_DEVINL void attn_block_mask_v(AttnV<HD>& V, int key0, int L, int lane) {
 // and staged per wave in padded LDS, where the MFMA B fragments are read back conflict-free) -> S[head][key] = Q K^T as 16x16x32 tiles
 // (attn_scores_kernel's operands and order) into sc, the wave's maxima into bm[wave].  nk: keys of the block inside the context.
 template <int HD> struct AttnFusedK { static constexpr int KLD = HD + 8, LPK = HD / 8, KPL = 64 / LPK, NLD = 16 / KPL, TPW = 512 / 16 / 8; };
-template <int HD>
-ZN_DEVINL void attn_fused_load_k(u32x4 (&kk)[AttnFusedK<HD>::TPW][AttnFusedK<HD>::NLD], const bf16_t* kcol0, size_t kvrow, int tb, int row_max, int wave, int lane) {
+template <int HD, class KV = AttnKvBf16>
+ZN_DEVINL void attn_fused_load_k(u32x4 (&kk)[AttnFusedK<HD>::TPW][AttnFusedK<HD>::NLD], const typename KV::elem* kcol0, size_t kvrow, int tb, int row_max, int wave, int lane) {
   using C = AttnFusedK<HD>;
   const int kq = lane / C::LPK, kd = lane % C::LPK;
 #pragma unroll
   for (int tl = 0; tl < C::TPW; ++tl)
 #pragma unroll
-    for (int i = 0; i < C::NLD; ++i) kk[tl][i] = ld16(kcol0 + kd * 8 + (size_t)min(tb + (tl * 8 + wave) * 16 + C::KPL * i + kq, row_max) * kvrow);
+    for (int i = 0; i < C::NLD; ++i) kk[tl][i] = KV::ld8(kcol0 + kd * 8 + (size_t)min(tb + (tl * 8 + wave) * 16 + C::KPL * i + kq, row_max) * kvrow);
 }
 template <int HD, int G>
 ZN_DEVINL void attn_fused_scores(const zn_bf16x8 (&qa)[HD / 32], const u32x4 (&kk)[AttnFusedK<HD>::TPW][AttnFusedK<HD>::NLD], bf16_t* kw, float (*sc)[512],
@@ -1301,8 +1330,8 @@ ZN_DEVINL void attn_fused_scores(const zn_bf16x8 (&qa)[HD / 32], const u32x4 (&k
 //   columns - every output column keeps its arithmetic (a column of P.V depends on P and its own V column only), the K rows are read DS times
 //   (the second reader of a pair sits 8 workgroups later, i.e. on the same XCD's L2 as dispatch goes), the V read per CU halves: a CU sustains
 //   only a few tens of GB/s and 16 rows x 4 kv heads are 64 workgroups.
-template <int HD, int G, bool FUSED, int DS = 1>
-__global__ __launch_bounds__(512) void attn_block_kernel(AttnArgs a) {
+template <int HD, int G, bool FUSED, int DS, class KV>
+ZN_DEVINL void attn_block_body(const AttnArgs& a) {
   constexpr int NW = 8, GL = (G + 3) / 4, HDV = HD / DS;
   static_assert(HD % DS == 0 && HDV % 32 == 0, "value-column split");
   int kvh, r, jb, hv = 0;
@@ -1324,7 +1353,7 @@ __global__ __launch_bounds__(512) void attn_block_kernel(AttnArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int vsub = lane & 3;
   const size_t kvrow = (size_t)2 * a.n_heads_kv * HD;
-  const bf16_t* kvr = a.kv + (size_t)r * a.max_len * kvrow;
+  const typename KV::elem* kvr = KV::cache(a) + (size_t)r * a.max_len * kvrow;
   const int tb = jb * 512;
   __shared__ float s_sc[G][512];
   __shared__ __attribute__((aligned(16))) bf16_t s_p[G][512];
@@ -1332,7 +1361,7 @@ __global__ __launch_bounds__(512) void attn_block_kernel(AttnArgs a) {
   __shared__ float s_l[NW][G];
   __shared__ float s_bm[NW][G];
   AttnV<HDV> V;
-  attn_block_load_v<HDV>(V, kvr + (size_t)(a.n_heads_kv + kvh) * HD + hv * HDV, kvrow, tb + wave * 64, a.max_len - 1, lane);
+  attn_block_load_v<HDV, KV>(V, kvr + (size_t)(a.n_heads_kv + kvh) * HD + hv * HDV, kvrow, tb + wave * 64, a.max_len - 1, lane);
   float mnew[GL];
   int L, nb;
   if constexpr (FUSED) {
@@ -1350,7 +1379,7 @@ __global__ __launch_bounds__(512) void attn_block_kernel(AttnArgs a) {
     using KC = AttnFusedK<HD>;
     __shared__ __attribute__((aligned(16))) bf16_t s_k[NW][16 * KC::KLD];
     u32x4 kk[KC::TPW][KC::NLD];
-    attn_fused_load_k<HD>(kk, kvr + (size_t)kvh * HD, kvrow, 0, a.max_len - 1, wave, lane);
+    attn_fused_load_k<HD, KV>(kk, kvr + (size_t)kvh * HD, kvrow, 0, a.max_len - 1, wave, lane);
     __builtin_amdgcn_sched_barrier(0);
     L = Lraw + 1; nb = 1;
     stamp();
@@ -1499,6 +1528,9 @@ __global__ __launch_bounds__(512) void attn_block_kernel(AttnArgs a) {
     }
   }
 }
+
+template <int HD, int G, bool FUSED, int DS = 1>
+__global__ __launch_bounds__(512) void attn_block_kernel(AttnArgs a) { attn_block_body<HD, G, FUSED, DS, AttnKvBf16>(a); }
 
 // (Measured and dropped, round 4: a one-launch shape that walks TWO blocks per workgroup - scores, e / P, P.V per block, the recurrence in the
 // split shape's arithmetic; bit-identical - for 5..16 rows at 513..1024 keys: 1.699 vs 1.697 ms per batch-8 step.  One CU then pulls the K rows

@@ -61,6 +61,21 @@ ZN_DEVINL unsigned fp8_encode(bf16_t w, float inv_scale) {
   return sign | (code > 0x7eu ? 0x7eu : code);                         // beyond 464: saturate at 448 (never a NaN code)
 }
 
+// ---- the FP8 KV cache (kv_round_e4m3 of zonos_amd/quant.py): a K or V element's code at scale exponent 0.  Finite values and the infinities
+// saturate at +-448; a NaN keeps its sign and becomes the NaN code.
+ZN_DEVINL unsigned kv_fp8_encode(bf16_t w) {
+  if ((w & 0x7fffu) > 0x7f80u) return ((w >> 8) & 0x80u) | 0x7fu;
+  return fp8_encode(w, 1.0f);
+}
+// A packed bf16 pair as the KV appends hold it -> the pair rounded to the E4M3 grid (one v_cvt_scalef32_pk_bf16_fp8 at scale 1 decodes the two
+// codes: the bits every FP8 reader of the cache widens them to) and its two codes (byte 0 = the low element).
+ZN_DEVINL unsigned kv_fp8_round_pair(unsigned pr, unsigned& codes) {
+  codes = kv_fp8_encode((bf16_t)(pr & 0xffffu)) | (kv_fp8_encode((bf16_t)(pr >> 16)) << 8);
+  return fp8x4_to_bf16(codes, 1.0f).x;
+}
+// 2 / 4 / 8 codes -> as many bf16 at scale 1 (the widening of the FP8 decode attention's loaders, zn_attn_fp8_kernels.h)
+ZN_DEVINL unsigned kv_fp8x2_to_bf16(unsigned v) { return fp8x4_to_bf16(v, 1.0f).x; }
+
 // One workgroup (256 threads) per weight row: row amax, exponent, codes.  K a multiple of 8.  Load time, not the hot path.
 __global__ __launch_bounds__(256) void fp8_quantize_rows_kernel(const bf16_t* __restrict__ W, int K, uint8_t* __restrict__ q, int8_t* __restrict__ exps) {
   __shared__ unsigned s_max[4];

@@ -325,8 +325,11 @@ __global__ __launch_bounds__(256) void gemm_bf16s_kernel(GemmArgs a) {
 // ------------------------------------------------------------------------------------------------ row-wise pieces
 // q|k|v split, interleaved-pair RoPE (fp32, separate roundings) and KV append for all positions (_torch.py:399-411).
 // qkv [R][S][nq + 2*nkv]: q is rotated in place, k (rotated) and v go to the cache at position base + s.
+// kv_round != 0 (the FP8 KV cache in effect): k and v are rounded to the E4M3 grid first and kv8 (may be NULL) receives their codes, as in gemv_epilogue<EPI_ROPE_KV>.
 __global__ __launch_bounds__(256) void rope_kv_rows_kernel(bf16_t* qkv, bf16_t* kv, const float* rope, int S, int base, int max_len, int n_heads,
-                                                           int n_heads_kv, int hd, int rope_positions) {
+                                                           int n_heads_kv, int hd, int rope_positions, uint8_t* kv8, int kv_round) {
+  GemvArgs ka{};
+  ka.kv = kv; ka.kv8 = kv8; ka.kv_round = kv_round;
   const int s = blockIdx.x, r = blockIdx.y;
   const int nq = n_heads * hd, nk = n_heads_kv * hd, ld = nq + 2 * nk;
   const int pos = base + s;
@@ -342,9 +345,9 @@ __global__ __launch_bounds__(256) void rope_kv_rows_kernel(bf16_t* qkv, bf16_t* 
       zn_rope_pair(x0, x1, cs, sn, re, im);
       const unsigned o = pack2(re, im);
       if (n < nq) *(unsigned*)(row + n) = o;
-      else if (pos < max_len) *(unsigned*)(kv + (((size_t)r * max_len + pos) * 2 + 0) * nk + (n - nq)) = o;
+      else if (pos < max_len) kv_append_pair(ka, (((size_t)r * max_len + pos) * 2 + 0) * nk + (n - nq), o);
     } else if (pos < max_len) {
-      *(unsigned*)(kv + (((size_t)r * max_len + pos) * 2 + 1) * nk + (n - nq - nk)) = pr;
+      kv_append_pair(ka, (((size_t)r * max_len + pos) * 2 + 1) * nk + (n - nq - nk), pr);
     }
   }
 }
@@ -781,7 +784,7 @@ __global__ __launch_bounds__(256) void assemble_prefill_kernel(AssembleArgs a) {
 // Grid (n * halves, n_layer + 1, ZN_ADMIT_PARTS): workgroup (i, li, z) copies every ZN_ADMIT_PARTS-th 16-byte piece of layer li's bytes; the plane
 // y == n_layer gathers and writes the words.  Nothing of a row that is not named is touched.
 #define ZN_ADMIT_PARTS 4
-struct AdmitLayer { const void* src; void* dst; int kind; int pad; };       // kind 0: KV cache, 1: Mamba2 conv + SSM state buffer
+struct AdmitLayer { const void* src; void* dst; int kind; int pad; void* dst8; };       // kind 0: KV cache, 1: Mamba2 conv + SSM state buffer; dst8: the session's code cache of the layer (FP8 KV cache in effect), or NULL
 struct AdmitArgs {
   const AdmitLayer* layers; int n_layer;
   int n, halves, B;                        // requests of this admission, rows per request, slots of the session
@@ -798,6 +801,18 @@ struct AdmitArgs {
   int *lengths, *remaining, *stopping, *shift, *step0;
   zn_row_params* rows;
 };
+// The codes of `bytes` bytes of K/V that the admission's prefill has already rounded to the E4M3 grid: encoding such a value gives back its code.
+ZN_DEVINL void admit_codes(const void* src, void* dst8, size_t bytes, int part, int parts) {
+  const u32x4* sp = (const u32x4*)src;
+  u32x2* dp = (u32x2*)dst8;
+  for (size_t k = (size_t)part * 256 + threadIdx.x; k < bytes / 16; k += (size_t)parts * 256) {
+    const u32x4 v = sp[k];
+    unsigned c[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { c[2 * j] = kv_fp8_encode((bf16_t)(v[j] & 0xffffu)); c[2 * j + 1] = kv_fp8_encode((bf16_t)(v[j] >> 16)); }
+    dp[k] = u32x2{c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24), c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24)};
+  }
+}
 ZN_DEVINL void admit_copy(const void* src, void* dst, size_t bytes, int part, int parts) {
   const u32x4* sp = (const u32x4*)src;
   u32x4* dp = (u32x4*)dst;
@@ -810,6 +825,7 @@ __global__ __launch_bounds__(256) void admit_rows_kernel(AdmitArgs a) {
     const AdmitLayer L = a.layers[li];
     if (L.kind == 0) {
       admit_copy((const char*)L.src + (size_t)i * a.S * a.kv_row_bytes, (char*)L.dst + (size_t)r * a.max_len * a.kv_row_bytes, (size_t)len * a.kv_row_bytes, z, ZN_ADMIT_PARTS);
+      if (L.dst8) admit_codes((const char*)L.src + (size_t)i * a.S * a.kv_row_bytes, (char*)L.dst8 + (size_t)r * a.max_len * (a.kv_row_bytes / 2), (size_t)len * a.kv_row_bytes, z, ZN_ADMIT_PARTS);
     } else {
       admit_copy((const char*)L.src + (size_t)i * a.conv_row_bytes, (char*)L.dst + (size_t)r * a.conv_row_bytes, a.conv_row_bytes, z, ZN_ADMIT_PARTS);
       admit_copy((const char*)L.src + a.ssm_off_src + (size_t)i * a.ssm_row_bytes, (char*)L.dst + a.ssm_off_dst + (size_t)r * a.ssm_row_bytes, a.ssm_row_bytes, z, ZN_ADMIT_PARTS);

@@ -24,6 +24,7 @@ from .backbone import BACKBONES, HipEngine
 from .codebook_pattern import revert_delay_pattern
 from .conditioning import ConditioningCache, PrefixConditioner, prepare_conditioning_with_cache
 from .config import InferenceParams, ZonosConfig
+from .quant import KV_FP8_MIN_ROWS
 from .rows import (GenCall, GenRequest, Hooks, check_request_shapes, code_rows, draw_seed, finalise_codes, finalise_row, map_codes, row_end_offset,  # noqa: F401
                    sampling_struct as _sampling_struct, stop_check_at)
 from .serving import ServeChunk, ServeResult, SlotScheduler, StreamLedger, check_serve_request, release_limit  # noqa: F401
@@ -111,6 +112,7 @@ class Zonos(nn.Module):
         self.mlp_weights = "bf16"                     # "fp8" after quantize_mlp_fp8()
         self.mamba_weights = "bf16"                   # "fp8" after quantize_mamba_fp8()
         self.fp8_small_rows = False                   # decode steps of 1..4 rows on the launches path read an attached FP8 stream too (set_fp8_small_rows)
+        self.kv_cache = "bf16"                        # "fp8" after set_kv_cache("fp8"): generations of 5 rows and more keep an E4M3 copy of K/V for the decode attention
 
     # ------------------------------------------------------------------ loading
     @property
@@ -128,16 +130,18 @@ class Zonos(nn.Module):
 
     @classmethod
     def from_local(cls, config_path: str, model_path: str, device: str = DEFAULT_DEVICE, backbone: str | None = None,
-                   mlp_weights: str = "bf16", mamba_weights: str = "bf16", fp8_small_rows: bool = False) -> "Zonos":
+                   mlp_weights: str = "bf16", mamba_weights: str = "bf16", fp8_small_rows: bool = False, kv_cache: str = "bf16") -> "Zonos":
         """model.py:128-176: bf16 model, embeddings zero-padded to the 1032-row tables, heads.{i} fused.  mlp_weights="fp8":
         quantize_mlp_fp8() after loading (lossy with respect to the checkpoint; see there); mamba_weights="fp8": quantize_mamba_fp8() (the
-        hybrid checkpoint; likewise); fp8_small_rows: set_fp8_small_rows() (decode steps of 1..4 rows read the stream too); the defaults
-        change nothing."""
+        hybrid checkpoint; likewise); fp8_small_rows: set_fp8_small_rows() (decode steps of 1..4 rows read the stream too); kv_cache="fp8":
+        set_kv_cache("fp8") (lossy with respect to the bf16 model; see there); the defaults change nothing."""
         import safetensors
         if mlp_weights not in ("bf16", "fp8"):
             raise _lib.ZonosHipError(f"mlp_weights must be 'bf16' or 'fp8', not {mlp_weights!r}")
         if mamba_weights not in ("bf16", "fp8"):
             raise _lib.ZonosHipError(f"mamba_weights must be 'bf16' or 'fp8', not {mamba_weights!r}")
+        if kv_cache not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache must be 'bf16' or 'fp8', not {kv_cache!r}")
         config = ZonosConfig.from_dict(json.load(open(config_path)))
         backbone_cls = BACKBONES[backbone] if backbone else DEFAULT_BACKBONE_CLS
         model = cls(config, backbone_cls).to(device, torch.bfloat16)
@@ -167,6 +171,8 @@ class Zonos(nn.Module):
             model.quantize_mamba_fp8()
         if fp8_small_rows:
             model.set_fp8_small_rows(True)
+        if kv_cache == "fp8":
+            model.set_kv_cache("fp8")
         return model
 
     @torch.inference_mode()
@@ -252,6 +258,52 @@ class Zonos(nn.Module):
         self.backbone._engine = None
         return self
 
+    def set_kv_cache(self, mode: str) -> "Zonos":
+        """"fp8": generations and serving sessions whose decode step has 5 rows or more (three guided utterances, five unguided ones) round K (after RoPE)
+        and V to the E4M3 grid at every KV append (zonos_amd/quant.py kv_round_e4m3: no scale, saturation at +-448), keep the rounded values in the
+        bf16 cache - the prefill attention and every other reader see them - and the one-byte codes in a second cache, which the decode attention reads:
+        half the K/V bytes per step.  Lossy with respect to the bf16 model (relative error up to 2^-4 per K/V element, absolute floor 2^-10), exact with
+        respect to its own rounded cache; its effect on audio quality is unmeasured.  It costs memory today: 1.5 x the KV bytes (the bf16 copy stays).
+        With fewer rows the mode is inert (generate(batch_size <= 2), stream()).  "bf16" (the default) switches it off.  A hybrid model raises ValueError.
+        Cached engines are dropped."""
+        if mode not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache must be 'bf16' or 'fp8', not {mode!r}")
+        if mode == "fp8" and self.config.backbone.ssm_cfg:
+            raise ValueError("kv_cache='fp8': the hybrid stack's attention layers keep a bf16 KV cache")
+        self.kv_cache = mode
+        self._engine = self._spare = None
+        self.backbone._engine = None
+        return self
+
+    def kv_fp8_plan(self, rows: int) -> dict:
+        """What a generation whose decode step has `rows` rows (two per guided utterance) does with its K/V as this model is set now: {"rounded": whether
+        the appends round to the E4M3 grid and keep the code cache, "attention_reads": "fp8" where the decode attention reads the codes, else "bf16"}."""
+        rows = int(rows)
+        if rows < 1:
+            raise ValueError("kv_fp8_plan: rows must be >= 1")
+        rounded = self.kv_cache == "fp8" and not self.config.backbone.ssm_cfg and rows >= KV_FP8_MIN_ROWS
+        reads = rounded
+        if rounded and self._engine is not None:      # (an engine's tune keys - ZN_TUNE_KV_FP8 = 2 - and the library's own plan decide where one exists)
+            out = (C.c_int32 * 2)()
+            self._engine.call("zn_kv_fp8_plan", rows, out)
+            rounded, reads = bool(out[0]), bool(out[1])
+        return {"rounded": rounded, "attention_reads": "fp8" if reads else "bf16"}
+
+    def _bind_kv_codes(self, eng: HipEngine, rows: int, max_len: int):
+        """The code caches of the generation just begun on `eng` (zn_gen_bind_kv_fp8) where the FP8 KV cache is in effect for `rows` rows: one uint8
+        tensor [rows, max_len, 2, Hkv, hd] per layer, which the caller keeps alive to the generation's end; else None."""
+        if self.kv_cache != "fp8":
+            return None
+        out = (C.c_int32 * 2)()
+        eng.call("zn_kv_fp8_plan", rows, out)
+        if not out[0]:
+            return None
+        n_layer = self.config.backbone.n_layer
+        per = int(eng.lib.zn_kv_fp8_bytes_per_layer(C.byref(eng.zc), rows, max_len))
+        codes = [torch.empty(per, dtype=torch.uint8, device=self.device) for _ in range(n_layer)]
+        eng.call("zn_gen_bind_kv_fp8", (C.c_void_p * n_layer)(*[t.data_ptr() for t in codes]))
+        return codes
+
     def mamba_fp8_plan(self, rows: int) -> dict:
         """Whether in_proj and out_proj of the Mamba2 layers would read the FP8 stream in a decode step of `rows` rows (two per guided
         utterance) as this model's engine runs it now: {"in_proj": bool, "out_proj": bool}; both False before quantize_mamba_fp8(), up to
@@ -283,6 +335,8 @@ class Zonos(nn.Module):
                         eos_id=self.eos_token_id, mask_id=self.masked_token_id)
         if self.fp8_small_rows:      # (every engine of the model: the cached one and the spare)
             eng.call("zn_debug_tune", _lib.ZN_TUNE_FP8_SMALL_ROWS, 2)
+        if self.kv_cache == "fp8":
+            eng.call("zn_set_kv_fp8", 1)
         return eng
 
     def engine(self, batch_size: int = 1) -> HipEngine:
@@ -645,6 +699,7 @@ class Zonos(nn.Module):
         eng.call("zn_gen_begin", B, kv_ptrs, ip.max_seqlen, ip.lengths_per_sample.data_ptr(), delayed.data_ptr(), t_total, P + 1,
                  call.max_new_tokens, float(call.cfg_scale), C.byref(call.sp), st)
         try:
+            kv_codes = self._bind_kv_codes(eng, call.engine_rows, ip.max_seqlen)      # noqa: F841  (alive until zn_gen_end)
             if call.table is not None:
                 eng.call("zn_gen_set_rows", call.table, B)
             if call.ragged:

@@ -31,6 +31,7 @@ import torch
 
 E4M3_MAX = 448.0
 EXP_MIN, EXP_MAX = -100, 100
+KV_FP8_MIN_ROWS = 5          # the FP8 KV cache (Zonos.set_kv_cache) is in effect from this many rows per decode step on; below it is inert
 
 
 def e4m3_value_table() -> torch.Tensor:
@@ -93,3 +94,23 @@ def quantize_rows_fp8(W: torch.Tensor):
     v = torch.ldexp(wd.abs(), (-k).expand_as(wd))
     q = encode_e4m3(v, torch.signbit(wd))
     return q, exp, dequantize_rows_fp8(q, exp)
+
+
+def kv_round_e4m3(x: torch.Tensor):
+    """The FP8 KV cache's rounding (Zonos.set_kv_cache("fp8"); the KV appends of zonos_amd/csrc are tested against it bit for bit).
+    x: bf16, any shape -> (codes uint8, dequantised bf16), both of x's shape.
+
+    The element rounding of the weight format above at scale exponent 0: code = RNE_e4m3fn(x), value(code) exact in bf16.  No scale is
+    applied - the fused append epilogue holds two elements of a head vector per thread and cannot take an absmax (per-layer static scales
+    are a possible follow-up).  Finite values beyond +-448 saturate there, and so do the infinities; a NaN keeps its sign and takes the NaN
+    code (0x7F / 0xFF), whose dequantised value is a NaN.  The sign bit is kept (-0 and negative values that round to zero give 0x80).
+    |dq - x| <= 2^-4 |x| for 2^-6 <= |x| <= 448 (half an ulp of 3 mantissa bits), <= 2^-10 below (half of the subnormal step 2^-9).
+    Idempotent: the dequantised values round to themselves and to the same codes."""
+    assert x.dtype == torch.bfloat16
+    xd = x.detach().cpu().to(torch.float64)
+    nan = torch.isnan(xd)
+    neg = torch.signbit(xd)
+    q = encode_e4m3(torch.where(nan, torch.zeros_like(xd), xd.abs()), neg)
+    q = torch.where(nan, torch.full_like(q, 0x7F) | (neg.to(torch.uint8) << 7), q)
+    dq = e4m3_value_table()[q.long()].to(torch.float32).to(torch.bfloat16)
+    return q, dq

@@ -50,6 +50,7 @@ class ServeSession:
             eng.call("zn_gen_begin", self.slots, kv_ptrs, ip.max_seqlen, ip.lengths_per_sample.data_ptr(), self.delayed.data_ptr(), self.width, 1,
                      shape.max_new_tokens, 2.0 if self.guided else 1.0, C.byref(sp), self.st)
             self.begun = True
+            self.kv_codes = model._bind_kv_codes(eng, self.R, ip.max_seqlen)          # (FP8 KV cache: the code caches live as long as the session)
             eng.call("zn_gen_open_slots", self.slack)
 
     def close(self) -> None:
