@@ -162,7 +162,8 @@ size_t zn_mamba_state_bytes_per_layer(const zn_config* cfg, int32_t rows, size_t
  * (device, zeroed by the caller), the delay-patterned code buffer int32 [B, n_codebooks, t_total] with -1 for
  * unknown (model.py:414-420), the first column to write `offset0` = prefix_len + 1, cfg_scale and sampling.
  * R = 2B rows [cond ‖ uncond] with guidance; cfg_scale == 1: R = B conditional rows and no CFG mix (model.py:230).
- * R <= max_rows. */
+ * R <= max_rows.  kv_layers_dev may be NULL, or hold NULL entries, exactly in a codes-only generation (zn_set_kv_fp8_only in effect for R rows): it has no bf16
+ * caches, and pointers passed anyway are never read or written. */
 /* (zn_gen_begin discards the hipGraphs captured for the previous generation: call it only when that generation's steps have drained from
  * their stream - `Zonos.generate` synchronises before it returns.) */
 int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_layers_dev, int32_t max_len,
@@ -359,7 +360,8 @@ enum zn_tune_key {
                                        here too.  Same bits either way; the persistent kernels always read the bf16 copy, and the key never changes the path a
                                        generation takes */
   ZN_TUNE_KV_FP8 = 25,              /* 2 = the decode attention ignores the code cache of zn_set_kv_fp8 and reads the bf16 cache; the appends still round and still write both
-                                       caches, so the result is the same bits.  The key never changes the path a generation takes */
+                                       caches, so the result is the same bits.  The key never changes the path a generation takes.  Ignored for a codes-only generation
+                                       (zn_set_kv_fp8_only): it has no bf16 cache to read, and its plans report the codes */
   ZN_TUNE_NKEYS = 26
 };
 /* Values of ZN_TUNE_HOOK.  The first three arm the next zn_gen_begin, which consumes them. */
@@ -500,7 +502,7 @@ int zn_mamba_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
  * rope_kv_rows_kernel, an admission's prefill) rounds K (after RoPE) and V to the E4M3 grid, writes the dequantised bf16 values into the cache of zn_gen_begin, so that every
  * reader, the prefill attention included, sees the rounded values, and writes the one-byte codes into a second cache uint8 [rows][max_len][2][Hkv][hd] per layer, which
  * the decode attention then reads instead (half the bytes, the same bits).  With fewer rows the mode is inert: nothing is rounded (the persistent kernels and the
- * 1..4-row GEMV).  The bf16 cache stays allocated and current: the mode costs 1.5 x the KV bytes. */
+ * 1..4-row GEMV).  The bf16 cache stays allocated and current: the mode costs 1.5 x the KV bytes, unless zn_set_kv_fp8_only (below) drops the bf16 cache. */
 /* on != 0 switches the mode on for the generations begun afterwards.  ZN_ERR_UNSUPPORTED: a hybrid handle (arch 1: its attention layers stay bf16).  ZN_ERR_STATE: between
  * zn_gen_begin and zn_gen_end.  Drops the captured graphs. */
 int zn_set_kv_fp8(zn_handle h, int32_t on);
@@ -513,10 +515,23 @@ int zn_gen_bind_kv_fp8(zn_handle h, const void* const* codes_layers_dev);
 /* out[0]: whether a generation of `rows` rows begun on this handle now rounds its K/V (the mode is on and in effect at that row count); out[1]: whether its decode
  * attention reads the codes (out[0], ZN_TUNE_KV_FP8 != 2, and the row count is one the plan has not declined: see DESIGN.md 4.1k). */
 int zn_kv_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
+/* Codes only: a second flag that matters only in a generation where the FP8 KV cache is in effect (zn_set_kv_fp8 on, transformer, 5 rows or more).  Such a
+ * generation keeps no bf16 cache: the bound code caches (zn_gen_bind_kv_fp8) are its only KV storage - half the bytes of the bf16 model's cache, a third of the two-cache
+ * mode's - and the same bits as the two-cache mode everywhere.  zn_gen_begin then accepts kv_layers_dev == NULL or NULL entries, and neither reads nor writes what is passed
+ * anyway; every KV append writes the codes alone; the decode attention and the prefill attention (FP8 forms of both prefill kernels, zn_prefill_attn_fp8_kernels.h) read them;
+ * an admission's library-owned scratch cache holds codes.  Without bound code caches the prefill, admissions and decode steps return ZN_ERR_STATE, as in the two-cache
+ * mode: never a silent bf16 generation.  ZN_TUNE_KV_FP8 = 2 is ignored for such a generation.  With the FP8 KV cache off or not in effect the flag changes nothing.
+ * The refusals of zn_set_kv_fp8: ZN_ERR_UNSUPPORTED on a hybrid handle, ZN_ERR_STATE between zn_gen_begin and zn_gen_end.  Drops the captured graphs. */
+int zn_set_kv_fp8_only(zn_handle h, int32_t on);
+/* out[0], out[1]: as zn_kv_fp8_plan (rounded; the decode attention reads the codes); out[2]: whether a generation of `rows` rows begun on this handle now needs the bf16
+ * caches of zn_gen_begin (0: codes only). */
+int zn_kv_cache_plan(zn_handle h, int32_t rows, int32_t out[3]);
 /* Per-op tests: while codes_dev != NULL, zn_op_linear_fused's RoPE + KV append (decode and prefill epilogue) and zn_op_rope_kv_rows round and write the codes of the cache
  * they append to into codes_dev (same rows and max_len as that cache), and zn_op_attn_decode reads codes_dev where zn_kv_fp8_plan's out[1] would be 1 for its row count
  * with the mode on.  NULL (the default) restores the bf16 behaviour.  Independent of zn_set_kv_fp8. */
 int zn_op_bind_kv_fp8(zn_handle h, void* codes_dev);
+/* While a code cache is bound, the bf16 cache of those entry points may be NULL: zn_op_linear_fused's RoPE + KV append and zn_op_rope_kv_rows then write the codes alone,
+ * and zn_op_attn_decode accepts kv_dev == NULL where it reads the codes.  Without a bound code cache (or where the codes are not read) a NULL cache stays ZN_ERR_ARG. */
 /* The prefill's row-wise split + RoPE + KV append alone (rope_kv_rows_kernel, what follows a projection whose plan reports ZN_LP_ROPE_DONE = 0): qkv bf16
  * [rows][S][(Hq + 2 Hkv) hd], q rotated in place, k and v to positions base .. base + S - 1 of kv [rows][max_len][2][Hkv][hd]; positions at or past max_len write nothing. */
 int zn_op_rope_kv_rows(zn_handle h, void* qkv_dev, void* kv_dev, int32_t max_len, int32_t S, int32_t base, int32_t rows, zn_stream stream);
@@ -560,6 +575,11 @@ int zn_op_attn_prefill(zn_handle h, const void* q_dev, const void* kv_dev, int32
  * read as keys nor written.  Refused before any launch: base < 0, base + positions > max_len, a null pointer, rows > max_rows. */
 int zn_op_attn_prefill_rows(zn_handle h, const void* q_dev, const void* kv_dev, int32_t max_len, void* out_dev, int32_t positions,
                             int32_t rows, int32_t base, const int32_t* row_len_dev, zn_stream stream);
+/* The same call on a code cache uint8 [rows, max_len, 2, Hkv, hd] of E4M3 codes (the FP8 KV cache's format, zn_set_kv_fp8): the FP8 forms of the two prefill
+ * attention kernels, which a codes-only generation (zn_set_kv_fp8_only) runs.  The output has the bits of zn_op_attn_prefill_rows on the dequantised codes.  The same
+ * refusals.  Additive to ABI 9: look the symbol up. */
+int zn_op_attn_prefill_rows_fp8(zn_handle h, const void* q_dev, const void* codes_dev, int32_t max_len, void* out_dev, int32_t positions,
+                                int32_t rows, int32_t base, const int32_t* row_len_dev, zn_stream stream);
 /* mamba_ssm layer_norm_fn(prenorm=True) of the hybrid Block: s = h + res (fp32), res <- bf16(s) in place (res NULL:
  * s = h), out = bf16(LayerNorm(s)).  h/out bf16 [rows, d].  flags bit 0: RMSNorm instead of LayerNorm (rms_norm; b may be
  * NULL), bit 1: res is float [rows, d] and keeps the unrounded sum (residual_in_fp32). */

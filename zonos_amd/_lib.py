@@ -170,6 +170,8 @@ SIGNATURES = {
     "zn_kv_fp8_bytes_per_layer": (C.c_size_t, [C.POINTER(zn_config), C.c_int32, C.c_int32]),
     "zn_gen_bind_kv_fp8": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "zn_kv_fp8_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "zn_set_kv_fp8_only": (C.c_int, [C.c_void_p, C.c_int32]),
+    "zn_kv_cache_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "zn_op_bind_kv_fp8": (C.c_int, [C.c_void_p, C.c_void_p]),
     "zn_op_rope_kv_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "zn_decode_rows_plan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
@@ -183,6 +185,7 @@ SIGNATURES = {
     "zn_op_backbone_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "zn_op_attn_prefill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "zn_op_attn_prefill_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "zn_op_attn_prefill_rows_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "zn_op_attn_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "zn_op_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "zn_op_add_layernorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),

@@ -9,6 +9,7 @@
 #include "zn_chain_kernel.h"
 #include "zn_step_kernel.h"
 #include "zn_prefill_kernels.h"
+#include "zn_prefill_attn_fp8_kernels.h"
 #include "zn_cond_kernels.h"
 #include "zn_mamba_kernels.h"
 
@@ -48,6 +49,7 @@ struct zn_handle_s {
   std::vector<MambaFp8> mamba_fp8;
   // FP8 KV cache (zn_set_kv_fp8): the mode, this generation's code caches (zn_gen_bind_kv_fp8; empty: none bound) and the code cache of the per-op entry points
   bool kv_fp8 = false;
+  bool kv_fp8_only = false;          // zn_set_kv_fp8_only: where the FP8 KV cache is in effect, the code caches are the only KV storage (no bf16 cache)
   std::vector<const void*> kv8_layers;
   uint8_t* op_kv8 = nullptr;
   const void* heads = nullptr;
@@ -659,7 +661,12 @@ static bool kv_fp8_gen(zn_handle h) { return h->kv_fp8 && kv_fp8_rows(h, h->rows
 static uint8_t* kv8_of(zn_handle h, int li) { return kv_fp8_gen(h) && !h->kv8_layers.empty() ? (uint8_t*)const_cast<void*>(h->kv8_layers[li]) : nullptr; }
 // The decode attention's side of the plan, in one place: does an attention launch over `rows` rows that has a code cache read it?  ZN_TUNE_KV_FP8 = 2: never (the bf16
 // cache holds the dequantised codes: the same bits).  No row count is declined: the FP8 reads have not been measured against the bf16 reads yet (tools/kvfp8bench.py).
-static bool kv_fp8_attn_reads(zn_handle h, int rows) { return h->tune[ZN_TUNE_KV_FP8] != 2 && kv_fp8_rows(h, rows); }
+// codes_only: there is no bf16 cache to read instead (a codes-only generation, a per-op call without one): the key is ignored.
+static bool kv_fp8_attn_reads(zn_handle h, int rows, bool codes_only = false) { return (codes_only || h->tune[ZN_TUNE_KV_FP8] != 2) && kv_fp8_rows(h, rows); }
+// Codes only (zn_set_kv_fp8_only): a generation in which the FP8 KV cache is in effect on a handle with the second flag on keeps no bf16 cache - the
+// appends write the codes alone, the decode and the prefill attention read them, an admission's scratch cache holds codes.
+static bool kv_codes_only_rows(zn_handle h, int rows) { return h->kv_fp8 && h->kv_fp8_only && kv_fp8_rows(h, rows); }
+static bool kv_codes_only_gen(zn_handle h) { return kv_codes_only_rows(h, h->rows); }
 static int kv_fp8_bound(zn_handle h, const char* who) {
   if (kv_fp8_gen(h) && h->kv8_layers.empty()) ZN_FAIL(h, ZN_ERR_STATE, "%s: the FP8 KV cache is in effect (zn_set_kv_fp8, %d rows) and no code caches are bound (zn_gen_bind_kv_fp8)", who, h->rows);
   return ZN_OK;
@@ -691,7 +698,8 @@ static int run_attention(zn_handle h, const bf16_t* q, const bf16_t* kv, int max
   a.q = q; a.kv = kv; a.lengths = lengths; a.ext = ext; a.ext_scalar = ext_scalar; a.max_len = max_len;
   a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv; a.lcap = h->lcap; a.scale = (float)(1.0 / std::sqrt((double)h->hd));
   a.scores = h->scores; a.cmax = h->cmax; a.out = out; a.rows = rows; a.stamps = stamps;
-  a.kv8 = kv8 && kv_fp8_attn_reads(h, rows) ? kv8 : nullptr;      // kv8: the code cache of `kv` (the FP8 KV cache in effect), or NULL
+  a.kv8 = kv8 && kv_fp8_attn_reads(h, rows, kv == nullptr) ? kv8 : nullptr;      // kv8: the code cache of `kv` (the FP8 KV cache in effect), or NULL; kv == NULL: codes only
+  if (!a.kv8 && !kv) ZN_FAIL(h, ZN_ERR_STATE, "attention: neither a bf16 cache nor a code cache it may read (%d rows)", rows);
   const int hd = h->hd;
   dim3 grid((max_len + ZN_ACHUNK - 1) / ZN_ACHUNK, c.n_heads_kv, rows);
   // fused: one launch for contexts of one 512-key block (the caller bounds the context: attn_fused_for); else: scores, then the P.V pass
@@ -1279,11 +1287,14 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
                             int32_t* delayed_codes_dev, int32_t t_total, int32_t offset0, int32_t max_new_tokens, float cfg_scale,
                             const zn_sampling* sp, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
-  if (!kv_layers_dev || !lengths_dev || !delayed_codes_dev || !sp) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_begin: null argument");
+  if (!lengths_dev || !delayed_codes_dev || !sp) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_begin: null argument");
   if (!h->has_io) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_begin: handle was created without embeddings/heads");
   // cfg_scale == 1: no guidance, one row per utterance (the reference's _compute_logits skips the mix, model.py:230); else [cond ‖ uncond]
   const int rows = cfg_scale == 1.0f ? batch : 2 * batch;
   if (batch < 1 || rows > h->max_rows) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_begin: batch %d needs %d rows, max_rows is %d", batch, rows, h->max_rows);
+  // a codes-only generation (zn_set_kv_fp8_only) has no bf16 caches: the argument may be NULL, and what it holds is never read or written
+  const bool codes_only = kv_codes_only_rows(h, rows);
+  if (!codes_only && !kv_layers_dev) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_begin: null argument");
   if (max_len < 1 || t_total < 1 || offset0 < 1 || offset0 >= t_total) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_begin: bad lengths");
   if (max_len > h->cfg.rope_positions)
     ZN_FAIL(h, ZN_ERR_ARG, "sequence length %d exceeds the %d-position RoPE table (zonos/backbone/_torch.py:206)", max_len, h->cfg.rope_positions);
@@ -1294,7 +1305,8 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   free_graph(h);
   h->batch = batch; h->rows = rows; h->max_len = max_len; h->t_total = t_total; h->offset0 = offset0; h->max_new = max_new_tokens;
   h->cfg_scale = cfg_scale; h->sp = *sp;
-  h->kv_layers.assign(kv_layers_dev, kv_layers_dev + h->cfg.n_layer);
+  if (codes_only) h->kv_layers.assign(h->cfg.n_layer, nullptr);
+  else h->kv_layers.assign(kv_layers_dev, kv_layers_dev + h->cfg.n_layer);
   h->kv8_layers.clear();
   h->lengths = lengths_dev; h->codes = delayed_codes_dev;
   // The hand-off tags are 32-bit and advance by n_layer per decode step (~41 hours of continuous batch-1 decoding): long before they
@@ -1378,38 +1390,44 @@ static int ensure_prefill_ws(zn_handle h, size_t M) {
   return ZN_OK;
 }
 
+// FP8: the same launches reading the code cache a.kv8 (zn_prefill_attn_fp8_kernels.h) - the form prefill_attention chose by leaving a code cache in the arguments.
+#define ZN_PA_LAUNCH(FP8, BF16, grid_) do { if (a.kv8) hipLaunchKernelGGL(FP8, grid_, dim3(256), 0, s, a); else hipLaunchKernelGGL(BF16, grid_, dim3(256), 0, s, a); } while (0)
 template <int HD>
 static int launch_prefill_attn(const PrefillAttnArgs& a, int G, int R, bool mfma, hipStream_t s) {
   if constexpr (HD == 128) {
     if (mfma) {   // both contractions on the matrix cores (same row semantics)
       dim3 grid((a.S + 64 / G - 1) / (64 / G), a.n_heads_kv, R);
       switch (G) {
-        case 1: hipLaunchKernelGGL((attn_prefill_mfma_kernel<1>), grid, dim3(256), 0, s, a); return 0;
-        case 2: hipLaunchKernelGGL((attn_prefill_mfma_kernel<2>), grid, dim3(256), 0, s, a); return 0;
-        case 4: hipLaunchKernelGGL((attn_prefill_mfma_kernel<4>), grid, dim3(256), 0, s, a); return 0;
-        case 8: hipLaunchKernelGGL((attn_prefill_mfma_kernel<8>), grid, dim3(256), 0, s, a); return 0;
+        case 1: ZN_PA_LAUNCH((attn_prefill_mfma_fp8_kernel<1>), (attn_prefill_mfma_kernel<1>), grid); return 0;
+        case 2: ZN_PA_LAUNCH((attn_prefill_mfma_fp8_kernel<2>), (attn_prefill_mfma_kernel<2>), grid); return 0;
+        case 4: ZN_PA_LAUNCH((attn_prefill_mfma_fp8_kernel<4>), (attn_prefill_mfma_kernel<4>), grid); return 0;
+        case 8: ZN_PA_LAUNCH((attn_prefill_mfma_fp8_kernel<8>), (attn_prefill_mfma_kernel<8>), grid); return 0;
       }
     }
   }
   switch (G) {
-#define ZN_PA(GG) case GG: hipLaunchKernelGGL((attn_prefill_kernel<HD, GG>), dim3((a.S + 64 / GG - 1) / (64 / GG), a.n_heads_kv, R), dim3(256), 0, s, a); return 0;
+#define ZN_PA(GG) case GG: ZN_PA_LAUNCH((attn_prefill_fp8_kernel<HD, GG>), (attn_prefill_kernel<HD, GG>), dim3((a.S + 64 / GG - 1) / (64 / GG), a.n_heads_kv, R)); return 0;
     ZN_PA(1) ZN_PA(2) ZN_PA(4) ZN_PA(8)
 #undef ZN_PA
   }
   return -1;
 }
+#undef ZN_PA_LAUNCH
 
 static int qsplit(int S) { return S >= 768 ? 256 : S >= 192 ? 64 : 32; }   // query split of the CPU flash kernel
 
 // All S positions at once: row-wise kernels over M = R*S rows, MFMA GEMMs, tiled exact causal attention.
 // causal attention of S prefill positions over the keys already written for them (SDPA is_causal=True, _torch.py:415)
 // row_len (device, [R]): right-padded rows, row r holds row_len[r] <= S positions; each row then takes the query split and key extents of its own length
+// kv8: the code cache of `kv`, or NULL.  The form is chosen here: the FP8 kernels read kv8 exactly where there is no bf16 cache (kv == NULL: a codes-only generation,
+// an admission's scratch cache of codes, zn_op_attn_prefill_rows_fp8); with both caches the bf16 kernels read kv, as before the codes-only mode existed.
 static int prefill_attention(zn_handle h, const bf16_t* q, int ldq, const bf16_t* kv, int max_len, bf16_t* out, int ldo, int S, int R,
-                             hipStream_t s, int base = 0, const int* row_len = nullptr) {
+                             hipStream_t s, int base = 0, const int* row_len = nullptr, const uint8_t* kv8 = nullptr) {
   const zn_config& c = h->cfg;
   const int hd = h->hd;
+  if (!kv && !kv8) ZN_FAIL(h, ZN_ERR_STATE, "prefill attention: neither a bf16 cache nor a code cache");
   PrefillAttnArgs pa{};
-  pa.q = q; pa.ldq = ldq; pa.kv = kv; pa.out = out; pa.ldo = ldo; pa.S = S; pa.base = base; pa.max_len = max_len;
+  pa.q = q; pa.ldq = ldq; pa.kv = kv; pa.kv8 = kv ? nullptr : kv8; pa.out = out; pa.ldo = ldo; pa.S = S; pa.base = base; pa.max_len = max_len;
   pa.n_heads = c.n_heads; pa.n_heads_kv = c.n_heads_kv; pa.qsplit = qsplit(S); pa.scale = (float)(1.0 / std::sqrt((double)hd));
   pa.row_len = row_len;
   const bool mfma = h->tune[ZN_TUNE_PREFILL_ATTN_VALU] != 2;   // 2: the VALU kernel at every head size
@@ -1424,6 +1442,7 @@ static int prefill_attention(zn_handle h, const bf16_t* q, int ldq, const bf16_t
 // every row by row_len[r]); RoPE and the KV append run over the pad positions too - cache slots at or past row_len[r], which the row's own
 // decode steps overwrite, one per step, before the attention's extent reaches them.
 // kv_round: the FP8 KV cache is in effect for these appends (rounded K/V into kv_layers); kv8_layers (may be NULL: an admission's scratch cache) receive the codes.
+// kv_layers NULL or NULL entries (codes only): the appends write kv8_layers alone and the attention reads them.
 static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, int R, const void* const* kv_layers, int max_len, int base, hipStream_t s,
                                     const int* row_len = nullptr, const void* const* kv8_layers = nullptr, bool kv_round = false) {
   const zn_config& c = h->cfg;
@@ -1433,7 +1452,7 @@ static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, in
   HIPCHK(h, hipMemcpyAsync(h->pf_x, hidden, (size_t)M * d * 2, hipMemcpyDeviceToDevice, s));
   for (int li = 0; li < c.n_layer; ++li) {
     const zn_layer_weights& lw = h->layers[li];
-    bf16_t* kv = (bf16_t*)kv_layers[li];
+    bf16_t* kv = kv_layers ? (bf16_t*)kv_layers[li] : nullptr;
     // short prompts (<= 64 rows): every projection streams its weights through a small-M kernel (10.7 -> ~2.5 ms per prefill); prefill_linear
     // (LayerNorm as gemm16k's prologue over four row groups: 22.0 us against 4.7 + 9 for the launch pair: 768 workgroups repeat the statistics)
     hipLaunchKernelGGL(layernorm_kernel, dim3(M), dim3(64), 0, s, h->pf_x, (const bf16_t*)lw.norm_w, (const bf16_t*)lw.norm_b, h->pf_n, d, c.norm_eps);
@@ -1444,7 +1463,7 @@ static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, in
     bool rope_done = false;
     if ((rc = prefill_linear<EPI_ROPE_KV>(h, g, M, s, true, &rope_done))) return rc;
     if (!rope_done) hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(S, R), dim3(256), 0, s, h->pf_qkv, kv, h->rope, S, base, max_len, c.n_heads, c.n_heads_kv, hd, c.rope_positions, g.kv8, g.kv_round);
-    rc = prefill_attention(h, h->pf_qkv, rope_done ? nq : nqkv, kv, max_len, h->pf_a, nq, S, R, s, base, row_len);
+    rc = prefill_attention(h, h->pf_qkv, rope_done ? nq : nqkv, kv, max_len, h->pf_a, nq, S, R, s, base, row_len, g.kv8);
     if (rc) return rc;
     if (c.double_out_proj && (rc = prefill_linear<EPI_STORE>(h, linear_args(h, lw.out_proj, d, nq, h->pf_a, h->pf_n, nullptr), M, s))) return rc;
     if ((rc = prefill_linear<EPI_RESID>(h, linear_args(h, lw.out_proj, d, nq, c.double_out_proj ? h->pf_n : h->pf_a, h->pf_x, h->pf_x), M, s))) return rc;
@@ -1746,7 +1765,8 @@ static int ensure_admit_cache(zn_handle h, int S, hipStream_t s) {
   if (S <= h->adm_cap_S) return ZN_OK;
   const zn_config& c = h->cfg;
   const int cap = ((S + 63) / 64) * 64;
-  const size_t attn = zn_kv_bytes_per_layer(&c, h->max_rows, cap), mamba = zn_mamba_state_bytes_per_layer(&c, h->max_rows, nullptr);
+  const bool codes_only = kv_codes_only_gen(h);      // the scratch cache holds codes: half the bytes
+  const size_t attn = codes_only ? zn_kv_fp8_bytes_per_layer(&c, h->max_rows, cap) : zn_kv_bytes_per_layer(&c, h->max_rows, cap), mamba = zn_mamba_state_bytes_per_layer(&c, h->max_rows, nullptr);
   const size_t per = ((attn > mamba ? attn : mamba) + 255) / 256 * 256;
   if (per > h->adm_layer_bytes) {
     HIPCHK(h, hipStreamSynchronize(s));
@@ -1758,7 +1778,7 @@ static int ensure_admit_cache(zn_handle h, int S, hipStream_t s) {
   h->adm_caches.resize(c.n_layer);
   for (int li = 0; li < c.n_layer; ++li) {
     h->adm_caches[li] = (char*)h->adm_cache + (size_t)li * h->adm_layer_bytes;
-    tab[li] = AdmitLayer{h->adm_caches[li], const_cast<void*>(h->kv_layers[li]), (c.arch == 1 && h->layers[li].kind == 1) ? 1 : 0, 0, kv8_of(h, li)};
+    tab[li] = AdmitLayer{h->adm_caches[li], const_cast<void*>(h->kv_layers[li]), (c.arch == 1 && h->layers[li].kind == 1) ? 1 : 0, codes_only ? 1 : 0, kv8_of(h, li)};
   }
   HIPCHK(h, hipMemcpyAsync(h->adm_layers, tab.data(), tab.size() * sizeof(AdmitLayer), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipStreamSynchronize(s));      // the host vector goes out of scope
@@ -1839,6 +1859,8 @@ extern "C" int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const voi
     for (int li = 0; li < c.n_layer; ++li)                               // a prefill continues the state it finds: the scratch rows begin at zero
       if (h->layers[li].kind == 1) HIPCHK(h, hipMemsetAsync(const_cast<void*>(h->adm_caches[li]), 0, zb, s));
     if ((rc = hybrid_prefill_core(h, (const bf16_t*)hidden_dev, S, Rs, h->adm_caches.data(), S, 0, h->prefill_mode == 2, s, row_len_dev))) return rc;
+  } else if (kv_codes_only_gen(h)) {       // codes only: the scratch cache holds codes, which admit_rows_kernel copies as they are
+    if ((rc = transformer_prefill_core(h, (const bf16_t*)hidden_dev, S, Rs, nullptr, S, 0, s, row_len_dev, h->adm_caches.data(), true))) return rc;
   } else if ((rc = transformer_prefill_core(h, (const bf16_t*)hidden_dev, S, Rs, h->adm_caches.data(), S, 0, s, row_len_dev, nullptr, kv_fp8_gen(h)))) return rc;   // (FP8 KV cache: the scratch rows are rounded, admit_rows_kernel writes their codes)
   AdmitArgs m{};
   m.layers = h->adm_layers; m.n_layer = c.n_layer; m.n = n; m.halves = halves; m.B = B; m.S = S; m.max_len = h->max_len;
@@ -2276,7 +2298,7 @@ static int linear_fused_impl(zn_handle h, zn_linear_op* op, const void* W_q, con
       (epi == EPI_F32 && !op->out_f32) || (epi == EPI_SILU && N % 2) || (op->bias && (epi != EPI_STORE || prefill)))
     ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: an operand of the epilogue is missing or not served");
   if (epi == EPI_ROPE_KV) {
-    if (!op->kv || !op->q_out || op->max_len < 1 || N != (c.n_heads + 2 * c.n_heads_kv) * h->hd) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: RoPE + KV append needs kv, q_out, max_len and N = (Hq + 2 Hkv) hd");
+    if ((!op->kv && !h->op_kv8) || !op->q_out || op->max_len < 1 || N != (c.n_heads + 2 * c.n_heads_kv) * h->hd) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: RoPE + KV append needs kv, q_out, max_len and N = (Hq + 2 Hkv) hd");
     if (prefill ? (op->pf_S < 1 || rows % op->pf_S || op->pf_base < 0 || op->pf_base + op->pf_S > op->max_len) : !op->lengths)
       ZN_FAIL(h, ZN_ERR_ARG, "zn_op_linear_fused: RoPE + KV append needs lengths (decode) or pf_S dividing rows with pf_base + pf_S <= max_len (prefill)");
   }
@@ -2407,6 +2429,14 @@ extern "C" int zn_set_kv_fp8(zn_handle h, int32_t on) {
   free_graph(h); h->emb_valid = false;
   return ZN_OK;
 }
+extern "C" int zn_set_kv_fp8_only(zn_handle h, int32_t on) {
+  if (!h) return ZN_ERR_ARG;
+  if (h->cfg.arch == 1) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_kv_fp8_only: the hybrid stack's attention layers keep a bf16 KV cache");
+  if (h->gen_active && !h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_set_kv_fp8_only inside a generation (between zn_gen_begin and zn_gen_end)");
+  h->kv_fp8_only = on != 0;
+  free_graph(h); h->emb_valid = false;
+  return ZN_OK;
+}
 extern "C" size_t zn_kv_fp8_bytes_per_layer(const zn_config* c, int32_t rows, int32_t max_len) { return zn_kv_bytes_per_layer(c, rows, max_len) / 2; }
 extern "C" int zn_gen_bind_kv_fp8(zn_handle h, const void* const* codes_layers_dev) {
   if (!h) return ZN_ERR_ARG;
@@ -2422,7 +2452,15 @@ extern "C" int zn_gen_bind_kv_fp8(zn_handle h, const void* const* codes_layers_d
 extern "C" int zn_kv_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
   if (!h || !out || rows < 1) return ZN_ERR_ARG;
   out[0] = h->kv_fp8 && kv_fp8_rows(h, rows);
-  out[1] = out[0] && kv_fp8_attn_reads(h, rows);
+  out[1] = out[0] && kv_fp8_attn_reads(h, rows, kv_codes_only_rows(h, rows));
+  return ZN_OK;
+}
+extern "C" int zn_kv_cache_plan(zn_handle h, int32_t rows, int32_t out[3]) {
+  if (!h || !out || rows < 1) return ZN_ERR_ARG;
+  const bool codes_only = kv_codes_only_rows(h, rows);
+  out[0] = h->kv_fp8 && kv_fp8_rows(h, rows);
+  out[1] = out[0] && kv_fp8_attn_reads(h, rows, codes_only);
+  out[2] = !codes_only;
   return ZN_OK;
 }
 extern "C" int zn_op_bind_kv_fp8(zn_handle h, void* codes_dev) {
@@ -2434,7 +2472,7 @@ extern "C" int zn_op_bind_kv_fp8(zn_handle h, void* codes_dev) {
 extern "C" int zn_op_rope_kv_rows(zn_handle h, void* qkv_dev, void* kv_dev, int32_t max_len, int32_t S, int32_t base, int32_t rows, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
   const zn_config& c = h->cfg;
-  if (!qkv_dev || !kv_dev || max_len < 1 || S < 1 || base < 0 || rows < 1) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_rope_kv_rows: bad argument");
+  if (!qkv_dev || (!kv_dev && !h->op_kv8) || max_len < 1 || S < 1 || base < 0 || rows < 1) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_rope_kv_rows: bad argument");
   if (c.arch != 0) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_op_rope_kv_rows: the transformer prefill's kernel (interleaved pairs)");
   hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(S, rows), dim3(256), 0, (hipStream_t)stream, (bf16_t*)qkv_dev, (bf16_t*)kv_dev, h->rope, S, base, max_len, c.n_heads, c.n_heads_kv,
                      h->hd, c.rope_positions, h->op_kv8, h->op_kv8 != nullptr ? 1 : 0);
@@ -2706,8 +2744,10 @@ extern "C" int zn_op_mamba_step(zn_handle h, int32_t layer, const void* x, void*
 extern "C" int zn_op_attn_decode(zn_handle h, const void* q, const void* kv, int32_t max_len, const int32_t* lengths, const int32_t* ext,
                                  void* out, int32_t rows, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
-  if (!q || !kv || !lengths || !out || rows < 1 || max_len < 1) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_decode: bad argument");
+  if (!q || !lengths || !out || rows < 1 || max_len < 1) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_decode: bad argument");
   if (rows > h->max_rows) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_decode: rows > max_rows");
+  // no bf16 cache: legal exactly where a bound code cache (zn_op_bind_kv_fp8) is what the launch reads
+  if (!kv && !(h->op_kv8 && kv_fp8_attn_reads(h, rows))) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_decode: bad argument (no cache, and no bound code cache that %d rows read)", rows);
   int rc = ensure_attn_ws(h, max_len);
   if (rc) return rc;
   rc = run_attention(h, (const bf16_t*)q, (const bf16_t*)kv, max_len, lengths, ext, 0, (bf16_t*)out, rows, attn_fused_for(h, max_len), (hipStream_t)stream, nullptr, h->op_kv8);
@@ -2736,6 +2776,20 @@ extern "C" int zn_op_attn_prefill_rows(zn_handle h, const void* q, const void* k
   if (rows > h->max_rows) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_prefill_rows: rows %d > max_rows %d", rows, h->max_rows);
   const int nq = h->cfg.n_heads * h->hd;
   int rc = prefill_attention(h, (const bf16_t*)q, nq, (const bf16_t*)kv, max_len, (bf16_t*)out, nq, positions, rows, (hipStream_t)stream, base, row_len);
+  if (rc) return rc;
+  HIPCHK(h, hipGetLastError());
+  return ZN_OK;
+}
+
+// Test entry: zn_op_attn_prefill_rows on a code cache uint8 [rows][max_len][2][Hkv][hd] - the FP8 forms of the two prefill attention kernels (zn_prefill_attn_fp8_kernels.h)
+extern "C" int zn_op_attn_prefill_rows_fp8(zn_handle h, const void* q, const void* codes, int32_t max_len, void* out, int32_t positions, int32_t rows,
+                                           int32_t base, const int32_t* row_len, zn_stream stream) {
+  if (!h) return ZN_ERR_ARG;
+  if (!q || !codes || !out || rows < 1 || positions < 1 || base < 0 || max_len < 1 || (int64_t)base + positions > max_len)
+    ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_prefill_rows_fp8: bad argument (positions %d + %d of %d)", base, positions, max_len);
+  if (rows > h->max_rows) ZN_FAIL(h, ZN_ERR_ARG, "zn_op_attn_prefill_rows_fp8: rows %d > max_rows %d", rows, h->max_rows);
+  const int nq = h->cfg.n_heads * h->hd;
+  int rc = prefill_attention(h, (const bf16_t*)q, nq, nullptr, max_len, (bf16_t*)out, nq, positions, rows, (hipStream_t)stream, base, row_len, (const uint8_t*)codes);
   if (rc) return rc;
   HIPCHK(h, hipGetLastError());
   return ZN_OK;

@@ -59,7 +59,8 @@ struct GemvArgs {
   const uint8_t* W8q;
   const int8_t* W8exp;
   // EPI_ROPE_KV with the FP8 KV cache in effect (zn_set_kv_fp8): kv_round != 0 rounds K (after RoPE) and V to the E4M3 grid before the append (kv receives the
-  // dequantised values), and kv8 (uint8 [rows][max_len][2][Hkv][hd], may be NULL: a scratch cache whose codes nobody reads) receives the codes
+  // dequantised values), and kv8 (uint8 [rows][max_len][2][Hkv][hd], may be NULL: a scratch cache whose codes nobody reads) receives the codes.  kv == NULL (a
+  // codes-only generation, zn_set_kv_fp8_only: there is no bf16 cache): the bf16 store is skipped and the codes are all the append writes
   uint8_t* kv8;
   int kv_round;
 };
@@ -99,13 +100,14 @@ ZN_DEVINL void zn_rope_pair(float x0, float x1, float cs, float sn, float& re, f
 }
 
 // One packed pair of K or V into the cache at element offset o; with the FP8 KV cache in effect, rounded to the E4M3 grid first, its two codes beside it.
+// a.kv == NULL (a codes-only generation): the codes alone.
 ZN_DEVINL void kv_append_pair(const GemvArgs& a, size_t o, unsigned pr) {
   if (a.kv_round) {
     unsigned codes;
     pr = kv_fp8_round_pair(pr, codes);
     if (a.kv8) *(unsigned short*)(a.kv8 + o) = (unsigned short)codes;
   }
-  *(unsigned*)(a.kv + o) = pr;
+  if (a.kv) *(unsigned*)(a.kv + o) = pr;
 }
 
 // Fused epilogues shared by the GEMV (rows <= 4) and the small-M MFMA kernel (rows <= 16): finishes activation row r
@@ -891,7 +893,7 @@ __global__ __launch_bounds__(ZN_G16K_NKW * 64) void gemm16k_kernel(GemvArgs a) {
       if (a.pf_S == 0) {
         a.lengths += r0;
         a.q_out += r0 * a.n_heads * a.hd;
-        a.kv += r0 * a.max_len * 2 * a.n_heads_kv * a.hd;
+        if (a.kv) a.kv += r0 * a.max_len * 2 * a.n_heads_kv * a.hd;
         if (a.kv8) a.kv8 += r0 * a.max_len * 2 * a.n_heads_kv * a.hd;
       }
     }

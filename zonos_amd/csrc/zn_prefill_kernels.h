@@ -419,6 +419,7 @@ __global__ void gather_last_kernel(const bf16_t* xP, bf16_t* x, int S, int d, co
 struct PrefillAttnArgs {
   const bf16_t* q; int ldq;     // rows (r*S + s), head h at column h*HD
   const bf16_t* kv;             // [R][max_len][2][Hkv][HD]
+  const uint8_t* kv8;           // the same cache as E4M3 codes, one byte per element: the source of the forms instantiated with PrefillKvFp8 (zn_prefill_attn_fp8_kernels.h); else unused
   bf16_t* out; int ldo;
   int S, base, max_len, n_heads, n_heads_kv, qsplit;
   float scale;
@@ -430,8 +431,16 @@ struct PrefillAttnArgs {
 };
 // query split of the reference's CPU flash kernel for a sequence of S positions (the host's qsplit())
 ZN_DEVINL int prefill_qsplit(int S) { return S >= 768 ? 256 : S >= 192 ? 64 : 32; }
-template <int HD, int G>
-__global__ __launch_bounds__(256) void attn_prefill_kernel(PrefillAttnArgs a) {
+// Where the two prefill attention kernels' K and V tiles come from, as AttnKvBf16 / AttnKvFp8 say it for the decode attention: the cache's element type and
+// the request of 8 consecutive elements of a key's row, returned as 8 bf16.  The kernels' bodies are templates over it (attn_prefill_body,
+// attn_prefill_mfma_body) and use it in their staging loads only: addresses are element offsets, so they, the clamping, the LDS layouts, the operands, the
+// two passes, nvec, the masking and the epilogue do not depend on it.  PrefillKvFp8 (zn_prefill_attn_fp8_kernels.h, with the FP8 forms of the two kernels)
+// reads one-byte codes.
+struct PrefillKvBf16 : AttnKvBf16 {
+  static ZN_DEVINL const elem* cache(const PrefillAttnArgs& a) { return a.kv; }
+};
+template <int HD, int G, class KV>
+ZN_DEVINL void attn_prefill_body(const PrefillAttnArgs& a) {
   constexpr int TQ = 64 / G;              // positions per workgroup
   constexpr int KP = HD + 8;              // padded LDS row (bf16 elements): 16 B of padding breaks the 256-B bank period
   constexpr int NQ = HD / 8;              // 16-B pieces per head row
@@ -461,8 +470,8 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(PrefillAttnArgs a) {
   for (int d = 0; d < HD; ++d) acc[d] = 0.f;
   float lsum = 0.f, m_run = -INFINITY;
   const size_t kvrow = (size_t)2 * a.n_heads_kv * HD;
-  const bf16_t* kg = a.kv + (size_t)r * a.max_len * kvrow + (size_t)kvh * HD;
-  const bf16_t* vg = kg + (size_t)a.n_heads_kv * HD;
+  const typename KV::elem* kg = KV::cache(a) + (size_t)r * a.max_len * kvrow + (size_t)kvh * HD;
+  const typename KV::elem* vg = kg + (size_t)a.n_heads_kv * HD;
 
   for (int t0 = 0; t0 < Lmax; t0 += 512) {
     const int nch = min(8, (Lmax - t0 + 63) / 64);
@@ -473,7 +482,7 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(PrefillAttnArgs a) {
       __syncthreads();
       for (int i = tid; i < 64 * NQ; i += 256) {
         const int key = i / NQ, pc = i % NQ, t = t0 + c * 64 + key;
-        *(u32x4*)(s_k + key * KP + 8 * pc) = (t < Lmax) ? ld16(kg + (size_t)t * kvrow + 8 * pc) : u32x4{0, 0, 0, 0};
+        *(u32x4*)(s_k + key * KP + 8 * pc) = (t < Lmax) ? KV::ld8(kg + (size_t)t * kvrow + 8 * pc) : u32x4{0, 0, 0, 0};
       }
       __syncthreads();
 #pragma unroll 4
@@ -500,8 +509,8 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(PrefillAttnArgs a) {
       for (int i = tid; i < 64 * NQ; i += 256) {
         const int key = i / NQ, pc = i % NQ, t = t0 + c * 64 + key;
         const bool ok = t < Lmax;
-        *(u32x4*)(s_k + key * KP + 8 * pc) = ok ? ld16(kg + (size_t)t * kvrow + 8 * pc) : u32x4{0, 0, 0, 0};
-        *(u32x4*)(s_v + key * KP + 8 * pc) = ok ? ld16(vg + (size_t)t * kvrow + 8 * pc) : u32x4{0, 0, 0, 0};
+        *(u32x4*)(s_k + key * KP + 8 * pc) = ok ? KV::ld8(kg + (size_t)t * kvrow + 8 * pc) : u32x4{0, 0, 0, 0};
+        *(u32x4*)(s_v + key * KP + 8 * pc) = ok ? KV::ld8(vg + (size_t)t * kvrow + 8 * pc) : u32x4{0, 0, 0, 0};
       }
       __syncthreads();
       for (int kk = 0; kk < 16; ++kk) {
@@ -548,6 +557,8 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(PrefillAttnArgs a) {
     }
   }
 }
+template <int HD, int G>
+__global__ __launch_bounds__(256) void attn_prefill_kernel(PrefillAttnArgs a) { attn_prefill_body<HD, G, PrefillKvBf16>(a); }
 
 // ------------------------------------------------------------------------------------------------ attention on the matrix cores
 // Same row semantics as attn_prefill_kernel (the reference CPU flash kernel: 512-key blocks, running max, fexp_u20 on the
@@ -561,8 +572,8 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(PrefillAttnArgs a) {
 // 8-byte LDS store), and column fn of output tile dt is dim 8*fn + dt, which lets a lane fetch V as eight 16-byte row
 // pieces (keys of its k-slots x dims 8*fn..8*fn+7) and transpose them in registers (v_perm_b32) into the eight B operands.
 // The accumulators (16 rows x 128 dims per wave) live in registers in the D layout: col = lane & 15, row = 4*(lane>>4)+reg.
-template <int G>
-__global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(PrefillAttnArgs a) {
+template <int G, class KV>
+ZN_DEVINL void attn_prefill_mfma_body(const PrefillAttnArgs& a) {
   constexpr int HD = 128, TQ = 64 / G, KP = HD + 8, PP = 64 + 8, OP = HD + 4;
   constexpr int K_BYTES = 64 * KP * 2, P_BYTES = 4 * 16 * PP * 2, O_BYTES = 4 * 16 * OP * 4;
   constexpr int SMEM = (2 * K_BYTES + P_BYTES) > O_BYTES ? (2 * K_BYTES + P_BYTES) : O_BYTES;
@@ -600,8 +611,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(PrefillAttnArgs 
   for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   float lsum[4] = {0.f, 0.f, 0.f, 0.f}, m_run[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
   const size_t kvrow = (size_t)2 * a.n_heads_kv * HD;
-  const bf16_t* kg = a.kv + (size_t)r * a.max_len * kvrow + (size_t)kvh * HD;
-  const bf16_t* vg = kg + (size_t)a.n_heads_kv * HD;
+  const typename KV::elem* kg = KV::cache(a) + (size_t)r * a.max_len * kvrow + (size_t)kvh * HD;
+  const typename KV::elem* vg = kg + (size_t)a.n_heads_kv * HD;
   bf16_t* pw = s_p + wave * 16 * PP;
 
   // scaled scores of one staged chunk: sc[ct][reg] = row 4*fg+reg, key ct*16 + fn
@@ -624,11 +635,11 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(PrefillAttnArgs 
     for (int j = 0; j < 4; ++j) {
       const int i = tid + 256 * j, key = i >> 4, pc = i & 15, t = tb + key;
       const size_t off = (size_t)min(t, Lmax - 1) * kvrow + 8 * pc;
-      u32x4 kx = ld16(kg + off);
+      u32x4 kx = KV::ld8(kg + off);
       if (t >= Lmax) kx = u32x4{0, 0, 0, 0};
       *(u32x4*)(s_k + key * KP + 8 * pc) = kx;
       if (with_v) {
-        u32x4 vx = ld16(vg + off);
+        u32x4 vx = KV::ld8(vg + off);
         if (t >= Lmax) vx = u32x4{0, 0, 0, 0};
         *(u32x4*)(s_v + key * KP + 8 * pc) = vx;
       }
@@ -734,6 +745,8 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(PrefillAttnArgs 
     *(u32x4*)(a.out + ((size_t)r * a.S + s) * a.ldo + (size_t)(kvh * G + g) * HD + 8 * pc) = ov;
   }
 }
+template <int G>
+__global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(PrefillAttnArgs a) { attn_prefill_mfma_body<G, PrefillKvBf16>(a); }
 
 // ------------------------------------------------------------------------------------------------ ragged prefill rows, assembled on the device
 // hidden[r] = [cond_r[:L_b] ‖ embed(delayed_b[:, 0 : P_b + 1]) ‖ zeros] for the R rows of a call whose B utterances (b = r mod B) bring
@@ -784,7 +797,9 @@ __global__ __launch_bounds__(256) void assemble_prefill_kernel(AssembleArgs a) {
 // Grid (n * halves, n_layer + 1, ZN_ADMIT_PARTS): workgroup (i, li, z) copies every ZN_ADMIT_PARTS-th 16-byte piece of layer li's bytes; the plane
 // y == n_layer gathers and writes the words.  Nothing of a row that is not named is touched.
 #define ZN_ADMIT_PARTS 4
-struct AdmitLayer { const void* src; void* dst; int kind; int pad; void* dst8; };       // kind 0: KV cache, 1: Mamba2 conv + SSM state buffer; dst8: the session's code cache of the layer (FP8 KV cache in effect), or NULL
+// kind 0: KV cache, 1: Mamba2 conv + SSM state buffer; dst8: the session's code cache of the layer (FP8 KV cache in effect), or NULL; src_codes != 0 (a codes-only
+// session, zn_set_kv_fp8_only): src holds codes already (half the bytes per position), they are copied to dst8 as they are, and dst (NULL) is never written
+struct AdmitLayer { const void* src; void* dst; int kind; int src_codes; void* dst8; };
 struct AdmitArgs {
   const AdmitLayer* layers; int n_layer;
   int n, halves, B;                        // requests of this admission, rows per request, slots of the session
@@ -823,7 +838,9 @@ __global__ __launch_bounds__(256) void admit_rows_kernel(AdmitArgs a) {
   const int b = a.slot[j], r = half * a.B + b, len = a.row_len[i];
   if (li < a.n_layer) {
     const AdmitLayer L = a.layers[li];
-    if (L.kind == 0) {
+    if (L.kind == 0 && L.src_codes) {
+      admit_copy((const char*)L.src + (size_t)i * a.S * (a.kv_row_bytes / 2), (char*)L.dst8 + (size_t)r * a.max_len * (a.kv_row_bytes / 2), (size_t)len * (a.kv_row_bytes / 2), z, ZN_ADMIT_PARTS);
+    } else if (L.kind == 0) {
       admit_copy((const char*)L.src + (size_t)i * a.S * a.kv_row_bytes, (char*)L.dst + (size_t)r * a.max_len * a.kv_row_bytes, (size_t)len * a.kv_row_bytes, z, ZN_ADMIT_PARTS);
       if (L.dst8) admit_codes((const char*)L.src + (size_t)i * a.S * a.kv_row_bytes, (char*)L.dst8 + (size_t)r * a.max_len * (a.kv_row_bytes / 2), (size_t)len * a.kv_row_bytes, z, ZN_ADMIT_PARTS);
     } else {

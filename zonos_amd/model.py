@@ -21,10 +21,11 @@ import torch.nn as nn
 from . import _lib
 from .autoencoder import DACAutoencoder
 from .backbone import BACKBONES, HipEngine
+from .backbone._hip import attention_options
 from .codebook_pattern import revert_delay_pattern
 from .conditioning import ConditioningCache, PrefixConditioner, prepare_conditioning_with_cache
 from .config import InferenceParams, ZonosConfig
-from .quant import KV_FP8_MIN_ROWS
+from .quant import KV_CACHE_MODES, KV_FP8_MIN_ROWS
 from .rows import (GenCall, GenRequest, Hooks, check_request_shapes, code_rows, draw_seed, finalise_codes, finalise_row, map_codes, row_end_offset,  # noqa: F401
                    sampling_struct as _sampling_struct, stop_check_at)
 from .serving import ServeChunk, ServeResult, SlotScheduler, StreamLedger, check_serve_request, release_limit  # noqa: F401
@@ -40,6 +41,15 @@ class StreamChunk(NamedTuple):
     completed (float32 [1, 1, m] on the model's device).  k or m may be 0, never both."""
     codes: torch.Tensor
     wav: torch.Tensor
+
+
+class KvBuffers(NamedTuple):
+    """The KV buffers of one generation or session (`Zonos._kv_buffers`): `ip` (its key_value_memory_dict holds the bf16 caches, or nothing where the
+    generation keeps codes only), `kv_ptrs` (the pointer array for zn_gen_begin; None: no bf16 cache, NULL there) and `codes` (one uint8 tensor per
+    layer for zn_gen_bind_kv_fp8, or None where nothing is rounded)."""
+    ip: InferenceParams
+    kv_ptrs: object
+    codes: list | None
 
 
 MAX_BATCH_REQUESTS = 64       # utterances of one generate_batch() call: the batch the sampler tail's tables are sized for (ZN_TAIL_MAXB)
@@ -112,7 +122,8 @@ class Zonos(nn.Module):
         self.mlp_weights = "bf16"                     # "fp8" after quantize_mlp_fp8()
         self.mamba_weights = "bf16"                   # "fp8" after quantize_mamba_fp8()
         self.fp8_small_rows = False                   # decode steps of 1..4 rows on the launches path read an attached FP8 stream too (set_fp8_small_rows)
-        self.kv_cache = "bf16"                        # "fp8" after set_kv_cache("fp8"): generations of 5 rows and more keep an E4M3 copy of K/V for the decode attention
+        self.kv_cache = "bf16"                        # "fp8" after set_kv_cache("fp8"): generations of 5 rows and more keep an E4M3 copy of K/V for the decode attention;
+                                                      # "fp8-only": they keep the E4M3 codes alone (no bf16 KV cache)
 
     # ------------------------------------------------------------------ loading
     @property
@@ -133,15 +144,15 @@ class Zonos(nn.Module):
                    mlp_weights: str = "bf16", mamba_weights: str = "bf16", fp8_small_rows: bool = False, kv_cache: str = "bf16") -> "Zonos":
         """model.py:128-176: bf16 model, embeddings zero-padded to the 1032-row tables, heads.{i} fused.  mlp_weights="fp8":
         quantize_mlp_fp8() after loading (lossy with respect to the checkpoint; see there); mamba_weights="fp8": quantize_mamba_fp8() (the
-        hybrid checkpoint; likewise); fp8_small_rows: set_fp8_small_rows() (decode steps of 1..4 rows read the stream too); kv_cache="fp8":
-        set_kv_cache("fp8") (lossy with respect to the bf16 model; see there); the defaults change nothing."""
+        hybrid checkpoint; likewise); fp8_small_rows: set_fp8_small_rows() (decode steps of 1..4 rows read the stream too); kv_cache="fp8"
+        or "fp8-only": set_kv_cache() with that mode (lossy with respect to the bf16 model; see there); the defaults change nothing."""
         import safetensors
         if mlp_weights not in ("bf16", "fp8"):
             raise _lib.ZonosHipError(f"mlp_weights must be 'bf16' or 'fp8', not {mlp_weights!r}")
         if mamba_weights not in ("bf16", "fp8"):
             raise _lib.ZonosHipError(f"mamba_weights must be 'bf16' or 'fp8', not {mamba_weights!r}")
-        if kv_cache not in ("bf16", "fp8"):
-            raise ValueError(f"kv_cache must be 'bf16' or 'fp8', not {kv_cache!r}")
+        if kv_cache not in KV_CACHE_MODES:
+            raise ValueError(f"kv_cache must be 'bf16', 'fp8' or 'fp8-only', not {kv_cache!r}")
         config = ZonosConfig.from_dict(json.load(open(config_path)))
         backbone_cls = BACKBONES[backbone] if backbone else DEFAULT_BACKBONE_CLS
         model = cls(config, backbone_cls).to(device, torch.bfloat16)
@@ -171,8 +182,8 @@ class Zonos(nn.Module):
             model.quantize_mamba_fp8()
         if fp8_small_rows:
             model.set_fp8_small_rows(True)
-        if kv_cache == "fp8":
-            model.set_kv_cache("fp8")
+        if kv_cache != "bf16":
+            model.set_kv_cache(kv_cache)
         return model
 
     @torch.inference_mode()
@@ -263,13 +274,17 @@ class Zonos(nn.Module):
         and V to the E4M3 grid at every KV append (zonos_amd/quant.py kv_round_e4m3: no scale, saturation at +-448), keep the rounded values in the
         bf16 cache - the prefill attention and every other reader see them - and the one-byte codes in a second cache, which the decode attention reads:
         half the K/V bytes per step.  Lossy with respect to the bf16 model (relative error up to 2^-4 per K/V element, absolute floor 2^-10), exact with
-        respect to its own rounded cache; its effect on audio quality is unmeasured.  It costs memory today: 1.5 x the KV bytes (the bf16 copy stays).
-        With fewer rows the mode is inert (generate(batch_size <= 2), stream()).  "bf16" (the default) switches it off.  A hybrid model raises ValueError.
-        Cached engines are dropped."""
-        if mode not in ("bf16", "fp8"):
-            raise ValueError(f"kv_cache must be 'bf16' or 'fp8', not {mode!r}")
-        if mode == "fp8" and self.config.backbone.ssm_cfg:
-            raise ValueError("kv_cache='fp8': the hybrid stack's attention layers keep a bf16 KV cache")
+        respect to its own rounded cache; its effect on audio quality is unmeasured.  It costs memory: 1.5 x the KV bytes (the bf16 copy stays) - "fp8-only"
+        drops that copy.
+        "fp8-only": the same rounding, the same codes and the same results bit for bit, with the codes as the only KV storage of such a generation or
+        session: no bf16 KV tensor is allocated, the appends write the codes alone, and the prefill attention and an admission's scratch cache read and
+        hold codes too.  Half the KV bytes of the bf16 model, a third of "fp8" (kv_cache_bytes).
+        With fewer rows either mode is inert (generate(batch_size <= 2), stream()).  "bf16" (the default) switches it off.  A hybrid model raises
+        ValueError.  Cached engines are dropped."""
+        if mode not in KV_CACHE_MODES:
+            raise ValueError(f"kv_cache must be 'bf16', 'fp8' or 'fp8-only', not {mode!r}")
+        if mode != "bf16" and self.config.backbone.ssm_cfg:
+            raise ValueError(f"kv_cache={mode!r}: the hybrid stack's attention layers keep a bf16 KV cache")
         self.kv_cache = mode
         self._engine = self._spare = None
         self.backbone._engine = None
@@ -281,7 +296,7 @@ class Zonos(nn.Module):
         rows = int(rows)
         if rows < 1:
             raise ValueError("kv_fp8_plan: rows must be >= 1")
-        rounded = self.kv_cache == "fp8" and not self.config.backbone.ssm_cfg and rows >= KV_FP8_MIN_ROWS
+        rounded = self.kv_cache != "bf16" and not self.config.backbone.ssm_cfg and rows >= KV_FP8_MIN_ROWS
         reads = rounded
         if rounded and self._engine is not None:      # (an engine's tune keys - ZN_TUNE_KV_FP8 = 2 - and the library's own plan decide where one exists)
             out = (C.c_int32 * 2)()
@@ -289,10 +304,59 @@ class Zonos(nn.Module):
             rounded, reads = bool(out[0]), bool(out[1])
         return {"rounded": rounded, "attention_reads": "fp8" if reads else "bf16"}
 
+    def kv_cache_plan(self, rows: int) -> dict:
+        """kv_fp8_plan's two keys with the same meaning, and "bf16_cache": whether a generation whose decode step has `rows` rows allocates the bf16 KV
+        cache at all (False: codes only, set_kv_cache("fp8-only") in effect)."""
+        plan = self.kv_fp8_plan(rows)
+        codes_only = plan["rounded"] and self.kv_cache == "fp8-only"
+        if codes_only and self._engine is not None:
+            out = (C.c_int32 * 3)()
+            self._engine.call("zn_kv_cache_plan", int(rows), out)
+            codes_only = not out[2]
+        return {**plan, "bf16_cache": not codes_only}
+
+    def kv_cache_bytes(self, rows: int, max_len: int) -> dict:
+        """The KV bytes a generation of `rows` rows and `max_len` positions (rounded up to a multiple of 8, as setup_cache does) allocates over all layers as
+        this model is set now: {"bf16": n, "codes": n}, from the library's zn_kv_bytes_per_layer / zn_kv_fp8_bytes_per_layer."""
+        rows, max_len = int(rows), find_multiple(int(max_len), 8)
+        if rows < 1 or max_len < 1:
+            raise ValueError("kv_cache_bytes: rows and max_len must be >= 1")
+        plan = self.kv_cache_plan(rows)
+        ao = attention_options(self.config.backbone)      # (the byte functions read the head geometry alone)
+        zc = _lib.zn_config(d_model=self.config.backbone.d_model, n_heads=ao["num_heads"], n_heads_kv=ao["num_heads_kv"])
+        lib, n_layer = _lib.load(), self.config.backbone.n_layer
+        return {"bf16": n_layer * int(lib.zn_kv_bytes_per_layer(C.byref(zc), rows, max_len)) if plan["bf16_cache"] else 0,
+                "codes": n_layer * int(lib.zn_kv_fp8_bytes_per_layer(C.byref(zc), rows, max_len)) if plan["rounded"] else 0}
+
+    def _kv_buffers(self, eng: HipEngine, rows: int, max_seqlen: int) -> "KvBuffers":
+        """The KV buffers of one generation or session of `rows` rows on `eng`, decided in one place from the library's plan (zn_kv_cache_plan): the
+        InferenceParams (its key_value_memory_dict stays empty where no bf16 cache is needed: no bf16 KV tensor is allocated), the pointer array for
+        zn_gen_begin (None -> NULL there) and the code caches (None where nothing is rounded), which `_bind_kv_buffers` hands to the library after
+        zn_gen_begin.  The caller keeps the result alive to the generation's end."""
+        out = (C.c_int32 * 3)()
+        eng.call("zn_kv_cache_plan", rows, out)
+        n_layer = self.config.backbone.n_layer
+        if out[2]:
+            ip = self.setup_cache(batch_size=rows, max_seqlen=max_seqlen)
+            kv_ptrs = (C.c_void_p * n_layer)(*[ip.key_value_memory_dict[i][0].data_ptr() for i in range(n_layer)])
+        else:
+            ip = InferenceParams(find_multiple(max_seqlen, 8), rows, 0, 0, {}, torch.zeros(rows, dtype=torch.int32, device=self.device))
+            kv_ptrs = None
+        codes = None
+        if out[0]:
+            per = int(eng.lib.zn_kv_fp8_bytes_per_layer(C.byref(eng.zc), rows, ip.max_seqlen))
+            codes = [torch.empty(per, dtype=torch.uint8, device=self.device) for _ in range(n_layer)]
+        return KvBuffers(ip, kv_ptrs, codes)
+
+    def _bind_kv_buffers(self, eng: HipEngine, bufs: "KvBuffers") -> None:
+        """After zn_gen_begin: the code caches of `_kv_buffers`, where there are any (zn_gen_bind_kv_fp8)."""
+        if bufs.codes is not None:
+            eng.call("zn_gen_bind_kv_fp8", (C.c_void_p * len(bufs.codes))(*[t.data_ptr() for t in bufs.codes]))
+
     def _bind_kv_codes(self, eng: HipEngine, rows: int, max_len: int):
         """The code caches of the generation just begun on `eng` (zn_gen_bind_kv_fp8) where the FP8 KV cache is in effect for `rows` rows: one uint8
         tensor [rows, max_len, 2, Hkv, hd] per layer, which the caller keeps alive to the generation's end; else None."""
-        if self.kv_cache != "fp8":
+        if self.kv_cache == "bf16":
             return None
         out = (C.c_int32 * 2)()
         eng.call("zn_kv_fp8_plan", rows, out)
@@ -335,8 +399,10 @@ class Zonos(nn.Module):
                         eos_id=self.eos_token_id, mask_id=self.masked_token_id)
         if self.fp8_small_rows:      # (every engine of the model: the cached one and the spare)
             eng.call("zn_debug_tune", _lib.ZN_TUNE_FP8_SMALL_ROWS, 2)
-        if self.kv_cache == "fp8":
+        if self.kv_cache != "bf16":
             eng.call("zn_set_kv_fp8", 1)
+            if self.kv_cache == "fp8-only":
+                eng.call("zn_set_kv_fp8_only", 1)
         return eng
 
     def engine(self, batch_size: int = 1) -> HipEngine:
@@ -692,14 +758,14 @@ class Zonos(nn.Module):
         else:
             L_c = call.cond.shape[1] if call.cond_lengths is None else max(call.cond_lengths)      # the KV capacity follows the longest VALID row
         t_total = P + call.max_new_tokens + nq
-        ip = self.setup_cache(batch_size=call.engine_rows, max_seqlen=L_c + t_total)
+        bufs = self._kv_buffers(eng, call.engine_rows, L_c + t_total)      # (alive until zn_gen_end)
+        ip = bufs.ip
         delayed = code_rows(call.prefixes, call.budgets, t_total, nq, self.masked_token_id, self.device)       # [B, nq, t_total]
         st = ts.cuda_stream
-        kv_ptrs = (C.c_void_p * self.config.backbone.n_layer)(*[ip.key_value_memory_dict[i][0].data_ptr() for i in range(self.config.backbone.n_layer)])
-        eng.call("zn_gen_begin", B, kv_ptrs, ip.max_seqlen, ip.lengths_per_sample.data_ptr(), delayed.data_ptr(), t_total, P + 1,
+        eng.call("zn_gen_begin", B, bufs.kv_ptrs, ip.max_seqlen, ip.lengths_per_sample.data_ptr(), delayed.data_ptr(), t_total, P + 1,
                  call.max_new_tokens, float(call.cfg_scale), C.byref(call.sp), st)
         try:
-            kv_codes = self._bind_kv_codes(eng, call.engine_rows, ip.max_seqlen)      # noqa: F841  (alive until zn_gen_end)
+            self._bind_kv_buffers(eng, bufs)
             if call.table is not None:
                 eng.call("zn_gen_set_rows", call.table, B)
             if call.ragged:

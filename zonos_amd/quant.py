@@ -32,6 +32,7 @@ import torch
 E4M3_MAX = 448.0
 EXP_MIN, EXP_MAX = -100, 100
 KV_FP8_MIN_ROWS = 5          # the FP8 KV cache (Zonos.set_kv_cache) is in effect from this many rows per decode step on; below it is inert
+KV_CACHE_MODES = ("bf16", "fp8", "fp8-only")      # Zonos.set_kv_cache: no FP8 cache | codes beside the bf16 cache | the codes alone
 
 
 def e4m3_value_table() -> torch.Tensor:
@@ -97,7 +98,8 @@ def quantize_rows_fp8(W: torch.Tensor):
 
 
 def kv_round_e4m3(x: torch.Tensor):
-    """The FP8 KV cache's rounding (Zonos.set_kv_cache("fp8"); the KV appends of zonos_amd/csrc are tested against it bit for bit).
+    """The FP8 KV cache's rounding (Zonos.set_kv_cache("fp8") and "fp8-only" - the codes beside the bf16 cache, or the codes alone; the KV
+    appends of zonos_amd/csrc are tested against it bit for bit).
     x: bf16, any shape -> (codes uint8, dequantised bf16), both of x's shape.
 
     The element rounding of the weight format above at scale exponent 0: code = RNE_e4m3fn(x), value(code) exact in bf16.  No scale is

@@ -42,15 +42,14 @@ class ServeSession:
     def open(self, eng) -> None:
         model, shape, self.eng = self.model, self.shape, eng
         with torch.inference_mode(), torch.cuda.device(self.dev), torch.cuda.stream(self.ts):
-            self.ip = ip = model.setup_cache(batch_size=self.R, max_seqlen=self.width)       # (the KV cache lives as long as the session)
+            self.kv = model._kv_buffers(eng, self.R, self.width)       # (the KV caches - bf16, codes or both - live as long as the session)
+            self.ip = ip = self.kv.ip
             self.delayed = torch.full((self.slots, self.nq, self.width), self.mask, dtype=torch.int32, device=self.dev)   # an idle slot's cells are never -1
-            n_layer = model.config.backbone.n_layer
-            kv_ptrs = (C.c_void_p * n_layer)(*[ip.key_value_memory_dict[i][0].data_ptr() for i in range(n_layer)])
             sp = sampling_struct({}, 0)                                # (every sampler of a session reads its slot's entry)
-            eng.call("zn_gen_begin", self.slots, kv_ptrs, ip.max_seqlen, ip.lengths_per_sample.data_ptr(), self.delayed.data_ptr(), self.width, 1,
+            eng.call("zn_gen_begin", self.slots, self.kv.kv_ptrs, ip.max_seqlen, ip.lengths_per_sample.data_ptr(), self.delayed.data_ptr(), self.width, 1,
                      shape.max_new_tokens, 2.0 if self.guided else 1.0, C.byref(sp), self.st)
             self.begun = True
-            self.kv_codes = model._bind_kv_codes(eng, self.R, ip.max_seqlen)          # (FP8 KV cache: the code caches live as long as the session)
+            model._bind_kv_buffers(eng, self.kv)
             eng.call("zn_gen_open_slots", self.slack)
 
     def close(self) -> None:
