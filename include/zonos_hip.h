@@ -474,7 +474,8 @@ int zn_set_mlp_fp8(zn_handle h, int32_t layer, const void* fc1_q, const void* fc
  * ZN_ERR_UNSUPPORTED: any other (prologue, epilogue) pair, a prefill op, K no multiple of 256, a plan that would not read the stream
  * (zn_debug_tune(ZN_TUNE_MLP_FP8, 2) included). */
 int zn_op_linear_fp8(zn_handle h, zn_linear_op* op, const void* W_q, const void* W_exp, zn_stream stream);
-/* out[0], out[1]: whether fc1 and fc2 of a decode step over `rows` rows would read FP8 in EVERY block of this handle now (the tune keys; a
+/* Reads the decode step's own table of linears (zn_step_linears.h), as the launches do.
+ * out[0], out[1]: whether fc1 and fc2 of a decode step over `rows` rows would read FP8 in EVERY block of this handle now (the tune keys; a
  * handle with streams attached to some blocks only reports 0, 0 although those blocks do read them).  rows <= 4 says what the launches path (the GEMV)
  * reads: 1, 1 only under zn_debug_tune(ZN_TUNE_FP8_SMALL_ROWS, 2); a generation that runs on a persistent kernel reads the bf16 copy whatever this reports. */
 int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
@@ -488,7 +489,8 @@ int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
  * ZN_ERR_UNSUPPORTED: a transformer handle, an attention layer of a hybrid handle, widths the FP8 kernels do not serve (d_model != 2048 or d_inner != 4096).
  * ZN_ERR_STATE: between zn_gen_begin and zn_gen_end.  ZN_ERR_ARG: a layer out of range, or some but not all pointers NULL. */
 int zn_set_mamba_fp8(zn_handle h, int32_t layer, const void* in_q, const void* in_exp, const void* out_q, const void* out_exp);
-/* out[0], out[1]: whether in_proj and out_proj of a decode step over `rows` rows would read FP8 in EVERY Mamba2 layer of this handle now (the tune keys; a
+/* Reads the decode step's own table of linears (zn_step_linears.h), as the launches do.
+ * out[0], out[1]: whether in_proj and out_proj of a decode step over `rows` rows would read FP8 in EVERY Mamba2 layer of this handle now (the tune keys; a
  * handle with streams attached to some Mamba2 layers only, or with no Mamba2 layer, reports 0, 0).  rows <= 4: 1, 1 only under
  * zn_debug_tune(ZN_TUNE_FP8_SMALL_ROWS, 2), where the GEMV launches read the stream too. */
 int zn_mamba_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]);
@@ -537,10 +539,10 @@ int zn_op_bind_kv_fp8(zn_handle h, void* codes_dev);
 int zn_op_rope_kv_rows(zn_handle h, void* qkv_dev, void* kv_dev, int32_t max_len, int32_t S, int32_t base, int32_t rows, zn_stream stream);
 /* ---------------------------------------------------------------- decode steps of 17..64 rows (additive to ABI 9, like the FP8 calls above: look the symbol up)
  * out[0..4]: activation rows per weight pass of in_proj, out_proj, fc1, fc2 and the heads in a decode step of `rows` rows as this handle would
- * run it now (4 up to 4 rows, 16 up to 16 rows and under zn_debug_tune(ZN_TUNE_WIDE_ROWS, 1), 64 where the wide plan applies): a step of R rows
+ * run it now - the query reads the step's own table of linears (zn_step_linears.h), which the launches plan from - (4 up to 4 rows, 16 up to 16 rows and under zn_debug_tune(ZN_TUNE_WIDE_ROWS, 1), 64 where the wide plan applies): a step of R rows
  * reads the projection's weights ceil(R / out[k]) times. */
 int zn_decode_rows_plan(zn_handle h, int32_t rows, int32_t out[5]);
-/* The same report for a hybrid handle (arch 1), as its decode step plans them: out[0..6] = Mamba2 in_proj, Mamba2 out_proj, attention in_proj, out_proj,
+/* The same report for a hybrid handle (arch 1), read from the same table: out[0..6] = Mamba2 in_proj, Mamba2 out_proj, attention in_proj, out_proj,
  * fc1, fc2, heads (the first layer of each kind; 0 for a kind the stack does not have).  ZN_ERR_STATE on a transformer handle. */
 int zn_hybrid_rows_plan(zn_handle h, int32_t rows, int32_t out[7]);
 /* Prefix-conditioner pieces (zonos/conditioning.py): nn.Linear with bias (Conditioner.project, :52-60; bias added in fp32

@@ -4,8 +4,10 @@
     python tools/linear_launch_trace.py list DIR OUT.txt      # DIR's kernel trace -> one "name grid=(..) wg=(..)" line per launch of this library (argument types dropped), in start order, repeated blocks folded
 
 Without arguments: a few greedy frames with one launch per op (ZN_TUNE_PERSISTENT = 2) at Zonos-v0.1 dimensions - batch 1 guided (2 rows)
-and unguided (1 row), batch 3 (6 rows, 48-row prefill), batch 8 (16 rows, 64-row prefill), prefills of 120 and 400 rows - then the same
-row counts on the tiny hybrid model and on the d_model 512 chain model.  ZONOS_HIP_LIB selects the library."""
+and unguided (1 row), batch 3 (6 rows, 48-row prefill), batch 8 (16 rows, 64-row prefill), batch 17 (34 rows: the wide plan), prefills of 120 and 400
+rows - then the same row counts on the tiny hybrid model and on the d_model 512 chain model; a two-layer transformer of the same widths with quantize_mlp_fp8() at
+6 rows, and at 2 rows with set_fp8_small_rows(True); the two-layer full-width hybrid of tests/test_gpu_mamba_fp8.py, plain and with quantize_mamba_fp8(), at 2, 6
+and 34 rows.  Every transformer engine applies out_proj twice (double_out_proj), so each transformer case traces that linear too.  ZONOS_HIP_LIB selects the library."""
 import csv
 import glob
 import os
@@ -15,18 +17,20 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(cfg, seed, cases):
+def run(cfg, seed, cases, prepare=None, label=""):
     import torch
     from zonos_amd import _lib, synth
     from zonos_amd.testing import build_model
     model, _ = build_model(cfg, seed, "cuda:0")
-    model.engine(8).call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 2)
+    if prepare:
+        prepare(model)      # (quantising drops the cached engines: before the one below exists)
+    model.engine(max(8, max(B for B, _, _ in cases))).call("zn_debug_tune", _lib.ZN_TUNE_PERSISTENT, 2)
     for B, scale, S in cases:
         rows = B if scale == 1.0 else 2 * B
         cond = synth.conditioning(seed, "cond%d_%d" % (rows, S), rows, S, cfg["d_model"]).to("cuda:0")
         out = model.generate(cond, max_new_tokens=10, cfg_scale=scale, batch_size=B, sampling_params={"temperature": 0.0})
         torch.cuda.synchronize()
-        print("case d_model", cfg["d_model"], "batch", B, "cfg_scale", scale, "conditioning", S, "-> codes checksum", int(out.sum()), flush=True)
+        print("case", label, "d_model", cfg["d_model"], "batch", B, "cfg_scale", scale, "conditioning", S, "-> codes checksum", int(out.sum()), flush=True)
 
 
 def listing(d, out):
@@ -68,6 +72,12 @@ if __name__ == "__main__":
         listing(sys.argv[2], sys.argv[3])
     else:
         from zonos_amd import synth
-        run(synth.FULL_CFG, 1, [(1, 2.0, 6), (1, 1.0, 6), (3, 2.0, 8), (8, 2.0, 4), (1, 2.0, 60), (1, 2.0, 200)])
-        run(synth.HYBRID_TINY_CFG, 3, [(1, 2.0, 6), (3, 2.0, 5), (8, 2.0, 4)])
-        run(synth.CHAIN_CFG, 5, [(1, 2.0, 6), (3, 2.0, 8), (8, 2.0, 4)])
+        run(synth.FULL_CFG, 1, [(1, 2.0, 6), (1, 1.0, 6), (3, 2.0, 8), (8, 2.0, 4), (17, 2.0, 3), (1, 2.0, 60), (1, 2.0, 200)], label="full")
+        run(synth.HYBRID_TINY_CFG, 3, [(1, 2.0, 6), (3, 2.0, 5), (8, 2.0, 4)], label="hybrid tiny")
+        run(synth.CHAIN_CFG, 5, [(1, 2.0, 6), (3, 2.0, 8), (8, 2.0, 4)], label="chain")
+        two = dict(synth.FULL_CFG, n_layer=2)
+        run(two, 7, [(3, 2.0, 8)], lambda m: m.quantize_mlp_fp8(), "fp8 mlp")
+        run(two, 7, [(1, 2.0, 6)], lambda m: m.quantize_mlp_fp8(small_rows=True), "fp8 mlp, small rows")
+        wide = dict(synth.HYBRID_FULL_CFG, n_layer=2, attn_layer_idx=[1])
+        run(wide, 9, [(1, 2.0, 6), (3, 2.0, 5), (17, 2.0, 3)], label="hybrid wide")
+        run(wide, 9, [(1, 2.0, 6), (3, 2.0, 5), (17, 2.0, 3)], lambda m: m.quantize_mamba_fp8(), "hybrid wide, fp8 mamba")

@@ -12,6 +12,7 @@
 #include "zn_prefill_attn_fp8_kernels.h"
 #include "zn_cond_kernels.h"
 #include "zn_mamba_kernels.h"
+#include "zn_step_linears.h"
 
 #include <cmath>
 #include <cstdio>
@@ -486,8 +487,6 @@ static LinearEnv linear_env(zn_handle h, bool step = true) {
   e.g16_part_bytes = h->g16_part_bytes; e.has_g16_part = h->g16_part != nullptr; e.has_ln_part = h->ln_part != nullptr;
   return e;
 }
-// ZN_TUNE_FP8_SMALL_ROWS: the GEMV launches (1..4 rows) of a projection whose FP8 stream is offered read it (LinearEnv::w8v_offered); 3 = with a ring of two units ahead
-static bool fp8_small_rows(zn_handle h) { return h->tune[ZN_TUNE_FP8_SMALL_ROWS] == 2 || h->tune[ZN_TUNE_FP8_SMALL_ROWS] == 3; }
 // g serves the row group [r0, r0 + nr) of the rows it described: every per-row pointer moves there.
 static void advance_rows(GemvArgs& g, int r0, int nr, int out_cols) {
   g.nrows = nr;
@@ -714,75 +713,111 @@ static int run_attention(zn_handle h, const bf16_t* q, const bf16_t* kv, int max
   return ZN_OK;
 }
 
-// The arguments of a transformer block's projections and of the heads, shared by the decode step and by zn_bench_kernel (which prices the step's launches).
+// ---- The linears of a decode step: what each is, is zn_step_linears.h's table; here, the handle's side of it (which layer offers a stream, the W8 pointers, the
+// arguments) and the ONE launcher every step linear goes through.
+static bool mlp_fp8_offered(zn_handle h, int li) { return li >= 0 && h->mlp_fp8[li].fc1_q != nullptr && h->tune[ZN_TUNE_MLP_FP8] != 2; }
+static bool mamba_fp8_offered(zn_handle h, int li) { return li >= 0 && h->mamba_fp8[li].in_q != nullptr && h->tune[ZN_TUNE_MAMBA_FP8] != 2; }
+// layer li offers linear `lin` the FP8 stream the table names for it
+static bool stream_offered(zn_handle h, int lin, int li) {
+  const int offer = step_linear_offer(lin);
+  return offer == SO_MLP ? mlp_fp8_offered(h, li) : offer == SO_MAMBA ? mamba_fp8_offered(h, li) : false;
+}
+// ... and so does EVERY layer that has the linear (the plan queries: a handle with streams on some layers only reports none)
+static bool every_layer_offers(zn_handle h, int lin) {
+  const int offer = step_linear_offer(lin);
+  if (offer == SO_NONE || h->cfg.arch != (offer == SO_MAMBA ? 1 : 0)) return false;
+  int n = 0;
+  for (int li = 0; li < h->cfg.n_layer; ++li)
+    if (offer == SO_MLP || h->layers[li].kind == 1) { ++n; if (!stream_offered(h, lin, li)) return false; }
+  return n > 0;
+}
+static void attach_w8(zn_handle h, int lin, int li, GemvArgs& a) {
+  if (li < 0) return;
+  const zn_handle_s::MlpFp8& f = h->mlp_fp8[li];
+  const zn_handle_s::MambaFp8& m = h->mamba_fp8[li];
+  switch (lin) {
+    case SL_FC1: a.W8q = f.fc1_q; a.W8exp = f.fc1_exp; break;
+    case SL_FC2: a.W8q = f.fc2_q; a.W8exp = f.fc2_exp; break;
+    case SL_M_IN_PROJ: a.W8q = m.in_q; a.W8exp = m.in_exp; break;
+    case SL_M_OUT_PROJ: a.W8q = m.out_q; a.W8exp = m.out_exp; break;
+  }
+}
+// li: the layer (its qkv bias decides the hybrid in_proj's epilogue), -1 = none
+static bool step_in_proj_bias(zn_handle h, int lin, int li) { return lin == SL_H_IN_PROJ && li >= 0 && h->layers[li].in_proj_bias != nullptr; }
+static LinearPlan step_plan(zn_handle h, int lin, int li, int rows, bool offered, bool stats_in = false) {
+  return plan_step_linear(linear_env(h), h->cfg, h->tune, lin, rows, offered, stats_in, step_in_proj_bias(h, lin, li));
+}
 static GemvArgs linear_args(zn_handle h, const void* W, int N, int K, const bf16_t* x, bf16_t* out, const bf16_t* resid = nullptr) {
   GemvArgs a{};
   a.W = (const bf16_t*)W; a.N = N; a.K = K; a.x = x; a.out = out; a.resid = resid; a.eps = h->cfg.norm_eps;
   return a;
 }
+// the arguments of a step linear; N and K are the table's: launch_step_linear fills them
+static GemvArgs step_args(zn_handle h, const void* W, const bf16_t* x, bf16_t* out, const bf16_t* resid = nullptr) { return linear_args(h, W, 0, 0, x, out, resid); }
+// Launches step linear `lin` of layer li as plan p says.  The call site names the kernel pair; the table decides it: a pair that is not the table's launches nothing.
+// d: the table's description, when the caller has it already
+template <int PRO, int EPI>
+static int launch_step_linear(zn_handle h, int lin, int li, const LinearPlan& p, GemvArgs a, int rows, hipStream_t s, const StepLinearDesc* known = nullptr) {
+  const StepLinearDesc d = known ? *known : step_linear_desc(h->cfg, h->tune, lin, rows, step_in_proj_bias(h, lin, li));
+  if (d.pro != PRO || d.epi != EPI) ZN_FAIL(h, ZN_ERR_STATE, "step linear %d: the call launches <%d, %d>, the table says <%d, %d>", lin, PRO, EPI, d.pro, d.epi);
+  a.N = d.N; a.K = d.K;
+  attach_w8(h, lin, li, a);
+  return launch_linear<PRO, EPI>(h, p, a, rows, s);
+}
+template <int PRO, int EPI>
+static int run_step_linear(zn_handle h, int lin, int li, const GemvArgs& a, int rows, hipStream_t s) {
+  const StepLinearDesc d = step_linear_desc(h->cfg, h->tune, lin, rows, step_in_proj_bias(h, lin, li));
+  return launch_step_linear<PRO, EPI>(h, lin, li, plan_step_linear(linear_env(h), h->tune, d, rows, stream_offered(h, lin, li), false), a, rows, s, &d);
+}
 static GemvArgs in_proj_args(zn_handle h, const zn_layer_weights& lw, const bf16_t* x, bf16_t* kv, int max_len, const int* lengths, uint8_t* kv8 = nullptr, bool kv_round = false) {
   const zn_config& c = h->cfg;
-  GemvArgs a = linear_args(h, lw.in_proj, (c.n_heads + 2 * c.n_heads_kv) * h->hd, c.d_model, x, nullptr);
+  GemvArgs a = step_args(h, lw.in_proj, x, nullptr);
   a.ln_w = (const bf16_t*)lw.norm_w; a.ln_b = (const bf16_t*)lw.norm_b; a.lengths = lengths; a.hd = h->hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
   a.q_out = h->q; a.kv = kv; a.rope = h->rope; a.max_len = max_len; a.rope_positions = c.rope_positions;
   a.kv8 = kv8; a.kv_round = kv_round ? 1 : 0;
   return a;
 }
-static GemvArgs out_proj_args(zn_handle h, const zn_layer_weights& lw, const bf16_t* in, bf16_t* out, const bf16_t* resid) {
-  return linear_args(h, lw.out_proj, h->cfg.d_model, h->cfg.n_heads * h->hd, in, out, resid);
-}
 static GemvArgs fc1_args(zn_handle h, const zn_layer_weights& lw, const bf16_t* x, const float* ln_stats) {   // ln_stats: left by x's producer, or null
-  GemvArgs a = linear_args(h, lw.fc1, 2 * h->cfg.d_ff, h->cfg.d_model, x, h->mbuf);
+  GemvArgs a = step_args(h, lw.fc1, x, h->mbuf);
   a.ln_w = (const bf16_t*)lw.norm2_w; a.ln_b = (const bf16_t*)lw.norm2_b; a.ln_part_in = ln_stats;
-  return a;
-}
-static GemvArgs fc2_args(zn_handle h, const zn_layer_weights& lw, bf16_t* x) { return linear_args(h, lw.fc2, h->cfg.d_model, h->cfg.d_ff, h->mbuf, x, x); }
-static GemvArgs heads_args(zn_handle h, const bf16_t* x) {
-  GemvArgs a = linear_args(h, h->heads, h->cfg.n_codebooks * h->cfg.vocab_head, h->cfg.d_model, x, nullptr);
-  a.ln_w = (const bf16_t*)h->norm_f_w; a.ln_b = (const bf16_t*)h->norm_f_b; a.out_f32 = h->logits_raw;
   return a;
 }
 // The projection that completes the residual stream (the second out_proj call under double_out_proj, else the single one) and fc1, planned
 // together: fc1 normalises from handed-over LayerNorm statistics exactly when that projection's plan writes them (rows 5..16).
-// mlp_w8: the layer's fc1 / fc2 are offered as an FP8 stream too (mlp_fp8_offered); fc2's plan rides along because the offer is made in one place.
+// mlp_w8: the layer's fc1 / fc2 are offered as an FP8 stream too (mlp_fp8_offered).
 struct PostAttnPlans { LinearPlan out, fc1, fc2; };
-static bool mlp_fp8_offered(zn_handle h, int li) { return li >= 0 && h->mlp_fp8[li].fc1_q != nullptr && h->tune[ZN_TUNE_MLP_FP8] != 2; }
 static PostAttnPlans plan_post_attention(zn_handle h, int rows, bool mlp_w8 = false) {
-  const zn_config& c = h->cfg;
-  const LinearEnv e = linear_env(h);
-  LinearEnv em = e;
-  em.w8_offered = mlp_w8;
-  em.w8v_offered = mlp_w8 && fp8_small_rows(h);
   PostAttnPlans pp;
-  pp.out = plan_linear(e, PRO_NONE, EPI_RESID, rows, c.d_model, c.n_heads * h->hd, h->tune[ZN_TUNE_WG_OUT_PROJ], false, true, false);
-  pp.fc1 = plan_linear(em, PRO_LN, EPI_SILU, rows, 2 * c.d_ff, c.d_model, h->tune[ZN_TUNE_WG_FC1], false, false, pp.out.writes_ln_stats);
-  pp.fc2 = plan_linear(em, PRO_NONE, EPI_RESID, rows, c.d_model, c.d_ff, h->tune[ZN_TUNE_WG_FC2], false, false, false);
+  pp.out = step_plan(h, SL_OUT_PROJ, -1, rows, false);
+  pp.fc1 = step_plan(h, SL_FC1, -1, rows, mlp_w8, pp.out.writes_ln_stats);
+  pp.fc2 = step_plan(h, SL_FC2, -1, rows, mlp_w8);
   return pp;
 }
 
 // LayerNorm -> in_proj -> split -> RoPE(q,k) -> KV append of block `li` (q in h->q, k/v in the cache row lengths[r])
 static int layer_in_proj(zn_handle h, int li, bf16_t* x, bf16_t* kv, int max_len, const int* lengths, int rows, hipStream_t s, uint8_t* kv8 = nullptr, bool kv_round = false) {
-  return run_gemv<PRO_LN, EPI_ROPE_KV>(h, in_proj_args(h, h->layers[li], x, kv, max_len, lengths, kv8, kv_round), rows, h->tune[ZN_TUNE_WG_IN_PROJ], s);
+  return run_step_linear<PRO_LN, EPI_ROPE_KV>(h, SL_IN_PROJ, li, in_proj_args(h, h->layers[li], x, kv, max_len, lengths, kv8, kv_round), rows, s);
 }
 
 // out_proj (-> out_proj again, _torch.py:419-420) -> residual -> LayerNorm -> fc1 -> y * silu(gate) -> fc2 -> residual
-static int layer_post_attention(zn_handle h, int li, bf16_t* x, int rows, hipStream_t s, bf16_t* x1_copy = nullptr) {
+// pp: the plans, when the caller made them already (zn_bench_kernel); which: all three launches, or one of SL_OUT_PROJ / SL_FC1 / SL_FC2 alone
+static int layer_post_attention(zn_handle h, int li, bf16_t* x, int rows, hipStream_t s, bf16_t* x1_copy = nullptr, const PostAttnPlans* planned = nullptr, int which = -1) {
   const zn_layer_weights& lw = h->layers[li];
-  const PostAttnPlans pp = plan_post_attention(h, rows, mlp_fp8_offered(h, li));
-  const zn_handle_s::MlpFp8& f8 = h->mlp_fp8[li];
+  const PostAttnPlans pp = planned ? *planned : plan_post_attention(h, rows, mlp_fp8_offered(h, li));
   int rc;
-  GemvArgs o = out_proj_args(h, lw, h->o1, x, x);
-  o.ln_part_out = h->ln_part;
-  if (h->cfg.double_out_proj) {   // q is dead after attention: reuse it for the intermediate projection
-    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, out_proj_args(h, lw, h->o1, h->q, nullptr), rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s))) return rc;
-    o.x = h->q;
+  if (which < 0 || which == SL_OUT_PROJ) {
+    GemvArgs o = step_args(h, lw.out_proj, h->o1, x, x);
+    o.ln_part_out = h->ln_part;
+    if (h->cfg.double_out_proj && which < 0) {   // q is dead after attention: reuse it for the intermediate projection
+      if ((rc = run_step_linear<PRO_NONE, EPI_STORE>(h, SL_OUT_PROJ_FIRST, li, step_args(h, lw.out_proj, h->o1, h->q), rows, s))) return rc;
+      o.x = h->q;
+    }
+    if ((rc = launch_step_linear<PRO_NONE, EPI_RESID>(h, SL_OUT_PROJ, li, pp.out, o, rows, s))) return rc;
+    if (x1_copy) (void)hipMemcpyAsync(x1_copy, x, (size_t)rows * h->cfg.d_model * 2, hipMemcpyDeviceToDevice, s);      // diagnostic trace
   }
-  if ((rc = launch_linear<PRO_NONE, EPI_RESID>(h, pp.out, o, rows, s))) return rc;
-  if (x1_copy) (void)hipMemcpyAsync(x1_copy, x, (size_t)rows * h->cfg.d_model * 2, hipMemcpyDeviceToDevice, s);      // diagnostic trace
-  GemvArgs f1 = fc1_args(h, lw, x, pp.out.writes_ln_stats ? h->ln_part : nullptr), f2 = fc2_args(h, lw, x);
-  f1.W8q = f8.fc1_q; f1.W8exp = f8.fc1_exp; f2.W8q = f8.fc2_q; f2.W8exp = f8.fc2_exp;
-  if ((rc = launch_linear<PRO_LN, EPI_SILU>(h, pp.fc1, f1, rows, s))) return rc;
-  return launch_linear<PRO_NONE, EPI_RESID>(h, pp.fc2, f2, rows, s);
+  if ((which < 0 || which == SL_FC1) && (rc = launch_step_linear<PRO_LN, EPI_SILU>(h, SL_FC1, li, pp.fc1, fc1_args(h, lw, x, pp.out.writes_ln_stats ? h->ln_part : nullptr), rows, s))) return rc;
+  if (which < 0 || which == SL_FC2) return launch_step_linear<PRO_NONE, EPI_RESID>(h, SL_FC2, li, pp.fc2, step_args(h, lw.fc2, h->mbuf, x, x), rows, s);
+  return ZN_OK;
 }
 
 // One decode step of block `li` on x [rows][d] in place (_torch.py:307-328), as launches.
@@ -1054,7 +1089,9 @@ static int decode_blocks(zn_handle h, const StepPlan& p, const int* ext, int ext
 }
 
 static int heads_logits(zn_handle h, const bf16_t* x, int rows, hipStream_t s) {
-  return run_gemv<PRO_LN, EPI_F32>(h, heads_args(h, x), rows, h->tune[ZN_TUNE_WG_HEADS], s);
+  GemvArgs a = step_args(h, h->heads, x, nullptr);
+  a.ln_w = (const bf16_t*)h->norm_f_w; a.ln_b = (const bf16_t*)h->norm_f_b; a.out_f32 = h->logits_raw;
+  return run_step_linear<PRO_LN, EPI_F32>(h, SL_HEADS, -1, a, rows, s);
 }
 
 // ------------------------------------------------------------------------------------------------ hybrid backbone
@@ -1068,46 +1105,27 @@ static void launch_add_ln(zn_handle h, const bf16_t* hid, bf16_t* res, int has_r
 }
 
 // The Mamba2 in_proj with the conv window update + SiLU of its xBC rows in the epilogue (causal_conv1d_update; one launch less): n [rows][d] -> m_zx, m_xbc
-static bool mamba_fp8_offered(zn_handle h, int li) { return li >= 0 && h->mamba_fp8[li].in_q != nullptr && h->tune[ZN_TUNE_MAMBA_FP8] != 2; }
-// linear_env of a generation step with layer li's FP8 streams offered (LinearEnv::w8k_offered): the ONE env mamba_mixer and zn_mamba_fp8_plan plan from
-static LinearEnv mamba_env(zn_handle h, bool w8k) {
-  LinearEnv e = linear_env(h);
-  e.w8k_offered = w8k;
-  e.w8v_offered = w8k && fp8_small_rows(h);      // the GEMV launches of 1..4 rows: an offer of its own
-  return e;
-}
 static int mamba_in_proj(zn_handle h, int li, const bf16_t* n, void* conv_state, int rows, hipStream_t s) {
   const zn_config& c = h->cfg;
   const zn_layer_weights& lw = h->layers[li];
-  GemvArgs a{};
-  a.W = (const bf16_t*)lw.m_in_proj; a.N = h->m_d_in_proj; a.K = c.d_model; a.x = n; a.out = h->m_zx;
+  GemvArgs a = step_args(h, lw.m_in_proj, n, h->m_zx);
   a.conv_state = (bf16_t*)conv_state; a.conv_w = (const bf16_t*)lw.m_conv_w; a.conv_b = (const bf16_t*)lw.m_conv_b; a.xbc = h->m_xbc;
   a.d_inner = c.m_d_inner; a.conv_dim = h->m_conv_dim;
-  a.W8q = h->mamba_fp8[li].in_q; a.W8exp = h->mamba_fp8[li].in_exp;
-  return launch_linear<PRO_NONE, EPI_MAMBA>(h, plan_linear(mamba_env(h, mamba_fp8_offered(h, li)), PRO_NONE, EPI_MAMBA, rows, a.N, a.K, (h->m_d_in_proj / 2 + 3) / 4, false, false, false), a, rows, s);
+  return run_step_linear<PRO_NONE, EPI_MAMBA>(h, SL_M_IN_PROJ, li, a, rows, s);
 }
 
 // The Mamba2 out_proj without a prologue (more than 4 rows, or several norm groups: g [rows][d_inner] is the gated norm's output) -> out [rows][d]
 static int mamba_out_proj(zn_handle h, int li, const bf16_t* g, bf16_t* out, int rows, hipStream_t s) {
-  const zn_config& c = h->cfg;
-  GemvArgs o{};
-  o.W = (const bf16_t*)h->layers[li].m_out_proj; o.N = c.d_model; o.K = c.m_d_inner; o.out = out; o.x = g;
-  o.W8q = h->mamba_fp8[li].out_q; o.W8exp = h->mamba_fp8[li].out_exp;
-  return launch_linear<PRO_NONE, EPI_STORE>(h, plan_linear(mamba_env(h, mamba_fp8_offered(h, li)), PRO_NONE, EPI_STORE, rows, o.N, o.K, h->tune[ZN_TUNE_WG_FC2], false, false, false), o, rows, s);
+  return run_step_linear<PRO_NONE, EPI_STORE>(h, SL_M_OUT_PROJ, li, step_args(h, h->layers[li].m_out_proj, g, out), rows, s);
 }
 
-// The Mamba2 out_proj of up to 4 rows with RMSNormGated (one group) as its prologue: m_vg [rows][d_inner] fp32 gated values -> out [rows][d].  Planned from
-// mamba_env like the other two projections of the mixer: with the default env this is the plan of a plain GEMV, under ZN_TUNE_FP8_SMALL_ROWS it reads the stream.
+// The Mamba2 out_proj of up to 4 rows with RMSNormGated (one group) as its prologue: m_vg [rows][d_inner] fp32 gated values -> out [rows][d].  With the default
+// settings this is the plan of a plain GEMV, under ZN_TUNE_FP8_SMALL_ROWS it reads the stream.
 static int mamba_out_proj_gated(zn_handle h, int li, bf16_t* out, int rows, hipStream_t s) {
-  const zn_config& c = h->cfg;
-  const zn_layer_weights& lw = h->layers[li];
-  GemvArgs o{};
-  o.W = (const bf16_t*)lw.m_out_proj; o.N = c.d_model; o.K = c.m_d_inner; o.out = out;
-  o.gv = h->m_vg; o.ln_w = (const bf16_t*)lw.m_norm_w; o.eps = c.norm_eps;
-  o.W8q = h->mamba_fp8[li].out_q; o.W8exp = h->mamba_fp8[li].out_exp;
-  return launch_linear<PRO_GATED, EPI_STORE>(h, plan_linear(mamba_env(h, mamba_fp8_offered(h, li)), PRO_GATED, EPI_STORE, rows, o.N, o.K, h->tune[ZN_TUNE_WG_FC2], false, false, false), o, rows, s);
+  GemvArgs o = step_args(h, h->layers[li].m_out_proj, nullptr, out);
+  o.gv = h->m_vg; o.ln_w = (const bf16_t*)h->layers[li].m_norm_w;
+  return run_step_linear<PRO_GATED, EPI_STORE>(h, SL_M_OUT_PROJ, li, o, rows, s);
 }
-static bool mamba_gated_pro(const zn_config& c, int rows) { return c.m_ngroups == 1 && c.m_d_inner % 8 == 0 && rows <= 4 && c.m_d_inner <= 4096; }
 
 // One token through the Mamba2 mixer of layer li (mamba_ssm Mamba2.step): n [rows][d] normalised -> out [rows][d]
 static int mamba_mixer(zn_handle h, int li, const bf16_t* n, void* state, bf16_t* out, int rows, hipStream_t s) {
@@ -1142,52 +1160,38 @@ static int mamba_mixer(zn_handle h, int li, const bf16_t* n, void* state, bf16_t
 static int hybrid_layer(zn_handle h, int li, void* cache, int max_len, const int* lengths, int rows, int attn_fused, hipStream_t s) {
   const zn_config& c = h->cfg;
   const zn_layer_weights& lw = h->layers[li];
-  const int d = c.d_model, hd = h->hd, nq = c.n_heads * hd, nkv = c.n_heads_kv * hd;
   int rc;
   // (the add + LayerNorm as a prologue of the GEMV that consumes it - every workgroup repeating it, the residual
   // ping-ponging between two buffers - was measured slower than this launch: batch-1 step 1.17 -> 1.24 ms)
   launch_add_ln(h, h->x, h->res, li > 0, 1, lw.norm_w, lw.norm_b, h->hn, rows, s);
   if (lw.kind == 1) return mamba_mixer(h, li, h->hn, cache, h->x, rows, s);
-  if (c.rope_mode == 0 && !lw.in_proj_bias) {  // MHA: in_proj -> split -> interleaved RoPE(q,k) -> KV append, one launch
-    GemvArgs a{};
-    a.W = (const bf16_t*)lw.in_proj; a.N = nq + 2 * nkv; a.K = d; a.x = h->hn;
-    a.lengths = lengths; a.hd = hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
+  if (step_linear_desc(c, h->tune, SL_H_IN_PROJ, rows, step_in_proj_bias(h, SL_H_IN_PROJ, li)).epi == EPI_ROPE_KV) {  // MHA: in_proj -> split -> interleaved RoPE(q,k) -> KV append, one launch
+    GemvArgs a = step_args(h, lw.in_proj, h->hn, nullptr);
+    a.lengths = lengths; a.hd = h->hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
     a.q_out = h->q; a.kv = (bf16_t*)cache; a.rope = h->rope; a.max_len = max_len; a.rope_positions = c.rope_positions;
-    if ((rc = run_gemv<PRO_NONE, EPI_ROPE_KV>(h, a, rows, h->tune[ZN_TUNE_WG_IN_PROJ], s))) return rc;
+    if ((rc = run_step_linear<PRO_NONE, EPI_ROPE_KV>(h, SL_H_IN_PROJ, li, a, rows, s))) return rc;
   } else {   // the other attn_cfg forms (half-split or no rotary, qkv bias): projection (+ bias), then rotation + KV append
-    GemvArgs a{};
-    a.W = (const bf16_t*)lw.in_proj; a.N = nq + 2 * nkv; a.K = d; a.x = h->hn; a.out = h->qkv_tmp; a.bias = (const bf16_t*)lw.in_proj_bias;
-    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[ZN_TUNE_WG_IN_PROJ], s))) return rc;
-    hipLaunchKernelGGL(rope_kv_any_kernel, dim3(1, rows), dim3(256), 0, s, h->qkv_tmp, h->q, nq, (bf16_t*)cache, h->rope, 1, 0, lengths, max_len,
-                       c.n_heads, c.n_heads_kv, hd, c.rope_positions, c.rope_mode);
+    GemvArgs a = step_args(h, lw.in_proj, h->hn, h->qkv_tmp);
+    a.bias = (const bf16_t*)lw.in_proj_bias;
+    if ((rc = run_step_linear<PRO_NONE, EPI_STORE>(h, SL_H_IN_PROJ, li, a, rows, s))) return rc;
+    hipLaunchKernelGGL(rope_kv_any_kernel, dim3(1, rows), dim3(256), 0, s, h->qkv_tmp, h->q, c.n_heads * h->hd, (bf16_t*)cache, h->rope, 1, 0, lengths, max_len,
+                       c.n_heads, c.n_heads_kv, h->hd, c.rope_positions, c.rope_mode);
   }
   if ((rc = run_attention(h, h->q, (const bf16_t*)cache, max_len, lengths, nullptr, 0, h->o1, rows, attn_fused, s))) return rc;
-  {
-    GemvArgs a{};
-    a.W = (const bf16_t*)lw.out_proj; a.N = d; a.K = nq; a.x = h->o1; a.out = h->x; a.bias = (const bf16_t*)lw.out_proj_bias;
-    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s))) return rc;
-  }
+  GemvArgs o = step_args(h, lw.out_proj, h->o1, h->x);
+  o.bias = (const bf16_t*)lw.out_proj_bias;
+  if ((rc = run_step_linear<PRO_NONE, EPI_STORE>(h, SL_H_OUT_PROJ, li, o, rows, s))) return rc;
   launch_add_ln(h, h->x, h->res, 1, 1, lw.norm2_w, lw.norm2_b, h->hn, rows, s);
-  {
-    GemvArgs a{};
-    a.W = (const bf16_t*)lw.fc1; a.N = 2 * c.d_ff; a.K = d; a.x = h->hn; a.out = h->mbuf;
-    if ((rc = run_gemv<PRO_NONE, EPI_SILU>(h, a, rows, h->tune[ZN_TUNE_WG_FC1], s))) return rc;
-  }
-  {
-    GemvArgs a{};
-    a.W = (const bf16_t*)lw.fc2; a.N = d; a.K = c.d_ff; a.x = h->mbuf; a.out = h->x;
-    if ((rc = run_gemv<PRO_NONE, EPI_STORE>(h, a, rows, h->tune[ZN_TUNE_WG_FC2], s))) return rc;
-  }
-  return ZN_OK;
+  if ((rc = run_step_linear<PRO_NONE, EPI_SILU>(h, SL_H_FC1, li, step_args(h, lw.fc1, h->hn, h->mbuf), rows, s))) return rc;
+  return run_step_linear<PRO_NONE, EPI_STORE>(h, SL_H_FC2, li, step_args(h, lw.fc2, h->mbuf, h->x), rows, s);
 }
 
 // final add + norm (_mamba_ssm.py:111-119) of the token in h->x / h->res, then the heads
 static int hybrid_heads(zn_handle h, hipStream_t s) {
-  const zn_config& c = h->cfg;
   launch_add_ln(h, h->x, h->res, 1, 0, h->norm_f_w, h->norm_f_b, h->hn, h->rows, s);
-  GemvArgs a{};
-  a.W = (const bf16_t*)h->heads; a.N = c.n_codebooks * c.vocab_head; a.K = c.d_model; a.x = h->hn; a.out_f32 = h->logits_raw;
-  return run_gemv<PRO_NONE, EPI_F32>(h, a, h->rows, h->tune[ZN_TUNE_WG_HEADS], s);
+  GemvArgs a = step_args(h, h->heads, h->hn, nullptr);
+  a.out_f32 = h->logits_raw;
+  return run_step_linear<PRO_NONE, EPI_F32>(h, SL_H_HEADS, -1, a, h->rows, s);
 }
 
 // All layers for the token in h->x, then the final add + LayerNorm and the heads.
@@ -2192,33 +2196,17 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   HIPCHK(h, hipEventCreate(&e0));
   HIPCHK(h, hipEventCreate(&e1));
   int rc = ZN_OK;
-  // which == 0 at 5..16 rows: the launch a decode step makes there - fc1 normalising from the statistics its producer left (plan_post_attention);
-  // the producer runs once, outside the timed loop, on the zeroed rows
-  // up to 4 rows: fc1 / fc2 as layer_post_attention plans them for a block whose FP8 stream is offered (the GEMV reads it under ZN_TUNE_FP8_SMALL_ROWS = 2);
-  // without a stream on every block, and from 5 rows on, the plans of the bf16 weights as before
-  bool mlp_w8 = rows <= 4 && c.arch == 0;
-  for (int li = 0; mlp_w8 && li < c.n_layer; ++li) mlp_w8 = mlp_fp8_offered(h, li);
-  const PostAttnPlans pp = plan_post_attention(h, rows, mlp_w8);
-  if (which == 0 && pp.out.writes_ln_stats) {
-    GemvArgs b = out_proj_args(h, h->layers[0], h->o1, h->x, h->x);
-    b.ln_part_out = h->ln_part;
-    rc = launch_linear<PRO_NONE, EPI_RESID>(h, pp.out, b, rows, s);
-  }
+  // which 0, 1, 2: one launch of layer_post_attention, which 3, 4, 7, 8: heads_logits, layer_in_proj and the Mamba2 projections - the step's own code, so what is priced is what runs.
+  // which == 0 at 5..16 rows: fc1 normalises from the statistics its producer left; the producer runs once, outside the timed loop, on the zeroed rows.
+  // Up to 4 rows fc1 / fc2 are planned as for a block whose FP8 stream is offered (the GEMV reads it under ZN_TUNE_FP8_SMALL_ROWS = 2) when every block has one;
+  // from 5 rows on, the plans of the bf16 weights
+  const PostAttnPlans pp = plan_post_attention(h, rows, rows <= 4 && every_layer_offers(h, SL_FC1));
+  if (which == 0 && pp.out.writes_ln_stats) rc = layer_post_attention(h, 0, h->x, rows, s, nullptr, &pp, SL_OUT_PROJ);
   for (int pass = 0; pass < 2 && rc == ZN_OK; ++pass) {   // pass 0 = warm-up
     if (pass == 1) HIPCHK(h, hipEventRecord(e0, s));
     for (int i = 0; i < (pass ? iters : (iters < 8 ? iters : 8)) && rc == ZN_OK; ++i) {
-      const zn_layer_weights& lw = h->layers[same_layer ? 0 : i % c.n_layer];
-      const zn_handle_s::MlpFp8& f8 = h->mlp_fp8[same_layer ? 0 : i % c.n_layer];
-      if (which == 0) {
-        GemvArgs f1 = fc1_args(h, lw, h->x, pp.out.writes_ln_stats ? h->ln_part : nullptr);
-        f1.W8q = f8.fc1_q; f1.W8exp = f8.fc1_exp;
-        rc = launch_linear<PRO_LN, EPI_SILU>(h, pp.fc1, f1, rows, s);
-      } else if (which == 1 && pp.fc2.w8) {      // (the plan of run_gemv below in every other field)
-        GemvArgs f2 = fc2_args(h, lw, h->x);
-        f2.W8q = f8.fc2_q; f2.W8exp = f8.fc2_exp;
-        rc = launch_linear<PRO_NONE, EPI_RESID>(h, pp.fc2, f2, rows, s);
-      } else if (which == 1) rc = run_gemv<PRO_NONE, EPI_RESID>(h, fc2_args(h, lw, h->x), rows, h->tune[ZN_TUNE_WG_FC2], s);
-      else if (which == 2) rc = run_gemv<PRO_NONE, EPI_RESID>(h, out_proj_args(h, lw, h->o1, h->x, h->x), rows, h->tune[ZN_TUNE_WG_OUT_PROJ], s);
+      const int li = same_layer ? 0 : i % c.n_layer;
+      if (which <= 2) rc = layer_post_attention(h, li, h->x, rows, s, nullptr, &pp, which == 0 ? SL_FC1 : which == 1 ? SL_FC2 : SL_OUT_PROJ);
       else if (which == 6) rc = launch_stack(h, s, rows, stack_nbk);
       else if (which == 7) rc = mamba_in_proj(h, mamba_layers[same_layer ? 0 : i % mamba_layers.size()], h->x, tconv, rows, s);
       else if (which == 8 && out_gated) rc = mamba_out_proj_gated(h, mamba_layers[same_layer ? 0 : i % mamba_layers.size()], h->x, rows, s);
@@ -2226,7 +2214,7 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
       else if (which == 5) {
         if (i % c.n_layer == c.n_layer - 1) continue;       // the last block's launch has no in_proj: not the launch being priced
         rc = launch_chain(h, i % c.n_layer, std::vector<const void*>(c.n_layer, tkv), 8, tlen, s);
-      } else if (which == 4) rc = run_gemv<PRO_LN, EPI_ROPE_KV>(h, in_proj_args(h, lw, h->x, tkv, 8, tlen), rows, h->tune[ZN_TUNE_WG_IN_PROJ], s);
+      } else if (which == 4) rc = layer_in_proj(h, li, h->x, tkv, 8, tlen, rows, s);
       else rc = heads_logits(h, h->x, rows, s);
     }
   }
@@ -2310,7 +2298,7 @@ static int linear_fused_impl(zn_handle h, zn_linear_op* op, const void* W_q, con
     if (prefill) ZN_F8_REFUSE(ZN_ERR_UNSUPPORTED, "zn_op_linear_fp8: the prefill kernels read bf16 weights");
     if (K % ZN_G16_KC) ZN_F8_REFUSE(ZN_ERR_UNSUPPORTED, "zn_op_linear_fp8: K=%d is no multiple of %d", K, ZN_G16_KC);
     env.w8_offered = h->tune[ZN_TUNE_MLP_FP8] != 2;
-    env.w8v_offered = env.w8_offered && fp8_small_rows(h);
+    env.w8v_offered = env.w8_offered && fp8_small_rows_on(h->tune);
   }
   LinearPlan p = plan_linear(env, pro, epi, rows, N, K, op->target_blocks > 0 ? op->target_blocks : 1, prefill, op->want_ln_stats_out != 0, op->ln_stats_in != 0);
   int* o = op->plan;
@@ -2397,6 +2385,21 @@ static long long fp8_mismatches(const void* q, const void* e, const void* W, int
   (void)hipFree(cnt);
   return ok ? (long long)host : -1;
 }
+// What zn_set_mlp_fp8 and zn_set_mamba_fp8 share once their own refusals have passed: all four pointers or none, the ZN_FP8_VERIFY comparison of both matrices, the graph drop.
+struct Fp8Stream { const char* name; const void *q, *exp, *W; int N, K; };
+static int attach_fp8_pair(zn_handle h, const char* who, int layer, const Fp8Stream& a, const Fp8Stream& b) {
+  const int n_set = (a.q != nullptr) + (a.exp != nullptr) + (b.q != nullptr) + (b.exp != nullptr);
+  if (n_set != 0 && n_set != 4) ZN_FAIL(h, ZN_ERR_ARG, "%s: all four pointers, or none", who);
+  const char* v = getenv("ZN_FP8_VERIFY");
+  if (n_set == 4 && v && atoi(v) == 1) {
+    const long long b1 = fp8_mismatches(a.q, a.exp, a.W, a.N, a.K);
+    const long long b2 = b1 < 0 ? -1 : fp8_mismatches(b.q, b.exp, b.W, b.N, b.K);
+    if (b1 < 0 || b2 < 0) ZN_FAIL(h, ZN_ERR_HIP, "%s: the verification could not run", who);
+    if (b1 || b2) ZN_FAIL(h, ZN_ERR_ARG, "%s: layer %d's bf16 weights are not the dequantised stream (%s: %lld, %s: %lld pieces of 8 differ)", who, layer, a.name, b1, b.name, b2);
+  }
+  free_graph(h); h->emb_valid = false;
+  return ZN_OK;
+}
 extern "C" int zn_set_mlp_fp8(zn_handle h, int32_t layer, const void* fc1_q, const void* fc1_exp, const void* fc2_q, const void* fc2_exp) {
   if (!h) return ZN_ERR_ARG;
   const zn_config& c = h->cfg;
@@ -2405,20 +2408,9 @@ extern "C" int zn_set_mlp_fp8(zn_handle h, int32_t layer, const void* fc1_q, con
   if (h->layers[layer].kind != 0) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mlp_fp8: layer %d is a Mamba2 layer", layer);
   if (c.d_model % ZN_G16_KC || c.d_ff % ZN_G16_KC) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mlp_fp8: d_model %d / d_ff %d must be multiples of %d", c.d_model, c.d_ff, ZN_G16_KC);
   if (h->gen_active && !h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_set_mlp_fp8 inside a generation (between zn_gen_begin and zn_gen_end)");
-  const int n_set = (fc1_q != nullptr) + (fc1_exp != nullptr) + (fc2_q != nullptr) + (fc2_exp != nullptr);
-  if (n_set != 0 && n_set != 4) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mlp_fp8: all four pointers, or none");
-  if (n_set == 4) {
-    const char* v = getenv("ZN_FP8_VERIFY");
-    if (v && atoi(v) == 1) {
-      const long long b1 = fp8_mismatches(fc1_q, fc1_exp, h->layers[layer].fc1, 2 * c.d_ff, c.d_model);
-      const long long b2 = b1 < 0 ? -1 : fp8_mismatches(fc2_q, fc2_exp, h->layers[layer].fc2, c.d_model, c.d_ff);
-      if (b1 < 0 || b2 < 0) ZN_FAIL(h, ZN_ERR_HIP, "zn_set_mlp_fp8: the verification could not run");
-      if (b1 || b2) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mlp_fp8: layer %d's bf16 weights are not the dequantised stream (fc1: %lld, fc2: %lld pieces of 8 differ)", layer, b1, b2);
-    }
-  }
+  if (int rc = attach_fp8_pair(h, "zn_set_mlp_fp8", layer, {"fc1", fc1_q, fc1_exp, h->layers[layer].fc1, 2 * c.d_ff, c.d_model}, {"fc2", fc2_q, fc2_exp, h->layers[layer].fc2, c.d_model, c.d_ff})) return rc;
   zn_handle_s::MlpFp8& f = h->mlp_fp8[layer];
   f.fc1_q = (const uint8_t*)fc1_q; f.fc1_exp = (const int8_t*)fc1_exp; f.fc2_q = (const uint8_t*)fc2_q; f.fc2_exp = (const int8_t*)fc2_exp;
-  free_graph(h); h->emb_valid = false;
   return ZN_OK;
 }
 extern "C" int zn_set_kv_fp8(zn_handle h, int32_t on) {
@@ -2449,18 +2441,18 @@ extern "C" int zn_gen_bind_kv_fp8(zn_handle h, const void* const* codes_layers_d
   h->adm_cap_S = 0;          // a session's admission table names the code caches: rebuilt by the next admission
   return ZN_OK;
 }
-extern "C" int zn_kv_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
-  if (!h || !out || rows < 1) return ZN_ERR_ARG;
-  out[0] = h->kv_fp8 && kv_fp8_rows(h, rows);
-  out[1] = out[0] && kv_fp8_attn_reads(h, rows, kv_codes_only_rows(h, rows));
-  return ZN_OK;
-}
 extern "C" int zn_kv_cache_plan(zn_handle h, int32_t rows, int32_t out[3]) {
   if (!h || !out || rows < 1) return ZN_ERR_ARG;
   const bool codes_only = kv_codes_only_rows(h, rows);
   out[0] = h->kv_fp8 && kv_fp8_rows(h, rows);
   out[1] = out[0] && kv_fp8_attn_reads(h, rows, codes_only);
   out[2] = !codes_only;
+  return ZN_OK;
+}
+extern "C" int zn_kv_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
+  int32_t o[3];
+  if (!out || zn_kv_cache_plan(h, rows, o) != ZN_OK) return ZN_ERR_ARG;
+  out[0] = o[0]; out[1] = o[1];
   return ZN_OK;
 }
 extern "C" int zn_op_bind_kv_fp8(zn_handle h, void* codes_dev) {
@@ -2479,15 +2471,6 @@ extern "C" int zn_op_rope_kv_rows(zn_handle h, void* qkv_dev, void* kv_dev, int3
   HIPCHK(h, hipGetLastError());
   return ZN_OK;
 }
-extern "C" int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
-  if (!h || !out || rows < 1) return ZN_ERR_ARG;
-  bool all = h->cfg.arch == 0;                   // 1 only when every block has a stream: a handle with some blocks attached reports 0
-  for (int li = 0; all && li < h->cfg.n_layer; ++li) all = mlp_fp8_offered(h, li);
-  const PostAttnPlans pp = plan_post_attention(h, rows, all);
-  out[0] = pp.fc1.w8; out[1] = pp.fc2.w8;
-  return ZN_OK;
-}
-
 extern "C" int zn_set_mamba_fp8(zn_handle h, int32_t layer, const void* in_q, const void* in_exp, const void* out_q, const void* out_exp) {
   if (!h) return ZN_ERR_ARG;
   const zn_config& c = h->cfg;
@@ -2497,92 +2480,54 @@ extern "C" int zn_set_mamba_fp8(zn_handle h, int32_t layer, const void* in_q, co
   if (c.d_model != 2 * ZN_G16K_NKW * ZN_G16K_KCH || c.m_d_inner != 4 * ZN_G16K_NKW * ZN_G16K_KCH)
     ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mamba_fp8: the FP8 kernels serve d_model 2048 and d_inner 4096 (got d_model %d, d_inner %d)", c.d_model, c.m_d_inner);
   if (h->gen_active && !h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_set_mamba_fp8 inside a generation (between zn_gen_begin and zn_gen_end)");
-  const int n_set = (in_q != nullptr) + (in_exp != nullptr) + (out_q != nullptr) + (out_exp != nullptr);
-  if (n_set != 0 && n_set != 4) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mamba_fp8: all four pointers, or none");
-  if (n_set == 4) {
-    const char* v = getenv("ZN_FP8_VERIFY");
-    if (v && atoi(v) == 1) {
-      const long long b1 = fp8_mismatches(in_q, in_exp, h->layers[layer].m_in_proj, h->m_d_in_proj, c.d_model);
-      const long long b2 = b1 < 0 ? -1 : fp8_mismatches(out_q, out_exp, h->layers[layer].m_out_proj, c.d_model, c.m_d_inner);
-      if (b1 < 0 || b2 < 0) ZN_FAIL(h, ZN_ERR_HIP, "zn_set_mamba_fp8: the verification could not run");
-      if (b1 || b2) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mamba_fp8: layer %d's bf16 weights are not the dequantised stream (in_proj: %lld, out_proj: %lld pieces of 8 differ)", layer, b1, b2);
-    }
-  }
+  if (int rc = attach_fp8_pair(h, "zn_set_mamba_fp8", layer, {"in_proj", in_q, in_exp, h->layers[layer].m_in_proj, h->m_d_in_proj, c.d_model},
+                               {"out_proj", out_q, out_exp, h->layers[layer].m_out_proj, c.d_model, c.m_d_inner})) return rc;
   zn_handle_s::MambaFp8& f = h->mamba_fp8[layer];
   f.in_q = (const uint8_t*)in_q; f.in_exp = (const int8_t*)in_exp; f.out_q = (const uint8_t*)out_q; f.out_exp = (const int8_t*)out_exp;
-  free_graph(h); h->emb_valid = false;
   return ZN_OK;
 }
-// the two plans mamba_mixer makes for a layer whose streams are offered (the same calls of plan_linear)
+
+// ---- The plan queries read the step's own table (zn_step_linears.h) through step_plan and plan_post_attention, as the launches do.
+extern "C" int zn_mlp_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
+  if (!h || !out || rows < 1) return ZN_ERR_ARG;
+  const bool all = every_layer_offers(h, SL_FC1);      // 1 only when every block has a stream: a handle with some blocks attached reports 0
+  const PostAttnPlans pp = plan_post_attention(h, rows, all);
+  out[0] = pp.fc1.w8; out[1] = pp.fc2.w8;
+  return ZN_OK;
+}
 extern "C" int zn_mamba_fp8_plan(zn_handle h, int32_t rows, int32_t out[2]) {
   if (!h || !out || rows < 1) return ZN_ERR_ARG;
-  const zn_config& c = h->cfg;
-  out[0] = out[1] = 0;
-  if (c.arch != 1) return ZN_OK;
-  int n_mamba = 0;
-  bool all = true;                               // 1 only when every Mamba2 layer has a stream
-  for (int li = 0; li < c.n_layer; ++li)
-    if (h->layers[li].kind == 1) { ++n_mamba; all = all && mamba_fp8_offered(h, li); }
-  if (!n_mamba || !all) return ZN_OK;
-  const LinearEnv e = mamba_env(h, true);
-  const bool gated_pro = c.m_ngroups == 1 && c.m_d_inner % 8 == 0 && rows <= 4 && c.m_d_inner <= 4096;
-  out[0] = plan_linear(e, PRO_NONE, EPI_MAMBA, rows, h->m_d_in_proj, c.d_model, (h->m_d_in_proj / 2 + 3) / 4, false, false, false).w8;
-  out[1] = plan_linear(e, gated_pro ? PRO_GATED : PRO_NONE, EPI_STORE, rows, c.d_model, c.m_d_inner, h->tune[ZN_TUNE_WG_FC2], false, false, false).w8;
+  const bool all = every_layer_offers(h, SL_M_IN_PROJ);      // 1 only when every Mamba2 layer has a stream
+  out[0] = all && step_plan(h, SL_M_IN_PROJ, -1, rows, true).w8;
+  out[1] = all && step_plan(h, SL_M_OUT_PROJ, -1, rows, true).w8;
   return ZN_OK;
 }
-
-// Activation rows per weight pass of a decode step of `rows` rows as this handle would run it now: in_proj, out_proj, fc1, fc2, heads (the plans of
-// layer_in_proj, plan_post_attention and heads_logits for a transformer block; with FP8 streams attached to every block, the plans that read them).
+// Activation rows per weight pass of a decode step of `rows` rows as this handle would run it now: in_proj, out_proj, fc1, fc2, heads (with FP8 streams attached to
+// every block, the plans that read them).
 extern "C" int zn_decode_rows_plan(zn_handle h, int32_t rows, int32_t out[5]) {
   if (!h || !out || rows < 1) return ZN_ERR_ARG;
-  const zn_config& c = h->cfg;
-  bool all = c.arch == 0;
-  for (int li = 0; all && li < c.n_layer; ++li) all = mlp_fp8_offered(h, li);
-  const PostAttnPlans pp = plan_post_attention(h, rows, all);
-  const LinearEnv e = linear_env(h);
-  const LinearPlan in = plan_linear(e, PRO_LN, EPI_ROPE_KV, rows, (c.n_heads + 2 * c.n_heads_kv) * h->hd, c.d_model, h->tune[ZN_TUNE_WG_IN_PROJ], false, false, false);
-  const LinearPlan hd = plan_linear(e, PRO_LN, EPI_F32, rows, c.n_codebooks * c.vocab_head, c.d_model, h->tune[ZN_TUNE_WG_HEADS], false, false, false);
-  const LinearPlan* ps[5] = {&in, &pp.out, &pp.fc1, &pp.fc2, &hd};
+  const PostAttnPlans pp = plan_post_attention(h, rows, every_layer_offers(h, SL_FC1));
+  const LinearPlan ps[5] = {step_plan(h, SL_IN_PROJ, -1, rows, false), pp.out, pp.fc1, pp.fc2, step_plan(h, SL_HEADS, -1, rows, false)};
   for (int k = 0; k < 5; ++k) {
-    if (ps[k]->err) ZN_FAIL(h, ps[k]->err, "%s", ps[k]->msg);
-    out[k] = ps[k]->rows_per_launch;
+    if (ps[k].err) ZN_FAIL(h, ps[k].err, "%s", ps[k].msg);
+    out[k] = ps[k].rows_per_launch;
   }
   return ZN_OK;
 }
 
-// Activation rows per weight pass of a hybrid decode step of `rows` rows: the plans mamba_mixer, hybrid_layer and hybrid_heads make (the same calls of
-// plan_linear: prologue, epilogue, shape and target of each run_gemv there), for the first Mamba2 and the first attention layer; 0 where the stack has no such layer.
+// The same for a hybrid decode step: the table's hybrid linears in its order, each planned for the first layer that has it; 0 where the stack has no such layer.
 extern "C" int zn_hybrid_rows_plan(zn_handle h, int32_t rows, int32_t out[7]) {
   if (!h || !out || rows < 1) return ZN_ERR_ARG;
-  const zn_config& c = h->cfg;
-  if (c.arch != 1) ZN_FAIL(h, ZN_ERR_STATE, "zn_hybrid_rows_plan: not a hybrid handle");
-  const LinearEnv e = linear_env(h);
-  const int d = c.d_model, nq = c.n_heads * h->hd, nkv = c.n_heads_kv * h->hd;
-  int mamba = -1, attn = -1;
-  for (int li = c.n_layer - 1; li >= 0; --li) (h->layers[li].kind == 1 ? mamba : attn) = li;
+  if (h->cfg.arch != 1) ZN_FAIL(h, ZN_ERR_STATE, "zn_hybrid_rows_plan: not a hybrid handle");
+  int first[2] = {-1, -1};      // the first attention layer, the first Mamba2 layer
+  for (int li = h->cfg.n_layer - 1; li >= 0; --li) first[h->layers[li].kind == 1] = li;
   for (int k = 0; k < 7; ++k) out[k] = 0;
-  LinearPlan ps[7];
-  bool on[7] = {};
-  if (mamba >= 0) {
-    const bool gated_pro = c.m_ngroups == 1 && c.m_d_inner % 8 == 0 && rows <= 4 && c.m_d_inner <= 4096;
-    ps[0] = plan_linear(e, PRO_NONE, EPI_MAMBA, rows, h->m_d_in_proj, d, (h->m_d_in_proj / 2 + 3) / 4, false, false, false);
-    ps[1] = plan_linear(e, gated_pro ? PRO_GATED : PRO_NONE, EPI_STORE, rows, d, c.m_d_inner, h->tune[ZN_TUNE_WG_FC2], false, false, false);
-    on[0] = on[1] = true;
-  }
-  if (attn >= 0) {
-    const bool rope_epi = c.rope_mode == 0 && !h->layers[attn].in_proj_bias;
-    ps[2] = plan_linear(e, PRO_NONE, rope_epi ? EPI_ROPE_KV : EPI_STORE, rows, nq + 2 * nkv, d, h->tune[ZN_TUNE_WG_IN_PROJ], false, false, false);
-    ps[3] = plan_linear(e, PRO_NONE, EPI_STORE, rows, d, nq, h->tune[ZN_TUNE_WG_OUT_PROJ], false, false, false);
-    ps[4] = plan_linear(e, PRO_NONE, EPI_SILU, rows, 2 * c.d_ff, d, h->tune[ZN_TUNE_WG_FC1], false, false, false);
-    ps[5] = plan_linear(e, PRO_NONE, EPI_STORE, rows, d, c.d_ff, h->tune[ZN_TUNE_WG_FC2], false, false, false);
-    on[2] = on[3] = on[4] = on[5] = true;
-  }
-  ps[6] = plan_linear(e, PRO_NONE, EPI_F32, rows, c.n_codebooks * c.vocab_head, d, h->tune[ZN_TUNE_WG_HEADS], false, false, false);
-  on[6] = true;
-  for (int k = 0; k < 7; ++k) {
-    if (!on[k]) continue;
-    if (ps[k].err) ZN_FAIL(h, ps[k].err, "%s", ps[k].msg);
-    out[k] = ps[k].rows_per_launch;
+  for (int lin = SL_M_IN_PROJ; lin <= SL_H_HEADS; ++lin) {
+    const int li = lin == SL_H_HEADS ? -1 : first[step_linear_offer(lin) == SO_MAMBA];
+    if (lin != SL_H_HEADS && li < 0) continue;
+    const LinearPlan p = step_plan(h, lin, li, rows, stream_offered(h, lin, li));
+    if (p.err) ZN_FAIL(h, p.err, "%s", p.msg);
+    out[lin - SL_M_IN_PROJ] = p.rows_per_launch;
   }
   return ZN_OK;
 }
