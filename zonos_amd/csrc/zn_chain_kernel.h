@@ -270,8 +270,8 @@ __global__ __launch_bounds__(ZN_CH_THREADS) void chain_kernel(ChainArgs a) {
       if (op == 3) {
         const int qt = wave & 3, j = (wave >> 2) + (CW / 4) * t;
         ok = j < ppw_fc2;
-        const int u = c * ppw_fc2 + (ok ? j : 0);
-        pa = a.W_fc2 + (size_t)(2 * u) * (4 * D) + qt * D + lane * 8;
+        const int u = ok ? c * ppw_fc2 + j : 0;
+        pa = a.W_fc2 + (size_t)(2 * u) * (4 * D) + qt * D + (ok ? lane * 8 : 0);
         pb = pa + 4 * D;
         ridx = j * 4 + qt;
         return;
@@ -279,19 +279,21 @@ __global__ __launch_bounds__(ZN_CH_THREADS) void chain_kernel(ChainArgs a) {
       const int j = wave + CW * t;
       const int ppw = op <= 1 ? ppw_out : op == 2 ? ppw_fc1 : ppw_in;
       ok = j < ppw && (op < 4 || c * ppw + j < units_in);
-      const int u = c * ppw + (ok ? j : 0);
+      const int u = ok ? c * ppw + j : 0;
+      const int lo = ok ? lane * 8 : 0;
       ridx = j;
-      if (op <= 1) { pa = a.W_out + (size_t)(2 * u) * D + lane * 8; pb = pa + D; }
-      else if (op == 2) { pa = a.W_fc1 + (size_t)u * D + lane * 8; pb = pa + (size_t)F * D; }
-      else { pa = a.W_in + (size_t)(2 * u) * D + lane * 8; pb = (2 * u + 1 < a.nqkv) ? pa + D : pa; }   // half pair: row B repeats row A, result dropped
+      if (op <= 1) { pa = a.W_out + (size_t)(2 * u) * D + lo; pb = pa + D; }
+      else if (op == 2) { pa = a.W_fc1 + (size_t)u * D + lo; pb = pa + (size_t)F * D; }
+      else { pa = a.W_in + (size_t)(2 * u) * D + lo; pb = (2 * u + 1 < a.nqkv) ? pa + D : pa; }   // half pair: row B repeats row A, result dropped
     };
+    // The eight loads of a tile are issued whether the tile exists or not: a wave-uniform branch around them makes the compiler wait
+    // vmcnt(0 .. 7) for every older buffer (zn_step_kernel.h, load_into), which drains the NB tiles requested ahead.  An absent tile reads
+    // the first rows of the op's matrix without the lane offset - one cache line per load - and its buffer is never contracted.
     auto load = [&](int s, WT& w) {
       bool ok; const bf16_t *pa, *pb; int ridx;
       tile(s, ok, pa, pb, ridx);
-      if (ok) {                                           // wave-uniform
 #pragma unroll
-        for (int c2 = 0; c2 < NCH; ++c2) { w.a[c2] = ld_nt16(pa + c2 * 512); w.b[c2] = ld_nt16(pb + c2 * 512); }
-      }
+      for (int c2 = 0; c2 < NCH; ++c2) { w.a[c2] = ld_nt16(pa + c2 * 512); w.b[c2] = ld_nt16(pb + c2 * 512); }
     };
     auto slot_of_load = [](int l) constexpr { return l < S1 ? l : l + T_OUT; };
     auto load_req = [&](auto LC) { constexpr int l = decltype(LC)::value; load(slot_of_load(l), bufs[l % NB]); };

@@ -55,8 +55,11 @@
 #define ZN_SK_HELP_AT 0                                     // where the helper requests them: 0 = block start, 1 = after B(0) (attention output in), 2 = after P(0)
 #endif
 #ifndef ZN_SK_EARLY
-#define ZN_SK_EARLY 0                                       // requests for a LATER op's tiles that a wave may raise per op before that op's results are published (the
-#endif                                                      // rest wait for the publish: ZN_CH_DEFER_MASK).  Measured, 400 tokens: 0 0.8694 ms per step, 1 0.8907, 2 0.9398
+#define ZN_SK_EARLY 1                                       // requests for a LATER op's tiles that a wave may raise per op before that op's results are published (the
+#endif                                                      // rest wait for the publish: ZN_CH_DEFER_MASK).  While the tile requests stood under a branch (every contraction
+                                                            // drained the ring, load_into) 0 was best: 0 / 1 / 2 = 0.8694 / 0.8907 / 0.9398 ms per step over 400 tokens.  With
+                                                            // the ring really in flight, ms per step at contexts 300 / 600 / 1600 (profiles/step_ring_ctxsweep.txt):
+                                                            // 0: .7972 .8194 .8218, 1: .7828 .8070 .8131, 2: .8163 .8447 .8469
 #ifndef ZN_SK_MSWEEP_DELAY
 #define ZN_SK_MSWEEP_DELAY 0                                // the same for fc2's input, swept by the compute waves behind fc2's held-back tile requests (24 / 48: 0.837 vs 0.8335;
                                                             // that sweep's first pass issued AHEAD of those requests, 1 us after the publish: 0.868 vs 0.829)
@@ -529,15 +532,20 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
   auto slot_of_load = [](int l) constexpr { return SC::slot_of_load(l); };
   struct WT { u32x4 a[NCH], b[NCH]; };
   // tile of slot s for compute wave w: exists?, weight pointers of rows A and B (lane's first chunk), result index
-  struct LW { const bf16_t *out, *fc1, *fc2, *in; };           // the block's weight matrices, read from the layer table ONCE per block (SGPRs)
+  struct LW { const bf16_t *out, *fc1, *fc2, *in, *dm; };      // the block's weight matrices (and the dummy of absent tiles), read from the layer table ONCE per block (SGPRs)
+  // An absent tile (ok = false: the workgroup's share is smaller than the static schedule) still gets an address, because its request is
+  // issued all the same (load_into): the block's norm2 weight vector (Lr.dm: d_model bf16 = 4 KB, so the c2 * 512 element offsets of both
+  // rows stay inside it whatever the shapes) WITHOUT the lane offset.  All 64 lanes of such a load read the same 16 bytes, one cache line
+  // per instruction, and every streaming workgroup reads that vector with plain loads at the start of the block, so the line is in L2.
+  // The selects are on wave-uniform values: the address arithmetic stays scalar plus the lane offset, as for a present tile.
   auto tile_of = [&](const LW& Lr, int rows_in, int n_in, int s_in, int s, int w, bool& ok, const bf16_t*& pa, const bf16_t*& pb, int& ridx) {
     const int op = op_of(s), t = s - first_of(op);
     if (op == 3) {                                             // fc2: (row pair j, K quarter qt) in turn over the compute waves; with 4 of them wave w keeps quarter w
       const int i = w + CW * t, qt = i & 3, j = i >> 2;
       ok = j < n_out;
       const int u = s_out + (ok ? j : 0);
-      pa = Lr.fc2 + (size_t)(2 * u) * (4 * D) + qt * D + lane * 8;
-      pb = pa + 4 * D;
+      pa = (ok ? Lr.fc2 + (size_t)(2 * u) * (4 * D) + qt * D : Lr.dm) + (ok ? lane * 8 : 0);
+      pb = pa + (ok ? 4 * D : 0);
       ridx = j * 4 + qt;
       return;
     }
@@ -546,10 +554,11 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
     const int st = op <= 1 ? s_out : op == 2 ? s_fc1 : s_in;
     ok = j < n;
     const int u = st + (ok ? j : 0);
+    const int lo = ok ? lane * 8 : 0;
     ridx = j;
-    if (op <= 1) { pa = Lr.out + (size_t)(2 * u) * D + lane * 8; pb = pa + D; }
-    else if (op == 2) { pa = Lr.fc1 + (size_t)u * D + lane * 8; pb = pa + (size_t)F * D; }
-    else { pa = Lr.in + (size_t)(2 * u) * D + lane * 8; pb = (2 * u + 1 < rows_in) ? pa + D : pa; }   // half pair: row B repeats row A, result dropped
+    if (op <= 1) { pa = (ok ? Lr.out + (size_t)(2 * u) * D : Lr.dm) + lo; pb = pa + (ok ? D : 0); }
+    else if (op == 2) { pa = (ok ? Lr.fc1 + (size_t)u * D : Lr.dm) + lo; pb = pa + (ok ? (size_t)F * D : (size_t)0); }
+    else { pa = (ok ? Lr.in + (size_t)(2 * u) * D : Lr.dm) + lo; pb = pa + ((ok && 2 * u + 1 < rows_in) ? D : 0); }   // half pair: row B repeats row A, result dropped
   };
   auto park_of = [&](int w) { return reinterpret_cast<u32x4*>(zn_dyn_lds) + (size_t)w * (P * 2 * NCH * 64) + lane; };
 
@@ -559,13 +568,12 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
 #pragma unroll
     for (int t = 0; t < NPT; ++t) {
       const int j = pw + NPW * t;
-      if (j < n_qkv) {                                      // wave-uniform
-        const int u = s_qkv + j;
-        const bf16_t* pa = a.pre_W + (size_t)(2 * u) * D + lane * 8;
-        const bf16_t* pb = (2 * u + 1 < a.nqkv) ? pa + D : pa;
+      const bool ok = j < n_qkv;                            // wave-uniform; an absent pair is requested all the same: the matrix's first rows, no lane offset
+      const int u = ok ? s_qkv + j : 0;
+      const bf16_t* pa = a.pre_W + (size_t)(2 * u) * D + (ok ? lane * 8 : 0);
+      const bf16_t* pb = (2 * u + 1 < a.nqkv) ? pa + D : pa;
 #pragma unroll
-        for (int c2 = 0; c2 < NCH; ++c2) { pt[t].a[c2] = ld_nt16(pa + c2 * 512); pt[t].b[c2] = ld_nt16(pb + c2 * 512); }
-      }
+      for (int c2 = 0; c2 < NCH; ++c2) { pt[t].a[c2] = ld_nt16(pa + c2 * 512); pt[t].b[c2] = ld_nt16(pb + c2 * 512); }
     }
     while (__hip_atomic_load(&s_pf[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < R) __builtin_amdgcn_s_sleep(1);
     u32x4 xr[NCH][R];
@@ -601,17 +609,15 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
     if (pre) pre_contract(hw);
 #pragma unroll 1
     for (int li = 0; li < a.n_layer; ++li) {
-      const LW Lr{a.layers[li].W_out, a.layers[li].W_fc1, a.layers[li].W_fc2, a.layers[li].W_in};
+      const LW Lr{a.layers[li].W_out, a.layers[li].W_fc1, a.layers[li].W_fc2, a.layers[li].W_in, a.layers[li].ln2_w};
       auto hload = [&]() {
         if constexpr (NH > 0) {
           zn_static_for<0, 2 * NH>([&](auto IC) {
             constexpr int i = decltype(IC)::value, cwi = i / NH, hh = i % NH;
             bool ok; const bf16_t *pa, *pb; int ridx;
             tile_of(Lr, a.nqkv, 0, 0, slot_of_load(L_F2 - NH + hh), 2 * hw + cwi, ok, pa, pb, ridx);     // an fc1 tile: the op-4 arguments are unused
-            if (ok) {
 #pragma unroll
-              for (int c2 = 0; c2 < NCH; ++c2) { hb[i].a[c2] = ld_nt16g(pa + c2 * 512); hb[i].b[c2] = ld_nt16g(pb + c2 * 512); }
-            }
+            for (int c2 = 0; c2 < NCH; ++c2) { hb[i].a[c2] = ld_nt16g(pa + c2 * 512); hb[i].b[c2] = ld_nt16g(pb + c2 * 512); }   // unconditional, as load_into's
           });
         }
       };
@@ -659,7 +665,7 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
     const bool st_on = a.stamps && sc == 0 && wave == 0 && lane == 0;
 #pragma unroll 1
     for (int li = 0; li < a.n_layer; ++li) {
-      const LW Lr{a.layers[li].W_out, a.layers[li].W_fc1, a.layers[li].W_fc2, a.layers[li].W_in};
+      const LW Lr{a.layers[li].W_out, a.layers[li].W_fc1, a.layers[li].W_fc2, a.layers[li].W_in, a.layers[li].ln2_w};
       const bool last = li + 1 == a.n_layer;
       const int rows_in = last ? a.heads_rows : a.nqkv;
       const int n_in = last ? n_hd : n_qkv, s_in = last ? s_hd : s_qkv;
@@ -667,22 +673,23 @@ ZN_DEVINL void step_body(const ChainArgs& a) {
       const bool stamped = st_on && li == a.stamp_layer;
       auto cstamp = [&](int i) { if (stamped) a.stamps[40 + i] = __builtin_amdgcn_s_memrealtime(); };
       auto tile = [&](int s, bool& ok, const bf16_t*& pa, const bf16_t*& pb, int& ridx) { tile_of(Lr, rows_in, n_in, s_in, s, wave, ok, pa, pb, ridx); };
-      // load l into register buffer b
+      // load l into register buffer b.  The eight loads are issued whether the tile exists or not (an absent one reads tile_of's dummy
+      // address, its buffer is never contracted): a wave-uniform branch around them would join a path on which the PREVIOUS tile's loads are
+      // the youngest outstanding, and the compiler's wait for any older buffer then has to be vmcnt(0 .. 7) - it would drain the NB tiles
+      // requested ahead at every contraction.  Unconditional requests keep every wait at 8 x (tiles requested since).
       auto load_into = [&](auto LC, auto BC) {
         constexpr int l = decltype(LC)::value, b = decltype(BC)::value;
         if constexpr (l >= 0 && l < NL) {
           bool ok; const bf16_t *pa, *pb; int ridx;
           tile(slot_of_load(l), ok, pa, pb, ridx);
-          if (ok) {                                         // wave-uniform
-            WT& w = bufs[b];
+          WT& w = bufs[b];
 #ifdef ZN_TIMING_HANDOFFS_ONLY
 #pragma unroll
-            for (int c2 = 0; c2 < NCH; ++c2) { w.a[c2] = u32x4{0, 0, 0, 0}; w.b[c2] = u32x4{0, 0, 0, 0}; }
+          for (int c2 = 0; c2 < NCH; ++c2) { w.a[c2] = u32x4{0, 0, 0, 0}; w.b[c2] = u32x4{0, 0, 0, 0}; }
 #else
 #pragma unroll
-            for (int c2 = 0; c2 < NCH; ++c2) { w.a[c2] = ld_nt16g(pa + c2 * 512); w.b[c2] = ld_nt16g(pb + c2 * 512); }
+          for (int c2 = 0; c2 < NCH; ++c2) { w.a[c2] = ld_nt16g(pa + c2 * 512); w.b[c2] = ld_nt16g(pb + c2 * 512); }
 #endif
-          }
         }
       };
       // REG load number k lives in buffer (k + P) % NB: the buffer that the prefetch phase's transit of load k + P - NB ... has just left
