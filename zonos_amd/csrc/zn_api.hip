@@ -13,6 +13,7 @@
 #include "zn_cond_kernels.h"
 #include "zn_mamba_kernels.h"
 #include "zn_step_linears.h"
+#include "zn_gen_state.h"
 
 #include <cmath>
 #include <cstdio>
@@ -48,10 +49,9 @@ struct zn_handle_s {
   // the same for a Mamba2 layer's in_proj / out_proj (zn_set_mamba_fp8); read by gemm16k8_kernel / gemm16k8_rows_kernel only
   struct MambaFp8 { const uint8_t *in_q = nullptr, *out_q = nullptr; const int8_t *in_exp = nullptr, *out_exp = nullptr; };
   std::vector<MambaFp8> mamba_fp8;
-  // FP8 KV cache (zn_set_kv_fp8): the mode, this generation's code caches (zn_gen_bind_kv_fp8; empty: none bound) and the code cache of the per-op entry points
+  // FP8 KV cache (zn_set_kv_fp8): the mode and the code cache of the per-op entry points (this generation's code caches: gen.kv8_layers)
   bool kv_fp8 = false;
   bool kv_fp8_only = false;          // zn_set_kv_fp8_only: where the FP8 KV cache is in effect, the code caches are the only KV storage (no bf16 cache)
-  std::vector<const void*> kv8_layers;
   uint8_t* op_kv8 = nullptr;
   const void* heads = nullptr;
   const void *norm_f_w = nullptr, *norm_f_b = nullptr;
@@ -81,7 +81,6 @@ struct zn_handle_s {
   bf16_t* dbg_trace = nullptr;               // diagnostic: [n_layer][2][rows * d] copies of (x after the block, attention output) per decode step
   bf16_t* x_emb = nullptr;                  // [max_rows][d] embedding of the column the next decode step consumes (written by the step's tail)
   int* tail_ticket = nullptr;               // arrival ticket of the sampler launch whose last workgroup runs the step's tail
-  bool emb_valid = false;                   // x_emb holds the embedding of column st->offset
   unsigned long long* ch_stamps = nullptr;   // diagnostic: [n_layer][32] timeline stamps of workgroup 0 (zn_debug_chain_stamps)
   int device = 0;              // the HIP device the handle was created on
   // hand-off timeouts (zn_get_counters): a reported timeout demotes the handle to the launches path (no in-launch hand-offs) until ZN_REARM_AFTER
@@ -89,9 +88,7 @@ struct zn_handle_s {
   bool demoted = false;
   int clean_since_demotion = 0;
   long long n_timeouts = 0, n_generations = 0, n_fallback_generations = 0, n_rearms = 0;
-  bool gen_timed_out = false;         // this generation reported a hand-off timeout
   hipStream_t gen_stream = nullptr;   // the stream the generation's steps were last enqueued on (handoff_timeout drains it)
-  bool persist_ok = true;      // this handle may launch the persistent kernels (zn_gen_begin: it holds the device's tenancy, or nobody competes)
   int ch_variant = 0;          // 0 = shapes do not fit (launches path), 1 = <4,1,8,4,2> (Zonos-v0.1 dims), 2 = <1,1,2,1,1> (d_model 512)
   float* g16_part = nullptr;   // gemm16s_kernel: split-K partial tiles
   int* g16_tickets = nullptr;
@@ -109,24 +106,15 @@ struct zn_handle_s {
   int* fw_lengths = nullptr;   // [max_rows] positions of zn_op_backbone_forward's rows
   int* row_len = nullptr;      // [max_rows] valid positions per row of a right-padded prefill (zn_prefill_rows)
   std::vector<int> row_len_host;   // source of the copy into row_len (kept until the next zn_gen_begin has drained the stream)
-  bool rows_unequal2 = false;  // this generation's two unguided rows have different lengths: its steps run the launches path (persist_allowed)
   bf16_t* qkv_tmp = nullptr;   // [rows][(H + 2 Hkv) hd]: in_proj output of an attention layer whose RoPE / bias form the fused epilogue does not cover
   int prefill_mode = 1;     // 1 = batched (MFMA GEMMs + tiled attention), 0 = position by position through the decode kernels
   int lcap = 0;
   GenState* st = nullptr;
   int *remaining = nullptr, *stopping = nullptr;
   zn_row_params* row_tab = nullptr;   // [max_rows] per-utterance settings of this generation (zn_gen_set_rows)
-  bool rows_set = false;              // this generation's samplers read row_tab
-  bool pairs_set = false;             // some entry of row_tab names a row pair (a mixed generation): the samplers follow it
   int* prefix_shift = nullptr;        // [max_rows] column shift per utterance of this generation (zn_gen_set_prefix_rows: <= 0; zn_gen_admit: either sign)
-  bool prefix_set = false;            // some shift is not 0: this generation's embedding, sampler and bookkeeping launches read prefix_shift
-  bool gen_prefilled = false;         // zn_prefill / zn_prefill_rows has run since zn_gen_begin
   // slotted session (zn_gen_open_slots): requests join the running generation slot by slot
-  bool slots_open = false;
-  int slot_slack = 0;                 // steps a request may run past its own end before it is retired
   int* step0 = nullptr;               // [max_rows] device: session step at which slot b's request was admitted, -1 = idle
-  std::vector<int> slot_len;          // [batch] host mirror of a busy slot's lengths[b] (they advance by one per step), 0 = idle
-  std::vector<char> slot_busy;
   void* adm_cache = nullptr;          // scratch cache of an admission's prefill: n_layer buffers of adm_layer_bytes
   size_t adm_layer_bytes = 0;
   int adm_cap_S = 0;                  // positions per row the scratch cache holds (max_rows rows)
@@ -138,18 +126,9 @@ struct zn_handle_s {
   bool adm_pending = false;
   int* done_host = nullptr;  // pinned: [0..3] synchronous stop check, [4..7] asynchronous one
   hipEvent_t stop_event = nullptr;
-  bool stop_pending = false;
-  // per-generation state (host mirror)
-  bool gen_active = false;
-  bool gen_ended = false;      // zn_gen_end was called: the state stays readable, no further steps until the next zn_gen_begin
-  int batch = 0, rows = 0, max_len = 0, t_total = 0, offset0 = 0, max_new = 0;
-  float cfg_scale = 2.f;
-  zn_sampling sp{};
-  std::vector<const void*> kv_layers;
-  int *lengths = nullptr, *codes = nullptr;
+  GenHost gen;                      // this generation's host record (zn_gen_state.h): zn_gen_begin starts it afresh
   int force_eos_step = -1;
   float eos_bias = 0.f;
-  unsigned dbg_pause = 0;           // ChainArgs::dbg_pause of this generation's whole-step launches
   int tune[ZN_TUNE_NKEYS] = {};     // settings of zn_debug_tune by enum zn_tune_key (include/zonos_hip.h); defaults: zn_create.  0 = never set
   int pending_hook = 0;             // zn_debug_tune(ZN_TUNE_HOOK, v): the one-shot test hook the next zn_gen_begin consumes (enum zn_tune_hook)
   const int* tok_override = nullptr;
@@ -161,7 +140,6 @@ struct zn_handle_s {
   hipGraphExec_t graph_exec[ZN_NGRAPHS] = {};
   hipGraph_t graph[ZN_NGRAPHS] = {};
   bool graph_tried[ZN_NGRAPHS] = {};
-  int len_hi = 0;            // host-side upper bound of the rows' KV lengths (keys already cached)
   StepPlan last_plan;        // of the decode steps enqueued last (zn_decode_path_detail)
   std::string err;
 };
@@ -176,6 +154,12 @@ struct zn_handle_s {
   do {                                                                                        \
     hipError_t _e = (call);                                                                   \
     if (_e != hipSuccess) ZN_FAIL(h, ZN_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(_e)); \
+  } while (0)
+// A check of zn_gen_state.h: its code and message are the call's.
+#define ZN_GEN_CHECK(h, check)                                  \
+  do {                                                          \
+    const GenErr _g = (check);                                  \
+    if (_g.code) ZN_FAIL(h, _g.code, "%s", _g.msg);             \
   } while (0)
 
 extern "C" int zn_abi_version(void) { return ZN_ABI_VERSION; }
@@ -656,8 +640,8 @@ static int launch_attn_g(const AttnArgs& a, int G, dim3 grid, int fused, bool sp
 // (the persistent kernels serve one or two rows).  Then every KV append rounds to the E4M3 grid and writes both caches.
 #define ZN_KV_FP8_MIN_ROWS 5
 static bool kv_fp8_rows(zn_handle h, int rows) { return h->cfg.arch == 0 && rows >= ZN_KV_FP8_MIN_ROWS; }
-static bool kv_fp8_gen(zn_handle h) { return h->kv_fp8 && kv_fp8_rows(h, h->rows); }
-static uint8_t* kv8_of(zn_handle h, int li) { return kv_fp8_gen(h) && !h->kv8_layers.empty() ? (uint8_t*)const_cast<void*>(h->kv8_layers[li]) : nullptr; }
+static bool kv_fp8_gen(zn_handle h) { return h->kv_fp8 && kv_fp8_rows(h, h->gen.rows); }
+static uint8_t* kv8_of(zn_handle h, int li) { return kv_fp8_gen(h) && !h->gen.kv8_layers.empty() ? (uint8_t*)const_cast<void*>(h->gen.kv8_layers[li]) : nullptr; }
 // The decode attention's side of the plan, in one place: does an attention launch over `rows` rows that has a code cache read it?  ZN_TUNE_KV_FP8 = 2: never (the bf16
 // cache holds the dequantised codes: the same bits).  No row count is declined: the FP8 reads have not been measured against the bf16 reads yet (tools/kvfp8bench.py).
 // codes_only: there is no bf16 cache to read instead (a codes-only generation, a per-op call without one): the key is ignored.
@@ -665,9 +649,9 @@ static bool kv_fp8_attn_reads(zn_handle h, int rows, bool codes_only = false) { 
 // Codes only (zn_set_kv_fp8_only): a generation in which the FP8 KV cache is in effect on a handle with the second flag on keeps no bf16 cache - the
 // appends write the codes alone, the decode and the prefill attention read them, an admission's scratch cache holds codes.
 static bool kv_codes_only_rows(zn_handle h, int rows) { return h->kv_fp8 && h->kv_fp8_only && kv_fp8_rows(h, rows); }
-static bool kv_codes_only_gen(zn_handle h) { return kv_codes_only_rows(h, h->rows); }
+static bool kv_codes_only_gen(zn_handle h) { return kv_codes_only_rows(h, h->gen.rows); }
 static int kv_fp8_bound(zn_handle h, const char* who) {
-  if (kv_fp8_gen(h) && h->kv8_layers.empty()) ZN_FAIL(h, ZN_ERR_STATE, "%s: the FP8 KV cache is in effect (zn_set_kv_fp8, %d rows) and no code caches are bound (zn_gen_bind_kv_fp8)", who, h->rows);
+  if (kv_fp8_gen(h) && h->gen.kv8_layers.empty()) ZN_FAIL(h, ZN_ERR_STATE, "%s: the FP8 KV cache is in effect (zn_set_kv_fp8, %d rows) and no code caches are bound (zn_gen_bind_kv_fp8)", who, h->gen.rows);
   return ZN_OK;
 }
 
@@ -854,7 +838,7 @@ static int launch_chain(zn_handle h, int li, const std::vector<const void*>& kv_
   a.a = h->o1; a.xin = xin ? xin : chain_x(h, li); a.xout = chain_x(h, li + 1);
   a.g_y1 = h->ch_gy1; a.g_x1 = h->ch_gx1; a.g_x2 = h->ch_gx2; a.g_m = h->ch_gm;
   a.epoch = h->ch_epoch; a.tmo = &h->st->pad[0]; a.diag = h->ch_diag;
-  a.dbg_pause = h->dbg_pause; a.stamp_layer = li;
+  a.dbg_pause = h->gen.dbg_pause; a.stamp_layer = li;
   a.stamps = h->ch_stamps ? h->ch_stamps + (size_t)li * 32 : nullptr;
   if (!last) {
     const zn_layer_weights& nx = h->layers[li + 1];
@@ -944,7 +928,8 @@ static bool stack_shapes_ok(zn_handle h) {
 // Nor a column shift per utterance (zn_gen_set_prefix_rows): the fused tail's sampler and sample1_kernel do not read it, so two unguided rows whose audio prefixes differ run the launches
 // path even when their lengths advance in lockstep.
 // Nor a slotted session (zn_gen_open_slots): its samplers read the row table, the shifts and the slots' step origins.
-static bool persist_allowed(zn_handle h) { return h->tune[ZN_TUNE_PERSISTENT] != 2 && !h->demoted && h->persist_ok && !h->rows_unequal2 && !h->prefix_set && !h->slots_open && !h->pairs_set; }
+// The handle's half is here; the generation's half is GenHost::persist_eligible.
+static bool persist_allowed(zn_handle h) { return h->tune[ZN_TUNE_PERSISTENT] != 2 && !h->demoted && h->gen.persist_eligible(); }
 // Row counts a persistent kernel can serve on this model: two (the per-block chain and step_kernel) or one (step_r1_kernel, the whole-step
 // kernel only: one row beyond its 6144-key bound, or with it switched off, runs the launches path).
 static bool persist_shape(zn_handle h, int rows) { return h->ch_variant != 0 && (rows == 2 || (rows == 1 && h->ch_variant == 1)); }
@@ -972,9 +957,9 @@ static StepPlan plan_blocks(zn_handle h, int rows, int keys) {
 // at once).  Fused tail: at batch 1 on a persistent kernel the step's tail (bookkeeping + next step's embedding) runs in the sampler launch's last workgroup.  Larger batches keep three launches
 // (one workgroup embedding 8 utterances in turn cost 31 us per step at batch 8), and so does the launches path (its first op reads h->x): one row has the fused tail only on whole-step steps.
 static StepPlan plan_steps(zn_handle h, int steps_left) {
-  const int rows = h->rows, keys = h->len_hi + 1, keys_run = h->len_hi + ZN_GRAPH_STEPS;
+  const int rows = h->gen.rows, keys = h->gen.len_hi + 1, keys_run = h->gen.len_hi + ZN_GRAPH_STEPS;
   const bool want_run = steps_left >= ZN_GRAPH_STEPS && h->tune[ZN_TUNE_GRAPH_RUNS] > 1;
-  const bool tail_ok = h->cfg.arch == 0 && persist_active(h, rows) && h->batch <= 2;
+  const bool tail_ok = h->cfg.arch == 0 && persist_active(h, rows) && h->gen.batch <= 2;
   const int nb_run = tail_ok && want_run ? stack_blocks_for(h, rows, keys_run) : -1;
   const int nb_one = tail_ok ? stack_blocks_for(h, rows, keys) : -1;
   StepPlan p = plan_blocks(h, rows, keys);
@@ -994,9 +979,9 @@ static int launch_stack(zn_handle h, hipStream_t s, int rows, int nbk) {
   a.g_y1 = h->ch_gy1; a.g_x1 = h->ch_gx1; a.g_x2 = h->ch_gx2; a.g_m = h->ch_gm; a.g_qkv = h->ch_gqkv; a.g_a = h->ch_ga;
   a.g_bmax = h->ch_gbmax; a.g_part = h->ch_gpart;
   a.epoch = h->ch_epoch; a.tmo = &h->st->pad[0]; a.diag = h->ch_diag;
-  a.dbg_pause = h->dbg_pause;
+  a.dbg_pause = h->gen.dbg_pause;
   a.stamps = h->ch_stamps; a.stamp_layer = c.n_layer / 2;
-  a.rope = h->rope; a.lengths = h->lengths; a.max_len = h->max_len; a.hd = h->hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
+  a.rope = h->rope; a.lengths = h->gen.lengths; a.max_len = h->gen.max_len; a.hd = h->hd; a.n_heads = c.n_heads; a.n_heads_kv = c.n_heads_kv;
   a.rope_positions = c.rope_positions;
   a.layers = h->stack_layers; a.n_layer = c.n_layer; a.q0 = h->q; a.scale = (float)(1.0 / std::sqrt((double)h->hd));
   a.heads_rows = c.n_codebooks * c.vocab_head; a.heads_out = h->logits_raw; a.trace = h->dbg_trace;
@@ -1004,7 +989,7 @@ static int launch_stack(zn_handle h, hipStream_t s, int rows, int nbk) {
   a.natt = npairs * (mode < 1 ? 1 : mode);
   if (stack_pre(h)) {       // block 0's LayerNorm + in_proj + RoPE + KV append inside the launch (ZN_TUNE_STACK_PRE = 2: as a launch before it)
     a.pre_W = (const bf16_t*)h->layers[0].in_proj; a.pre_ln_w = (const bf16_t*)h->layers[0].norm_w; a.pre_ln_b = (const bf16_t*)h->layers[0].norm_b;
-    a.pre_kv = (bf16_t*)h->kv_layers[0];
+    a.pre_kv = (bf16_t*)h->gen.kv_layers[0];
   }
   const dim3 grid(ZN_CH_GRID), block(ZN_SK_THREADS);
   if (rows == 1) {
@@ -1033,11 +1018,11 @@ static int build_stack_table(zn_handle h) {
     StackLayer& L = t[li];
     L.W_out = (const bf16_t*)lw.out_proj; L.W_fc1 = (const bf16_t*)lw.fc1; L.W_fc2 = (const bf16_t*)lw.fc2;
     L.ln2_w = (const bf16_t*)lw.norm2_w; L.ln2_b = (const bf16_t*)lw.norm2_b;
-    L.kv = (const bf16_t*)h->kv_layers[li];
+    L.kv = (const bf16_t*)h->gen.kv_layers[li];
     if (last) { L.W_in = (const bf16_t*)h->heads; L.lnn_w = (const bf16_t*)h->norm_f_w; L.lnn_b = (const bf16_t*)h->norm_f_b; L.kv_next = nullptr; }
     else {
       const zn_layer_weights& nx = h->layers[li + 1];
-      L.W_in = (const bf16_t*)nx.in_proj; L.lnn_w = (const bf16_t*)nx.norm_w; L.lnn_b = (const bf16_t*)nx.norm_b; L.kv_next = (bf16_t*)h->kv_layers[li + 1];
+      L.W_in = (const bf16_t*)nx.in_proj; L.lnn_w = (const bf16_t*)nx.norm_w; L.lnn_b = (const bf16_t*)nx.norm_b; L.kv_next = (bf16_t*)h->gen.kv_layers[li + 1];
     }
   }
   HIPCHK(h, ZN_NOT_IN_CAPTURE(hipMemcpy(h->stack_layers, t.data(), t.size() * sizeof(StackLayer), hipMemcpyHostToDevice)));
@@ -1050,14 +1035,14 @@ static int build_stack_table(zn_handle h) {
 static int decode_blocks(zn_handle h, const StepPlan& p, const int* ext, int ext_scalar, hipStream_t s, const bf16_t* x0 = nullptr, bool* heads_done = nullptr) {
   const zn_config& c = h->cfg;
   int rc;
-  const size_t tb = (size_t)h->rows * c.d_model * 2;
+  const size_t tb = (size_t)h->gen.rows * c.d_model * 2;
   const bool chain = p.path == StepPlan::CHAIN;
   if (x0 && !chain) ZN_FAIL(h, ZN_ERR_STATE, "decode_blocks: a separate input buffer is the chain path's");
   auto trace = [&](int li) {        // slots per block: x after the block, attention output, q, m (first d values per row pair), x after the attention half
     if (!h->dbg_trace) return;
     (void)hipMemcpyAsync((char*)h->dbg_trace + (size_t)(8 * li) * tb, chain ? chain_x(h, li + 1) : h->x, tb, hipMemcpyDeviceToDevice, s);
     (void)hipMemcpyAsync((char*)h->dbg_trace + (size_t)(8 * li + 1) * tb, h->o1, tb, hipMemcpyDeviceToDevice, s);
-    if (!chain) (void)hipMemcpyAsync((char*)h->dbg_trace + (size_t)(8 * li + 3) * tb, h->mbuf, (size_t)h->rows * c.d_ff * 2 <= 4 * tb ? (size_t)h->rows * c.d_ff * 2 : 4 * tb, hipMemcpyDeviceToDevice, s);
+    if (!chain) (void)hipMemcpyAsync((char*)h->dbg_trace + (size_t)(8 * li + 3) * tb, h->mbuf, (size_t)h->gen.rows * c.d_ff * 2 <= 4 * tb ? (size_t)h->gen.rows * c.d_ff * 2 : 4 * tb, hipMemcpyDeviceToDevice, s);
   };
   auto trace_q = [&](int li) {      // q of block li, as the attention launch reads it
     if (h->dbg_trace) (void)hipMemcpyAsync((char*)h->dbg_trace + (size_t)(8 * li + 2) * tb, h->q, tb, hipMemcpyDeviceToDevice, s);
@@ -1065,22 +1050,22 @@ static int decode_blocks(zn_handle h, const StepPlan& p, const int* ext, int ext
   if (!chain) {
     for (int li = 0; li < c.n_layer; ++li) {
       // (the FP8 KV cache in effect - 5 rows or more, so never the chain below: the append rounds and writes both caches, the attention reads what its plan says)
-      if ((rc = layer_in_proj(h, li, h->x, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, h->rows, s, kv8_of(h, li), kv_fp8_gen(h)))) return rc;
+      if ((rc = layer_in_proj(h, li, h->x, (bf16_t*)h->gen.kv_layers[li], h->gen.max_len, h->gen.lengths, h->gen.rows, s, kv8_of(h, li), kv_fp8_gen(h)))) return rc;
       trace_q(li);
-      if ((rc = run_attention(h, h->q, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, ext, ext_scalar, h->o1, h->rows, p.attn_fused, s, nullptr, kv8_of(h, li)))) return rc;
-      if ((rc = layer_post_attention(h, li, h->x, h->rows, s, h->dbg_trace ? (bf16_t*)((char*)h->dbg_trace + (size_t)(8 * li + 7) * tb) : nullptr))) return rc;
+      if ((rc = run_attention(h, h->q, (bf16_t*)h->gen.kv_layers[li], h->gen.max_len, h->gen.lengths, ext, ext_scalar, h->o1, h->gen.rows, p.attn_fused, s, nullptr, kv8_of(h, li)))) return rc;
+      if ((rc = layer_post_attention(h, li, h->x, h->gen.rows, s, h->dbg_trace ? (bf16_t*)((char*)h->dbg_trace + (size_t)(8 * li + 7) * tb) : nullptr))) return rc;
       trace(li);
     }
     return ZN_OK;
   }
-  if ((rc = layer_in_proj(h, 0, x0 ? const_cast<bf16_t*>(x0) : h->x, (bf16_t*)h->kv_layers[0], h->max_len, h->lengths, h->rows, s))) return rc;
+  if ((rc = layer_in_proj(h, 0, x0 ? const_cast<bf16_t*>(x0) : h->x, (bf16_t*)h->gen.kv_layers[0], h->gen.max_len, h->gen.lengths, h->gen.rows, s))) return rc;
   h->epoch_bound += c.n_layer;                             // one tag per chain launch (counted again by zn_decode_steps: the bound stays an upper bound)
   for (int li = 0; li < c.n_layer; ++li) {
     trace_q(li);
-    if ((rc = run_attention(h, h->q, (bf16_t*)h->kv_layers[li], h->max_len, h->lengths, ext, ext_scalar, h->o1, h->rows, p.attn_fused, s,
+    if ((rc = run_attention(h, h->q, (bf16_t*)h->gen.kv_layers[li], h->gen.max_len, h->gen.lengths, ext, ext_scalar, h->o1, h->gen.rows, p.attn_fused, s,
                             h->ch_stamps ? h->ch_stamps + (size_t)(c.n_layer + li) * 32 : nullptr))) return rc;
     const bool wh = heads_done && li + 1 == c.n_layer && chain_heads_fit(h);
-    if ((rc = launch_chain(h, li, h->kv_layers, h->max_len, h->lengths, s, li == 0 ? x0 : nullptr, wh))) return rc;
+    if ((rc = launch_chain(h, li, h->gen.kv_layers, h->gen.max_len, h->gen.lengths, s, li == 0 ? x0 : nullptr, wh))) return rc;
     if (wh) *heads_done = true;
     trace(li);
   }
@@ -1188,10 +1173,10 @@ static int hybrid_layer(zn_handle h, int li, void* cache, int max_len, const int
 
 // final add + norm (_mamba_ssm.py:111-119) of the token in h->x / h->res, then the heads
 static int hybrid_heads(zn_handle h, hipStream_t s) {
-  launch_add_ln(h, h->x, h->res, 1, 0, h->norm_f_w, h->norm_f_b, h->hn, h->rows, s);
+  launch_add_ln(h, h->x, h->res, 1, 0, h->norm_f_w, h->norm_f_b, h->hn, h->gen.rows, s);
   GemvArgs a = step_args(h, h->heads, h->hn, nullptr);
   a.out_f32 = h->logits_raw;
-  return run_step_linear<PRO_NONE, EPI_F32>(h, SL_H_HEADS, -1, a, h->rows, s);
+  return run_step_linear<PRO_NONE, EPI_F32>(h, SL_H_HEADS, -1, a, h->gen.rows, s);
 }
 
 // All layers for the token in h->x, then the final add + LayerNorm and the heads.
@@ -1199,7 +1184,7 @@ static int hybrid_token(zn_handle h, bool want_logits, int attn_fused, hipStream
   const zn_config& c = h->cfg;
   int rc;
   for (int li = 0; li < c.n_layer; ++li)
-    if ((rc = hybrid_layer(h, li, (void*)h->kv_layers[li], h->max_len, h->lengths, h->rows, attn_fused, s))) return rc;
+    if ((rc = hybrid_layer(h, li, (void*)h->gen.kv_layers[li], h->gen.max_len, h->gen.lengths, h->gen.rows, attn_fused, s))) return rc;
   if (!want_logits) return ZN_OK;
   return hybrid_heads(h, s);
 }
@@ -1216,29 +1201,56 @@ static SampleArgs make_sample_args(zn_handle h, const zn_sampling& sp) {
 }
 static_assert(sizeof(zn_row_params) == ZN_ROW_PARAMS_BYTES, "zn_row_params is one 64-byte entry per utterance");
 
-// With guidance every utterance has a conditional and an unconditional row (rows = 2 batch); cfg_scale == 1: one row per utterance.
-static bool guided(zn_handle h) { return h->rows == 2 * h->batch; }
+static bool guided(zn_handle h) { return h->gen.guided(); }
 
 static EmbedArgs make_embed_args(zn_handle h) {
   const zn_config& c = h->cfg;
   EmbedArgs e{};
-  e.tables = h->emb_tables_dev; e.codes = h->codes; e.col_dev = &h->st->offset; e.sb = c.n_codebooks * h->t_total; e.si = h->t_total;
-  e.col = 0; e.n_q = c.n_codebooks; e.d = c.d_model; e.batch = h->batch; e.vocab_embed = c.vocab_embed; e.out = h->x_emb; e.dup = guided(h) ? 1 : 0;
-  e.shift = h->prefix_set ? h->prefix_shift : nullptr;
-  e.step0 = h->slots_open ? h->step0 : nullptr;
+  e.tables = h->emb_tables_dev; e.codes = h->gen.codes; e.col_dev = &h->st->offset; e.sb = c.n_codebooks * h->gen.t_total; e.si = h->gen.t_total;
+  e.col = 0; e.n_q = c.n_codebooks; e.d = c.d_model; e.batch = h->gen.batch; e.vocab_embed = c.vocab_embed; e.out = h->x_emb; e.dup = guided(h) ? 1 : 0;
+  e.shift = h->gen.prefix_set ? h->prefix_shift : nullptr;
+  e.step0 = h->gen.slots_open ? h->step0 : nullptr;
   return e;
 }
 
 // The sampler arguments of this generation's launches (first frame, decode steps of every path): the call-wide parameters, and the
 // per-utterance table once zn_gen_set_rows has filled it, the column shifts once zn_gen_set_prefix_rows has.
 static SampleArgs gen_sample_args(zn_handle h) {
-  SampleArgs a = make_sample_args(h, h->sp);
-  a.cfg_scale = h->cfg_scale; a.ctx = h->max_new < 100 ? h->max_new : 100;
-  a.rows = h->rows_set ? h->row_tab : nullptr;
-  a.pairs = h->pairs_set ? 1 : 0;
-  a.shift = h->prefix_set ? h->prefix_shift : nullptr;
-  a.step0 = h->slots_open ? h->step0 : nullptr;
+  SampleArgs a = make_sample_args(h, h->gen.sp);
+  a.cfg_scale = h->gen.cfg_scale; a.ctx = h->gen.max_new < 100 ? h->gen.max_new : 100;
+  a.rows = h->gen.rows_set ? h->row_tab : nullptr;
+  a.pairs = h->gen.pairs_set ? 1 : 0;
+  a.shift = h->gen.prefix_set ? h->prefix_shift : nullptr;
+  a.step0 = h->gen.slots_open ? h->step0 : nullptr;
   return a;
+}
+// The sampler launch over the heads' logits: of a decode step (the logit bias, the penalty over the codes, a draw), or of a first frame (the mix alone).
+static SampleArgs make_frame_sampler(zn_handle h, bool step) {
+  SampleArgs a = gen_sample_args(h);
+  a.raw = h->logits_raw; a.mix = guided(h) ? 1 : 0; a.apply_bias = step ? 1 : 0; a.batch = h->gen.batch;
+  if (step) { a.codes = h->gen.codes; a.t_total = h->gen.t_total; }
+  a.use_penalty = step && (h->gen.rows_set || (h->gen.sp.repetition_penalty != 1.0f)); a.st = h->st; a.logits_out = h->last_logits; a.tokens = h->tok_raw;
+  a.draw = step ? 1 : 0;
+  return a;
+}
+// The bookkeeping that follows the sampler launch `a` (frame_update_kernel, or the tail in that launch's last workgroup).  slot >= 0: that slot of a session alone
+// (an admission), which the test hook's token override leaves alone.
+static FrameArgs make_frame_args(zn_handle h, const SampleArgs& a, int first, int slot) {
+  const zn_config& c = h->cfg;
+  FrameArgs f{};
+  f.st = h->st; f.codes = h->gen.codes; f.t_total = h->gen.t_total; f.batch = h->gen.batch; f.n_q = c.n_codebooks; f.eos_id = c.eos_id;
+  f.mask_id = c.mask_id; f.tokens = h->tok_raw; f.remaining = h->remaining; f.stopping = h->stopping; f.lengths = h->gen.lengths;
+  f.rows = h->gen.rows; f.first = first; f.shift = a.shift; f.step0 = a.step0;
+  if (slot >= 0) { f.slot_base = slot; f.slot_count = 1; }
+  else { f.override = h->tok_override; f.override_calls = h->tok_override_calls; }
+  return f;
+}
+// The first frame after a prefill: of every utterance (slot < 0: zn_sample_first), or of one admitted slot.
+static void launch_first_frame(zn_handle h, int slot, hipStream_t s) {
+  SampleArgs a = make_frame_sampler(h, false);
+  if (slot >= 0) a.slot_base = slot;
+  hipLaunchKernelGGL(sample_kernel, dim3(h->cfg.n_codebooks, slot >= 0 ? 1 : h->gen.batch), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(frame_update_kernel, dim3(1), dim3(256), 0, s, make_frame_args(h, a, 1, slot));
 }
 
 // One iteration of model.py:467-502: embed -> 26 blocks -> heads -> CFG/bias/penalty/sample -> bookkeeping.  With the fused tail the
@@ -1251,37 +1263,30 @@ static int enqueue_step(zn_handle h, const StepPlan& p, hipStream_t s) {
   if (!fused) {
     EmbedArgs e = make_embed_args(h);
     e.out = h->x;
-    hipLaunchKernelGGL(embed_kernel, dim3(h->batch), dim3(256), 0, s, e);
+    hipLaunchKernelGGL(embed_kernel, dim3(h->gen.batch), dim3(256), 0, s, e);
   }
   if (c.arch == 1) {
     if ((rc = hybrid_token(h, true, p.attn_fused, s))) return rc;
   } else {
     bool heads_done = false;
     if (p.path == StepPlan::STACK) {                                 // every block + the heads in one launch (in_proj of block 0 inside it, or as a launch before it)
-      if (!stack_pre(h) && (rc = layer_in_proj(h, 0, h->x_emb, (bf16_t*)h->kv_layers[0], h->max_len, h->lengths, h->rows, s))) return rc;
-      if ((rc = launch_stack(h, s, h->rows, p.nbk))) return rc;
+      if (!stack_pre(h) && (rc = layer_in_proj(h, 0, h->x_emb, (bf16_t*)h->gen.kv_layers[0], h->gen.max_len, h->gen.lengths, h->gen.rows, s))) return rc;
+      if ((rc = launch_stack(h, s, h->gen.rows, p.nbk))) return rc;
       heads_done = true;
     } else if ((rc = decode_blocks(h, p, nullptr, 0, s, fused ? h->x_emb : nullptr, &heads_done))) return rc;
-    if (!heads_done && (rc = heads_logits(h, h->x, h->rows, s))) return rc;
+    if (!heads_done && (rc = heads_logits(h, h->x, h->gen.rows, s))) return rc;
   }
-  SampleArgs a = gen_sample_args(h);
-  a.raw = h->logits_raw; a.mix = guided(h) ? 1 : 0; a.apply_bias = 1; a.batch = h->batch;
-  a.codes = h->codes; a.t_total = h->t_total;
-  a.use_penalty = h->rows_set || (h->sp.repetition_penalty != 1.0f); a.st = h->st; a.logits_out = h->last_logits; a.tokens = h->tok_raw;
-  a.draw = 1;
-  FrameArgs& f = a.fr;
-  f.st = h->st; f.codes = h->codes; f.t_total = h->t_total; f.batch = h->batch; f.n_q = c.n_codebooks; f.eos_id = c.eos_id;
-  f.mask_id = c.mask_id; f.tokens = h->tok_raw; f.remaining = h->remaining; f.stopping = h->stopping; f.lengths = h->lengths;
-  f.rows = h->rows; f.first = 0; f.override = h->tok_override; f.override_calls = h->tok_override_calls; f.shift = a.shift; f.step0 = a.step0;
+  SampleArgs a = make_frame_sampler(h, true);
+  const FrameArgs f = a.fr = make_frame_args(h, a, 0, -1);
   if (fused) { a.ticket = h->tail_ticket; a.em = make_embed_args(h); }
   // batch 1, greedy decoding: sampling, bookkeeping and the next embedding in one workgroup (sample1_kernel: 0.8337 -> 0.8312 ms per step).  With a
   // temperature its one wave per codebook carries 17 exp / log / hash evaluations per lane and the nine ticketed workgroups are ahead again (0.8396 vs
   // 0.8415): they keep those steps.  ZN_TUNE_SAMPLER = 2: always the ticketed kernel; 3: the one-workgroup kernel for every parameter set it implements (tests).
-  const bool one_wg = fused && h->batch == 1 && !h->rows_set && h->tune[ZN_TUNE_SAMPLER] != 2 && (h->tune[ZN_TUNE_SAMPLER] == 3 || !(h->sp.temperature > 0.f)) && c.vocab_head <= 64 * ZN_S1_IT &&
-                      c.n_codebooks <= 16 && !(h->sp.top_p > 0.f) && h->sp.top_k <= 0 && !(h->sp.linear > 0.f) &&
-                      (!a.use_penalty || h->sp.repetition_penalty_window <= 16) && h->rows <= 1024;
+  const bool one_wg = fused && h->gen.batch == 1 && !h->gen.rows_set && h->tune[ZN_TUNE_SAMPLER] != 2 && (h->tune[ZN_TUNE_SAMPLER] == 3 || !(h->gen.sp.temperature > 0.f)) && c.vocab_head <= 64 * ZN_S1_IT &&
+                      c.n_codebooks <= 16 && !(h->gen.sp.top_p > 0.f) && h->gen.sp.top_k <= 0 && !(h->gen.sp.linear > 0.f) &&
+                      (!a.use_penalty || h->gen.sp.repetition_penalty_window <= 16) && h->gen.rows <= 1024;
   if (one_wg) { hipLaunchKernelGGL(sample1_kernel, dim3(1), dim3(1024), 0, s, a); return ZN_OK; }
-  hipLaunchKernelGGL(sample_kernel, dim3(c.n_codebooks, h->batch), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(sample_kernel, dim3(c.n_codebooks, h->gen.batch), dim3(256), 0, s, a);
   if (!fused) hipLaunchKernelGGL(frame_update_kernel, dim3(1), dim3(256), 0, s, f);
   return ZN_OK;
 }
@@ -1307,12 +1312,9 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   int rc = ensure_attn_ws(h, max_len);
   if (rc) return rc;
   free_graph(h);
-  h->batch = batch; h->rows = rows; h->max_len = max_len; h->t_total = t_total; h->offset0 = offset0; h->max_new = max_new_tokens;
-  h->cfg_scale = cfg_scale; h->sp = *sp;
-  if (codes_only) h->kv_layers.assign(h->cfg.n_layer, nullptr);
-  else h->kv_layers.assign(kv_layers_dev, kv_layers_dev + h->cfg.n_layer);
-  h->kv8_layers.clear();
-  h->lengths = lengths_dev; h->codes = delayed_codes_dev;
+  h->gen.begin(batch, rows, max_len, t_total, offset0, max_new_tokens, cfg_scale, *sp, lengths_dev, delayed_codes_dev);   // = GenHost{} and these: every flag of the last generation is gone
+  if (codes_only) h->gen.kv_layers.assign(h->cfg.n_layer, nullptr);
+  else h->gen.kv_layers.assign(kv_layers_dev, kv_layers_dev + h->cfg.n_layer);
   // The hand-off tags are 32-bit and advance by n_layer per decode step (~41 hours of continuous batch-1 decoding): long before they
   // can wrap, between two generations, the epoch restarts at 1 over zeroed granule buffers (tag 0 is never a launch's epoch).
   if (h->pending_hook == ZN_HOOK_TAG_WRAP) { h->epoch_bound = 0x70000001ull; h->pending_hook = 0; }   // test hook: behave as if the tags were about to wrap
@@ -1336,15 +1338,14 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   const bool persist_rows = h->cfg.arch == 0 && persist_shape(h, rows);
   if (h->demoted && persist_rows && h->tune[ZN_TUNE_PERSISTENT] != 2) h->n_fallback_generations++;
   // one or two rows on a model the persistent kernels serve: claim the device for them, or run this generation on the launches path
-  h->persist_ok = !persist_rows || zn_tenant_try_claim(h->device, h) != 0;
+  h->gen.persist_ok = !persist_rows || zn_tenant_try_claim(h->device, h) != 0;
   if (h->cfg.arch == 0 && h->ch_variant == 1) {
     if (!h->stack_checked) { h->stack_ok = stack_shapes_ok(h); h->stack_checked = true; }
     if (h->stack_ok) { int rc = build_stack_table(h); if (rc) return rc; }
   }
   GenState st{};
   st.offset = offset0; st.step = 0; st.all_done = 0; st.force_eos_step = h->force_eos_step; st.eos_bias = h->eos_bias;
-  h->dbg_pause = 0;
-  if (h->pending_hook == ZN_HOOK_PAUSE) { h->dbg_pause = 3000000u; h->pending_hook = 0; }   // test hook: every launch of this generation pauses all its waves for 30 ms in block 2
+  if (h->pending_hook == ZN_HOOK_PAUSE) { h->gen.dbg_pause = 3000000u; h->pending_hook = 0; }   // test hook: every launch of this generation pauses all its waves for 30 ms in block 2
   if (h->pending_hook == ZN_HOOK_TIMEOUT_WORD) { st.pad[0] = 1; h->pending_hook = 0; }   // test hook: this generation's hand-off waits find the timeout word set
   HIPCHK(h, hipMemcpyAsync(h->st, &st, sizeof st, hipMemcpyHostToDevice, s));
   std::vector<int> rem(batch, t_total - offset0), stop(batch, 0);   // model.py:439-441
@@ -1353,20 +1354,9 @@ extern "C" int zn_gen_begin(zn_handle h, int32_t batch, const void* const* kv_la
   std::vector<int> len0(rows, 0);
   HIPCHK(h, hipMemcpyAsync(len0.data(), lengths_dev, rows * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));  // host vectors go out of scope
-  h->len_hi = 0;
-  for (int v : len0) if (v > h->len_hi) h->len_hi = v;
-  h->gen_active = true;
-  h->rows_set = false;
-  h->pairs_set = false;
-  h->prefix_set = false;
-  h->slots_open = false;
-  h->gen_prefilled = false;
-  h->rows_unequal2 = false;
-  h->gen_ended = false;
-  h->gen_timed_out = false;
+  for (int v : len0) if (v > h->gen.len_hi) h->gen.len_hi = v;
+  h->gen.gen_active = true;
   h->gen_stream = s;
-  h->stop_pending = false;
-  h->emb_valid = false;
   return ZN_OK;
 }
 
@@ -1480,11 +1470,11 @@ static int transformer_prefill_core(zn_handle h, const bf16_t* hidden, int S, in
 
 static int prefill_batched(zn_handle h, const bf16_t* hidden, int S, hipStream_t s, const int* row_len) {
   const zn_config& c = h->cfg;
-  const int R = h->rows, d = c.d_model;
-  int rc = transformer_prefill_core(h, hidden, S, R, h->kv_layers.data(), h->max_len, 0, s, row_len, kv_fp8_gen(h) ? h->kv8_layers.data() : nullptr, kv_fp8_gen(h));
+  const int R = h->gen.rows, d = c.d_model;
+  int rc = transformer_prefill_core(h, hidden, S, R, h->gen.kv_layers.data(), h->gen.max_len, 0, s, row_len, kv_fp8_gen(h) ? h->gen.kv8_layers.data() : nullptr, kv_fp8_gen(h));
   if (rc) return rc;
   hipLaunchKernelGGL(gather_last_kernel, dim3(R), dim3(256), 0, s, h->pf_x, h->x, S, d, row_len);
-  hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > R ? 64 : R), 0, s, h->lengths, R, S, row_len);
+  hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > R ? 64 : R), 0, s, h->gen.lengths, R, S, row_len);
   return ZN_OK;
 }
 
@@ -1568,180 +1558,98 @@ static int prefill_impl(zn_handle h, const void* hidden_dev, int32_t S, const in
   const bool at_once = prefill_all_at_once(h, S);
   if (c.arch == 1 && at_once) {
     // all positions at once (mode 2: projections row by row through the step's GEMV: bit-comparable with single steps)
-    if ((rc = hybrid_prefill_core(h, (const bf16_t*)hidden_dev, S, h->rows, h->kv_layers.data(), h->max_len, 0, h->prefill_mode == 2, s, row_len))) return rc;
-    hipLaunchKernelGGL(gather_last_kernel, dim3(h->rows), dim3(256), 0, s, h->pf_x, h->x, S, c.d_model, row_len);
-    hipLaunchKernelGGL(gather_last_bytes_kernel, dim3(h->rows), dim3(256), 0, s, (const void*)h->pf_res, (void*)h->res, S, c.d_model * (c.residual_in_fp32 ? 4 : 2), row_len);
-    hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > h->rows ? 64 : h->rows), 0, s, h->lengths, h->rows, S, row_len);
-    h->len_hi += S;
+    if ((rc = hybrid_prefill_core(h, (const bf16_t*)hidden_dev, S, h->gen.rows, h->gen.kv_layers.data(), h->gen.max_len, 0, h->prefill_mode == 2, s, row_len))) return rc;
+    hipLaunchKernelGGL(gather_last_kernel, dim3(h->gen.rows), dim3(256), 0, s, h->pf_x, h->x, S, c.d_model, row_len);
+    hipLaunchKernelGGL(gather_last_bytes_kernel, dim3(h->gen.rows), dim3(256), 0, s, (const void*)h->pf_res, (void*)h->res, S, c.d_model * (c.residual_in_fp32 ? 4 : 2), row_len);
+    hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > h->gen.rows ? 64 : h->gen.rows), 0, s, h->gen.lengths, h->gen.rows, S, row_len);
+    h->gen.len_hi += S;
     if ((rc = hybrid_heads(h, s))) return rc;
   } else if (c.arch == 0 && at_once) {
     if ((rc = prefill_batched(h, (const bf16_t*)hidden_dev, S, s, row_len))) return rc;
-    h->len_hi += S;
+    h->gen.len_hi += S;
   } else {
     // Position by position through the decode kernels.  Row-wise ops are independent of S; attention reproduces the
     // reference's causal flash-attention blocking through `ext` = keys spanned by the query block of this position.
     const int qb = qsplit(S);
     for (int p = 0; p < S; ++p) {
-      hipLaunchKernelGGL(gather_pos_kernel, dim3(h->rows), dim3(256), 0, s, (const bf16_t*)hidden_dev, h->x, S, p, c.d_model);
+      hipLaunchKernelGGL(gather_pos_kernel, dim3(h->gen.rows), dim3(256), 0, s, (const bf16_t*)hidden_dev, h->x, S, p, c.d_model);
       int ext = (p / qb) * qb + qb; if (ext > S) ext = S;
-      const StepPlan plan = plan_blocks(h, h->rows, ++h->len_hi);
+      const StepPlan plan = plan_blocks(h, h->gen.rows, ++h->gen.len_hi);
       if ((rc = c.arch == 1 ? hybrid_token(h, p == S - 1, plan.attn_fused, s) : decode_blocks(h, plan, nullptr, ext, s))) return rc;
-      hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > h->rows ? 64 : h->rows), 0, s, h->lengths, h->rows, 1);
+      hipLaunchKernelGGL(add_lengths_kernel, dim3(1), dim3(64 > h->gen.rows ? 64 : h->gen.rows), 0, s, h->gen.lengths, h->gen.rows, 1);
     }
   }
-  if (c.arch == 0 && (rc = heads_logits(h, h->x, h->rows, s))) return rc;
+  if (c.arch == 0 && (rc = heads_logits(h, h->x, h->gen.rows, s))) return rc;
   HIPCHK(h, hipGetLastError());
   return ZN_OK;
 }
 
 extern "C" int zn_prefill(zn_handle h, const void* hidden_dev, int32_t S, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
-  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill before zn_gen_begin");
-  if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill in a slotted session: zn_gen_admit fills the slots");
-  if (!hidden_dev || S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill: bad S=%d (max_len %d)", S, h->max_len);
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_PREFILL));
+  if (!hidden_dev || S < 1 || S > h->gen.max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill: bad S=%d (max_len %d)", S, h->gen.max_len);
   if (int rc = kv_fp8_bound(h, "zn_prefill")) return rc;
-  h->gen_prefilled = true;
+  h->gen.gen_prefilled = true;
   return prefill_impl(h, hidden_dev, S, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int zn_prefill_rows(zn_handle h, const void* hidden_dev, int32_t S, const int32_t* row_len, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
-  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill_rows before zn_gen_begin");
-  if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_prefill_rows in a slotted session: zn_gen_admit fills the slots");
-  if (!hidden_dev || !row_len || S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: null argument or bad S=%d (max_len %d)", S, h->max_len);
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_PREFILL_ROWS));
+  if (!hidden_dev || !row_len || S < 1 || S > h->gen.max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: null argument or bad S=%d (max_len %d)", S, h->gen.max_len);
   if (int rc = kv_fp8_bound(h, "zn_prefill_rows")) return rc;
-  const int R = h->rows, B = h->batch;
-  int hi = 0;
-  bool uniform = true;
-  for (int r = 0; r < R; ++r) {
-    if (row_len[r] < 1 || row_len[r] > S) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: row %d holds %d positions, not in 1..%d", r, row_len[r], S);
-    if (row_len[r] > hi) hi = row_len[r];
-    uniform = uniform && row_len[r] == S;
-  }
-  if (hi != S) ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: the longest row holds %d positions, S is %d (no row may be all padding at its end)", hi, S);
-  if (R == 2 * B)
-    for (int b = 0; b < B; ++b)
-      if (row_len[b] != row_len[B + b])
-        ZN_FAIL(h, ZN_ERR_ARG, "zn_prefill_rows: utterance %d has %d conditional and %d unconditional positions (a guided pair advances in lockstep)", b, row_len[b], row_len[B + b]);
+  const int R = h->gen.rows;
+  bool uniform, unequal2;
+  ZN_GEN_CHECK(h, gen_check_prefill_rows(h->gen, row_len, S, &uniform, &unequal2));
   hipStream_t s = (hipStream_t)stream;
-  h->gen_prefilled = true;
+  h->gen.gen_prefilled = true;
   if (uniform) return prefill_impl(h, hidden_dev, S, nullptr, s);          // zn_prefill: the same launches, the same bits
   if (!prefill_all_at_once(h, S))
     ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_prefill_rows: rows of different lengths need the batched prefill; this handle prefills position by position "
             "(zn_debug_prefill_mode 0, S = 1, or dimensions that are not multiples of 32)");
   h->row_len_host.assign(row_len, row_len + R);
   HIPCHK(h, hipMemcpyAsync(h->row_len, h->row_len_host.data(), R * sizeof(int), hipMemcpyHostToDevice, s));
-  h->rows_unequal2 = R == 2 && B == 2 && row_len[0] != row_len[1];
+  h->gen.rows_unequal2 = unequal2;
   return prefill_impl(h, hidden_dev, S, h->row_len, s);                     // len_hi += S: the bound of the longest row
-}
-
-// A guided entry of a generation begun without guidance (a mixed generation): legal exactly when it names a row pair
-// (reserved[0] = cond_row + 1, reserved[1] = uncond_row + 1), both rows in range and distinct, one of them the entry's own, and the partner's
-// entry - present in the same call - names the same pair with byte-equal parameters.  `slot_of(j)`: the row of entry j of the call; `entry(j)`.
-// Returns the index of the partner's entry, or -1 with `why` set.
-template <typename SlotOf, typename Entry>
-static int pair_partner(int j, int n, int B, SlotOf slot_of, Entry entry, const char** why) {
-  const zn_row_params& r = entry(j);
-  const int own = slot_of(j), rc = r.reserved[0] - 1, ru = r.reserved[1] - 1;
-  if (r.reserved[0] <= 0 && r.reserved[1] <= 0) { *why = "has a cfg_scale != 1 in a generation begun without guidance and names no row pair"; return -1; }
-  if (rc < 0 || rc >= B || ru < 0 || ru >= B) { *why = "names a row pair out of range"; return -1; }
-  if (rc == ru) { *why = "names the same row twice as its pair"; return -1; }
-  if (rc != own && ru != own) { *why = "names a row pair that does not hold its own row"; return -1; }
-  const int other = rc == own ? ru : rc;
-  for (int k = 0; k < n; ++k) {
-    if (slot_of(k) != other) continue;
-    if (memcmp(&entry(k), &r, sizeof(zn_row_params)) != 0) { *why = "and its pair's other row differ in their entries (the same pair, byte-equal parameters)"; return -1; }
-    return k;
-  }
-  *why = "names a row pair whose other row is not part of this call";
-  return -1;
 }
 
 extern "C" int zn_gen_set_rows(zn_handle h, const zn_row_params* rows_host, int32_t n) {
   if (!h) return ZN_ERR_ARG;
-  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_rows before zn_gen_begin");
-  if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_rows in a slotted session: zn_gen_admit fills the slots");
-  if (h->gen_prefilled) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_rows after zn_prefill: the table belongs between zn_gen_begin and the generation's prefill");
-  if (!rows_host) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: null argument");
-  if (n != h->batch) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: %d entries for a generation of %d utterances", n, h->batch);
-  const int nq = h->cfg.n_codebooks, budget = h->t_total - h->offset0 - nq + 1;   // zn_gen_begin's max_new_tokens (t_total = prefix + max_new_tokens + n_q)
-  std::vector<int> rem(n);
-  bool pairs = false;
-  for (int b = 0; b < n; ++b) {
-    const zn_row_params& r = rows_host[b];
-    if (r.sp.repetition_penalty_window < 0 || r.sp.repetition_penalty_window > 64)
-      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d: repetition_penalty_window out of range", b);
-    if (r.max_new_tokens < 1 || r.max_new_tokens > budget)
-      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d: max_new_tokens %d not in 1..%d (the generation's own)", b, r.max_new_tokens, budget);
-    const bool named = r.reserved[0] != 0 || r.reserved[1] != 0;
-    if (named && (guided(h) || r.cfg_scale == 1.0f))
-      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d names a row pair %s (pairs belong to guided entries of a generation begun with cfg_scale == 1)", b,
-              guided(h) ? "in a generation begun with guidance" : "at cfg_scale == 1");
-    if (!guided(h) && r.cfg_scale != 1.0f) {
-      const char* why = nullptr;
-      if (pair_partner(b, n, n, [](int j) { return j; }, [&](int j) -> const zn_row_params& { return rows_host[j]; }, &why) < 0)
-        ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d %s", b, why);
-      pairs = true;
-    } else if ((r.cfg_scale == 1.0f) == guided(h))
-      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_rows: utterance %d has cfg_scale %g in a generation begun %s guidance (cfg_scale == 1 for every row or for none)", b,
-              (double)r.cfg_scale, guided(h) ? "with" : "without");
-    rem[b] = r.max_new_tokens + nq - 1;
-  }
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_SET_ROWS));
+  std::vector<int> rem;
+  bool pairs;
+  ZN_GEN_CHECK(h, gen_check_set_rows(h->gen, h->cfg.n_codebooks, rows_host, n, &rem, &pairs));
   hipStream_t s = h->gen_stream;
   HIPCHK(h, hipMemcpyAsync(h->row_tab, rows_host, (size_t)n * sizeof(zn_row_params), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemcpyAsync(h->remaining, rem.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipStreamSynchronize(s));  // the host arrays are the caller's / go out of scope
-  h->rows_set = true;
-  h->pairs_set = pairs;
+  h->gen.rows_set = true;
+  h->gen.pairs_set = pairs;
   return ZN_OK;
 }
 
 extern "C" int zn_gen_set_prefix_rows(zn_handle h, const int32_t* prefix_len_host, int32_t n) {
   if (!h) return ZN_ERR_ARG;
-  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_prefix_rows before zn_gen_begin");
-  if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_prefix_rows in a slotted session: zn_gen_admit fills the slots");
-  if (h->gen_prefilled) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_set_prefix_rows after zn_prefill: the prefix lengths belong between zn_gen_begin and the generation's prefill");
-  if (!prefix_len_host) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_prefix_rows: null argument");
-  if (n != h->batch) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_prefix_rows: %d entries for a generation of %d utterances", n, h->batch);
-  const int p_call = h->offset0 - 1;        // zn_gen_begin's offset0 = the longest prefix + 1
-  std::vector<int> shift(n);
-  bool longest = false, any = false;
-  for (int b = 0; b < n; ++b) {
-    const int p = prefix_len_host[b];
-    if (p < 0 || p > p_call) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_prefix_rows: utterance %d: prefix length %d not in 0..%d (zn_gen_begin's offset0 - 1)", b, p, p_call);
-    shift[b] = p - p_call;
-    longest = longest || p == p_call; any = any || p != p_call;
-  }
-  if (!longest) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_set_prefix_rows: no utterance has the %d prefix frames zn_gen_begin's offset0 stands for", p_call);
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_SET_PREFIX_ROWS));
+  std::vector<int> shift;
+  bool any;
+  ZN_GEN_CHECK(h, gen_check_prefix_rows(h->gen, prefix_len_host, n, &shift, &any));
   if (any) {
     hipStream_t s = h->gen_stream;
     HIPCHK(h, hipMemcpyAsync(h->prefix_shift, shift.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(h, hipStreamSynchronize(s));  // the host vector goes out of scope
   }
-  h->prefix_set = any;                  // every shift 0: the kernels keep their NULL branch (the same launches, the same bits)
+  h->gen.prefix_set = any;                  // every shift 0: the kernels keep their NULL branch (the same launches, the same bits)
   return ZN_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ slotted session
 static int handoff_timeout(zn_handle h, int count);
-// The host bound of the rows' KV lengths in a session: the longest busy slot (an idle slot's rows stay at 0).
-static void slots_len_hi(zn_handle h) {
-  h->len_hi = 0;
-  for (int b = 0; b < h->batch; ++b) if (h->slot_busy[b] && h->slot_len[b] > h->len_hi) h->len_hi = h->slot_len[b];
-}
-#define ZN_SESSION_CHECK(h, fn)                                                                              \
-  do {                                                                                                       \
-    if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, fn " before zn_gen_begin");                 \
-    if (!h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, fn ": the generation is not a slotted session (zn_gen_open_slots)"); \
-  } while (0)
 
 extern "C" int zn_gen_open_slots(zn_handle h, int32_t slack) {
   if (!h) return ZN_ERR_ARG;
-  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_open_slots before zn_gen_begin");
-  if (h->gen_prefilled) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_open_slots after zn_prefill: a session is opened between zn_gen_begin and the generation's first prefill");
-  if (h->slots_open || h->rows_set || h->prefix_set) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_open_slots: the generation already has a row table, column shifts or slots");
-  if (slack < 0) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_open_slots: slack %d < 0", slack);
-  if (h->len_hi != 0) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_open_slots: the session's lengths array must be zero (every slot begins idle)");
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_OPEN_SLOTS));
+  ZN_GEN_CHECK(h, gen_check_open_slots(h->gen, slack));
   const size_t R = h->max_rows;
   if (!h->step0) HIPCHK(h, hipMalloc(&h->step0, R * sizeof(int)));
   if (!h->adm_stage) HIPCHK(h, hipHostMalloc(&h->adm_stage, R * (4 * sizeof(int) + sizeof(zn_row_params))));
@@ -1749,17 +1657,14 @@ extern "C" int zn_gen_open_slots(zn_handle h, int32_t slack) {
   if (!h->adm_layers) HIPCHK(h, hipMalloc(&h->adm_layers, (size_t)h->cfg.n_layer * sizeof(AdmitLayer)));
   if (!h->adm_event) HIPCHK(h, hipEventCreateWithFlags(&h->adm_event, hipEventDisableTiming));
   hipStream_t s = h->gen_stream;
-  const int B = h->batch;
+  const int B = h->gen.batch;
   HIPCHK(h, hipMemsetAsync(h->remaining, 0, B * sizeof(int), s));
   HIPCHK(h, hipMemsetAsync(h->stopping, 0, B * sizeof(int), s));
   HIPCHK(h, hipMemsetAsync(h->prefix_shift, 0, B * sizeof(int), s));
   HIPCHK(h, hipMemsetAsync(h->step0, 0xFF, B * sizeof(int), s));                     // -1: idle
   HIPCHK(h, hipMemsetAsync(h->row_tab, 0, (size_t)B * sizeof(zn_row_params), s));    // an idle slot samples greedily, without a penalty
-  h->slot_len.assign(B, 0); h->slot_busy.assign(B, 0);
-  h->slot_slack = slack;
   h->adm_cap_S = 0;                        // the pointer table names this generation's caches: rebuilt by the first admission
-  h->rows_set = h->prefix_set = h->slots_open = true;
-  h->pairs_set = !guided(h);               // a session begun without guidance may admit row pairs at any point: its samplers (captured graphs included) follow the entries' pair words from the start
+  h->gen.open_slots(slack);
   return ZN_OK;
 }
 
@@ -1782,7 +1687,7 @@ static int ensure_admit_cache(zn_handle h, int S, hipStream_t s) {
   h->adm_caches.resize(c.n_layer);
   for (int li = 0; li < c.n_layer; ++li) {
     h->adm_caches[li] = (char*)h->adm_cache + (size_t)li * h->adm_layer_bytes;
-    tab[li] = AdmitLayer{h->adm_caches[li], const_cast<void*>(h->kv_layers[li]), (c.arch == 1 && h->layers[li].kind == 1) ? 1 : 0, codes_only ? 1 : 0, kv8_of(h, li)};
+    tab[li] = AdmitLayer{h->adm_caches[li], const_cast<void*>(h->gen.kv_layers[li]), (c.arch == 1 && h->layers[li].kind == 1) ? 1 : 0, codes_only ? 1 : 0, kv8_of(h, li)};
   }
   HIPCHK(h, hipMemcpyAsync(h->adm_layers, tab.data(), tab.size() * sizeof(AdmitLayer), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipStreamSynchronize(s));      // the host vector goes out of scope
@@ -1792,46 +1697,13 @@ static int ensure_admit_cache(zn_handle h, int S, hipStream_t s) {
 
 extern "C" int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const void* hidden_dev, int32_t S, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
-  ZN_SESSION_CHECK(h, "zn_gen_admit");
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_ADMIT));
   const zn_config& c = h->cfg;
-  const int B = h->batch, halves = guided(h) ? 2 : 1, nq = c.n_codebooks, MR = h->max_rows;
-  if (!a || !hidden_dev || n < 1 || n > B) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: null argument or %d requests for a session of %d slots", n, B);
-  if (S < 1 || S > h->max_len) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: bad S=%d (max_len %d)", S, h->max_len);
-  if (h->stop_pending) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_admit: steps are still owed to a deferred stop read-back (zn_all_stopped_end first)");
+  const int B = h->gen.batch, halves = guided(h) ? 2 : 1, nq = c.n_codebooks, MR = h->max_rows;
+  ZN_GEN_CHECK(h, gen_check_admit_call(h->gen, a && hidden_dev, n, S));
   if (int rc = kv_fp8_bound(h, "zn_gen_admit")) return rc;
-  bool longest = false;
-  for (int j = 0; j < n; ++j) {
-    const zn_admit& q = a[j];
-    if (q.slot < 0 || q.slot >= B) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d out of range 0..%d", q.slot, B - 1);
-    for (int k = 0; k < j; ++k) if (a[k].slot == q.slot) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d named twice in one call", q.slot);
-    if (h->slot_busy[q.slot]) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_admit: slot %d is busy (zn_gen_retire first)", q.slot);
-    if (q.row_len < 1 || q.row_len > S) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: %d positions, not in 1..%d", q.slot, q.row_len, S);
-    if (q.prefix_len < 0 || q.prefix_len > q.row_len - 2)
-      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: prefix length %d not in 0..%d (row_len = conditioning + prefix + 1)", q.slot, q.prefix_len, q.row_len - 2);
-    const zn_row_params& r = q.params;
-    if (r.sp.repetition_penalty_window < 0 || r.sp.repetition_penalty_window > 64) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: repetition_penalty_window out of range", q.slot);
-    if (r.max_new_tokens < 1) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: max_new_tokens %d < 1", q.slot, r.max_new_tokens);
-    if ((long long)q.row_len - 1 + r.max_new_tokens + nq + h->slot_slack > h->max_len)
-      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: %d positions + %d frames + %d + slack %d exceed the session's max_len %d", q.slot, q.row_len - 1, r.max_new_tokens, nq,
-              h->slot_slack, h->max_len);
-    if ((long long)q.prefix_len + r.max_new_tokens + nq + h->slot_slack > h->t_total)
-      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d: %d prefix frames + %d frames + %d + slack %d exceed the code buffer's width %d", q.slot, q.prefix_len, r.max_new_tokens, nq,
-              h->slot_slack, h->t_total);
-    const bool named = r.reserved[0] != 0 || r.reserved[1] != 0;
-    if (named && (guided(h) || r.cfg_scale == 1.0f))
-      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d names a row pair %s (pairs belong to guided entries of a session begun with cfg_scale == 1)", q.slot,
-              guided(h) ? "in a session begun with guidance" : "at cfg_scale == 1");
-    if (!guided(h) && r.cfg_scale != 1.0f) {
-      const char* why = nullptr;
-      const int k = pair_partner(j, n, B, [&](int i) { return (int)a[i].slot; }, [&](int i) -> const zn_row_params& { return a[i].params; }, &why);
-      if (k < 0) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d %s", q.slot, why);
-      if (a[k].row_len != q.row_len || a[k].prefix_len != q.prefix_len)
-        ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d and its pair's other slot %d differ in row_len or prefix_len", q.slot, a[k].slot);
-    } else if ((r.cfg_scale == 1.0f) == guided(h))
-      ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: slot %d has cfg_scale %g in a session begun %s guidance", q.slot, (double)r.cfg_scale, guided(h) ? "with" : "without");
-    longest = longest || q.row_len == S;
-  }
-  if (!longest) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_admit: no request holds S = %d positions (no row may be all padding at its end)", S);
+  bool uniform;
+  ZN_GEN_CHECK(h, gen_check_admit(h->gen, nq, a, n, S, &uniform));
   if (!prefill_all_at_once(h, S))
     ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_gen_admit needs the batched prefill; this handle prefills position by position (zn_debug_prefill_mode 0, S = 1, or dimensions that are not multiples of 32)");
   hipStream_t s = (hipStream_t)stream;
@@ -1843,21 +1715,19 @@ extern "C" int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const voi
   const int Rs = n * halves;
   int* w = (int*)h->adm_stage;
   zn_row_params* pw = (zn_row_params*)(h->adm_stage + (size_t)MR * 4 * sizeof(int));
-  bool uniform = true;
   for (int j = 0; j < n; ++j) {
     w[j] = a[j].slot; w[MR + j] = a[j].prefix_len; w[2 * MR + j] = a[j].params.max_new_tokens + nq - 1;
     for (int hf = 0; hf < halves; ++hf) w[3 * MR + hf * n + j] = a[j].row_len;
     pw[j] = a[j].params;
-    uniform = uniform && a[j].row_len == S;
   }
   HIPCHK(h, hipMemcpyAsync(h->adm_dev, h->adm_stage, (size_t)MR * (4 * sizeof(int) + sizeof(zn_row_params)), hipMemcpyHostToDevice, s));
   const int* dv = (const int*)h->adm_dev;
   const int* row_len_dev = uniform ? nullptr : dv + 3 * MR;           // every length S: zn_prefill's launches, as zn_prefill_rows makes them
-  h->gen_prefilled = true;
+  h->gen.gen_prefilled = true;
   size_t conv_src = 0, conv_dst = 0;
   if (c.arch == 1) {
     (void)zn_mamba_state_bytes_per_layer(&c, Rs, &conv_src);
-    const size_t state = zn_mamba_state_bytes_per_layer(&c, h->rows, &conv_dst);
+    const size_t state = zn_mamba_state_bytes_per_layer(&c, h->gen.rows, &conv_dst);
     (void)state;
     const size_t zb = zn_mamba_state_bytes_per_layer(&c, Rs, nullptr);
     for (int li = 0; li < c.n_layer; ++li)                               // a prefill continues the state it finds: the scratch rows begin at zero
@@ -1867,7 +1737,7 @@ extern "C" int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const voi
     if ((rc = transformer_prefill_core(h, (const bf16_t*)hidden_dev, S, Rs, nullptr, S, 0, s, row_len_dev, h->adm_caches.data(), true))) return rc;
   } else if ((rc = transformer_prefill_core(h, (const bf16_t*)hidden_dev, S, Rs, h->adm_caches.data(), S, 0, s, row_len_dev, nullptr, kv_fp8_gen(h)))) return rc;   // (FP8 KV cache: the scratch rows are rounded, admit_rows_kernel writes their codes)
   AdmitArgs m{};
-  m.layers = h->adm_layers; m.n_layer = c.n_layer; m.n = n; m.halves = halves; m.B = B; m.S = S; m.max_len = h->max_len;
+  m.layers = h->adm_layers; m.n_layer = c.n_layer; m.n = n; m.halves = halves; m.B = B; m.S = S; m.max_len = h->gen.max_len;
   m.kv_row_bytes = 2 * c.n_heads_kv * h->hd * 2;
   if (c.arch == 1) {
     m.conv_row_bytes = h->m_conv_dim * c.m_d_conv * 2; m.ssm_row_bytes = c.m_d_inner * c.m_d_state * 2; m.ssm_off_src = conv_src; m.ssm_off_dst = conv_dst;
@@ -1875,51 +1745,38 @@ extern "C" int zn_gen_admit(zn_handle h, const zn_admit* a, int32_t n, const voi
   }
   m.slot = dv; m.prefix = dv + MR; m.rem = dv + 2 * MR; m.row_len = dv + 3 * MR; m.params = (const zn_row_params*)(h->adm_dev + (size_t)MR * 4 * sizeof(int));
   m.pf_x = h->pf_x; m.x = h->x; m.d = c.d_model; m.st = h->st;
-  m.lengths = h->lengths; m.remaining = h->remaining; m.stopping = h->stopping; m.shift = h->prefix_shift; m.step0 = h->step0; m.rows = h->row_tab;
+  m.lengths = h->gen.lengths; m.remaining = h->remaining; m.stopping = h->stopping; m.shift = h->prefix_shift; m.step0 = h->step0; m.rows = h->row_tab;
   hipLaunchKernelGGL(admit_rows_kernel, dim3(Rs, c.n_layer + 1, ZN_ADMIT_PARTS), dim3(256), 0, s, m);
   HIPCHK(h, hipEventRecord(h->adm_event, s));
   h->adm_pending = true;
   // the heads over every row of h->x, as a prefill of the whole batch runs them (the logits of the rows not admitted are workspace: the next
   // step's heads rewrite them before any sampler reads them), then the first frame of each admitted slot alone
-  if ((rc = c.arch == 1 ? hybrid_heads(h, s) : heads_logits(h, h->x, h->rows, s))) return rc;
-  for (int j = 0; j < n; ++j) {
-    SampleArgs sa = gen_sample_args(h);
-    sa.raw = h->logits_raw; sa.mix = guided(h) ? 1 : 0; sa.apply_bias = 0; sa.batch = B;
-    sa.use_penalty = 0; sa.st = h->st; sa.logits_out = h->last_logits; sa.tokens = h->tok_raw; sa.draw = 0; sa.slot_base = a[j].slot;
-    hipLaunchKernelGGL(sample_kernel, dim3(nq, 1), dim3(256), 0, s, sa);
-    FrameArgs f{};
-    f.st = h->st; f.codes = h->codes; f.t_total = h->t_total; f.batch = B; f.n_q = nq; f.eos_id = c.eos_id;
-    f.mask_id = c.mask_id; f.tokens = h->tok_raw; f.remaining = h->remaining; f.stopping = h->stopping; f.lengths = h->lengths;
-    f.rows = h->rows; f.first = 1; f.shift = sa.shift; f.step0 = sa.step0; f.slot_base = a[j].slot; f.slot_count = 1;
-    hipLaunchKernelGGL(frame_update_kernel, dim3(1), dim3(256), 0, s, f);
-  }
-  for (int j = 0; j < n; ++j) { h->slot_busy[a[j].slot] = 1; h->slot_len[a[j].slot] = a[j].row_len; }
-  slots_len_hi(h);
-  h->emb_valid = false;
+  if ((rc = c.arch == 1 ? hybrid_heads(h, s) : heads_logits(h, h->x, h->gen.rows, s))) return rc;
+  for (int j = 0; j < n; ++j) launch_first_frame(h, a[j].slot, s);
+  h->gen.slots_admitted(a, n);
+  h->gen.emb_valid = false;
   HIPCHK(h, hipGetLastError());
   return ZN_OK;
 }
 
 extern "C" int zn_gen_retire(zn_handle h, int32_t slot) {
   if (!h) return ZN_ERR_ARG;
-  ZN_SESSION_CHECK(h, "zn_gen_retire");
-  if (slot < 0 || slot >= h->batch) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_retire: slot %d out of range 0..%d", slot, h->batch - 1);
-  if (!h->slot_busy[slot]) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_retire: slot %d is idle already", slot);
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_RETIRE));
+  ZN_GEN_CHECK(h, gen_check_retire(h->gen, slot));
   hipStream_t s = h->gen_stream;
-  HIPCHK(h, hipMemsetAsync(h->lengths + slot, 0, sizeof(int), s));
-  if (guided(h)) HIPCHK(h, hipMemsetAsync(h->lengths + h->batch + slot, 0, sizeof(int), s));
+  HIPCHK(h, hipMemsetAsync(h->gen.lengths + slot, 0, sizeof(int), s));
+  if (guided(h)) HIPCHK(h, hipMemsetAsync(h->gen.lengths + h->gen.batch + slot, 0, sizeof(int), s));
   HIPCHK(h, hipMemsetAsync(h->remaining + slot, 0, sizeof(int), s));
   HIPCHK(h, hipMemsetAsync(h->step0 + slot, 0xFF, sizeof(int), s));
-  h->slot_busy[slot] = 0; h->slot_len[slot] = 0;
-  slots_len_hi(h);
+  h->gen.slot_retired(slot);
   return ZN_OK;
 }
 
 extern "C" int zn_gen_row_state(zn_handle h, int32_t* remaining_host, int32_t* steps_host, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
-  ZN_SESSION_CHECK(h, "zn_gen_row_state");
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_ROW_STATE));
   hipStream_t s = (hipStream_t)stream;
-  const int B = h->batch;
+  const int B = h->gen.batch;
   std::vector<int> rem(B), s0(B);
   GenState st{};
   HIPCHK(h, hipMemcpyAsync(rem.data(), h->remaining, B * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1936,42 +1793,28 @@ extern "C" int zn_gen_row_state(zn_handle h, int32_t* remaining_host, int32_t* s
 
 extern "C" int zn_sample_first(zn_handle h, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
-  if (!h->gen_active) ZN_FAIL(h, ZN_ERR_STATE, "zn_sample_first before zn_gen_begin");
-  if (h->slots_open) ZN_FAIL(h, ZN_ERR_STATE, "zn_sample_first in a slotted session: zn_gen_admit samples each slot's first frame");
-  hipStream_t s = (hipStream_t)stream;
-  const zn_config& c = h->cfg;
-  SampleArgs a = gen_sample_args(h);
-  a.raw = h->logits_raw; a.mix = guided(h) ? 1 : 0; a.apply_bias = 0; a.batch = h->batch;
-  a.use_penalty = 0; a.st = h->st; a.logits_out = h->last_logits; a.tokens = h->tok_raw; a.draw = 0;
-  hipLaunchKernelGGL(sample_kernel, dim3(c.n_codebooks, h->batch), dim3(256), 0, s, a);
-  FrameArgs f{};
-  f.st = h->st; f.codes = h->codes; f.t_total = h->t_total; f.batch = h->batch; f.n_q = c.n_codebooks; f.eos_id = c.eos_id;
-  f.mask_id = c.mask_id; f.tokens = h->tok_raw; f.remaining = h->remaining; f.stopping = h->stopping; f.lengths = h->lengths;
-  f.rows = h->rows; f.first = 1; f.override = h->tok_override; f.override_calls = h->tok_override_calls; f.shift = a.shift;
-  hipLaunchKernelGGL(frame_update_kernel, dim3(1), dim3(256), 0, s, f);
-  h->emb_valid = false;
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_SAMPLE_FIRST));
+  launch_first_frame(h, -1, (hipStream_t)stream);
+  h->gen.emb_valid = false;
   HIPCHK(h, hipGetLastError());
   return ZN_OK;
 }
 
 extern "C" int zn_decode_steps(zn_handle h, int32_t n, zn_stream stream) {
   if (!h) return ZN_ERR_ARG;
-  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_decode_steps before zn_gen_begin");
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_DECODE_STEPS));
   if (n < 0) ZN_FAIL(h, ZN_ERR_ARG, "n < 0");
   hipStream_t s = (hipStream_t)stream;
   h->gen_stream = s;
   if (int rc = kv_fp8_bound(h, "zn_decode_steps")) return rc;
-  if (h->slots_open)
-    for (int b = 0; b < h->batch; ++b)
-      if (h->slot_busy[b] && h->slot_len[b] + n > h->max_len)
-        ZN_FAIL(h, ZN_ERR_STATE, "zn_decode_steps: %d steps would take slot %d (%d positions) past max_len %d: retire it first", n, b, h->slot_len[b], h->max_len);
+  ZN_GEN_CHECK(h, gen_check_steps(h->gen, n));
   for (int i = 0; i < n;) {
     const StepPlan p = h->last_plan = plan_steps(h, n - i);
     const int k = p.graph_slot, run = p.run;
     // steps with the fused tail read the embedding their predecessor's tail left: the first of them gets it from embed_kernel; steps
     // without it (one row off the whole-step kernel) embed into h->x themselves and leave x_emb stale
-    if (p.fused_tail && !h->emb_valid) hipLaunchKernelGGL(embed_kernel, dim3(h->batch), dim3(256), 0, s, make_embed_args(h));
-    h->emb_valid = p.fused_tail;
+    if (p.fused_tail && !h->gen.emb_valid) hipLaunchKernelGGL(embed_kernel, dim3(h->gen.batch), dim3(256), 0, s, make_embed_args(h));
+    h->gen.emb_valid = p.fused_tail;
     if (!h->graph_exec[k] && !h->graph_tried[k] && n > 1) {
       // capture; every step-varying quantity (column, positions) is read from device memory
       h->graph_tried[k] = true;
@@ -1989,12 +1832,9 @@ extern "C" int zn_decode_steps(zn_handle h, int32_t n, zn_stream stream) {
     }
     if (h->graph_exec[k]) HIPCHK(h, hipGraphLaunch(h->graph_exec[k], s));
     else for (int j = 0; j < run; ++j) { int rc = enqueue_step(h, p, s); if (rc) return rc; }
-    i += run; h->len_hi += run; h->epoch_bound += (unsigned long long)run * (h->cfg.n_layer + 1);
+    i += run; h->gen.len_hi += run; h->epoch_bound += (unsigned long long)run * (h->cfg.n_layer + 1);
   }
-  if (h->slots_open) {
-    for (int b = 0; b < h->batch; ++b) if (h->slot_busy[b]) h->slot_len[b] += n;
-    slots_len_hi(h);
-  }
+  if (h->gen.slots_open) h->gen.slots_advance(n);
   HIPCHK(h, hipGetLastError());
   return ZN_OK;
 }
@@ -2002,8 +1842,8 @@ extern "C" int zn_decode_steps(zn_handle h, int32_t n, zn_stream stream) {
 extern "C" int zn_gen_end(zn_handle h) {
   if (!h) return ZN_ERR_ARG;
   (void)zn_tenant_release(h->device, h);
-  if (h->gen_active && !h->gen_ended && h->demoted && !h->gen_timed_out) h->clean_since_demotion++;
-  h->gen_ended = true;
+  if (h->gen.gen_active && !h->gen.gen_ended && h->demoted && !h->gen.gen_timed_out) h->clean_since_demotion++;
+  h->gen.gen_ended = true;
   return ZN_OK;
 }
 
@@ -2021,9 +1861,9 @@ extern "C" int zn_get_counters(zn_handle h, int64_t* out, int32_t n) {
 }
 
 extern "C" int zn_decode_path_detail(zn_handle h) {
-  if (!h || !h->gen_active || h->cfg.arch != 0 || !persist_active(h, h->rows)) return 0;
+  if (!h || !h->gen.gen_active || h->cfg.arch != 0 || !persist_active(h, h->gen.rows)) return 0;
   // which persistent kernel: the last plan's; whether one is still allowed: asked now (a timeout reported since demotes at once).  One row: 2 or 0
-  return h->last_plan.path == StepPlan::STACK ? 2 : chain_allowed(h, h->rows) ? 1 : 0;
+  return h->last_plan.path == StepPlan::STACK ? 2 : chain_allowed(h, h->gen.rows) ? 1 : 0;
 }
 extern "C" int zn_decode_path(zn_handle h) { return zn_decode_path_detail(h) != 0 ? 1 : 0; }
 extern "C" int zn_graph_active(zn_handle h) {
@@ -2044,7 +1884,7 @@ static int handoff_timeout(zn_handle h, int count) {
   (void)ZN_NOT_IN_CAPTURE(hipMemcpy(h->diag_host, h->ch_diag, sizeof h->diag_host, hipMemcpyDeviceToHost));
   (void)ZN_NOT_IN_CAPTURE(hipMemset(h->ch_diag, 0, 32));                   // (the wait statistics in words 8, 9 stay)
   (void)ZN_NOT_IN_CAPTURE(hipMemset(&h->st->pad[0], 0, sizeof(int)));
-  h->demoted = true; h->clean_since_demotion = 0; h->n_timeouts++; h->gen_timed_out = true;
+  h->demoted = true; h->clean_since_demotion = 0; h->n_timeouts++; h->gen.gen_timed_out = true;
   free_graph(h);
   const unsigned* d = h->diag_host;
   ZN_FAIL(h, ZN_ERR_HIP, "decode chain: %d hand-off wait(s) timed out - the results of this generation are invalid. First: stage %u of block %u, workgroup %u wave %u lane %u "
@@ -2070,14 +1910,14 @@ extern "C" int zn_all_stopped_begin(zn_handle h, zn_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(h, hipMemcpyAsync(h->done_host + 4, &h->st->all_done, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipEventRecord(h->stop_event, s));
-  h->stop_pending = true;
+  h->gen.stop_pending = true;
   return ZN_OK;
 }
 extern "C" int zn_all_stopped_end(zn_handle h, int32_t* out) {
   if (!h || !out) return ZN_ERR_ARG;
-  if (!h->stop_pending) ZN_FAIL(h, ZN_ERR_STATE, "zn_all_stopped_end without zn_all_stopped_begin");
+  if (!h->gen.stop_pending) ZN_FAIL(h, ZN_ERR_STATE, "zn_all_stopped_end without zn_all_stopped_begin");
   HIPCHK(h, hipEventSynchronize(h->stop_event));
-  h->stop_pending = false;
+  h->gen.stop_pending = false;
   *out = h->done_host[4];
   if (h->done_host[7] != 0) return handoff_timeout(h, h->done_host[7]);
   return ZN_OK;
@@ -2087,12 +1927,12 @@ extern "C" int zn_get_step_outputs(zn_handle h, float* logits_dev, int32_t* toke
   if (!h) return ZN_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const zn_config& c = h->cfg;
-  if (logits_dev) HIPCHK(h, hipMemcpyAsync(logits_dev, h->last_logits, (size_t)h->batch * c.n_codebooks * c.vocab_head * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (tokens_dev) HIPCHK(h, hipMemcpyAsync(tokens_dev, h->tok_raw, (size_t)h->batch * c.n_codebooks * sizeof(int), hipMemcpyDeviceToDevice, s));
+  if (logits_dev) HIPCHK(h, hipMemcpyAsync(logits_dev, h->last_logits, (size_t)h->gen.batch * c.n_codebooks * c.vocab_head * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (tokens_dev) HIPCHK(h, hipMemcpyAsync(tokens_dev, h->tok_raw, (size_t)h->gen.batch * c.n_codebooks * sizeof(int), hipMemcpyDeviceToDevice, s));
   return ZN_OK;
 }
 
-extern "C" int zn_codes_changed(zn_handle h) { if (!h) return ZN_ERR_ARG; h->emb_valid = false; return ZN_OK; }
+extern "C" int zn_codes_changed(zn_handle h) { if (!h) return ZN_ERR_ARG; h->gen.emb_valid = false; return ZN_OK; }
 extern "C" int zn_debug_force_eos(zn_handle h, int32_t step) { if (!h) return ZN_ERR_ARG; h->force_eos_step = step; return ZN_OK; }
 extern "C" int zn_debug_token_override(zn_handle h, const int32_t* tokens_dev, int32_t calls) {
   if (!h) return ZN_ERR_ARG;
@@ -2106,7 +1946,7 @@ extern "C" int zn_debug_tune(zn_handle h, int32_t key, int32_t value) {
     if (h->ch_diag) { (void)hipDeviceSynchronize(); (void)ZN_NOT_IN_CAPTURE(hipMemset(h->ch_diag + 8, 0, 2 * sizeof(unsigned))); }
     return ZN_OK;
   }
-  (key == ZN_TUNE_HOOK ? h->pending_hook : h->tune[key]) = value; free_graph(h); h->emb_valid = false;      // (a hook waits for zn_gen_begin)
+  (key == ZN_TUNE_HOOK ? h->pending_hook : h->tune[key]) = value; free_graph(h); h->gen.emb_valid = false;      // (a hook waits for zn_gen_begin)
   if (key == ZN_TUNE_PERSISTENT && value == 1 && h->demoted) { h->demoted = false; h->clean_since_demotion = 0; h->n_rearms++; }
   return ZN_OK;
 }
@@ -2152,10 +1992,10 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   // which == 6: the whole-step kernel (every block of a decode step + the heads in ONE launch) on a scratch cache of its own per layer,
   // all rows at position ctx; the handle's generation state is put back afterwards
   std::vector<void*> skv;
-  std::vector<const void*> saved_kv = h->kv_layers;
-  const int saved_max_len = h->max_len; int* const saved_lengths = h->lengths;
+  GenHost saved_gen;
   const int ctx = ctx_arg > 0 ? ctx_arg : 450;
   if (which == 6) {
+    saved_gen = h->gen;
     if (!persist_active(h, rows)) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the whole-step kernel serves one or two rows of the transformer only");
     if (!h->stack_checked) { h->stack_ok = stack_shapes_ok(h); h->stack_checked = true; }
     if ((stack_nbk = stack_blocks_for(h, rows, ctx + 1)) < 0) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_bench_kernel: the whole-step kernel does not serve this model / context");
@@ -2164,13 +2004,13 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
     HIPCHK(h, hipMalloc(&tlen, (size_t)rows * sizeof(int)));
     HIPCHK(h, ZN_NOT_IN_CAPTURE(hipMemcpy(tlen, lens.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice)));
     skv.assign(c.n_layer, nullptr);
-    h->kv_layers.assign(c.n_layer, nullptr);
+    h->gen.kv_layers.assign(c.n_layer, nullptr);
     for (int li = 0; li < c.n_layer; ++li) {
       HIPCHK(h, hipMalloc(&skv[li], (size_t)rows * cap * 2 * nkv * 2));
       HIPCHK(h, hipMemsetAsync(skv[li], 0, (size_t)rows * cap * 2 * nkv * 2, s));
-      h->kv_layers[li] = skv[li];
+      h->gen.kv_layers[li] = skv[li];
     }
-    h->max_len = cap; h->lengths = tlen;
+    h->gen.max_len = cap; h->gen.lengths = tlen;
     HIPCHK(h, hipMemsetAsync(h->x_emb, 0, (size_t)rows * d * 2, s));
     HIPCHK(h, hipMemsetAsync(h->q, 0, (size_t)rows * d * 2, s));
     int rcb = build_stack_table(h);
@@ -2229,8 +2069,8 @@ extern "C" int zn_bench_kernel(zn_handle h, int32_t which, int32_t rows, int32_t
   if (tconv) (void)hipFree(tconv);
   if (which == 6) {
     for (void* p : skv) if (p) (void)hipFree(p);
-    h->kv_layers = saved_kv; h->max_len = saved_max_len; h->lengths = saved_lengths;
-    if (h->gen_active && (int)h->kv_layers.size() == c.n_layer) { int rcb = build_stack_table(h); if (rcb) return rcb; }
+    h->gen = saved_gen;
+    if (h->gen.gen_active && (int)h->gen.kv_layers.size() == c.n_layer) { int rcb = build_stack_table(h); if (rcb) return rcb; }
     int tmo = 0;
     HIPCHK(h, ZN_NOT_IN_CAPTURE(hipMemcpy(&tmo, &h->st->pad[0], sizeof(int), hipMemcpyDeviceToHost)));
     if (tmo != 0) return handoff_timeout(h, tmo);
@@ -2397,7 +2237,7 @@ static int attach_fp8_pair(zn_handle h, const char* who, int layer, const Fp8Str
     if (b1 < 0 || b2 < 0) ZN_FAIL(h, ZN_ERR_HIP, "%s: the verification could not run", who);
     if (b1 || b2) ZN_FAIL(h, ZN_ERR_ARG, "%s: layer %d's bf16 weights are not the dequantised stream (%s: %lld, %s: %lld pieces of 8 differ)", who, layer, a.name, b1, b.name, b2);
   }
-  free_graph(h); h->emb_valid = false;
+  free_graph(h); h->gen.emb_valid = false;
   return ZN_OK;
 }
 extern "C" int zn_set_mlp_fp8(zn_handle h, int32_t layer, const void* fc1_q, const void* fc1_exp, const void* fc2_q, const void* fc2_exp) {
@@ -2407,7 +2247,7 @@ extern "C" int zn_set_mlp_fp8(zn_handle h, int32_t layer, const void* fc1_q, con
   if (layer < 0 || layer >= c.n_layer) ZN_FAIL(h, ZN_ERR_ARG, "zn_set_mlp_fp8: layer %d out of range", layer);
   if (h->layers[layer].kind != 0) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mlp_fp8: layer %d is a Mamba2 layer", layer);
   if (c.d_model % ZN_G16_KC || c.d_ff % ZN_G16_KC) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mlp_fp8: d_model %d / d_ff %d must be multiples of %d", c.d_model, c.d_ff, ZN_G16_KC);
-  if (h->gen_active && !h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_set_mlp_fp8 inside a generation (between zn_gen_begin and zn_gen_end)");
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_SET_MLP_FP8));
   if (int rc = attach_fp8_pair(h, "zn_set_mlp_fp8", layer, {"fc1", fc1_q, fc1_exp, h->layers[layer].fc1, 2 * c.d_ff, c.d_model}, {"fc2", fc2_q, fc2_exp, h->layers[layer].fc2, c.d_model, c.d_ff})) return rc;
   zn_handle_s::MlpFp8& f = h->mlp_fp8[layer];
   f.fc1_q = (const uint8_t*)fc1_q; f.fc1_exp = (const int8_t*)fc1_exp; f.fc2_q = (const uint8_t*)fc2_q; f.fc2_exp = (const int8_t*)fc2_exp;
@@ -2416,28 +2256,27 @@ extern "C" int zn_set_mlp_fp8(zn_handle h, int32_t layer, const void* fc1_q, con
 extern "C" int zn_set_kv_fp8(zn_handle h, int32_t on) {
   if (!h) return ZN_ERR_ARG;
   if (h->cfg.arch == 1) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_kv_fp8: the hybrid stack's attention layers keep a bf16 KV cache");
-  if (h->gen_active && !h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_set_kv_fp8 inside a generation (between zn_gen_begin and zn_gen_end)");
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_SET_KV_FP8));
   h->kv_fp8 = on != 0;
-  free_graph(h); h->emb_valid = false;
+  free_graph(h); h->gen.emb_valid = false;
   return ZN_OK;
 }
 extern "C" int zn_set_kv_fp8_only(zn_handle h, int32_t on) {
   if (!h) return ZN_ERR_ARG;
   if (h->cfg.arch == 1) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_kv_fp8_only: the hybrid stack's attention layers keep a bf16 KV cache");
-  if (h->gen_active && !h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_set_kv_fp8_only inside a generation (between zn_gen_begin and zn_gen_end)");
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_SET_KV_FP8_ONLY));
   h->kv_fp8_only = on != 0;
-  free_graph(h); h->emb_valid = false;
+  free_graph(h); h->gen.emb_valid = false;
   return ZN_OK;
 }
 extern "C" size_t zn_kv_fp8_bytes_per_layer(const zn_config* c, int32_t rows, int32_t max_len) { return zn_kv_bytes_per_layer(c, rows, max_len) / 2; }
 extern "C" int zn_gen_bind_kv_fp8(zn_handle h, const void* const* codes_layers_dev) {
   if (!h) return ZN_ERR_ARG;
-  if (!h->gen_active || h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_bind_kv_fp8 before zn_gen_begin");
-  if (h->gen_prefilled) ZN_FAIL(h, ZN_ERR_STATE, "zn_gen_bind_kv_fp8 after the generation's prefill: the code caches are bound between zn_gen_begin and the first prefill or admission");
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_BIND_KV_FP8));
   if (!codes_layers_dev) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_bind_kv_fp8: null argument");
   for (int li = 0; li < h->cfg.n_layer; ++li)
     if (!codes_layers_dev[li] && h->layers[li].kind == 0) ZN_FAIL(h, ZN_ERR_ARG, "zn_gen_bind_kv_fp8: layer %d has no code cache", li);
-  h->kv8_layers.assign(codes_layers_dev, codes_layers_dev + h->cfg.n_layer);
+  h->gen.kv8_layers.assign(codes_layers_dev, codes_layers_dev + h->cfg.n_layer);
   h->adm_cap_S = 0;          // a session's admission table names the code caches: rebuilt by the next admission
   return ZN_OK;
 }
@@ -2479,7 +2318,7 @@ extern "C" int zn_set_mamba_fp8(zn_handle h, int32_t layer, const void* in_q, co
   if (h->layers[layer].kind != 1) ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mamba_fp8: layer %d is an attention layer", layer);
   if (c.d_model != 2 * ZN_G16K_NKW * ZN_G16K_KCH || c.m_d_inner != 4 * ZN_G16K_NKW * ZN_G16K_KCH)
     ZN_FAIL(h, ZN_ERR_UNSUPPORTED, "zn_set_mamba_fp8: the FP8 kernels serve d_model 2048 and d_inner 4096 (got d_model %d, d_inner %d)", c.d_model, c.m_d_inner);
-  if (h->gen_active && !h->gen_ended) ZN_FAIL(h, ZN_ERR_STATE, "zn_set_mamba_fp8 inside a generation (between zn_gen_begin and zn_gen_end)");
+  ZN_GEN_CHECK(h, gen_call_order(h->gen, GE_SET_MAMBA_FP8));
   if (int rc = attach_fp8_pair(h, "zn_set_mamba_fp8", layer, {"in_proj", in_q, in_exp, h->layers[layer].m_in_proj, h->m_d_in_proj, c.d_model},
                                {"out_proj", out_q, out_exp, h->layers[layer].m_out_proj, c.d_model, c.m_d_inner})) return rc;
   zn_handle_s::MambaFp8& f = h->mamba_fp8[layer];
