@@ -653,6 +653,45 @@ int zn_dac_decode_spans(zn_dac d, const int32_t* codes_dev, int32_t n_max, const
  * quantizer.quantizers.{i}.in_proj tensors at zn_dac_create. */
 int zn_dac_encode(zn_dac d, const float* wav_dev, int32_t batch, int32_t T, int32_t* codes_dev, zn_stream stream);
 
+/* ---------------------------------------------------------------- output resampling */
+/* Additions (no existing call or layout changes; ZN_ABI_VERSION does not tell whether a library has them).  The filter is
+ * torchaudio's sinc_interp_hann polyphase filter (zonos_amd/resample.py is the specification): with g = gcd(orig_freq, new_freq),
+ * o = orig_freq / g, n = new_freq / g, base = min(o, n) * rolloff, width = ceil(lowpass_filter_width * o / base), the table
+ * k fp32 [n][2 * width + o] is computed in double and rounded once; phase p's support [lo_p, hi_p) is the smallest interval holding its
+ * nonzero fp32 taps.  Output j = q * n + p of a signal x of T samples (0 <= j < ceil(n * T / o)) is ONE fp32 chain
+ *   acc = 0; for i = lo_p .. hi_p - 1 ascending: acc = fma(k[p][i], x[q * o - width + i], acc)        (x = 0 outside [0, T))
+ * so its value depends on j and the signal only: any window that holds the inputs it reads gives the same bits. */
+typedef struct zn_resampler_s* zn_resampler;
+/* Host only (no handle, no device).  Writes o, n, width (each optional) and, where the pointers are given, lo / hi (int32 [n], needs
+ * phases_cap >= n) and the table (fp32 [n][2 * width + o], needs table_cap >= n * (2 * width + o) elements).  ZN_ERR_ARG: a rate or
+ * lowpass_filter_width < 1, rolloff outside (0, 1], a buffer too small (o, n, width are written first: call once without buffers to
+ * size them).  ZN_ERR_UNSUPPORTED: a table of more than 2^22 entries.  Messages through zn_resampler_last_error(NULL). */
+int zn_resample_plan(int32_t orig_freq, int32_t new_freq, int32_t lowpass_filter_width, double rolloff, int32_t* o, int32_t* n,
+                     int32_t* width, int32_t* lo, int32_t* hi, int32_t phases_cap, float* table, int64_t table_cap);
+/* Host only, like zn_dac_span: the arithmetic of a stream.  With `avail` input samples [0, avail) known (at_end != 0: they are the
+ * whole signal), *n_final = how many leading outputs are final - output j is final once q * o - width + hi_p <= avail, and every one
+ * of the ceil(n * avail / o) outputs is when at_end.  *first_in = the first input that the outputs from out_index on still read
+ * (min over them of max(0, q * o - width + lo_p)); out_index < 0 stands for *n_final.  Either pointer may be NULL. */
+int zn_resample_span(int32_t orig_freq, int32_t new_freq, int32_t lowpass_filter_width, double rolloff, int64_t avail, int32_t at_end,
+                     int64_t out_index, int64_t* n_final, int64_t* first_in);
+/* A handle keeps the plan's table on the device, laid out [tap][phase] over the supports only (consecutive lanes read consecutive
+ * words); it is uploaded to the device current at the handle's first launch, so creating a handle touches no device.  orig_freq == new_freq gives the identity (o = n = 1, one tap of 1.0): no resampling, for the PCM16
+ * conversion alone.  Errors before a handle exists through zn_resampler_last_error(NULL). */
+int zn_resampler_create(int32_t orig_freq, int32_t new_freq, int32_t lowpass_filter_width, double rolloff, zn_resampler* out);
+int zn_resampler_destroy(zn_resampler r);
+const char* zn_resampler_last_error(zn_resampler r);
+/* One row of zn_resample_rows (HOST array): the row holds input samples [in0, in0 + in_len) of its own signal and receives outputs
+ * [out0, out0 + out_count); at_end != 0: in0 + in_len is the signal's end. */
+typedef struct zn_resample_row { int64_t in0; int32_t in_len; int64_t out0; int32_t out_count; int32_t at_end; } zn_resample_row;
+/* in fp32 [rows, in_max] (cells beyond in_len are never read) -> out fp32, or int16 when out_is_int16 (clamp(y * 32767, +-32767)
+ * truncated toward zero, decode_to_int16's arithmetic), [rows, out_max]: row r's outputs in its first out_count cells (cells beyond
+ * are never written).  One launch, one output per lane; 1 <= rows <= 64; a uniform batch is `rows` equal entries.  ZN_ERR_ARG, naming
+ * the row and launching nothing: in_len > in_max, out_count > out_max, a negative field, an output that reads an input outside the
+ * row's window (allowed only before sample 0, or past the end of a row with at_end), or, with at_end, an output at or beyond
+ * ceil(n * (in0 + in_len) / o).  A call whose rows all have out_count == 0 launches nothing. */
+int zn_resample_rows(zn_resampler r, const float* in_dev, int64_t in_max, const zn_resample_row* rows_host, int32_t rows, void* out_dev,
+                     int64_t out_max, int32_t out_is_int16, zn_stream stream);
+
 /* ---------------------------------------------------------------- speaker embedding (zonos/speaker_cloning.py) */
 /* ResNet293_based (speaker_cloning.py:419-472: ResNet293 of SimAM blocks -> ASP -> bottleneck Linear) and the LDA Linear
  * of SpeakerEmbeddingLDA (:800-883), fp32.  Tensors by the reference's state-dict names (front.*, pooling.*,

@@ -117,6 +117,11 @@ class zn_dac_span_row(C.Structure):
     _fields_ = [("c0", C.c_int32), ("n", C.c_int32), ("at_end", C.c_int32)]
 
 
+class zn_resample_row(C.Structure):
+    """One row of zn_resample_rows: the row holds inputs [in0, in0 + in_len) of its signal and receives outputs [out0, out0 + out_count)."""
+    _fields_ = [("in0", C.c_int64), ("in_len", C.c_int32), ("out0", C.c_int64), ("out_count", C.c_int32), ("at_end", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/zonos_hip.h declares
 SIGNATURES = {
     "zn_abi_version": (C.c_int, []),
@@ -204,6 +209,12 @@ SIGNATURES = {
     "zn_dac_span": (C.c_int, [C.POINTER(zn_dac_config), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "zn_dac_decode_span": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "zn_dac_decode_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(zn_dac_span_row), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "zn_resample_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double] + [C.POINTER(C.c_int32)] * 5 + [C.c_int32, C.POINTER(C.c_float), C.c_int64]),
+    "zn_resample_span": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "zn_resampler_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_void_p)]),
+    "zn_resampler_destroy": (C.c_int, [C.c_void_p]),
+    "zn_resampler_last_error": (C.c_char_p, [C.c_void_p]),
+    "zn_resample_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(zn_resample_row), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "zn_spk_create": (C.c_int, [C.POINTER(zn_dac_tensor), C.c_int32, C.POINTER(C.c_void_p)]),
     "zn_spk_destroy": (C.c_int, [C.c_void_p]),
     "zn_spk_last_error": (C.c_char_p, [C.c_void_p]),
@@ -250,6 +261,12 @@ def check(rc: int, handle=None, what: str = "") -> None:
 def check_dac(rc: int, handle=None, what: str = "") -> None:
     if rc != 0:
         msg = load().zn_dac_last_error(handle)
+        raise ZonosHipError(f"{what} failed (status {rc}): {msg.decode() if msg else ''}")
+
+
+def check_resample(rc: int, handle=None, what: str = "") -> None:
+    if rc != 0:
+        msg = load().zn_resampler_last_error(handle)
         raise ZonosHipError(f"{what} failed (status {rc}): {msg.decode() if msg else ''}")
 
 

@@ -629,7 +629,8 @@ class Zonos(nn.Module):
         return self._serve_gen(torch.cuda.current_stream(dev), iter(requests), shape, _trace, _stats)
 
     def serve_stream(self, requests, slots: int = 8, max_prompt: int = 64, max_new_tokens: int = 86 * 30, guided: bool | None = True,
-                     sched_every: int = 8, chunk_frames: int = 16, _stats: dict | None = None) -> Iterator[ServeChunk]:
+                     sched_every: int = 8, chunk_frames: int = 16, _stats: dict | None = None, sample_rate: int | None = None,
+                     pcm16: bool = False) -> Iterator[ServeChunk]:
         """`serve()` with audio as it happens: a generator of `ServeChunk(index, codes, wav, done, error)`.  The session is `serve()`'s -
         the same admissions, steps and retirements.  At a scheduling point every busy slot whose final frames (`release_limit` of its
         own column) have grown by at least `chunk_frames` since its last chunk yields them with the samples the DAC can decode from
@@ -637,11 +638,14 @@ class Zonos(nn.Module):
         The windows of all slots are decoded in one ragged pass (`DACAutoencoder.stream_set`, zn_dac_decode_spans) on the session's
         stream.  For every request the concatenated codes equal the `ServeResult.codes` of `serve()` for the same source and settings,
         and the concatenated wav `autoencoder.decode()` of them, bit for bit.  A refused request yields
-        ServeChunk(index, None, None, True, ValueError).  The engine is held as by `serve()`; `_stats` as there."""
+        ServeChunk(index, None, None, True, ValueError).  The engine is held as by `serve()`; `_stats` as there.  `sample_rate` / `pcm16`:
+        every request's wav is `autoencoder.decode(codes, sample_rate, pcm16)` instead, resampled on the session's stream in one launch
+        per scheduling point."""
         if int(chunk_frames) < 1:
             raise ValueError(f"serve_stream: chunk_frames must be >= 1, got {chunk_frames}")
+        self.autoencoder._resampler(sample_rate, pcm16)           # (a bad rate is refused here, not at the first next())
         dev, shape = self.device, self._serve_shape("serve_stream", slots, max_prompt, max_new_tokens, guided, sched_every)
-        return self._serve_gen(torch.cuda.current_stream(dev), iter(requests), shape, None, _stats, int(chunk_frames))
+        return self._serve_gen(torch.cuda.current_stream(dev), iter(requests), shape, None, _stats, int(chunk_frames), (sample_rate, pcm16))
 
     def _serve_shape(self, who: str, slots, max_prompt, max_new_tokens, guided, sched_every) -> ServeShape:
         """The arguments serve() and serve_stream() share, checked; `who` names the caller in the messages."""
@@ -653,10 +657,10 @@ class Zonos(nn.Module):
         self._check_device()
         return ServeShape(slots, max_prompt, max_new_tokens, None if guided is None else bool(guided), sched_every)
 
-    def _serve_gen(self, ts, source, shape: ServeShape, _trace, _stats=None, chunk_frames=None):
+    def _serve_gen(self, ts, source, shape: ServeShape, _trace, _stats=None, chunk_frames=None, audio=(None, False)):
         """The session of serve() (chunk_frames None: yields ServeResult) and of serve_stream() (yields ServeChunk): the engine is held
         while the generator is alive, and every scheduling point's results go out with the caller's device and stream current."""
-        session = ServeSession(self, ts, source, shape, _trace, _stats, chunk_frames)
+        session = ServeSession(self, ts, source, shape, _trace, _stats, chunk_frames, audio)
         with self._engine_held((session.R + 1) // 2) as eng:
             try:
                 session.open(eng)
@@ -669,7 +673,7 @@ class Zonos(nn.Module):
 
     def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor = None, max_new_tokens: int = 86 * 30,
                cfg_scale: float = 2.0, sampling_params: dict = dict(min_p=0.1), seed: int | None = None, chunk_frames: int = 16,
-               batch_size: int = 1) -> Iterator[StreamChunk]:
+               batch_size: int = 1, sample_rate: int | None = None, pcm16: bool = False) -> Iterator[StreamChunk]:
         """`generate()` + `autoencoder.decode()` as they happen: a generator of `StreamChunk(codes, wav)`.  Every `chunk_frames` decode steps
         it yields the frames that have become final (`release_limit`) and the samples the DAC can decode from them (`DACAutoencoder.stream`);
         the rest comes when the generation ends.  With the same arguments and seed, the concatenated codes equal `generate(...)` and the
@@ -677,24 +681,27 @@ class Zonos(nn.Module):
 
         The generation's engine and the device's persistent-kernel tenancy are held while the generator is alive; `close()`, leaving a for
         loop early or garbage collection releases them.  Every launch (decode steps and DAC) goes to the stream current when stream() is
-        called.  A hand-off timeout raises: it is not repeated on the launches path, as the caller may already hold audio."""
+        called.  A hand-off timeout raises: it is not repeated on the launches path, as the caller may already hold audio.
+        `sample_rate` / `pcm16`: the concatenated wav is `autoencoder.decode(generate(...), sample_rate, pcm16)` instead, resampled on the
+        generation's stream chunk by chunk."""
         if batch_size != 1:
             raise ValueError(f"stream() generates one utterance at a time, got batch_size={batch_size}")
         if int(chunk_frames) < 1:
             raise ValueError(f"chunk_frames must be >= 1, got {chunk_frames}")
         n = self._check_rows(prefix_conditioning, cfg_scale, 1)
+        self.autoencoder._resampler(sample_rate, pcm16)           # (a bad rate is refused here, not at the first next())
         seed, dev = draw_seed(seed), self.device
         # (the record is built at the first next(), where the errors of its arguments have always been raised)
         build = lambda: GenCall.plain(prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, 1, sampling_params, seed)
-        return self._stream_gen(dev, torch.cuda.current_stream(dev), (n + 1) // 2, build, int(chunk_frames))
+        return self._stream_gen(dev, torch.cuda.current_stream(dev), (n + 1) // 2, build, int(chunk_frames), (sample_rate, pcm16))
 
-    def _stream_gen(self, dev, ts, rows, build, chunk):
+    def _stream_gen(self, dev, ts, rows, build, chunk, audio=(None, False)):
         nq, eos = self.config.codebook_dimension, self.eos_token_id
         with contextlib.ExitStack() as held:               # closed by hand below; also by close(), an error or garbage collection
             eng = held.enter_context(self._engine_held(rows))
             # (each stretch between two yields runs with the generation's device and stream current, and leaves the caller's as it found them)
             with torch.inference_mode(), torch.cuda.device(dev), torch.cuda.stream(ts):
-                dac = self.autoencoder.stream(ts)
+                dac = self.autoencoder.stream(ts, *audio)
                 gen = self._generation(eng, build(), ts, Hooks(chunk=chunk))
 
             @held.callback

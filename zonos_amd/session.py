@@ -24,7 +24,7 @@ class ServeSession:
     steps, the row state, the ledger's scan, retirements and chunks - until it says stop; `close` (zn_gen_end) whatever happened.
     `chunk_frames` None: serve(), results are ServeResult; else serve_stream(), ServeChunk."""
 
-    def __init__(self, model, ts, source, shape: ServeShape, trace=None, stats=None, chunk_frames=None):
+    def __init__(self, model, ts, source, shape: ServeShape, trace=None, stats=None, chunk_frames=None, audio=(None, False)):
         self.model, self.ts, self.source, self.shape, self.trace, self.stats = model, ts, source, shape, trace, stats
         self.dev, self.st = model.device, ts.cuda_stream
         self.nq, self.d, self.mask = model.config.codebook_dimension, model.config.backbone.d_model, model.masked_token_id
@@ -35,7 +35,7 @@ class ServeSession:
         self.sched = SlotScheduler(shape.slots, self.nq, shape.sched_every)
         self.streaming = chunk_frames is not None
         self.ledger = StreamLedger(self.nq, chunk_frames, model.eos_token_id) if self.streaming else None
-        self.dacs = model.autoencoder.stream_set(ts) if self.streaming else None
+        self.dacs = model.autoencoder.stream_set(ts, *audio) if self.streaming else None      # audio: (sample_rate, pcm16)
         self.rem, self.own = (C.c_int32 * shape.slots)(), (C.c_int32 * shape.slots)()
         self.eng, self.begun = None, False
 
